@@ -10,8 +10,15 @@ spacing = diagonal/250, ACCURATE strategy) on one MI355X.  For N>1 (launched by 
 one rank per GPU) every rank owns the same number of points (weak scaling); points are exchanged once
 after the encode by their top Morton bits (RCCL all-to-all) and every rank then tiles its own octants.
 
-Rank 0 prints ONE JSON line with the metric, the roofline of the dominant kernel (HIP-event timing taken
-inside the timed region) and, at N=1, a CPU baseline (the oracle, timed on a bounded sample).
+Rank 0 prints ONE JSON line with the metric and the roofline of the dominant kernel (HIP-event timing taken
+inside the timed region).  A plain run does only that: set up, warm up, time the steps, print the line.
+
+    --full               also everything measured beside the headline, after the timed region: at N=1 the
+                         property-mode timing of MIN_DISTANCE (--md-mode both), the extra legs of --also and a CPU
+                         baseline (the oracle, timed on a bounded sample of --cpu-sample points)
+    --dump-outputs DIR   after the timed steps, write what the last step computed as DIR/<name>.npy (float32 /
+                         float64): a fixed, seeded sample of the keys, perm and level arrays, every point's level
+                         counted, and the tile stats; the inputs are the same in every run with the same arguments
 """
 import argparse
 import json
@@ -26,6 +33,9 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 SEED = 0x5C4A72A1D
+DUMP_SAMPLE = 1 << 20  # --dump-outputs: output positions written per array (all of them for smaller runs)
+DUMP_MAX_BYTES = 64 << 20
+STATS_FIELDS = ("num_nodes", "points_visited", "max_level", "fast_start_levels", "num_levels", "min_distance_rounds")
 
 
 def check_shard_stamps(rows, step_ms):
@@ -58,7 +68,7 @@ def parse_args():
     ap.add_argument("--sampler", default="MIN_DISTANCE", choices=["RANDOM_GRID", "GRID_CENTER", "MIN_DISTANCE", "JITTERED"])
     ap.add_argument("--diagonal-fraction", type=float, default=250.0)
     ap.add_argument("--max-points-per-node", type=int, default=20000)
-    ap.add_argument("--cpu-sample", type=int, default=100_000_000, help="points of the CPU-baseline sample (0 = skip); "
+    ap.add_argument("--cpu-sample", type=int, default=100_000_000, help="points of the CPU-baseline sample of --full (0 = skip); "
                     "100 M is what SURVEY.md section 8(d) asks for (about a minute on the GPU box's host cores)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (0 = all host cores available)")
     ap.add_argument("--strategy", default="ACCURATE", choices=["ACCURATE", "FAST"],
@@ -74,8 +84,8 @@ def parse_args():
     ap.add_argument("--md-mode", default="both", choices=["exact", "property", "both"], help="MIN_DISTANCE: exact = the "
                     "reference's Morton-order greedy set, bit-identical (the headline `value`); property = "
                     "SWZ_FLAG_MIN_DISTANCE_PROPERTY (same spacing + maximality guarantees, different priority order); "
-                    "both = `value` is exact and the property-mode timing of the same workload is reported beside it "
-                    "under \"min_distance_property\"")
+                    "both = `value` is exact and, with --full, the property-mode timing of the same workload is reported beside "
+                    "it under \"min_distance_property\"")
     ap.add_argument("--batches", type=int, default=1, help="tile the points in this many batches through the multi-batch "
                     "tiler (swz_tiler_*: cached-point re-read + merge like the reference with internal_cache_size < N); "
                     "a step is then the whole data set, batch after batch, into a fresh tiler")
@@ -95,7 +105,7 @@ def parse_args():
                     "ncclSend / ncclRecv or by hipMemcpyPeerAsync (peer copies also work with all shards on ONE device)")
     ap.add_argument("--group-devices", type=int, default=0, help="--driver group: devices the shards are dealt to (0 = as "
                     "many as there are shards; 1 = all shards share device 0, the only way to run it on a one-GPU box)")
-    ap.add_argument("--also", default="GRID_CENTER,GRID_CENTER@100000000,JITTERED,MIN_DISTANCE_FAST", help="N = 1, one batch, headline workload only: short extra legs "
+    ap.add_argument("--also", default="GRID_CENTER,GRID_CENTER@100000000,JITTERED,MIN_DISTANCE_FAST", help="--full, N = 1, one batch, headline workload only: short extra legs "
                     "after the timed region, reported under \"also\" and never part of `value` -- a sampler name runs the same points "
                     "through that sampler (GRID_CENTER: BASELINE configs[1]'s sampler at the headline size), <sampler>_FAST through the "
                     "FAST strategy (the reference's default, executable/main.cpp:299-301), <leg>@POINTS on the first POINTS points of the cloud "
@@ -109,6 +119,11 @@ def parse_args():
                     "scaling: `scaling` says so); overrides --points")
     ap.add_argument("--one-device", action="store_true", help="dry run of an N-rank configuration on ONE GPU: all ranks share "
                     "cuda:0 and talk over gloo (RCCL does not put two ranks on one device); the line is labelled a dry run")
+    ap.add_argument("--full", action="store_true", help="also measure what goes beside the headline (N = 1): the "
+                    "property-mode timing of --md-mode both, the legs of --also and the CPU baseline of --cpu-sample; "
+                    "a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step "
+                    "computed as DIR/<name>.npy (float32 / float64; a fixed, seeded sample of the per-point arrays)")
     args = ap.parse_args()
     if args.config == 4:
         args.sampler, args.strategy, args.batches = "JITTERED", "ACCURATE", 1
@@ -335,6 +350,52 @@ def committed_cpu_baseline():
         if cb:
             return dict(cb, source="profiles/%s/bench_1B_min_distance.json" % rnd)
     return None
+
+
+def dump_sample_index(n, m=DUMP_SAMPLE, seed=SEED + 7):
+    """The output positions --dump-outputs writes: all of them when n <= m, else m draws of a fixed seeded generator,
+    sorted and unique -- the same positions in every run of the same size."""
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(seed).integers(0, n, size=m, dtype=np.int64))
+
+
+def stats_array(stats):
+    """The tile stats of a step as float64, in STATS_FIELDS order (-1 where a path does not report one)."""
+    return np.array([float((stats or {}).get(k, -1)) for k in STATS_FIELDS], dtype=np.float64)
+
+
+def tile_output_arrays(torch, keys, perm, level, stats):
+    """What a caller of the tile path receives -- keys (u64), perm (i32), level (i8) per sorted point and the tile stats --
+    as float64 / float32 host arrays: the arrays at dump_sample_index's positions (keys split into exact 32-bit halves), the
+    positions themselves and the level of EVERY point counted (level_histogram[i] = points at level i - 1; -1 = not taken)."""
+    n = int(keys.shape[0])
+    idx = dump_sample_index(n)
+    di = torch.from_numpy(idx).to(keys.device)
+    k = keys.index_select(0, di).cpu().numpy().view(np.uint64)
+    hist = torch.zeros(129, dtype=torch.int64, device=level.device)
+    chunk = 1 << 26  # (bounded temporaries: the sampling workspace may hold most of the HBM)
+    for lo in range(0, n, chunk):
+        hist += torch.bincount(level[lo:lo + chunk].to(torch.int32) + 1, minlength=129)[:129]
+    return {"sample_index": idx.astype(np.float64),
+            "keys_hi32": (k >> np.uint64(32)).astype(np.float64),
+            "keys_lo32": (k & np.uint64(0xFFFFFFFF)).astype(np.float64),
+            "perm": perm.index_select(0, di).cpu().numpy().astype(np.float64),
+            "level": level.index_select(0, di).cpu().numpy().astype(np.float32),
+            "level_histogram": hist.cpu().numpy().astype(np.float64),
+            "tile_stats": stats_array(stats)}
+
+
+def write_outputs(directory, arrays, suffix=""):
+    """DIR/<name><suffix>.npy for every array (float32 / float64 only, DUMP_MAX_BYTES at most in all)."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_MAX_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + suffix + ".npy"), a)
+    return sorted(name + suffix for name in arrays)
 
 
 def cpu_baseline(args, spacing):
@@ -687,6 +748,17 @@ def main():
         elapsed = float(t.item())
 
     prof = {} if args.no_profile else ctx.profile_get()
+    dumped = None
+    if args.dump_outputs:
+        # what the last timed step left for its caller, before any leg after the timed region reuses the buffers
+        if not distributed and mb is None:
+            arrays = tile_output_arrays(torch, keys, perm, level, stats)
+        elif distributed and not (args.batches > 1 or args.strategy == "FAST") and getattr(runner, "result", None):
+            rkeys, rperm, rlevel = runner.result[1:4]  # this rank's shard: its points' keys, perm and level
+            arrays = tile_output_arrays(torch, rkeys, rperm, rlevel, stats)
+        else:  # the batch tilers keep their nodes inside the tiler: their stats are what a caller receives
+            arrays = {"tile_stats": stats_array(stats)}
+        dumped = write_outputs(args.dump_outputs, arrays, "_rank%d" % rank if world > 1 else "")
     # the sharded single-batch driver: what every rank's last step spent where (events on the launch stream), which way the
     # MIN_DISTANCE root went, how many points the rank ended up owning
     shard_report = None
@@ -752,8 +824,10 @@ def main():
             "tile_stats": stats,
             "roofline": roofline,
             "kernels_ms_per_step": {k: round(v["total_ms"] / args.steps, 3) for k, v in sorted(prof.items())},
+            "full": bool(args.full),
+            "dumped_outputs": dumped,
         }
-        if args.md_mode == "both" and args.sampler == "MIN_DISTANCE" and not distributed and mb is None:
+        if args.full and args.md_mode == "both" and args.sampler == "MIN_DISTANCE" and not distributed and mb is None:
             import dataclasses
             pp = dataclasses.replace(params, flags=swz.FLAG_MIN_DISTANCE_PROPERTY)
 
@@ -788,7 +862,7 @@ def main():
                 "kernels_ms_per_step": {k: round(v["total_ms"] / psteps, 3) for k, v in sorted(pprof.items())},
                 "note": "same workload with SWZ_FLAG_MIN_DISTANCE_PROPERTY: spacing and maximality guaranteed "
                         "(tests/test_min_distance_property.py), taken set differs from the reference's"}
-        if (args.also and world == 1 and not distributed and mb is None and args.md_mode != "property" and args.sampler == "MIN_DISTANCE"
+        if (args.full and args.also and world == 1 and not distributed and mb is None and args.md_mode != "property" and args.sampler == "MIN_DISTANCE"
                 and args.strategy == "ACCURATE" and not args.payload):
             import dataclasses
             out["also"] = {}
@@ -822,7 +896,7 @@ def main():
                                      "batch i is tiled; copy_wait_ms is the time tiling had to wait for a copy"}
         if world == 1 and not distributed and args.payload and mb is None:
             out["payload"] = payload_leg(args, ctx, swz, torch, dev, xyz, keys, perm, level, n)
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             out["cpu_baseline"] = cpu_baseline(args, spacing)
         elif world > 1:
             out["cpu_baseline_reference"] = committed_cpu_baseline()

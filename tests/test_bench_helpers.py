@@ -77,3 +77,39 @@ def test_bench_looks_for_the_newest_committed_profile_first():
     assert rounds == sorted(rounds, reverse=True) and all(r[0] == "r" and r[1:].isdigit() for r in rounds)
     newest = sorted(d for d in os.listdir(os.path.join(bench.ROOT, "profiles")) if d[:1] == "r" and d[1:].isdigit())[-1]
     assert rounds[0] == newest
+
+
+def test_a_plain_run_measures_the_headline_only():
+    """What goes beside the headline (property-mode timing, --also legs, the CPU baseline) runs only with --full."""
+    a = _args(["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (4, 2, False, None)
+    a = _args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out" and a.md_mode == "both" and a.cpu_sample > 0 and a.also
+
+
+def test_dumped_outputs_are_a_fixed_sample_of_what_the_caller_receives(tmp_path):
+    """--dump-outputs: the same positions in every run, keys split into exact 32-bit halves, every point's level counted,
+    float32 / float64 only and DUMP_MAX_BYTES at most."""
+    import numpy as np
+    import torch
+    n = 3 * bench.DUMP_SAMPLE
+    idx = bench.dump_sample_index(n)
+    assert np.array_equal(idx, bench.dump_sample_index(n)) and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < n
+    assert np.array_equal(bench.dump_sample_index(1000), np.arange(1000))
+    rng = np.random.default_rng(3)
+    keys = torch.from_numpy(rng.integers(0, 1 << 63, size=n, dtype=np.int64))
+    perm = torch.from_numpy(rng.permutation(n).astype(np.int32))
+    level = torch.from_numpy(rng.integers(-1, 12, size=n).astype(np.int8))
+    stats = dict(num_nodes=17, points_visited=5 * n, max_level=11, fast_start_levels=-1, num_levels=12, min_distance_rounds=3)
+    out = bench.tile_output_arrays(torch, keys, perm, level, stats)
+    k = keys.numpy()[idx].view(np.uint64)
+    assert np.array_equal(out["keys_hi32"].astype(np.uint64) << np.uint64(32) | out["keys_lo32"].astype(np.uint64), k)
+    assert np.array_equal(out["perm"], perm.numpy()[idx]) and np.array_equal(out["level"], level.numpy()[idx])
+    assert np.array_equal(out["level_histogram"][:13], np.bincount(level.numpy().astype(np.int64) + 1))
+    assert out["level_histogram"].sum() == n
+    assert out["tile_stats"].tolist() == [17, 5 * n, 11, -1, 12, 3]
+    names = bench.write_outputs(str(tmp_path), out)
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(x + ".npy" for x in names)
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= bench.DUMP_MAX_BYTES
+    for p in tmp_path.iterdir():
+        assert np.load(p).dtype in (np.float32, np.float64)

@@ -1,11 +1,14 @@
 """Pins the oracle against every golden vector the reference's own unit tests hold for the hot path
-(SURVEY.md section 8(c)), restated case by case, and against oracle/_ref (the reference's stand-alone
-headers compiled where they lie) when that build is present.
+(SURVEY.md section 8(c)), restated case by case, and against what oracle/_ref (the reference's stand-alone
+headers compiled where they lie) computes: live when that build is present, as recorded in
+tests/golden/ref_build_results.npz everywhere else.
 
 Reference test files mirrored here (paths relative to /root/reference/schwarzwald/test/):
   TestMortonIndex.cpp:5-140, TestOctreeIndexing.cpp:72-600, TestAlgorithm.cpp:24-207.
 """
 import ctypes as C
+import hashlib
+import os
 
 import numpy as np
 import pytest
@@ -214,51 +217,109 @@ def test_merge_ranges(lists, expected):
 
 
 # ------------------------------------------------------------------ oracle vs oracle/_ref
-needs_ref = pytest.mark.skipif(O.ref() is None, reason="oracle/_ref not built (reference checkout absent)")
+# What oracle/_ref computes on the inputs below is recorded in tests/golden/ref_build_results.npz (tools/gen_golden.py):
+# the oracle is checked against the live build where oracle/_ref exists -- which must still give the recorded results --
+# and against the record everywhere else.
+REF_BUILD_RESULTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_build_results.npz")
+PARTITION_CASES = ((0.2, -1), (0.05, -1), (0.01, -1), (0.05, 1))
 
 
-@needs_ref
-def test_morton_index_ops_match_reference_build():
+def morton_ops_cases():
+    """(key, level, octant, levels) rows, seeded"""
     rng = np.random.default_rng(5)
-    R, L = O.ref(), O.lib()
+    rows = []
     for levels in (1, 2, 4, 5, 10, 20, 21):
         mask = (1 << (3 * levels)) - 1
         for _ in range(300):
             key = int(rng.integers(0, 1 << 63, dtype=np.uint64)) & mask
             lvl = int(rng.integers(0, levels))
-            assert L.orc_truncate_to_level(key, lvl, levels) == R.ref_truncate_to_level(key, lvl, levels)
-            assert L.orc_get_octant_at_level(key, lvl, levels) == R.ref_get_octant_at_level(key, lvl, levels)
-            o = int(rng.integers(0, 8))
-            assert L.orc_set_octant_at_level(key, lvl, o, levels) == R.ref_set_octant_at_level(key, lvl, o, levels)
-    # TestMortonIndex.cpp:26-36: the value constructor discards bits outside of range
-    assert R.ref_morton_ctor(0xFF, 2) == 0x3F
-    assert R.ref_morton_ctor(12345, 20) == 12345
-    octs = (C.c_uint8 * 4)(7, 6, 0, 3)
-    assert R.ref_morton_from_levels(octs, 4) == key_from_octants([7, 6, 0, 3], 4)
+            rows.append((key, lvl, int(rng.integers(0, 8)), levels))
+    return np.array(rows, dtype=np.uint64)
+
+
+def partition_input():
+    """20 000 seeded points, Morton-sorted: (sorted keys, their point indices, the points)"""
+    rng = np.random.default_rng(77)
+    xyz = rng.random((20000, 3))
+    keys, _ = O.index_points(xyz, [0, 0, 0], [1, 1, 1])
+    order = O.sort_by_key(keys)
+    return keys[order], order, xyz
+
+
+def partition_candidate_level(spacing, node_level):
+    return O.lib().orc_required_morton_index_depth(O.RANDOM_GRID, node_level, O._vec3([0, 0, 0]), O._vec3([1, 1, 1]),
+                                                   C.c_float(spacing))
+
+
+def _sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def reference_build_results(R):
+    """What the reference build R gives on morton_ops_cases() and PARTITION_CASES (arrays of a partition as SHA-256)."""
+    cases = morton_ops_cases()
+    res = {"morton_cases": cases,
+           "truncate_to_level": np.array([R.ref_truncate_to_level(int(k), int(l), int(n)) for k, l, _, n in cases], np.uint64),
+           "get_octant_at_level": np.array([R.ref_get_octant_at_level(int(k), int(l), int(n)) for k, l, _, n in cases], np.uint8),
+           "set_octant_at_level": np.array([R.ref_set_octant_at_level(int(k), int(l), int(o), int(n)) for k, l, o, n in cases],
+                                           np.uint64),
+           "morton_ctor_ff_2": np.uint64(R.ref_morton_ctor(0xFF, 2)),
+           "morton_ctor_12345_20": np.uint64(R.ref_morton_ctor(12345, 20)),
+           "morton_from_levels_7603": np.uint64(R.ref_morton_from_levels((C.c_uint8 * 4)(7, 6, 0, 3), 4))}
     buf = C.create_string_buffer(32)
     R.ref_morton64_to_string(key_from_octants(list(range(8)), 21), 8, buf, 32)
-    assert buf.value == b"01234567"  # TestMortonIndex.cpp:88-105
-    assert R.ref_morton64_from_string(b"r01234567") == key_from_octants(list(range(8)), 21)
+    res["morton64_to_string_01234567"] = np.array(buf.value.decode())
+    res["morton64_from_string_r01234567"] = np.uint64(R.ref_morton64_from_string(b"r01234567"))
+    skeys, sidx, _ = partition_input()
+    taken, kd, id_ = [], [], []
+    for spacing, node_level in PARTITION_CASES:
+        rk, ri = skeys.copy(), sidx.copy()
+        taken.append(R.ref_partition_first_of_cell(rk.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                   ri.ctypes.data_as(C.POINTER(C.c_uint32)), len(rk),
+                                                   partition_candidate_level(spacing, node_level)))
+        kd.append(_sha(rk))
+        id_.append(_sha(ri))
+    res.update(partition_taken=np.array(taken, np.int64), partition_keys_sha256=np.array(kd), partition_idx_sha256=np.array(id_))
+    return res
 
 
-@needs_ref
+def recorded_reference_results():
+    """the recorded results; where oracle/_ref is built it must still compute exactly those"""
+    rec = np.load(REF_BUILD_RESULTS)
+    rec = {k: rec[k] for k in rec.files}
+    assert np.array_equal(rec["morton_cases"], morton_ops_cases())  # (a record of these very inputs)
+    if O.ref() is not None:
+        live = reference_build_results(O.ref())
+        assert sorted(live) == sorted(rec)
+        for k, v in live.items():
+            assert np.array_equal(np.asarray(v), rec[k]), k
+    return rec
+
+
+def test_morton_index_ops_match_reference_build():
+    R, L = recorded_reference_results(), O.lib()
+    cases = morton_ops_cases()
+    assert [L.orc_truncate_to_level(int(k), int(l), int(n)) for k, l, _, n in cases] == R["truncate_to_level"].tolist()
+    assert [L.orc_get_octant_at_level(int(k), int(l), int(n)) for k, l, _, n in cases] == R["get_octant_at_level"].tolist()
+    assert [L.orc_set_octant_at_level(int(k), int(l), int(o), int(n)) for k, l, o, n in cases] == R["set_octant_at_level"].tolist()
+    # TestMortonIndex.cpp:26-36: the value constructor discards bits outside of range
+    assert int(R["morton_ctor_ff_2"]) == 0x3F
+    assert int(R["morton_ctor_12345_20"]) == 12345
+    assert int(R["morton_from_levels_7603"]) == key_from_octants([7, 6, 0, 3], 4)
+    assert str(R["morton64_to_string_01234567"]) == "01234567"  # TestMortonIndex.cpp:88-105
+    assert int(R["morton64_from_string_r01234567"]) == key_from_octants(list(range(8)), 21)
+
+
 def test_random_grid_core_matches_reference_partition_routine():
     """RandomSortedGridSampling's body is the reference's stable_partition_with_jumps + truncate_to_level +
     std::partition_point (Sampling.h:253-284); run exactly those through oracle/_ref and compare."""
-    rng = np.random.default_rng(77)
-    xyz = rng.random((20000, 3))
-    bmin, bmax = [0, 0, 0], [1, 1, 1]
-    keys, _ = O.index_points(xyz, bmin, bmax)
-    order = O.sort_by_key(keys)
-    for spacing, node_level in ((0.2, -1), (0.05, -1), (0.01, -1), (0.05, 1)):
-        cand = O.lib().orc_required_morton_index_depth(O.RANDOM_GRID, node_level, O._vec3(bmin), O._vec3(bmax),
-                                                       C.c_float(spacing))
-        taken, k2, i2 = O.sample_points(O.RANDOM_GRID, 1, keys[order], order, xyz, 0, node_level, bmin, bmax,
+    R = recorded_reference_results()
+    skeys, sidx, xyz = partition_input()
+    for i, (spacing, node_level) in enumerate(PARTITION_CASES):
+        taken, k2, i2 = O.sample_points(O.RANDOM_GRID, 1, skeys, sidx, xyz, 0, node_level, [0, 0, 0], [1, 1, 1],
                                         spacing, O.ALWAYS_ADHERE)
-        rk, ri = keys[order].copy(), order.copy()
-        rt = O.ref().ref_partition_first_of_cell(rk.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                 ri.ctypes.data_as(C.POINTER(C.c_uint32)), len(rk), cand)
-        assert rt == taken and np.array_equal(rk, k2) and np.array_equal(ri, i2)
+        assert taken == int(R["partition_taken"][i])
+        assert _sha(k2) == str(R["partition_keys_sha256"][i]) and _sha(i2) == str(R["partition_idx_sha256"][i])
 
 
 # ------------------------------------------------------------------ SURVEY.md section 8(a) known answers

@@ -5,6 +5,8 @@ Two kinds of fixtures, kept apart:
   ref_*.npz           outputs of the REFERENCE's own code: oracle/_ref/libswzref.so is compiled by oracle/Makefile from
                       core/datastructures/MortonIndex.h, util/algorithms/Algorithm.h and util/containers/Range.h where they
                       lie under /root/reference (nothing is copied); inputs are seeded here.
+  ref_build_results.npz  what oracle/_ref gives on the seeded inputs of tests/test_oracle_reference_kats.py (the arrays of
+                      a partition as SHA-256 digests): those tests check the oracle against it where oracle/_ref is absent.
   oracle_tile_*.json  SHA-256 digests of the oracle's tile outputs for small seeded batches.  They pin the oracle (and,
                       through the GPU tests, the HIP path) against silent drift; they are NOT reference outputs -- the
                       tiler itself cannot be built here.
@@ -123,6 +125,12 @@ def oracle_tiles():
     json.dump(res, open(os.path.join(OUT, "oracle_tile_digests.json"), "w"), indent=1, sort_keys=True)
 
 
+def ref_build_results(R):
+    """what tests/test_oracle_reference_kats.py checks the oracle against where oracle/_ref is not built"""
+    import test_oracle_reference_kats as K
+    np.savez_compressed(os.path.join(OUT, "ref_build_results.npz"), **K.reference_build_results(R))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     R = O.ref()
@@ -131,6 +139,7 @@ def main():
     ref_morton_index(R)
     ref_random_grid(R)
     ref_algorithm(R)
+    ref_build_results(R)
     oracle_tiles()
     print("wrote", sorted(os.listdir(OUT)))
 

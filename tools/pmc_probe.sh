@@ -1,12 +1,13 @@
 # Collects hardware counters per kernel for one cold step of the default bench (separate --pmc passes, kernel trace off)
 # and prints per-kernel sums: tools/pmc_probe.sh "CTR_A CTR_B" "CTR_C ..."   (run on the GPU box through gpurun)
+ROOT=$(cd "$(dirname "$0")/.." && pwd)  # the repository
 cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_probe
 rm -rf $OUT; mkdir -p $OUT
 i=0
 for set in "$@"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --pmc $set --output-format csv -d $OUT/p$i -o p -- python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --cpu-sample 0 ${PMC_BENCH_ARGS} > /dev/null 2>&1
+  timeout 600 rocprofv3 --pmc $set --output-format csv -d $OUT/p$i -o p -- python3 $ROOT/bench.py --full --steps 1 --warmup 0 --cpu-sample 0 ${PMC_BENCH_ARGS} > /dev/null 2>&1
 done
 python3 - <<'PY'
 import csv, glob, collections, os

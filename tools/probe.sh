@@ -40,18 +40,18 @@ list)
   while IFS='|' read -r tag envs args; do
     [ -z "$tag" ] && continue
     case $tag in sleep*) t=${tag#sleep}; sleep ${t%%_*} ;; esac   # (a tag "sleep20_..." waits that long first)
-    env $envs timeout 900 python bench.py $args > $O/$tag.json 2> $O/$tag.err
+    env $envs timeout 900 python bench.py --full $args > $O/$tag.json 2> $O/$tag.err
     line $O/$tag.json
   done ;;
 levels)
-  SWZ_DEBUG=1 timeout 900 python bench.py --steps 2 --warmup 1 --cpu-sample 0 --also "" "$@" > $O/levels.json 2> $O/levels.err
+  SWZ_DEBUG=1 timeout 900 python bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --also "" "$@" > $O/levels.json 2> $O/levels.err
   grep -E "block path|sparse path|sweep|rounds|can change|thread 0" $O/levels.err | tail -${TAIL:-24} | cut -c1-420
   line $O/levels.json ;;
 variants)
   for lib in schwarzwald_amd/lib/libswz_gpu.so schwarzwald_amd/lib/libswz_v*.so; do
     [ -f "$lib" ] || continue
     echo "== $lib $VAR_ENV"
-    env $VAR_ENV SWZ_GPU_LIBRARY=$PWD/$lib SWZ_DEBUG=1 timeout 600 python bench.py --steps 2 --warmup 1 --cpu-sample 0 --also "" "$@" 2>&1 >$O/variant.json \
+    env $VAR_ENV SWZ_GPU_LIBRARY=$PWD/$lib SWZ_DEBUG=1 timeout 600 python bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --also "" "$@" 2>&1 >$O/variant.json \
       | grep -E "block path|thread 0|property level" | tail -${TAIL:-4} | cut -c1-60,150-500
     line $O/variant.json
   done ;;
@@ -66,8 +66,8 @@ multibatch)
     done
   done ;;
 stats)
-  ( cd /tmp && export TMPDIR=/tmp && rm -rf $GRAFT_REPO_ROOT/$O/stats && timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/stats -o p -- \
-      python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --cpu-sample 0 --also "" "$@" > $GRAFT_REPO_ROOT/$O/stats.json 2> $GRAFT_REPO_ROOT/$O/stats.err )
+  ( R=$PWD && cd /tmp && export TMPDIR=/tmp && rm -rf $R/$O/stats && timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/stats -o p -- \
+      python3 $R/bench.py --full --steps 1 --warmup 0 --cpu-sample 0 --also "" "$@" > $R/$O/stats.json 2> $R/$O/stats.err )
   f=$(find $O/stats -name '*kernel_stats.csv' | head -1)
   [ -n "$f" ] && cp "$f" $O/stats_kernel_stats.csv && head -${TOP:-30} "$f" | awk -F'","' '{print substr($1,2,90), $2, $3, $4}'
   rm -rf $O/stats
