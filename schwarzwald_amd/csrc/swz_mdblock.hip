@@ -45,6 +45,12 @@ namespace swz {
 constexpr int SB_THREADS = 256;
 constexpr int SB_K = 4;               // undecided earlier neighbours recorded per point (0.73 expected at level 2 of the 1 B run); more: the point searches again
 constexpr int SB_PEND = 63;            // in-band pairs a wavefront puts aside per block (more: compared on the spot)
+// The search stores its count of a point's neighbours saturated at SB_CNT_SAT in one byte of a packed counter word; the
+// pending pairs -- up to SB_PEND, all of one point in the worst case -- are added to that byte afterwards.  The sum must stay
+// a byte, or the add carries into the count of the next point.  (Only cnt against SB_K and min(cnt, SB_K) are ever read.)
+constexpr uint32_t SB_CNT_SAT = 128;
+static_assert(SB_CNT_SAT + SB_PEND <= 255u, "a point's neighbour count must not carry into the next point's byte");
+static_assert(SB_CNT_SAT > (uint32_t)SB_K, "a saturated count must still read as 'more than the list holds'");
 constexpr int SB_PMAX = 12;           // staged points per thread: a block and its halo hold at most SB_THREADS * SB_PMAX points
 constexpr uint32_t SB_NC = 64;        // ticket counters (one per 128-byte line): nodes sn with sn % SB_NC == k draw from counter k
 constexpr uint32_t SB_CTR_STRIDE = 32;
@@ -591,7 +597,7 @@ __global__ __launch_bounds__(SB_THREADS, SB_MINW) void sb_block_kernel(SbArgs a)
       const bool have = j < jb;
       uint32_t cnt = 0;
       sb_search<WIDE>(a, l, k, j, have, l.nbr + (size_t)(have ? j : 0u) * SB_K, pend, &cnt, &my_steps);
-      if (have) cnt1[j] = (uint8_t)min(cnt, 200u);
+      if (have) cnt1[j] = (uint8_t)min(cnt, SB_CNT_SAT);
     }
     {
       const uint32_t np = min(pend[SB_PEND], (uint32_t)SB_PEND);
@@ -967,7 +973,8 @@ static int sb_run(swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp, con
     a.own_cap = own_cap;
     a.halo_cap = halo_cap;
 
-    ProfScope ps(c, "sample_min_distance", (uint64_t)in.points * 33ull, 1);
+    // (the level's points are charged once: a repeated launch reads them again, but the algorithm needs them once)
+    ProfScope ps(c, "sample_min_distance", attempt == 0 ? (uint64_t)in.points * 33ull : 0ull, 1);
     SWZ_HIP(c, memset_large(t.gtab, 0, (size_t)entries * sizeof(uint2), c->stream));
     SWZ_HIP(c, hipMemsetAsync(a.st2, 0, ((size_t)in.m / 16 + 2) * sizeof(uint32_t), c->stream));
     SWZ_HIP(c, hipMemsetAsync(a.ctr, 0, (size_t)(SB_NC * SB_CTR_STRIDE + SBW_COUNT) * sizeof(uint32_t), c->stream));
@@ -1325,7 +1332,8 @@ static int sb_incremental(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as
   SWZ_TRY(c->get("sbi_taken", (size_t)total, &staken));
   uint32_t hist[12] = {0};
   {
-    ProfScope ps(c, "sample_min_distance", (uint64_t)as.m * 17ull + (uint64_t)total * 33ull, 1);
+    // (the selected points' 33 B each are charged by sb_run below)
+    ProfScope ps(c, "sample_min_distance", (uint64_t)as.m * 17ull, 1);
     SWZ_TRY(fused_scan_apply(c, SbiSelF{a.sel}, SbiPackG{as.akey, as.aidx, lb.nid, snode_of, a.all_sampled, skey, saidx, ssn, sidx}, as.m,
                              d_partial));
     SWZ_HIP(c, hipMemsetAsync(staken, 0, (size_t)total, c->stream));
