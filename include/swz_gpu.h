@@ -63,28 +63,43 @@ int swz_abi_version(void);
  * device's default stream (a real stream: PyTorch's default); SWZ_OWN_STREAM restores the own stream. */
 #define SWZ_OWN_STREAM ((void*)(intptr_t)-1)
 int swz_set_stream(swz_ctx* ctx, void* hip_stream);
-/* Debug / tuning switches ("SWZ_DEBUG", "SWZ_MD_*", ...).  A context reads the SWZ_* variables
- * of the environment once, when it is created; afterwards they change only through this call (value NULL removes the
- * switch).  None of them changes a result; production code never needs them.  Two can make a call FAIL instead:
- * SWZ_MD_PERSISTENT=1 (an experiment that needs all its workgroups resident at once; SWZ_ERR_INTERNAL when the device
- * is shared) and the limits SWZ_MD_TIME_LIMIT / SWZ_MD_ROUND_LIMIT (a level that exceeds them is abandoned with an
- * error).  A NEGATIVE SWZ_MD_KEYS_BAND is the one exception to "no result changes": it narrows the band in which
- * MIN_DISTANCE repeats a compare on the exact positions below its proven width and exists so that a test can show that
- * the band is needed (tests/test_min_distance_keys.py).
- * SWZ_MD_ROUNDS_BLOCK=0: property mode's first kill pass by per-cell records / the mask loop of round 5 instead of by blocks
- * of cells (same set); SWZ_MD_ROUNDS_BLOCK_MIN_POP (0): the points per cell of a level from which the blocks are used.
- * Round 6, the sparse MIN_DISTANCE levels by blocks of cells (swz_mdblock.hip): SWZ_SP_BLOCK=0 keeps them on the
- * thread-per-point path; SWZ_SP_BLOCK_WIDE=1, _CL, _OWN, _HALO, _PER_CU, _MIN force the point format, the cell level, the
- * LDS capacities, the workgroups per CU, the points a block should hold -- results unchanged (a block that does not fit
- * stops the launch: it is repeated with larger capacities or finer cells, with forced capacities the level falls back;
- * SWZ_SP_BLOCK_CAP_SCALE scales the estimated capacities so that a test can make that happen);
- * SWZ_SP_INCREMENTAL (multi-batch tilers: a batch merged with node files samples only what its points can change) = 0
- * never, = a share in (0, 1]: whenever the files are that much of a level (default: half of it, and files of
- * max_points/2 per node on average), SWZ_SP_INCREMENTAL_MAX (0.35): the largest share of a level that is still
- * sampled as a subset, SWZ_SP_INCREMENTAL_SPREAD: how far from Poisson the subset's blocks are assumed to be -- results
- * unchanged; SWZ_SP_BLOCK_TIMEOUT_MS (default 10 000) bounds how long a wavefront waits for an earlier
- * block: when it expires the call returns SWZ_ERR_INTERNAL, nothing is restarted; SWZ_SP_BLOCK_DBG switches parts of the
- * search off for timing experiments and DOES change the result -- never set it outside a timing experiment (tools/probe.sh variants). */
+/* Debug / tuning switches.  A context reads the SWZ_* variables of the environment once, when it is
+ * created; afterwards they change only through this call (value NULL removes the switch).  Every name is accepted; one the
+ * library does not read has no effect.  Production code needs none of them.  The library reads these:
+ * - Diagnostics: SWZ_DEBUG (per-level lines on stderr), SWZ_TRACE (synchronise and report after every stage),
+ *   SWZ_SYNC_ENTRY (synchronise the device when swz_tile_device starts), SWZ_MD_STATS (count the key sweep's activations by
+ *   kind), SWZ_POISON=<byte> and SWZ_POISON_ONLY=<part of a buffer name> (fill new workspace memory),
+ *   SWZ_BIN_WRITER_THREADS (host threads that write node files).
+ * - Switches that only force a path, a schedule or a capacity -- the samplers' results stay what they are:
+ *   sort: SWZ_SORT_ONESWEEP=0, SWZ_SORT_HYBRID_MIN_N, SWZ_SORT_HYBRID_TOP, SWZ_SORT_FIX_SHORT, SWZ_SORT_FIX_LONG;
+ *   GRID_CENTER / JITTERED: SWZ_GRID_KEYS=0, SWZ_GRID_KEYS_SLACK >= 0 (a large one sends every run of more than one point
+ *   through the exact pass), SWZ_GRID_TABLE_DEPTH, SWZ_JITTER_TABLE=0, SWZ_LEVEL_NODES_SCAN;
+ *   MIN_DISTANCE, the path of a level: SWZ_MD_SPARSE_LIMIT, SWZ_MD_KEYS=0, SWZ_MD_KEYS_MIN_CELLS, SWZ_MD_KEYS_BAND >= 0 (a
+ *   wider band sends more pairs to the compare on the exact positions), SWZ_SP_FILTER_EPS (1e30: every compare within reach
+ *   exact), SWZ_GROUP_JOINT_ROOT=0;
+ *   the frontier sweeps: SWZ_MD_PATIENT, SWZ_MD_LAZY, SWZ_MD_LAZY_FRAC, SWZ_MD_BIG, SWZ_MD_GROUPS, SWZ_MD_GRID,
+ *   SWZ_MD_NBR_GRID, SWZ_MD_BATCH, SWZ_MD_COARSEN, SWZ_MD_COARSEN_MIN, SWZ_MD_FF_MIN, SWZ_MD_NO_DEAD_TEST=1 (blocker scans
+ *   without the dead-point test), SWZ_MD_CHAIN, SWZ_MD_KEYS_RG, SWZ_MD_DENSE_MIN;
+ *   the blocks of cells (swz_mdblock.hip): SWZ_SP_BLOCK=0 (the thread-per-point path instead), SWZ_SP_BLOCK_WIDE=1,
+ *   SWZ_SP_BLOCK_CL, SWZ_SP_BLOCK_OWN, SWZ_SP_BLOCK_HALO, SWZ_SP_BLOCK_PER_CU, SWZ_SP_BLOCK_MIN (point format, cell level,
+ *   LDS capacities, workgroups per CU, points a block should hold), SWZ_SP_BLOCK_CAP_SCALE (scales the estimated capacities:
+ *   a block that does not fit stops the launch, which is repeated with larger capacities or finer cells; with forced
+ *   capacities the level falls back), SWZ_SP_INCREMENTAL (multi-batch tilers: a batch merged with node files samples only
+ *   what its points can change; = 0 never, = a share in (0, 1]: whenever the files are that much of a level; default: half
+ *   of it, and files of max_points/2 per node on average), SWZ_SP_INCREMENTAL_MAX (0.35: the largest share of a level that
+ *   is still sampled as a subset);
+ *   property mode (SWZ_FLAG_MIN_DISTANCE_PROPERTY): SWZ_MD_ROUNDS=0, SWZ_MD_ROUNDS_LIST=0, SWZ_MD_ROUNDS_CELL_LISTS=0,
+ *   SWZ_MD_ROUNDS_BLOCK=0, SWZ_MD_ROUNDS_BLOCK_MIN_POP, SWZ_MD_ROUNDS_WLIST_MIN_POP -- the set keeps the mode's properties
+ *   on every path; which set it is may depend on the path a level takes;
+ *   the tiler's memory: SWZ_TILER_SPILL=off|host, SWZ_TILER_DEVICE_BUDGET_MB.
+ * - Switches that can make a call FAIL: SWZ_MD_TIME_LIMIT and SWZ_MD_ROUND_LIMIT (a MIN_DISTANCE level that exceeds them is
+ *   abandoned with an error), SWZ_SP_BLOCK_TIMEOUT_MS (default 10 000: how long a wavefront waits for an earlier block;
+ *   when it expires the call returns SWZ_ERR_INTERNAL, nothing is restarted), SWZ_FAIL_ALLOC=<buffer name, or prefix*>
+ *   (every first attempt to allocate that buffer reports out of memory: tests of the paths that recover).
+ * - Values that change a RESULT on purpose, so that a test can show that a bound is needed: a negative SWZ_MD_KEYS_BAND
+ *   (narrows the band in which MIN_DISTANCE repeats a compare on the exact positions below its proven width,
+ *   tests/test_min_distance_keys.py) and a negative SWZ_GRID_KEYS_SLACK (the same for the grid samplers on keys,
+ *   tests/test_grid_keys.py). */
 int swz_set_option(swz_ctx* ctx, const char* name, const char* value);
 /* Frees all device workspace held by the context (it regrows on demand). */
 int swz_release_workspace(swz_ctx* ctx);

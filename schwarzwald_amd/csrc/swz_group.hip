@@ -148,8 +148,7 @@ void group_barrier(void* p) { static_cast<swz_group*>(p)->barrier.wait(); }
 // hangs on the bounds, the spacing and the options only.
 bool joint_root_possible(const swz_ctx* c, const swz_tile_params& p, const double bmin[3], const double bmax[3]) {
   if (p.sampler != SWZ_MIN_DISTANCE) return false;  // (with SWZ_FLAG_MIN_DISTANCE_PROPERTY too: the root is always sampled exactly)
-  if (const char* e = c->opt("SWZ_GROUP_JOINT_ROOT"))
-    if (atoi(e) == 0) return false;
+  if (!c->opt_on("SWZ_GROUP_JOINT_ROOT", true)) return false;
   const swz::LevelPlan plan = swz::make_plan(-1, p.sampler, p.max_points_per_node, p.spacing_at_root, p.max_depth, bmin, bmax, true, true);
   static const double dummy_xyz = 0.0;
   static const uint32_t dummy_perm = 0;

@@ -102,6 +102,19 @@ struct swz_ctx {
     const auto it = options.find(name);
     return it == options.end() ? nullptr : it->second.c_str();
   }
+  // typed reads: `def` when the switch is absent, else its value as atoll / atof / atoi(v) != 0 read it
+  long opt_int(const char* name, long def) const {
+    const char* v = opt(name);
+    return v ? (long)atoll(v) : def;
+  }
+  double opt_num(const char* name, double def) const {
+    const char* v = opt(name);
+    return v ? atof(v) : def;
+  }
+  bool opt_on(const char* name, bool def) const {
+    const char* v = opt(name);
+    return v ? atoi(v) != 0 : def;
+  }
 };
 
 #define SWZ_HIP(ctx, expr)                                                \

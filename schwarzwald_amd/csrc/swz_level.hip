@@ -1163,8 +1163,7 @@ LevelPlan make_plan(int level, int sampler, uint64_t max_points, float spacing_a
 bool grid_level_uses_keys(const swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp, GridKeys* out) {
   if (plan.sampler != SWZ_GRID_CENTER && plan.sampler != SWZ_JITTERED) return false;
   if (!sp.xyz || !sp.perm) return false;
-  if (const char* e = c->opt("SWZ_GRID_KEYS"))
-    if (atoi(e) == 0) return false;
+  if (!c->opt_on("SWZ_GRID_KEYS", true)) return false;
   const double ext[3] = {plan.root.maxx - plan.root.minx, plan.root.maxy - plan.root.miny, plan.root.maxz - plan.root.minz};
   if (!(ext[0] > 0.0) || !(ext[1] > 0.0) || !(ext[2] > 0.0)) return false;
   if (plan.sampler == SWZ_JITTERED && !(ext[0] == ext[1] && ext[1] == ext[2])) return false;
@@ -1176,7 +1175,7 @@ bool grid_level_uses_keys(const swz_ctx* c, const LevelPlan& plan, const SortedP
   // rounding at the magnitude of the coordinates: 128 ulp of the largest one, in key cells of the narrowest axis; plus
   // the rounding of the encoder's (p - min) * scale.
   double slack = 1e-6 + 128.0 * 0x1.0p-52 * max_abs / (wmin / 2097152.0);
-  if (const char* e = c->opt("SWZ_GRID_KEYS_SLACK")) slack += atof(e);
+  slack += c->opt_num("SWZ_GRID_KEYS_SLACK", 0.0);
   if (!(slack < 0.25) && !c->opt("SWZ_GRID_KEYS_SLACK")) return false;  // bounds far from the origin relative to their size
   if (out) {
     for (int a = 0; a < 3; ++a) {
@@ -1290,10 +1289,9 @@ int level_step(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const Sor
     {  // all but the last three steps of the bounds chain from a table (worth it from a few thousand points per entry on)
       const int chain = plan.sampler == SWZ_GRID_CENTER ? plan.cand + 1 : plan.level + 1;
       int td = std::min(chain - 3, GRID_TABLE_MAX_DEPTH);
-      if (const char* e = c->opt("SWZ_GRID_TABLE_DEPTH")) td = std::min(std::min(atoi(e), chain), GRID_TABLE_MAX_DEPTH);
+      td = std::min(std::min((int)c->opt_int("SWZ_GRID_TABLE_DEPTH", td), chain), GRID_TABLE_MAX_DEPTH);
       while (td > 0 && ((uint64_t)1 << (3 * td)) * 64u > (uint64_t)m) --td;
-      const char* jt = c->opt("SWZ_JITTER_TABLE");
-      if (plan.sampler == SWZ_JITTERED && chain <= GRID_TABLE_MAX_DEPTH && !(jt && atoi(jt) == 0)) {
+      if (plan.sampler == SWZ_JITTERED && chain <= GRID_TABLE_MAX_DEPTH && c->opt_on("SWZ_JITTER_TABLE", true)) {
         // one entry per node prefix: the node's box and everything the sampler derives from it
         JitNode* d_nodes = nullptr;
         const uint32_t entries = 1u << (3 * chain);

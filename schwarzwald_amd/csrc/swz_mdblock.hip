@@ -87,7 +87,6 @@ struct SbArgs {
   uint32_t* ctr;           // SB_NC ticket counters (stride SB_CTR_STRIDE words), then SBW_* words
   uint32_t own_cap, halo_cap;
   uint64_t timeout_ticks;  // wall_clock64 ticks (100 MHz) a wavefront may wait without any progress
-  uint32_t dbg;            // SWZ_SP_BLOCK_DBG: timing experiments that BREAK the result (1: no candidate loop, 2: no reach test, 4: no order test, 8: undecided halo points count as rejected)
 };
 
 __device__ __forceinline__ uint32_t sb_expand3(uint32_t v) {  // 10 bits -> every third bit
@@ -276,8 +275,10 @@ __device__ __forceinline__ SbOwn sb_own_point(const SbArgs& a, const SbLds& l, c
     const uint32_t row = l.occ[(iz + (uint32_t)(i / 3) - 1u) * 10u + (iy + (uint32_t)(i % 3) - 1u)];
     mask |= ((row >> (ix - 1u)) & 7u) << (3 * i);
   }
-  if (!(a.dbg & 4u)) mask &= sb_earlier_mask(ix, iy, iz);
-  if (!WIDE && !(a.dbg & 2u)) {
+  mask &= sb_earlier_mask(ix, iy, iz);
+  // (mask holds at least the own cell here: the test never fails, but without it the narrow build spills 48 instead of 32
+  // bytes per lane -- the register allocator lays the kernel out around the branch)
+  if (!WIDE && mask) {
     const uint32_t cs = 1u << a.cell_bits;
     const int ox = (int)(p.ux & (cs - 1u)), oy = (int)(p.uy & (cs - 1u)), oz = (int)(p.uz & (cs - 1u));
     const uint32_t gx[3] = {(uint32_t)__mul24(ox, ox), 0u, (uint32_t)__mul24((int)cs - ox, (int)cs - ox)};
@@ -295,7 +296,6 @@ __device__ __forceinline__ SbOwn sb_own_point(const SbArgs& a, const SbLds& l, c
     }
     mask &= reach;
   }
-  if (a.dbg & 1u) mask = 0;
   p.mask = mask;
   p.corner = (ix - 1u) + 10u * (iy - 1u) + 100u * (iz - 1u);
   return p;
@@ -562,7 +562,6 @@ __global__ __launch_bounds__(SB_THREADS, SB_MINW) void sb_block_kernel(SbArgs a)
         l.pts[j] = sb_make_point<WIDE>(a, k, x, y, z, &cell);
         rc[j] = (uint16_t)cell;
         l.st[j] = (uint8_t)((sw[p] >> ((gi[p] & 15u) * 2u)) & 3u);
-        if ((a.dbg & 8u) && j >= n_own && l.st[j] == SB_U) l.st[j] = SB_R;  // (timing experiment: nobody waits for another block)
       }
     }
     __syncthreads();
@@ -868,8 +867,7 @@ static int sb_run(swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp, con
   const bool dbg = c->opt("SWZ_DEBUG") != nullptr;
   // cells: as fine as the spacing allows while a block of 8^3 of them still holds a workgroup's worth of points
   int cl = plan.cell_levels_geo;
-  double min_block = 128.0;
-  if (const char* e = c->opt("SWZ_SP_BLOCK_MIN")) min_block = atof(e);
+  const double min_block = c->opt_num("SWZ_SP_BLOCK_MIN", 128.0);
   auto per_block = [&](int l) { return (double)in.points / (double)std::max(1u, in.occupied[std::max(0, l - 3)]); };
   while (cl > 3 && per_block(cl) < min_block) --cl;
   bool cl_forced = false, caps_forced = false;
@@ -903,9 +901,10 @@ static int sb_run(swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp, con
   uint32_t own_cap = 0, halo_cap = 0;
   estimate(cl, &own_cap, &halo_cap);
   fill_free_lds(&own_cap, &halo_cap);
-  if (const char* e = c->opt("SWZ_SP_BLOCK_CAP_SCALE")) {  // tests: an estimate that is too small, so that launches are repeated
-    own_cap = std::max(32u, (uint32_t)(own_cap * atof(e)) / 32u * 32u);
-    halo_cap = std::max(32u, (uint32_t)(halo_cap * atof(e)) / 32u * 32u);
+  const double cap_scale = c->opt_num("SWZ_SP_BLOCK_CAP_SCALE", 1.0);  // tests: an estimate that is too small, so that launches are repeated
+  if (cap_scale != 1.0) {
+    own_cap = std::max(32u, (uint32_t)(own_cap * cap_scale) / 32u * 32u);
+    halo_cap = std::max(32u, (uint32_t)(halo_cap * cap_scale) / 32u * 32u);
   }
   if (const char* e = c->opt("SWZ_SP_BLOCK_OWN")) {
     own_cap = (uint32_t)std::max(64, atoi(e)) / 16u * 16u;
@@ -934,20 +933,17 @@ static int sb_run(swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp, con
   a.xyz = sp.xyz;
   a.f_lo = km.f_lo;
   a.f_hi = km.f_hi;
-  if (const char* e = c->opt("SWZ_SP_FILTER_EPS"))  // tests: 1e30 sends every compare within reach to the exact path
-    if (atof(e) >= 0.5) {
-      a.f_lo = 0.f;
-      a.f_hi = INFINITY;
-    }
+  if (c->opt_num("SWZ_SP_FILTER_EPS", 0.0) >= 0.5) {  // tests: 1e30 sends every compare within reach to the exact path
+    a.f_lo = 0.f;
+    a.f_hi = INFINITY;
+  }
   a.i_lo = a.f_lo >= 4294967040.f ? 0xFFFFFFFFu : (uint32_t)std::floor(a.f_lo);
   a.i_hi = a.f_hi >= 4294967040.f ? 0xFFFFFFFFu : (uint32_t)std::ceil(a.f_hi);
   a.sq_spacing = plan.sq_spacing;
   a.ns = sample_nodes;
   SWZ_TRY(c->get("sb_counters", (size_t)(SB_NC * SB_CTR_STRIDE + SBW_COUNT), &a.ctr));
-  double timeout_s = 10.0;
-  if (const char* e = c->opt("SWZ_SP_BLOCK_TIMEOUT_MS")) timeout_s = atof(e) * 1e-3;
+  const double timeout_s = c->opt_num("SWZ_SP_BLOCK_TIMEOUT_MS", 10000.0) * 1e-3;
   a.timeout_ticks = (uint64_t)(timeout_s * 1e8);
-  if (const char* e = c->opt("SWZ_SP_BLOCK_DBG")) a.dbg = (uint32_t)atoi(e);
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
 
@@ -981,12 +977,11 @@ static int sb_run(swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp, con
     hipLaunchKernelGGL(sb_table_kernel, dim3(div_up(in.m, 256)), dim3(256), 0, c->stream, t);
     SWZ_LAUNCH_CHECK(c);
     // (every time: the attribute belongs to the function on the CURRENT device, and a process may drive several)
-    bool wide = a.cell_bits > 12u;  // a region of ten cells must fit sixteen bits
-    if (const char* e = c->opt("SWZ_SP_BLOCK_WIDE")) wide = wide || atoi(e) != 0;
+    const bool wide = a.cell_bits > 12u || c->opt_on("SWZ_SP_BLOCK_WIDE", false);  // a region of ten cells must fit sixteen bits
     SWZ_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(wide ? sb_block_kernel<true> : sb_block_kernel<false>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(8, (160u * 1024u) / lds));
-    if (const char* e = c->opt("SWZ_SP_BLOCK_PER_CU")) per_cu = (uint32_t)std::max(1, atoi(e));
+    per_cu = (uint32_t)std::max(1L, c->opt_int("SWZ_SP_BLOCK_PER_CU", per_cu));
     const uint64_t blocks_total = (uint64_t)sample_nodes << (3 * (cl - 3));
     const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)cus * per_cu, std::max<uint64_t>(1, blocks_total));
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1276,8 +1271,8 @@ static int sb_incremental(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as
   a.cell_mask = (uint32_t)((1ull << (3 * cl)) - 1ull);
   a.cl = (uint32_t)cl;
   a.taken = lb.taken;
-  double worth = 0.35;  // of the level's points: above it the subset's own passes and its clumpier blocks cost what they save
-  if (const char* e = c->opt("SWZ_SP_INCREMENTAL_MAX")) worth = atof(e);
+  // of the level's points: above it the subset's own passes and its clumpier blocks cost what they save
+  const double worth = c->opt_num("SWZ_SP_INCREMENTAL_MAX", 0.35);
   if ((double)as.new_m > worth * (double)sample_points) return SWZ_OK;  // (the new points alone are more than that)
   uint8_t* indep = nullptr;
   SWZ_TRY(c->get("sbi_indep", (size_t)num_nodes, &indep));
@@ -1356,7 +1351,6 @@ static int sb_incremental(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as
   // (what a new point brings into a block it brings at once: itself and the old points around it -- ten of them when the batch
   // is thin on top of full files, none when it is a tile of its own beside the files of its neighbours)
   in.spread = 1.0 + 9.0 * std::min(1.0, std::max(0.0, ((double)total - (double)as.new_m) / (double)total));
-  if (const char* e = c->opt("SWZ_SP_INCREMENTAL_SPREAD")) in.spread = std::max(1.0, atof(e));
   in.what = " (what the new points can change)";
   bool ok = false;
   SWZ_TRY(sb_run(c, plan, sp, lb, snode_of, all_sampled, sample_nodes, km, in, &ok));
@@ -1372,8 +1366,7 @@ int min_distance_block_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet&
                              const uint32_t* snode_of, bool all_sampled, uint32_t num_nodes, uint32_t sample_nodes,
                              uint32_t sample_points, const uint32_t occupied[12], const KeyMetric& km, bool* done) {
   *done = false;
-  if (const char* e = c->opt("SWZ_SP_BLOCK"))
-    if (atoi(e) == 0) return SWZ_OK;
+  if (!c->opt_on("SWZ_SP_BLOCK", true)) return SWZ_OK;
   if (!km.ok || !sp.xyz || !sp.perm || sp.ghosts) return SWZ_OK;
   if (plan.cell_levels_geo < 3) return SWZ_OK;
   // a batch on top of the files of earlier ones: when those are most of the level, only what the batch can change

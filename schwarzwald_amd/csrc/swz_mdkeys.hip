@@ -59,14 +59,13 @@ enum : uint8_t { QS_OPEN = 0, QS_TAKEN = 1, QS_DEAD = 2 };
 KeyMetric key_metric(const swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp) {
   KeyMetric k;
   if (!sp.xyz || !sp.perm) return k;
-  if (const char* e = c->opt("SWZ_MD_KEYS"))
-    if (atoi(e) == 0) return k;
+  if (!c->opt_on("SWZ_MD_KEYS", true)) return k;
   const double ex = plan.root.maxx - plan.root.minx, ey = plan.root.maxy - plan.root.miny, ez = plan.root.maxz - plan.root.minz;
   if (!(ex > 0.0) || ex != ey || ey != ez) return k;  // one key cell must be a cube (the Tiler's bounds are)
   const double cell = ex / 2097152.0;
   const double T = std::sqrt(plan.sq_spacing) / cell;
-  double tmin = 64.0;  // below that most near pairs fall into the band (levels >= 7 at spacing = diagonal / 250)
-  if (const char* e = c->opt("SWZ_MD_KEYS_MIN_CELLS")) tmin = atof(e);
+  // below that most near pairs fall into the band (levels >= 7 at spacing = diagonal / 250)
+  const double tmin = c->opt_num("SWZ_MD_KEYS_MIN_CELLS", 64.0);
   if (!(T >= tmin) || !(T < 4.0e6)) return k;
   // A coordinate u = (p - min) * scale (calculate_morton_index, OctreeAlgorithms.h:64-87) has key coordinate
   // i = min(trunc(fl(u)), 2^21 - 1): u is within [i, i + 1] up to the rounding of fl (1e-9 cells).  Per axis
@@ -74,7 +73,7 @@ KeyMetric key_metric(const swz_ctx* c, const LevelPlan& plan, const SortedPoints
   // in float (exact differences, three roundings: relative 3 * 2^-24, i.e. T * 2^-23 cells of distance near the
   // spacing).  Band: 1.75 + T * 2^-20 cells -- the reference's own rounding (1e-16 relative) disappears in the slack.
   double band = 1.75 + T * 0x1.0p-20;
-  if (const char* e = c->opt("SWZ_MD_KEYS_BAND")) band += atof(e);  // tests: a wide band sends many / all pairs to the exact path
+  band += c->opt_num("SWZ_MD_KEYS_BAND", 0.0);  // tests: a wide band sends many / all pairs to the exact path
   const double lo = T - band, hi = T + band;
   float f_lo = 0.f;
   if (lo > 0.0) {
@@ -1303,11 +1302,11 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
   a.f_hi = km.f_hi;
   a.sq_spacing = plan.sq_spacing;
   a.all_sampled = sample_nodes == nnodes ? 1u : 0u;
-  a.no_dead_test = (c->opt("SWZ_MD_ABLATE") && (atoi(c->opt("SWZ_MD_ABLATE")) & 8)) ? 1u : 0u;
+  a.no_dead_test = c->opt_on("SWZ_MD_NO_DEAD_TEST", false) ? 1u : 0u;
   a.stats = c->opt("SWZ_MD_STATS") ? 1u : 0u;
   // (measured at 1 B points: 2 cells per chain root / level 0 / level 1 78 / 69 / 96 -> 73 / 62 / 91 ms; longer chains make
   // launches as long as their longest chain and lose again)
-  a.chain = c->opt("SWZ_MD_CHAIN") ? std::min<uint32_t>(MQ_CHAIN, (uint32_t)std::max(1, atoi(c->opt("SWZ_MD_CHAIN")))) : 2u;
+  a.chain = std::min<uint32_t>(MQ_CHAIN, (uint32_t)std::max(1L, c->opt_int("SWZ_MD_CHAIN", 2)));
   if (a.cell_bits > 21u) return SWZ_OK;
 
   ProfScope ps(c, "sample_min_distance", (uint64_t)sample_points * 33ull, 1);
@@ -1328,7 +1327,7 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
   // accepted points each: 78 ms with records of 3, 84 with records of 7: less to stage, more wavefronts per CU.)
   const double r_cell = std::ldexp(1.0, (int)a.cell_bits) / km.T;
   a.rg = (0.75 * r_cell * r_cell * r_cell <= 12.0) ? 4u : 8u;
-  if (const char* e = c->opt("SWZ_MD_KEYS_RG")) a.rg = atoi(e) >= 8 ? 8u : 4u;
+  a.rg = c->opt_int("SWZ_MD_KEYS_RG", a.rg) >= 8 ? 8u : 4u;
   a.rg2_shift = a.rg == 4u ? 3u : 4u;
 
   SWZ_TRY(c->get(("md_qpos" + sfx).c_str(), (size_t)m, &a.qpos));
@@ -1420,18 +1419,15 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
   }
   // scheduling: the same rules as the sweep on positions (swz_mindist.hip)
   const bool many_small = ncells >= (4u << 20) && (double)sample_points / (double)ncells <= 128.0;
-  a.patient = many_small ? 1u : 0u;
-  if (const char* e = c->opt("SWZ_MD_PATIENT")) a.patient = (uint32_t)atoi(e);
-  bool lazy = true;  // (on keys also for roots of thousands of points per cell: clustered root 99 -> 89 ms)
-  if (const char* e = c->opt("SWZ_MD_LAZY")) lazy = atoi(e) != 0;
-  a.lazy_frac = c->opt("SWZ_MD_LAZY_FRAC") ? (float)atof(c->opt("SWZ_MD_LAZY_FRAC")) : (many_small ? 0.5f : 0.0f);
+  a.patient = (uint32_t)c->opt_int("SWZ_MD_PATIENT", many_small ? 1 : 0);
+  const bool lazy = c->opt_on("SWZ_MD_LAZY", true);  // (on keys also for roots of thousands of points per cell: clustered root 99 -> 89 ms)
+  a.lazy_frac = (float)c->opt_num("SWZ_MD_LAZY_FRAC", many_small ? 0.5 : 0.0);
   // (the build for large cells from a few hundred points per typical cell on: at 113 -- level 1 of the clustered cloud --
   // the small-cell build is still ahead, 48 against 55 ms; at 478 and 710 the large-cell one, 72 / 81 against 100+)
-  bool big_cells = typical_pop > 256.0;
-  if (const char* e = c->opt("SWZ_MD_BIG")) big_cells = atoi(e) != 0;
+  const bool big_cells = c->opt_on("SWZ_MD_BIG", typical_pop > 256.0);
   uint32_t groups = 1;
   if (sample_nodes >= 2 && !big_cells) groups = 2;
-  if (const char* e = c->opt("SWZ_MD_GROUPS")) groups = (uint32_t)std::max(1, std::min(8, atoi(e)));
+  groups = (uint32_t)std::max(1L, std::min(8L, c->opt_int("SWZ_MD_GROUPS", groups)));
   groups = std::min(groups, sample_nodes);
   if (sharded) groups = 1;
   // dense cells: levels of large cells in one node group (mq_dense_reject_kernel)
@@ -1439,8 +1435,8 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
   a.dense_min = 0;
   a.dirty = nullptr;
   if (big_cells && groups == 1 && !sharded) {
-    uint32_t dense_min = 4096;  // (100 M clustered points, root: 2048 -> 99 ms, 4096 -> 95, 1024 -> 101, off -> 106; a sheet alone loses 4 ms of 34 to the extra rounds)
-    if (const char* e = c->opt("SWZ_MD_DENSE_MIN")) dense_min = (uint32_t)std::max(0, atoi(e));
+    // (100 M clustered points, root: 2048 -> 99 ms, 4096 -> 95, 1024 -> 101, off -> 106; a sheet alone loses 4 ms of 34 to the extra rounds)
+    const uint32_t dense_min = (uint32_t)std::max(0L, c->opt_int("SWZ_MD_DENSE_MIN", 4096));
     if (dense_min && m >= dense_min) {
       uint32_t* dl = nullptr;
       uint32_t* dcount = nullptr;
@@ -1466,7 +1462,6 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
   // the round's queue in segments with a counter each (a single counter word takes ~90 atomics per microsecond, and
   // every activation pushes): workgroup b reads segment b % nseg and pushes into it
   a.nseg_shift = 5;
-  if (const char* e = c->opt("SWZ_MD_KEYS_SEGS")) a.nseg_shift = (uint32_t)std::max(0, std::min(8, atoi(e)));
   a.nseg = 1u << a.nseg_shift;
   a.segcap = (uint32_t)std::min<uint64_t>(0x7FFFFFF0ull, 2ull * ncells / a.nseg + 4096ull);
   std::vector<MqArgs> ga(groups, a);
@@ -1534,10 +1529,9 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
   }
   uint32_t batch = 32, batches_done = 0;
   const bool fixed_batch = c->opt("SWZ_MD_BATCH") != nullptr;
-  if (fixed_batch) batch = std::max(1u, (uint32_t)atoi(c->opt("SWZ_MD_BATCH")));
+  if (fixed_batch) batch = std::max(1u, (uint32_t)c->opt_int("SWZ_MD_BATCH", 0));
   const auto wall0 = std::chrono::steady_clock::now();
-  double wall_limit = 900.0;
-  if (const char* e = c->opt("SWZ_MD_TIME_LIMIT")) wall_limit = atof(e);
+  const double wall_limit = c->opt_num("SWZ_MD_TIME_LIMIT", 900.0);
   uint64_t max_rounds = 8ull * m + 1024;
   if (sharded) {
     // A cell at the face of a lower shard looks again every round until that shard's sweep has got there, and a level only
@@ -1548,7 +1542,7 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
     for (int p = 0; p < shard_root->shard; ++p) below += shard_root->views[p].npoints;
     max_rounds += 64ull * below + 65536ull;
   }
-  if (const char* e = c->opt("SWZ_MD_ROUND_LIMIT")) max_rounds = (uint64_t)atoll(e);
+  max_rounds = (uint64_t)c->opt_int("SWZ_MD_ROUND_LIMIT", (long)max_rounds);
   hipEvent_t fork = nullptr;
   if (groups > 1) {
     fork = c->take_event();
@@ -1557,32 +1551,6 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
   }
   // a level is done when a round starts with an empty queue: only running cells wake sleeping ones
   std::vector<uint32_t> gleft(groups, 1);
-  // The grid of a round follows its queue.  The workgroups of a segment draw its entries by ticket, so any multiple of the
-  // segment count works; a round of a small level -- a 10 M batch of the multi-batch tiler holds a few hundred cells per
-  // round -- then starts a few hundred single-wavefront workgroups instead of the ~6000 that are resident at once, all but
-  // a few of which would find their segment empty (an empty launch of the full grid costs ~15 us, and such a level runs
-  // ~2000 rounds).  The host knows the size of the last queue it looked at; the queue of a round grows slowly (a front
-  // moving through the cells), so four times that size, at least eight workgroups per segment, covers the rounds until
-  // the next look -- a grid that turns out small only makes its workgroups draw more tickets.
-  // (Measured, round 5: no gain where it was meant to help -- 100 M points in 10 batches 372 vs 374 ms: a small round's 32 us
-  // are the latency of its activations, not the launch of empty workgroups -- and 3 ms lost at level 1 of the 1 B run.  Off
-  // unless SWZ_MD_ADAPT_GRID=1.)
-  const bool adapt_grid = c->opt("SWZ_MD_ADAPT_GRID") && atoi(c->opt("SWZ_MD_ADAPT_GRID")) != 0 && !c->opt("SWZ_MD_GRID");
-  std::vector<uint32_t> ggrid(groups, sweep_grid);
-  auto grid_for = [&](uint32_t queued) {
-    const uint64_t want = std::max<uint64_t>(8ull * a.nseg, 4ull * queued);
-    return (uint32_t)std::min<uint64_t>(sweep_grid, (want + a.nseg - 1u) / a.nseg * a.nseg);
-  };
-  if (adapt_grid) {  // the first rounds: what mq_nbr_build_kernel has queued
-    std::vector<uint32_t> h((size_t)a.nseg * 32u);
-    for (uint32_t g = 0; g < groups; ++g) {
-      SWZ_HIP(c, hipMemcpyAsync(h.data(), ga[g].qctr, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-      SWZ_HIP(c, hipStreamSynchronize(c->stream));
-      uint64_t queued = 0;
-      for (uint32_t sgm = 0; sgm < a.nseg; ++sgm) queued += std::min(h[(size_t)sgm * 32u], a.segcap);
-      ggrid[g] = grid_for((uint32_t)std::min<uint64_t>(queued, 0xFFFFFFFFull));
-    }
-  }
   uint32_t round = MQ_FIRST_ROUND;
   bool running = true;
   while (running) {
@@ -1591,14 +1559,14 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
         if (sharded) {
           hipLaunchKernelGGL(mq_round_word_kernel, dim3(1), dim3(1), 0, gs[g], a.round_word, round);
           if (big_cells)
-            hipLaunchKernelGGL((mq_sweep_kernel<4, true>), dim3(ggrid[g]), dim3(WAVE), lds_bytes, gs[g], ga[g], round);
+            hipLaunchKernelGGL((mq_sweep_kernel<4, true>), dim3(sweep_grid), dim3(WAVE), lds_bytes, gs[g], ga[g], round);
           else
-            hipLaunchKernelGGL((mq_sweep_kernel<1, true>), dim3(ggrid[g]), dim3(WAVE), lds_bytes, gs[g], ga[g], round);
+            hipLaunchKernelGGL((mq_sweep_kernel<1, true>), dim3(sweep_grid), dim3(WAVE), lds_bytes, gs[g], ga[g], round);
         } else if (big_cells) {
-          hipLaunchKernelGGL((mq_sweep_kernel<4, false>), dim3(ggrid[g]), dim3(WAVE), lds_bytes, gs[g], ga[g], round);
+          hipLaunchKernelGGL((mq_sweep_kernel<4, false>), dim3(sweep_grid), dim3(WAVE), lds_bytes, gs[g], ga[g], round);
           if (ndense) hipLaunchKernelGGL(mq_dense_reject_kernel, dim3(ndense), dim3(256), 0, gs[g], ga[g], round);
         } else {
-          hipLaunchKernelGGL((mq_sweep_kernel<1, false>), dim3(ggrid[g]), dim3(WAVE), lds_bytes, gs[g], ga[g], round);
+          hipLaunchKernelGGL((mq_sweep_kernel<1, false>), dim3(sweep_grid), dim3(WAVE), lds_bytes, gs[g], ga[g], round);
         }
       }
     }
@@ -1612,7 +1580,6 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
     for (uint32_t g = 0; g < groups; ++g) {
       SWZ_HIP(c, hipStreamSynchronize(gs[g]));
       running |= gleft[g] != 0u;
-      if (adapt_grid) ggrid[g] = grid_for(gleft[g]);
     }
     if (peer_err) return c->fail(SWZ_ERR_INTERNAL, "MIN_DISTANCE root of a sharded batch: a lower shard's sweep failed (or a queue overflowed); this shard gives up as well");
     if (std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() > wall_limit) {
@@ -1652,38 +1619,6 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
       snprintf(msg, sizeof(msg), "MIN_DISTANCE sweep on keys ended with %u of %u cells undecided at level %d after %u rounds (queue overflow: %s)",
                open_cells, ncells, plan.level, round - MQ_FIRST_ROUND, err ? "yes" : "no");
       return c->fail(SWZ_ERR_INTERNAL, msg);
-    }
-  }
-  if (const char* dc = c->opt("SWZ_MD_DUMP_CELL")) {  // debugging: the final state of one cell
-    const uint32_t cell = (uint32_t)atoll(dc);
-    if (cell < ncells) {
-      uint2 ci;
-      SWZ_HIP(c, hipMemcpy(&ci, a.cinfo + cell, sizeof(ci), hipMemcpyDeviceToHost));
-      std::vector<uint8_t> st(ci.y - ci.x), tk(ci.y - ci.x);
-      SWZ_HIP(c, hipMemcpy(st.data(), a.state + ci.x, st.size(), hipMemcpyDeviceToHost));
-      SWZ_HIP(c, hipMemcpy(tk.data(), a.taken + ci.x, tk.size(), hipMemcpyDeviceToHost));
-      std::vector<uint4> r(2 * a.rg);
-      SWZ_HIP(c, hipMemcpy(r.data(), a.rec + ((size_t)cell << a.rg2_shift), r.size() * sizeof(uint4), hipMemcpyDeviceToHost));
-      uint32_t nbr[32];
-      SWZ_HIP(c, hipMemcpy(nbr, a.qnbr + (size_t)cell * 32, sizeof(nbr), hipMemcpyDeviceToHost));
-      fprintf(stderr, "[swz] cell %u: [%u, %u)\n  state:", cell, ci.x, ci.y);
-      for (size_t i = 0; i < st.size(); ++i) fprintf(stderr, "%s%u", i % 64 == 0 ? "\n   " : "", (unsigned)st[i]);
-      fprintf(stderr, "\n  taken:");
-      for (size_t i = 0; i < tk.size(); ++i) fprintf(stderr, "%s%u", i % 64 == 0 ? "\n   " : "", (unsigned)tk[i]);
-      for (uint32_t b = 0; b < 2; ++b) {
-        const uint4 h = r[b * a.rg];
-        fprintf(stderr, "\n  record %u: pos %u cnt %u stamp %u end %u:", b, h.x, h.y, h.z, h.w);
-        for (uint32_t j = 0; j + 1 < a.rg; ++j) {
-          float4 en;
-          memcpy(&en, &r[b * a.rg + 1 + j], 16);
-          uint32_t id;
-          memcpy(&id, &en.w, 4);
-          fprintf(stderr, " (%.0f %.0f %.0f #%u)", en.x, en.y, en.z, id);
-        }
-      }
-      fprintf(stderr, "\n  neighbours:");
-      for (int k = 0; k < 27; ++k) fprintf(stderr, " %d", (int)nbr[k]);
-      fprintf(stderr, "\n");
     }
   }
   if (rounds_out) *rounds_out += round - MQ_FIRST_ROUND;

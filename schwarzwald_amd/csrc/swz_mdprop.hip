@@ -578,9 +578,7 @@ int min_distance_property_level(swz_ctx* c, const LevelPlan& plan, const ActiveS
     // declined at the door -- two or more points per occupied cell, the same test as in swz_mdsparse.hip -- is untouched.)
     int scl = plan.cell_levels_geo;
     while (scl > 0 && (double)sample_nodes * std::pow(8.0, scl) > 2147483648.0) --scl;
-    double limit = 2.0;
-    if (const char* e = c->opt("SWZ_MD_SPARSE_LIMIT")) limit = atof(e);
-    if ((double)sample_points / (double)std::max(1u, occupied[scl]) < limit) {
+    if ((double)sample_points / (double)std::max(1u, occupied[scl]) < c->opt_num("SWZ_MD_SPARSE_LIMIT", 2.0)) {
       hipLaunchKernelGGL(pm_clear_taken_kernel, dim3(div_up(m, 256)), dim3(256), 0, c->stream, lb.nid, lb.nmode, m, lb.taken);
       SWZ_LAUNCH_CHECK(c);
     }

@@ -650,17 +650,13 @@ int min_distance_rounds_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet
   *used = false;
   const KeyMetric km = key_metric(c, plan, sp);
   if (!km.ok || sp.ghosts) return SWZ_OK;
-  if (const char* e = c->opt("SWZ_MD_ROUNDS"))
-    if (atoi(e) == 0) return SWZ_OK;
+  if (!c->opt_on("SWZ_MD_ROUNDS", true)) return SWZ_OK;
   const uint32_t m = as.m;
   const uint32_t nsh = plan.node_shift == 63u ? 63u : plan.node_shift;
-  // the finest cells the spacing allows give the most candidates per round; on sparse levels the dense cell grid would
-  // dwarf the points, so cells are doubled while they hold fewer than four points on average
-  int cl = plan.cell_levels_geo;
+  // the finest cells the spacing allows give the most candidates per round (measured: coarser cells mean one candidate
+  // per LARGER cell and round -- 57 rounds instead of 7)
+  const int cl = plan.cell_levels_geo;
   if (cl < 0 || 3u * (uint32_t)cl > nsh || cl > 10) return SWZ_OK;
-  double min_pop = 0.0;  // (measured: coarser cells mean one candidate per LARGER cell and round -- 57 rounds instead of 7)
-  if (const char* e = c->opt("SWZ_MD_ROUNDS_MIN_POP")) min_pop = atof(e);
-  while (cl > 1 && (double)sample_points / ((double)sample_nodes * std::pow(8.0, cl)) < min_pop) --cl;
   PrArgs a{};
   a.cells_per_node = 1ull << (3 * cl);
   a.ncells = (uint64_t)sample_nodes * a.cells_per_node;
@@ -698,23 +694,19 @@ int min_distance_rounds_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet
   uint32_t cur = 0, rounds = 0, alive = sample_points, nlist = 0;
   bool use_list = false;
   const bool dbg = c->opt("SWZ_DEBUG") != nullptr;
-  const bool lists = !(c->opt("SWZ_MD_ROUNDS_LIST") && atoi(c->opt("SWZ_MD_ROUNDS_LIST")) == 0);
+  const bool lists = c->opt_on("SWZ_MD_ROUNDS_LIST", true);
   std::string trace;
   uint32_t* d_total = lb.counters + PRC_ALIVE;
   // the first kill passes (no list yet) read the winners around their cell from per-cell records (pr_kill_wlist_kernel) when
   // the records are affordable (448 bytes per cell: levels of dozens of points per cell)
-  double wl_min_pop = 24.0;
-  if (const char* e = c->opt("SWZ_MD_ROUNDS_WLIST_MIN_POP")) wl_min_pop = atof(e);
-  bool wl = (double)sample_points / (double)a.ncells >= wl_min_pop;
+  bool wl = (double)sample_points / (double)a.ncells >= c->opt_num("SWZ_MD_ROUNDS_WLIST_MIN_POP", 24.0);
   // ... or, round 6, by blocks of cells with the winners around them in LDS (pr_kill_block_kernel): no records, no masks
   PrBlockArgs g{};
   // (on every level: also on grids that are mostly empty -- the thin levels of surface-like data, 0.1-0.7 points per cell -- once an
   // empty block costs two loads and a block of millions of points, the blob of that cloud, is shared by many workgroups:
   // 100 M clustered points 60.5 ms against 70.1 with the mask loop; the first version, whole blocks only, took 100-112)
-  double blk_min_pop = 0.0;
-  if (const char* e = c->opt("SWZ_MD_ROUNDS_BLOCK_MIN_POP")) blk_min_pop = atof(e);
-  bool blk = cl >= 1 && !(c->opt("SWZ_MD_ROUNDS_BLOCK") && atoi(c->opt("SWZ_MD_ROUNDS_BLOCK")) == 0) &&
-             (double)sample_points / (double)a.ncells >= blk_min_pop;
+  bool blk = cl >= 1 && c->opt_on("SWZ_MD_ROUNDS_BLOCK", true) &&
+             (double)sample_points / (double)a.ncells >= c->opt_num("SWZ_MD_ROUNDS_BLOCK_MIN_POP", 0.0);
   if (blk) {
     g.cl = (uint32_t)cl;
     g.bl = (uint32_t)std::min(cl, 3);
@@ -754,7 +746,7 @@ int min_distance_rounds_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet
     g.eoff = eoff;
     kill_grid = g.blocks + m / PR_CHUNK + 1u;  // (as many further chunks as there can be: who finds none leaves at once)
   }
-  const bool cell_lists = !(c->opt("SWZ_MD_ROUNDS_CELL_LISTS") && atoi(c->opt("SWZ_MD_ROUNDS_CELL_LISTS")) == 0);
+  const bool cell_lists = c->opt_on("SWZ_MD_ROUNDS_CELL_LISTS", true);
   bool prev_list = false;   // the round before ran over a list (list[cur ^ 1], nprev entries: still intact)
   uint32_t nprev = 0;
   for (;;) {

@@ -356,10 +356,11 @@ __device__ __forceinline__ void sp_visit_earlier(const SpArgs& a, uint32_t p, F 
 // phase 1: record the earlier neighbours; points without any are accepted right away
 constexpr int SP_NB_THREADS = 256;
 template <bool T4>
-__global__ __launch_bounds__(SP_NB_THREADS, 8) void sp_neighbours_kernel(SpArgs a, uint32_t* __restrict__ overflow, uint32_t xcd) {
+__global__ __launch_bounds__(SP_NB_THREADS, 8) void sp_neighbours_kernel(SpArgs a, uint32_t* __restrict__ overflow) {
   // workgroups go round-robin over the 8 XCDs: XCD x takes the x-th contiguous eighth of the points, so the
-  // neighbourhoods a workgroup reads were mostly fetched into the same L2 by the workgroups just before it
-  const uint32_t blk = xcd ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+  // neighbourhoods a workgroup reads were mostly fetched into the same L2 by the workgroups just before it (the grid is a
+  // multiple of 8)
+  const uint32_t blk = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
   const uint32_t p = blk * SP_NB_THREADS + threadIdx.x;
   if (p >= a.m) return;
   uint32_t cnt = 0;
@@ -384,11 +385,12 @@ __global__ __launch_bounds__(SP_NB_THREADS, 8) void sp_neighbours_kernel(SpArgs 
 // phase 1b: the decisions, in one light pass in Morton order.  A point depends on earlier points only, and workgroups
 // are dispatched in the order of their index, so most of what a point waits for was decided by a workgroup that started
 // before its own: a few polls of the neighbours' states (agent-scope atomics) settle almost every point; what is
-// still open after max_polls goes to the list of the rounds below (so nothing here can wait forever).
+// still open after SP_MAX_POLLS goes to the list of the rounds below (so nothing here can wait forever).
 // (Until round 2 the search kernel polled eight times itself: the polls kept its wavefronts -- with all their
 // registers -- resident for 50 of level 2's 148 ms at 1 B points.  A strictly ordered variant -- stretches of points
 // handed out by an atomic ticket, polling until decided -- was no faster: 1.3 M tickets on one word and a chain of
 // five dependent round trips per stretch.)
+constexpr uint32_t SP_MAX_POLLS = 16;
 __global__ __launch_bounds__(256) void sp_resolve_kernel(SpArgs a, uint32_t max_polls, uint32_t* __restrict__ ulist,
                                                          uint32_t* __restrict__ ucount) {
   const uint64_t pp = (uint64_t)blockIdx.x * 256u + threadIdx.x;
@@ -526,8 +528,7 @@ int min_distance_sparse_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet
   while (cl > 0 && (double)sample_nodes * std::pow(8.0, cl) > 2147483648.0) --cl;
   // points per OCCUPIED cell: clustered data fills a small part of a node's volume
   const double per_cell = (double)sample_points / (double)std::max(1u, occupied[cl]);
-  double limit = 2.0;  // per occupied cell; a uniform level with 1.5 points per cell of volume has 1.93
-  if (const char* e = c->opt("SWZ_MD_SPARSE_LIMIT")) limit = atof(e);
+  const double limit = c->opt_num("SWZ_MD_SPARSE_LIMIT", 2.0);  // per occupied cell; a uniform level with 1.5 points per cell of volume has 1.93
   if (!(per_cell < limit)) return SWZ_OK;
   // the root of a sharded batch with ghosts in front, decided on keys: the sweep looks up two position arrays, this path one
   if (sp.ghosts && plan.level == -1 && !sp.X) return SWZ_OK;
@@ -587,11 +588,10 @@ int min_distance_sparse_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet
     SWZ_TRY(key_point_ids(c, as, sp, &a.ids));
     a.f_lo = km.f_lo;
     a.f_hi = km.f_hi;
-    if (const char* e = c->opt("SWZ_SP_FILTER_EPS"))  // tests: 1e30 sends every compare within reach to the exact path
-      if (atof(e) >= 0.5) {
-        a.f_lo = 0.f;
-        a.f_hi = INFINITY;
-      }
+    if (c->opt_num("SWZ_SP_FILTER_EPS", 0.0) >= 0.5) {  // tests: 1e30 sends every compare within reach to the exact path
+      a.f_lo = 0.f;
+      a.f_hi = INFINITY;
+    }
   } else {
     // Float filter.  A record coordinate is fl(x - corner) with |x - corner| <= E (the node's extent; twice that is
     // assumed): error <= 2^-24 * 2E; the float difference of two of them adds 2^-24 * 2E: |dxf - dx| <= delta =
@@ -600,8 +600,8 @@ int min_distance_sparse_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet
     const double ext = std::max({plan.root.maxx - plan.root.minx, plan.root.maxy - plan.root.miny, plan.root.maxz - plan.root.minz});
     const double E = std::ldexp(ext, -(plan.level + 1));
     const double r = std::ldexp(E, -22) / std::sqrt(plan.sq_spacing);
-    double eps = 4.0 * (2.0 * std::sqrt(3.0) * r * 1.001 + 3.0 * r * r + std::ldexp(1.0, -22));
-    if (const char* e = c->opt("SWZ_SP_FILTER_EPS")) eps = atof(e);  // tests: 1e30 sends every compare to the exact path
+    // (tests: SWZ_SP_FILTER_EPS=1e30 sends every compare to the exact path)
+    const double eps = c->opt_num("SWZ_SP_FILTER_EPS", 4.0 * (2.0 * std::sqrt(3.0) * r * 1.001 + 3.0 * r * r + std::ldexp(1.0, -22)));
     if (!(eps < 0.5)) {  // the filter decides nothing: everything that is not far beyond reach is compared exactly
       a.f_lo = 0.f;
       a.f_hi = INFINITY;
@@ -638,7 +638,6 @@ int min_distance_sparse_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet
     hipLaunchKernelGGL(sp_table_kernel, dim3(nb), dim3(256), 0, c->stream, a);
     SWZ_LAUNCH_CHECK(c);
   }
-  const uint32_t xcd = c->opt("SWZ_MD_XCD") ? ((uint32_t)atoi(c->opt("SWZ_MD_XCD")) >> 1) & 1u : 1u;
   const bool dbg = c->opt("SWZ_DEBUG") != nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
   if (dbg) {
@@ -649,15 +648,12 @@ int min_distance_sparse_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet
   }
   const uint32_t nbn = div_up(m, SP_NB_THREADS);
   if (t4)
-    hipLaunchKernelGGL(sp_neighbours_kernel<true>, dim3(xcd ? div_up(nbn, 8) * 8 : nbn), dim3(SP_NB_THREADS), 0, c->stream, a, cnt + 2, xcd);
+    hipLaunchKernelGGL(sp_neighbours_kernel<true>, dim3(div_up(nbn, 8) * 8), dim3(SP_NB_THREADS), 0, c->stream, a, cnt + 2);
   else
-    hipLaunchKernelGGL(sp_neighbours_kernel<false>, dim3(xcd ? div_up(nbn, 8) * 8 : nbn), dim3(SP_NB_THREADS), 0, c->stream, a, cnt + 2, xcd);
+    hipLaunchKernelGGL(sp_neighbours_kernel<false>, dim3(div_up(nbn, 8) * 8), dim3(SP_NB_THREADS), 0, c->stream, a, cnt + 2);
   SWZ_LAUNCH_CHECK(c);
-  {
-    const uint32_t max_polls = c->opt("SWZ_SP_POLLS") ? (uint32_t)atoi(c->opt("SWZ_SP_POLLS")) : 16u;
-    hipLaunchKernelGGL(sp_resolve_kernel, dim3(nb), dim3(256), 0, c->stream, a, max_polls, u0, cnt);
-    SWZ_LAUNCH_CHECK(c);
-  }
+  hipLaunchKernelGGL(sp_resolve_kernel, dim3(nb), dim3(256), 0, c->stream, a, SP_MAX_POLLS, u0, cnt);
+  SWZ_LAUNCH_CHECK(c);
   if (dbg) (void)hipEventRecord(ev1, c->stream);
   uint32_t* uin = u0;
   uint32_t* uout = u1;
@@ -673,7 +669,7 @@ int min_distance_sparse_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet
     // can be recorded, or long dependency chains.  Both are what the frontier sweep is good at: give up here
     // (every decision taken so far is exact and will simply be taken again).
     if (h[2] > std::max<uint32_t>(1024u, sample_points / 1024u) || rounds >= 512) {
-      if (c->opt("SWZ_DEBUG"))
+      if (dbg)
         fprintf(stderr, "[swz] MIN_DISTANCE level %d sparse path abandoned: %u overflow points, %u rounds, %u undecided\n",
                 plan.level, h[2], rounds, left);
       return SWZ_OK;

@@ -87,14 +87,12 @@ struct MdArgs {
   // blocker-scan culling: a cell is cut into 2^sub_levels slabs per axis; usq[a] = squared slab width
   uint32_t sub_levels;
   uint32_t batch_blockers;   // very sparse level: test all surviving lanes in one pass over the neighbours
-  uint32_t latest_first;     // blocker scans visit the latest adjacent cell first (else the earliest)
-  uint32_t patient;          // 1 = a stalled cell sleeps until the blocking CELL is finished, not just the blocking point
+  uint32_t patient;         // 1 = a stalled cell sleeps until the blocking CELL is finished, not just the blocking point
   float lazy_frac;           // lazy start: sleep until this fraction of the latest earlier neighbour is decided
   uint32_t ff_min;           // cells with more remaining points than this try the fast-forward first
   uint32_t all_sampled;      // every node of the level is sampled (the usual case): cell heads need no look at nid / nmode
   uint32_t group, groups;    // the sampled nodes are dealt to `groups` independent sets of cells (node % groups); this is set `group`
-  uint32_t xcd_chunks;       // 1 = each XCD sweeps a contiguous eighth of the queue
-  uint32_t ablate;           // debugging only (SWZ_MD_ABLATE): 1 = never blocked, 2 = no rejection tests
+  uint32_t no_dead_test;     // tests (SWZ_MD_NO_DEAD_TEST): blocker scans do not test for dead points
   double usq[3];
   double cull_sq;            // sq_spacing with a safety margin
 };
@@ -257,11 +255,9 @@ __global__ __launch_bounds__(256) void md_nbr_build_kernel(MdArgs a, uint32_t nc
  }
 }
 
-// next cell (rank) of a blocker scan: latest first when the level is throughput bound, earliest first when
-// it is latency bound (measured: 1 B points, root 229 vs 281 ms, level 0 476 vs 265 ms)
-__device__ __forceinline__ int md_next_rank(uint32_t m, uint32_t latest_first) {
-  return latest_first ? __ffs((int)m) - 1 : 31 - __clz((int)m);
-}
+// next cell (rank) of a blocker scan: the earliest adjacent cell first (the latest first, from before blocker scans
+// could tell dead points, no longer paid)
+__device__ __forceinline__ int md_next_rank(uint32_t m) { return 31 - __clz((int)m); }
 
 __device__ __forceinline__ double bcast_f64(double v, int src) {
   int lo = __double2loint(v), hi = __double2hiint(v);
@@ -486,7 +482,7 @@ __device__ void md_sweep_cell(const MdArgs& a, uint32_t slot, uint32_t c, MdLds&
   if (T > 0) wn0 = md_fill_window(a, lds, 0, T, maxcnt, n_cnt, n_start, off, nb);
 
   // the whole list of accepted points is resident in LDS: blocker scans can tell dead points
-  const uint32_t live_wn = (T <= (uint32_t)MD_EXT_CAP && !(a.ablate & 8u)) ? wn0 : 0u;
+  const uint32_t live_wn = (T <= (uint32_t)MD_EXT_CAP && !a.no_dead_test) ? wn0 : 0u;
   uint32_t fresh = 0;
 #ifdef SWZ_MD_STATS
   uint32_t dbg_chunk = 0, dbg_ranks = 0;
@@ -500,7 +496,7 @@ __device__ void md_sweep_cell(const MdArgs& a, uint32_t slot, uint32_t c, MdLds&
 
   // Very large cells (dense blobs: thousands of points per cell): skip stretches in which every point is already
   // rejected by the committed accepted points, four chunks per memory round trip.
-  if (U > 1 && live_wn && e - cur > a.ff_min && !(a.ablate & 16u)) {
+  if (U > 1 && live_wn && e - cur > a.ff_min) {
     while (e - cur > 4u * WAVE) {
       double x[4], y[4], z[4];
 #pragma unroll
@@ -539,7 +535,7 @@ __device__ void md_sweep_cell(const MdArgs& a, uint32_t slot, uint32_t c, MdLds&
 #endif
     bool rej = !valid;
     // (R) against the committed accepted points of the neighbourhood, window by window
-    for (uint32_t base = 0; base < T && !(a.ablate & 2u); base += MD_EXT_CAP) {
+    for (uint32_t base = 0; base < T; base += MD_EXT_CAP) {
       const uint32_t wn = (base == 0 && T <= (uint32_t)MD_EXT_CAP && cur == P)
                             ? wn0
                             : ((T <= (uint32_t)MD_EXT_CAP) ? wn0 : md_fill_window(a, lds, base, T, maxcnt, n_cnt, n_start, off, nb));
@@ -644,9 +640,8 @@ __device__ void md_sweep_cell(const MdArgs& a, uint32_t slot, uint32_t c, MdLds&
       } else {
         // few survivors: scan the earlier adjacent cells for this candidate, 64 points at a time
         uint32_t nm = bcast_u32(needrank, j);
-        if (a.ablate & 1u) nm = 0;
         while (nm && !blocked) {
-          const int r = md_next_rank(nm, a.latest_first);
+          const int r = md_next_rank(nm);
           nm &= ~(1u << r);
           const uint32_t qs = bcast_u32(n_pos, r);
           const uint32_t qe = bcast_u32(n_end, r);
@@ -666,7 +661,6 @@ __device__ void md_sweep_cell(const MdArgs& a, uint32_t slot, uint32_t c, MdLds&
           }
         }
       }
-      if (a.ablate & 4u) blocked = false;
       if (blocked) {
         out_pos = cand;
         out_status = ST_STALLED;
@@ -737,17 +731,7 @@ __global__ __launch_bounds__(MD_THREADS, U == 1 ? SWZ_MD_MIN_WAVES : 4) void md_
   if (blockIdx.x == 0 && threadIdx.x == 0) a.counters[CTR_Q0 + (round + 2) % 3] = 0;
   const uint32_t nq = a.counters[CTR_Q0 + round % 3];
   const uint32_t* qin = a.queue[round & 1];
-  // one loop for both mappings (the body is large: a second inlined copy doubles the kernel)
-  uint32_t first = blockIdx.x * MD_WAVES + w, end = nq, step = gridDim.x * MD_WAVES;
-  if (a.xcd_chunks && (gridDim.x & 7u) == 0) {
-    // workgroups go round-robin over the 8 XCDs: give every XCD one contiguous eighth of the queue so that
-    // neighbouring cells (which read each other's records and accepted points) share an L2
-    const uint32_t seg = (nq + 7u) / 8u, x = blockIdx.x & 7u;
-    first = x * seg + (blockIdx.x >> 3) * MD_WAVES + w;
-    end = min(nq, (x + 1u) * seg);
-    step = (gridDim.x >> 3) * MD_WAVES;
-  }
-  for (uint32_t i = first; i < end; i += step) md_sweep_cell<U, BATCH>(a, i, qin[i], lds[w]);
+  for (uint32_t i = blockIdx.x * MD_WAVES + w; i < nq; i += gridDim.x * MD_WAVES) md_sweep_cell<U, BATCH>(a, i, qin[i], lds[w]);
 }
 
 // append `value` of every lane with want == true to the queue: one atomic per wavefront
@@ -772,12 +756,11 @@ __device__ __forceinline__ void md_wave_push(bool want, uint32_t value, uint32_t
 // blocker's lane may see the entry now or in its next round, either is right (the wake test is the same data the
 // sleeper decided on).  (Until round 2 this was two launches, commit and requeue, with linked wait lists: 18 us per
 // round at 1 B points, now ~13.)
-// (wave0: index of this wavefront's first lane among all participating threads, stride: their number)
-__device__ __forceinline__ void md_commit_requeue_range(const MdArgs& a, uint32_t round, uint32_t wave0, uint32_t stride) {
+__global__ __launch_bounds__(256) void md_commit_requeue_kernel(MdArgs a, uint32_t round) {
   const uint32_t nq = a.counters[CTR_Q0 + round % 3];
   uint32_t* cout = &a.counters[CTR_Q0 + (round + 1) % 3];
   uint32_t* qout = a.queue[(round + 1) & 1];
-  for (uint32_t i0 = wave0; i0 < nq; i0 += stride) {  // wave-uniform
+  for (uint32_t i0 = blockIdx.x * 256 + (threadIdx.x & ~63u); i0 < nq; i0 += gridDim.x * 256) {  // wave-uniform
     const uint32_t i = i0 + lane_id();
     const bool valid = i < nq;
     // first round trip: what the activation in this slot of the queue ended with (written by the sweep)
@@ -838,82 +821,6 @@ __device__ __forceinline__ void md_commit_requeue_range(const MdArgs& a, uint32_
     }
   }
 }
-__global__ __launch_bounds__(256) void md_commit_requeue_kernel(MdArgs a, uint32_t round) {
-  md_commit_requeue_range(a, round, blockIdx.x * 256 + (threadIdx.x & ~63u), gridDim.x * 256);
-}
-
-// ---- the rounds of one level inside ONE launch ---------------------------------------------------------------------
-// A round of three launches costs about 44 us even when only a few cells are active, and a dense level runs well
-// over a thousand dependent rounds.  Here one workgroup per CU stays resident and the three steps of a round are
-// separated by grid barriers instead: every workgroup releases its stores at agent scope (buffer_wbl2), arrives on one
-// monotonic counter, polls it relaxed, and acquires (buffer_inv) -- cdna_hip_programming.md Guideline 16 in its counter
-// form; the state words are zeroed by the host before every launch and every spin is bounded: a workgroup that is not
-// resident -- another context's kernels or a staged copy kernel on the device are enough -- would otherwise hang the
-// others.  When a spin runs out the launch gives up and the CALL FAILS with SWZ_ERR_INTERNAL (the steps of a round are
-// not restartable, so there is no falling back to plain launches): SWZ_MD_PERSISTENT=1 is an experiment switch that
-// never changes a result but may fail a call; it is off by default and slower than the plain rounds.
-struct MdBarrier {
-  uint32_t arrived;   // monotonic over the launch
-  uint32_t timeout;   // set when a spin ran out
-  uint32_t rounds;    // rounds completed in this launch
-  uint32_t pad;
-};
-constexpr int MDP_THREADS = 1024;
-constexpr int MDP_WAVES = MDP_THREADS / WAVE;
-
-__device__ __forceinline__ bool md_grid_barrier(MdBarrier* bar, uint32_t nblocks, uint32_t& epoch, uint32_t* lds_flag) {
-  __syncthreads();  // every wave's stores are issued ...
-  ++epoch;
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // ... and written back before the arrival is visible
-    __hip_atomic_fetch_add(&bar->arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t target = epoch * nblocks;
-    uint32_t ok = 1;
-    for (uint32_t spins = 0;; ++spins) {
-      if (__hip_atomic_load(&bar->arrived, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= target) break;
-      if (spins > (1u << 22) || __hip_atomic_load(&bar->timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-        __hip_atomic_store(&bar->timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ok = 0;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(8);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    *lds_flag = ok;
-  }
-  __syncthreads();
-  return *lds_flag != 0;
-}
-
-__global__ __launch_bounds__(MDP_THREADS, 4) void md_persistent_kernel(MdArgs a, uint32_t ncells, uint32_t round0,
-                                                                       uint32_t max_rounds, MdBarrier* bar) {
-  __shared__ MdLds lds[MDP_WAVES];
-  __shared__ uint32_t s_flag, s_done;
-  const uint32_t w = threadIdx.x / WAVE;
-  const uint32_t nblocks = gridDim.x;
-  const uint32_t wave0 = blockIdx.x * MDP_THREADS + (threadIdx.x & ~63u);
-  const uint32_t stride = nblocks * MDP_THREADS;
-  uint32_t epoch = 0;
-  for (uint32_t round = round0; round - round0 < max_rounds; ++round) {
-    // sweep
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.counters[CTR_Q0 + (round + 2) % 3] = 0;
-    {
-      const uint32_t nq = a.counters[CTR_Q0 + round % 3];
-      const uint32_t* qin = a.queue[round & 1];
-      for (uint32_t i = blockIdx.x * MDP_WAVES + w; i < nq; i += nblocks * MDP_WAVES) md_sweep_cell<1, true>(a, i, qin[i], lds[w]);
-    }
-    if (!md_grid_barrier(bar, nblocks, epoch, &s_flag)) return;
-    md_commit_requeue_range(a, round, wave0, stride);
-    if (!md_grid_barrier(bar, nblocks, epoch, &s_flag)) return;
-    if (threadIdx.x == 0) {
-      s_done = __hip_atomic_load(&a.counters[CTR_DONE_CELLS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (blockIdx.x == 0) bar->rounds = round - round0 + 1u;
-    }
-    __syncthreads();
-    if (s_done >= ncells) return;
-  }
-}
 
 __global__ __launch_bounds__(256) void md_gather_active_kernel(const uint32_t* __restrict__ aidx, uint32_t m,
                                                                const double* __restrict__ X,
@@ -967,8 +874,7 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
     SWZ_HIP(c, hipMemsetAsync(d_hist, 0, 64, c->stream));
     const uint32_t nsh = plan.node_shift == 63u ? 63u : plan.node_shift;
     const uint32_t tiles = div_up(m, 256);
-    uint32_t skip = std::max(1u, m >> 23);  // about 8 M points are looked at
-    if (const char* e = c->opt("SWZ_MD_HIST_SKIP")) skip = std::max(1, atoi(e));
+    const uint32_t skip = std::max(1u, m >> 23);  // about 8 M points are looked at
     const uint32_t sampled_tiles = div_up(tiles, skip);
     hipLaunchKernelGGL(md_cell_hist_kernel, dim3(std::min<uint32_t>(sampled_tiles, 4096u)), dim3(256), 0, c->stream, as.akey,
                        lb.nid, lb.nmode, m, nsh, (uint32_t)plan.cell_levels_geo, skip, d_hist);
@@ -989,8 +895,7 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
   // of a dense sheet or blob far too large) and that the dense [node][cell] lookup table stays affordable
   int cl = plan.cell_levels_geo;
   const double avg = (double)sample_points / (double)sample_nodes;
-  double per_cell = 8.0;
-  if (const char* e = c->opt("SWZ_MD_DENSITY")) per_cell = atof(e);
+  const double per_cell = 8.0;
   // ... but only while the TYPICAL point would not end up in an oversized cell (points-weighted mean population
   // after the step <= 160): with mixed densities (a dense blob in a sparse background) the average over the cells
   // says little, and cells that are too large for the dense part cost far more (long serial activations) than
@@ -1011,17 +916,14 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
     SWZ_HIP(c, hipStreamSynchronize(c->stream));
     for (int k = 0; k < 4; ++k) pop[k] = h[4] ? (double)h[k] / (double)h[4] : 1e30;
   }
-  double max_pop = 160.0;
-  if (const char* e = c->opt("SWZ_MD_MAX_POP")) max_pop = atof(e);
+  const double max_pop = 160.0;
   while (cl > 0 && plan.cell_levels_geo - cl < 3 && (double)sample_points / (double)std::max(1u, occupied[cl]) < per_cell &&
          pop[plan.cell_levels_geo - cl + 1] <= max_pop)
     --cl;
   // the dense [node][cell] map: at most 2^31 entries (8.6 GB; it is memset once per level, a few ms)
   while (cl > 0 && (double)sample_nodes * std::pow(8.0, cl) > 2147483648.0) --cl;
-  if (const char* e = c->opt("SWZ_MD_COARSEN")) {
-    const double thr = c->opt("SWZ_MD_COARSEN_MIN") ? atof(c->opt("SWZ_MD_COARSEN_MIN")) : 32.0;
-    if (avg / std::pow(8.0, cl) >= thr) cl = std::max(0, cl - atoi(e));
-  }
+  if (const long coarsen = c->opt_int("SWZ_MD_COARSEN", 0))
+    if (avg / std::pow(8.0, cl) >= c->opt_num("SWZ_MD_COARSEN_MIN", 32.0)) cl = std::max(0, cl - (int)coarsen);
   const uint64_t cells_per_node = 1ull << (3 * cl);
 
   MdArgs a{};
@@ -1053,9 +955,8 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
       a.usq[ax] = u * u;
     }
     a.cull_sq = plan.sq_spacing * (1.0 + 0x1.0p-18);
-    a.ff_min = c->opt("SWZ_MD_FF_MIN") ? (uint32_t)atoi(c->opt("SWZ_MD_FF_MIN")) : 1024u;
-    a.xcd_chunks = c->opt("SWZ_MD_XCD") ? (uint32_t)atoi(c->opt("SWZ_MD_XCD")) & 1u : 0u;
-    a.ablate = c->opt("SWZ_MD_ABLATE") ? (uint32_t)atoi(c->opt("SWZ_MD_ABLATE")) : 0u;
+    a.ff_min = (uint32_t)c->opt_int("SWZ_MD_FF_MIN", 1024);
+    a.no_dead_test = c->opt_on("SWZ_MD_NO_DEAD_TEST", false) ? 1u : 0u;
     // expected points per spacing-sized cell; far below one almost every candidate is accepted
     a.batch_blockers = (avg / std::pow(8.0, plan.cell_levels_geo) < 0.25) ? 1u : 0u;
   }
@@ -1137,42 +1038,35 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
   SWZ_LAUNCH_CHECK(c);
   SWZ_STAGE(c, "md cells");
   hipLaunchKernelGGL(md_nbr_build_kernel,
-                     dim3(std::min<uint32_t>(div_up(ncells, 8), c->opt("SWZ_MD_NBR_GRID") ? (uint32_t)atoi(c->opt("SWZ_MD_NBR_GRID")) : 1u << 20)),
+                     dim3(std::min<uint32_t>(div_up(ncells, 8), (uint32_t)c->opt_int("SWZ_MD_NBR_GRID", 1u << 20))),
                      dim3(256), 0, c->stream, a, ncells);
   SWZ_LAUNCH_CHECK(c);
   SWZ_STAGE(c, "md neighbour tables");
   // With many small cells a level is bound by activation throughput: start lazily and let a stalled cell sleep
   // until the whole blocking cell is finished (fewer, later wake-ups; measured at 1 B points, level 1:
   // 302 -> 173 ms).  With few large cells it is bound by the latency of a round times the number of rounds:
-  // wake up as early as possible.  The latest-first scan order (from before blocker scans could tell dead points)
-  // no longer pays and stays off; it remains selectable for the scheduling tests.  (A cheap re-check of the stalled
-  // candidate before the full activation, from the same time, was removed in round 2: it cost the kernel registers.)
+  // wake up as early as possible.  (A cheap re-check of the stalled candidate before the full activation was removed in
+  // round 2: it cost the kernel registers.)
   const bool many_small = ncells >= (4u << 20) && (double)sample_points / (double)ncells <= 128.0;
-  a.latest_first = 0;
-  a.patient = many_small ? 1u : 0u;
-  if (const char* e = c->opt("SWZ_MD_PATIENT")) a.patient = (uint32_t)atoi(e);
-  if (const char* e = c->opt("SWZ_MD_LATEST_FIRST")) a.latest_first = (uint32_t)atoi(e);
+  a.patient = (uint32_t)c->opt_int("SWZ_MD_PATIENT", many_small ? 1 : 0);
   // every level starts lazily (no first round in which all cells scan their neighbourhood only to learn that
   // they must wait); levels bound by the number of rounds wake a cell as soon as its latest earlier neighbour has
   // decided its first point (1 B points, root: 147 -> 117 ms), throughput-bound ones once half of it is decided
   // -- unless the typical point sits in a very large cell (dense blobs, N x denser roots of sharded batches),
   // where an early wake-up only adds expensive activations
   const double typical = pop[std::min(3, plan.cell_levels_geo - cl)];
-  bool lazy = many_small || typical <= 1024.0;
-  if (const char* e = c->opt("SWZ_MD_LAZY")) lazy = atoi(e) != 0;
-  a.lazy_frac = c->opt("SWZ_MD_LAZY_FRAC") ? (float)atof(c->opt("SWZ_MD_LAZY_FRAC")) : (many_small ? 0.5f : 0.0f);
+  const bool lazy = c->opt_on("SWZ_MD_LAZY", many_small || typical <= 1024.0);
+  a.lazy_frac = (float)c->opt_num("SWZ_MD_LAZY_FRAC", many_small ? 0.5 : 0.0);
   // two builds of the sweep: for cells of hundreds of points and more (four chunks per memory round trip in blocker
   // scans and the fast-forward, 4 wavefronts per SIMD) and for levels of small cells (neither, 5 per SIMD)
-  bool big_cells = typical > 128.0;
-  if (const char* e = c->opt("SWZ_MD_BIG")) big_cells = atoi(e) != 0;
+  const bool big_cells = c->opt_on("SWZ_MD_BIG", typical > 128.0);
   // Node groups.  The nodes of a level are sampled independently, so their cells can be dealt to G sets that run their
   // rounds on G streams: while one set's second launch publishes (a few dependent round trips on a few thousand
   // cells) or its queue is short (the ramps at the start and the end of a level), the other sets' sweeps use the GPU.
   uint32_t groups = 1;
   if (sample_nodes >= 2 && !big_cells) groups = 2;
-  if (const char* e = c->opt("SWZ_MD_GROUPS")) groups = (uint32_t)std::max(1, std::min(8, atoi(e)));
+  groups = (uint32_t)std::max(1L, std::min(8L, c->opt_int("SWZ_MD_GROUPS", groups)));
   groups = std::min(groups, sample_nodes);
-  if (c->opt("SWZ_MD_PERSISTENT") && atoi(c->opt("SWZ_MD_PERSISTENT")) != 0) groups = 1;  // one launch runs all cells
   std::vector<MdArgs> ga(groups, a);
   std::vector<hipStream_t> gs(groups, c->stream);
   for (uint32_t g = 0; g < groups; ++g) {
@@ -1225,50 +1119,17 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
   const uint32_t sweep_grid = std::min<uint32_t>(std::max(8u, sweep_cap / groups), std::max<uint32_t>(1u, div_up(ncells, MD_WAVES)));
   const uint32_t commit_grid = std::min<uint32_t>(std::max(1u, commit_cap / groups), std::max<uint32_t>(1u, div_up(ncells, 256)));
   uint32_t round = 0, done = 0;
-  // SWZ_MD_PERSISTENT=1: one resident workgroup per CU runs the rounds inside one launch (md_persistent_kernel).
-  // Measured at 1 B points (round 2): root 169 ms against 117 ms with three launches per round (128 against 89 us
-  // per round), level 0 199 against 129 ms -- a round is bound by its ~15 dependent memory round trips, not by the
-  // launch boundaries (1.5-2 us each), and an agent-scope release (L2 write-back) per workgroup and barrier costs
-  // more than they do.  Off by default; kept selectable for the scheduling tests.
-  bool persistent = c->opt("SWZ_MD_PERSISTENT") && atoi(c->opt("SWZ_MD_PERSISTENT")) != 0;
-  if (persistent) {
-    int dev = 0, cus = 0, per_cu = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, md_persistent_kernel, MDP_THREADS, 0) != hipSuccess || per_cu < 1 || cus < 1)
-      persistent = false;
-    MdBarrier* bar = nullptr;
-    if (persistent) SWZ_TRY(c->get("md_barrier", sizeof(MdBarrier), reinterpret_cast<void**>(&bar)));
-    const uint32_t per_launch = c->opt("SWZ_MD_ROUNDS_PER_LAUNCH") ? (uint32_t)atoi(c->opt("SWZ_MD_ROUNDS_PER_LAUNCH")) : 4096u;
-    while (persistent && done < ncells) {
-      SWZ_HIP(c, hipMemsetAsync(bar, 0, sizeof(MdBarrier), c->stream));
-      hipLaunchKernelGGL(md_persistent_kernel, dim3((uint32_t)cus), dim3(MDP_THREADS), 0, c->stream, a, ncells, round,
-                         per_launch, bar);
-      SWZ_LAUNCH_CHECK(c);
-      MdBarrier hb{};
-      SWZ_HIP(c, hipMemcpyAsync(&hb, bar, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
-      SWZ_HIP(c, hipMemcpyAsync(&done, lb.counters + CTR_DONE_CELLS, 4, hipMemcpyDeviceToHost, c->stream));
-      SWZ_HIP(c, hipStreamSynchronize(c->stream));
-      round += hb.rounds;
-      if (hb.timeout) {  // a round may have been left half done: its steps are idempotent per cell only as a whole
-        return c->fail(SWZ_ERR_INTERNAL, "MIN_DISTANCE: grid barrier timed out (a workgroup of the persistent launch was not resident)");
-      }
-      if (round > 4ull * m + 1024) return c->fail(SWZ_ERR_INTERNAL, "MIN_DISTANCE frontier sweep did not terminate");
-    }
-  }
   // rounds queued between two looks at the level's progress (the streams drain for the look: 30-50 us): 32 at first,
   // 128 once a level has shown that it takes hundreds of rounds (a level that is done keeps running the queued rounds,
   // empty, 15 us each); SWZ_MD_BATCH fixes the number
   uint32_t batch = 32, batches_done = 0;
   const bool fixed_batch = c->opt("SWZ_MD_BATCH") != nullptr;
-  if (fixed_batch) batch = std::max(1u, (uint32_t)atoi(c->opt("SWZ_MD_BATCH")));
+  if (fixed_batch) batch = std::max(1u, (uint32_t)c->opt_int("SWZ_MD_BATCH", 0));
   // a level that does not finish is reported, not waited for: points that change while they are being tiled
   // (keys and positions no longer agree) can make single cells arbitrarily expensive
   const auto wall0 = std::chrono::steady_clock::now();
-  double wall_limit = 900.0;
-  if (const char* e = c->opt("SWZ_MD_TIME_LIMIT")) wall_limit = atof(e);
-  uint64_t max_rounds = 4ull * m + 1024;
-  if (const char* e = c->opt("SWZ_MD_ROUND_LIMIT")) max_rounds = (uint64_t)atoll(e);
+  const double wall_limit = c->opt_num("SWZ_MD_TIME_LIMIT", 900.0);
+  const uint64_t max_rounds = (uint64_t)c->opt_int("SWZ_MD_ROUND_LIMIT", 4l * m + 1024);
   // the side streams start after everything queued so far and are joined again when the level is done
   hipEvent_t fork = nullptr;
   if (groups > 1) {
@@ -1297,17 +1158,6 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
     for (uint32_t g = 0; g < groups; ++g) {
       SWZ_HIP(c, hipStreamSynchronize(gs[g]));
       done += gdone[g];
-    }
-    if (dbg && c->opt("SWZ_MD_TIMELINE")) {
-      float t = 0.f;
-      hipEvent_t e = c->take_event();
-      (void)hipEventRecord(e, c->stream);
-      (void)hipEventSynchronize(e);
-      (void)hipEventElapsedTime(&t, ev0, e);
-      c->event_pool.push_back(e);
-      uint32_t qn[3] = {0, 0, 0};
-      (void)hipMemcpy(qn, lb.counters + CTR_Q0, 12, hipMemcpyDeviceToHost);
-      fprintf(stderr, " r%u:%.1fms:%.3f%%:q%u", round, t, 100.0 * done / ncells, qn[round % 3]);
     }
     if (std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() > wall_limit) {
       char msg[200];

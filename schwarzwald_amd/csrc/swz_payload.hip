@@ -477,8 +477,7 @@ int swz_bin_persist_nodes(swz_ctx* c, const char* dir, uint64_t num_nodes, const
   // tasks of its tiling graph, TilingAlgorithms.cpp:330-334).  One thread wrote 2.7 GB/s -- a hundredth of what the device
   // hands over.  SWZ_BIN_WRITER_THREADS: the number of threads (default: the host's, at most 32).
   unsigned threads = std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
-  if (c)
-    if (const char* e = c->opt("SWZ_BIN_WRITER_THREADS")) threads = (unsigned)std::max(1, atoi(e));
+  if (c) threads = (unsigned)std::max(1L, c->opt_int("SWZ_BIN_WRITER_THREADS", threads));
   threads = (unsigned)std::min<uint64_t>(threads, std::max<uint64_t>(num_nodes, 1));
   std::atomic<uint64_t> next{0};
   std::atomic<int> status{SWZ_OK};

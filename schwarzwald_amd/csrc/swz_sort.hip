@@ -619,8 +619,7 @@ int radix_sort_pairs(swz_ctx* c, uint64_t* d_keys_in, uint32_t* d_vals_tmp, uint
   uint32_t* vin = d_vals_tmp;
   uint64_t* kout = d_keys_out;
   uint32_t* vout = d_vals_out;
-  const char* os_opt = c->opt("SWZ_SORT_ONESWEEP");
-  if (n < (1u << 30) && !(os_opt && atoi(os_opt) == 0)) {
+  if (n < (1u << 30) && c->opt_on("SWZ_SORT_ONESWEEP", true)) {
     static_assert(RADIX == RS_THREADS, "one thread per digit");
     uint32_t *d_ghist = nullptr, *d_status = nullptr, *d_ticket = nullptr;
     SWZ_TRY(c->get("radix_ghist", (size_t)RADIX_PASSES * RADIX, &d_ghist));
@@ -637,10 +636,9 @@ int radix_sort_pairs(swz_ctx* c, uint64_t* d_keys_in, uint32_t* d_vals_tmp, uint
     };
     // how many top digits: from a sorted sample of the keys
     int top = RADIX_PASSES;
-    uint32_t min_n = 1u << 24, short_max = FIX_SHORT, long_max = FIX_LONG;
-    if (const char* e = c->opt("SWZ_SORT_HYBRID_MIN_N")) min_n = (uint32_t)atoll(e);
-    if (const char* e = c->opt("SWZ_SORT_FIX_SHORT")) short_max = std::max(1u, std::min<uint32_t>(FIX_SHORT, (uint32_t)atoi(e)));
-    if (const char* e = c->opt("SWZ_SORT_FIX_LONG")) long_max = std::max(short_max, std::min<uint32_t>(FIX_LONG, (uint32_t)atoi(e)));
+    const uint32_t min_n = (uint32_t)c->opt_int("SWZ_SORT_HYBRID_MIN_N", 1u << 24);
+    const uint32_t short_max = std::max(1u, std::min<uint32_t>(FIX_SHORT, (uint32_t)c->opt_int("SWZ_SORT_FIX_SHORT", FIX_SHORT)));
+    const uint32_t long_max = std::max(short_max, std::min<uint32_t>(FIX_LONG, (uint32_t)c->opt_int("SWZ_SORT_FIX_LONG", FIX_LONG)));
     uint32_t* d_fix = nullptr;  // [0] long runs, [1] runs too long, [2..3] sample ties
     SWZ_TRY(c->get("radix_fix_counters", (size_t)4, &d_fix));
     if (n >= min_n) {
@@ -670,7 +668,7 @@ int radix_sort_pairs(swz_ctx* c, uint64_t* d_keys_in, uint32_t* d_vals_tmp, uint
       // (two tied pairs are tolerated: 32768 samples of 1 B uniform points tie in the top 32 bits with probability 0.12)
       top = h[2] <= 2u ? 4 : (h[3] <= 2u ? 6 : RADIX_PASSES);
     }
-    if (const char* e = c->opt("SWZ_SORT_HYBRID_TOP")) top = std::max(2, std::min(RADIX_PASSES, atoi(e) & ~1));
+    top = std::max(2, std::min(RADIX_PASSES, (int)c->opt_int("SWZ_SORT_HYBRID_TOP", top) & ~1));
     if (c->opt("SWZ_DEBUG") && n >= min_n) fprintf(stderr, "[swz] sort: %u keys, passes over the top %d digits\n", n, top);
     if (top < RADIX_PASSES) {
       const int first_pass = RADIX_PASSES - top;

@@ -63,3 +63,54 @@ def test_spacing_from_diagonal_matches_reference_value():
     import schwarzwald_amd as swz
     s = swz.spacing_from_diagonal([0, 0, 0], [1, 1, 1], 250)
     assert np.float32(s).view(np.uint32) == 0x3BE305FB
+
+
+# SWZ_* names only Python reads (bench.py, the suite, the sharded driver): they never reach the library
+PYTHON_ONLY_OPTIONS = ("SWZ_SHARD_JOINT_ROOT", "SWZ_GPU_LIBRARY", "SWZ_TEST_QUEUE_TIMEOUT")
+PYTHON_ONLY_PREFIXES = ("SWZ_BENCH_", "SWZ_FULLSIZE_")
+
+
+def _options_read_by_the_library():
+    csrc = os.path.join(ROOT, "schwarzwald_amd", "csrc")
+    names = set()
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".h")):
+            names |= set(re.findall(r'\bopt(?:_int|_num|_on)?\("(SWZ_\w+)"', open(os.path.join(csrc, f)).read()))
+    return names
+
+
+def _unknown_options(text, known):
+    """SWZ_* names that `text` sets -- quoted (set_option / setenv arguments, keys of option or environment dicts) or
+    assigned on a command line (NAME=value) -- and the library does not read."""
+    named = set(re.findall(r"[\"'](SWZ_\w+)[\"']", text)) | set(re.findall(r"\b(SWZ_\w+)=(?!=)", text))
+    return sorted(n for n in named
+                  if n not in known and n not in PYTHON_ONLY_OPTIONS and not n.startswith(PYTHON_ONLY_PREFIXES))
+
+
+def test_tests_and_tools_set_only_options_the_library_reads():
+    """swz_set_option accepts any name: a test mode that sets a switch the library no longer reads would pass without
+    testing anything."""
+    known = _options_read_by_the_library()
+    assert len(known) > 50
+    bad = {}
+    for sub in ("tests", "tools"):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, sub)):
+            for f in files:
+                if f.endswith((".py", ".sh", ".txt", ".cpp", ".hip", ".h")):
+                    path = os.path.join(dirpath, f)
+                    unknown = _unknown_options(open(path, errors="ignore").read(), known)
+                    if unknown:
+                        bad[os.path.relpath(path, ROOT)] = unknown
+    assert not bad, bad
+    # ... and a mode that still sets a switch the library has dropped is caught, in every form
+    gone = "_".join(["SWZ", "MD", "PERSISTENT"])  # (spelt out it would be one of the names this test finds)
+    assert _unknown_options('{"SWZ_MD_LAZY": "0", "%s": "1"}' % gone, known) == [gone]
+    assert _unknown_options('ctx.set_option("%s", "1")' % gone, known) == [gone]
+    assert _unknown_options("SWZ_DEBUG=1 %s=1 python bench.py" % gone, known) == [gone]
+
+
+def test_every_option_the_library_reads_is_documented():
+    header = open(os.path.join(ROOT, "include", "swz_gpu.h")).read()
+    doc = re.search(r"/\*((?:(?!\*/).)*)\*/\s*int swz_set_option\(", header, re.S).group(1)
+    missing = sorted(n for n in _options_read_by_the_library() if not re.search(r"\b%s\b" % n, doc))
+    assert not missing, "not described at swz_set_option in include/swz_gpu.h: %s" % missing

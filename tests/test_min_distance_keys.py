@@ -57,7 +57,7 @@ MODES = [
     {"SWZ_MD_PATIENT": "0", "SWZ_MD_LAZY": "0"},
     {"SWZ_MD_PATIENT": "1", "SWZ_MD_LAZY": "1", "SWZ_MD_LAZY_FRAC": "0"},
     {"SWZ_MD_PATIENT": "1", "SWZ_MD_LAZY": "1", "SWZ_MD_LAZY_FRAC": "1", "SWZ_MD_BIG": "1"},
-    {"SWZ_MD_PATIENT": "0", "SWZ_MD_LAZY": "1", "SWZ_MD_ABLATE": "8"},       # blocker scans without the dead-point test
+    {"SWZ_MD_PATIENT": "0", "SWZ_MD_LAZY": "1", "SWZ_MD_NO_DEAD_TEST": "1"},  # blocker scans without the dead-point test
     {"SWZ_MD_GRID": "3"},                                                    # 12 workgroups stride over every queue
     {"SWZ_MD_BIG": "1", "SWZ_MD_COARSEN": "2", "SWZ_MD_COARSEN_MIN": "0", "SWZ_MD_LAZY": "0"},  # cells of hundreds of points
     {"SWZ_MD_BIG": "0", "SWZ_MD_COARSEN": "2", "SWZ_MD_COARSEN_MIN": "0"},   # ... through the one-chunk build

@@ -21,10 +21,9 @@ sets = [
     {},
     {"SWZ_MD_LAZY": "0"},
     {"SWZ_MD_LAZY": "0", "SWZ_MD_KEYS_BAND": "1e9"},
-    {"SWZ_MD_LAZY": "0", "SWZ_MD_ABLATE": "8"},
+    {"SWZ_MD_LAZY": "0", "SWZ_MD_NO_DEAD_TEST": "1"},
     {"SWZ_MD_BIG": "1"},
     {"SWZ_MD_BIG": "0"},
-    {"SWZ_MD_DENSITY": "0"},
 ]
 with swz.Context(0) as ctx:
     ctx.set_option("SWZ_MD_SPARSE_LIMIT", "0")

@@ -6,7 +6,7 @@
 #                            (a tag that starts with sleep<seconds>_ waits first: the driver wipes the memory a process frees)
 #   levels [bench args]      bench.py with SWZ_DEBUG=1: the library's per-level lines (block path, sweeps, rounds, the incremental subset)
 #   variants [bench args]    the same with the default library and every schwarzwald_amd/lib/libswz_v*.so (tools/build_variant.sh;
-#                            -DSWZ_SB_STATS builds print the block kernel's phase times); VAR_ENV="SWZ_SP_BLOCK_DBG=8" passes switches on
+#                            -DSWZ_SB_STATS builds print the block kernel's phase times); VAR_ENV="SWZ_SP_BLOCK_PER_CU=4" passes switches on
 #   multibatch [orders]      1 B points in 100 batches, MIN_DISTANCE FAST exact (the reference's default operating point), per order
 #                            (default "tiles uniform"); MB_ENVS="default SWZ_SP_INCREMENTAL=0" runs every order under each environment
 #   stats [bench args]       rocprofv3 --kernel-trace --stats of one bench.py command: the top of the kernel summary
