@@ -418,6 +418,13 @@ int swz_shard_fast_finish_device(swz_ctx* ctx, uint64_t* d_keys_out, uint32_t* d
  *         stage(0); for k: { if (k+1 < K) stage(k+1); tile_staged(); }
  *     attrs_host (may be NULL) are the batch's attribute columns (host pointers); every batch must carry the same
  *     set.  The host copy of the positions is NOT clamped; the pools (swz_tiler_pools_device) hold the clamped ones.
+ *   Refused batches: swz_tiler_add_batch_device, swz_tiler_stage_batch and swz_tiler_add_batch answer SWZ_ERR_BAD_ARG
+ *     for a batch after swz_tiler_finalize and, under SWZ_FAST, for a batch of fewer than fast_concurrency points,
+ *     the EMPTY batch included (parallel::scatter throws, util/threading/Parallel.h:181-186).  The check comes before
+ *     anything is reserved, copied, staged or counted: a refused batch leaves the tiler as it was (not poisoned,
+ *     num_batches and num_points unchanged, no point id used up) and the data set goes on with the next batch.
+ *     Under SWZ_ACCURATE an empty batch (n = 0, d_xyz / xyz_host may be NULL) is counted in num_batches and changes
+ *     no file.  (swz_tiler_shard_begin_device is exempt from the FAST rule: the driver checks the whole batch.)
  *   swz_tiler_finalize: TilingAlgorithmBase::finalize (FAST: reconstruct_left_out_nodes); no more batches after.
  *   swz_tiler_export_device / swz_tiler_node_table: the node files: nodes ordered by (level, Morton index);
  *     entries [node_offset[k], +node_count[k]) of keys/ids/level are node k's points in file order (FAST stores

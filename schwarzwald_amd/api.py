@@ -830,8 +830,8 @@ class Tiler:
         """Asynchronous copy of a host batch (use pinned_empty arrays for real overlap) into the device pools."""
         x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
         cols, keep = _host_columns(attrs, x.shape[0])
-        self._keep.append((x, keep))
         self._ctx._check(self._lib.swz_tiler_stage_batch(self._t, C.c_void_p(x.ctypes.data), x.shape[0], C.byref(cols)))
+        self._keep.append((x, keep))  # (after the check: a refused batch is not staged, tile_staged pops one per staged batch)
 
     def tile_staged(self):
         stats = _TileStats()

@@ -1335,16 +1335,24 @@ static uint64_t stored_total(const swz_tiler* t) {
   return s;
 }
 
+// What TilingAlgorithmBase refuses before it touches anything: a batch after finalize, and under FAST a batch with fewer
+// points than indexing threads, the empty one included (parallel::scatter throws, util/threading/Parallel.h:181-186).
+// The entry points ask this BEFORE they reserve, copy or count anything, so that a refused batch leaves the tiler as
+// it was (not poisoned, no point id used up).  A sharded batch is exempt: its driver checks the whole batch.
+static int tiler_refuse_batch(swz_tiler* t, uint64_t n) {
+  if (t->finalized) return t->c->fail(SWZ_ERR_BAD_ARG, "swz_tiler: batches cannot be added after finalize");
+  if (t->p.strategy == SWZ_FAST && n < t->p.fast_concurrency && !t->shard_fast)
+    return t->c->fail(SWZ_ERR_BAD_ARG, "FAST: a batch needs at least fast_concurrency points");
+  return SWZ_OK;
+}
+
 // d_xyz: the batch inside the position pool (already there) or anywhere else on the device (copied in).
 // Index + sort + positions into Morton order (K1, K2, gather), exactly like a single batch; leaves the batch open.
 static int tiler_batch_prepare(swz_tiler* t, double* d_xyz, uint32_t n, uint32_t extra_pool) {
   swz_ctx* c = t->c;
   c->tiler_scratch_dead = false;  // (the batch's scratch lives until tiler_batch_close)
-  if (t->finalized) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler: batches cannot be added after finalize");
   if (t->batch_open) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler: the previous batch is still open (swz_tiler_shard_finish)");
-  // parallel::scatter throws for a batch with fewer points than indexing threads (util/threading/Parallel.h:181-186)
-  if (t->p.strategy == SWZ_FAST && n < t->p.fast_concurrency && !t->shard_fast)  // (a sharded batch: its driver checks the whole batch)
-    return c->fail(SWZ_ERR_BAD_ARG, "FAST: a batch needs at least fast_concurrency points");
+  SWZ_TRY(tiler_refuse_batch(t, n));
   const uint32_t base = t->total;
   uint64_t* keys = nullptr;
   uint32_t* perm = nullptr;
@@ -1451,7 +1459,7 @@ static void tiler_batch_close(swz_tiler* t, swz_tile_stats* stats) {
 static int tiler_add_batch(swz_tiler* t, double* d_xyz, uint32_t n, swz_tile_stats* stats) {
   zero_stats(stats);
   if (n == 0) {
-    if (t->finalized) return t->c->fail(SWZ_ERR_BAD_ARG, "swz_tiler: batches cannot be added after finalize");
+    SWZ_TRY(tiler_refuse_batch(t, 0));
     ++t->batches;
     return SWZ_OK;
   }
@@ -1680,6 +1688,7 @@ int swz_tiler_add_batch_device(swz_tiler* t, double* d_xyz, uint64_t n, swz_tile
   if (n && !d_xyz) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_add_batch_device: NULL buffer");
   if ((uint64_t)t->total + n > 0xFFFF0000ull) return c->fail(SWZ_ERR_TOO_MANY_POINTS, "more than 2^32-65536 points per tiler");
   if (t->attr_mask) return c->fail(SWZ_ERR_BAD_ARG, "this tiler carries attribute columns: use swz_tiler_stage_batch");
+  SWZ_TRY(tiler_refuse_batch(t, n));  // (a refusal up front changes nothing and does not poison)
   SWZ_TRY(pool_reserve(t, (size_t)t->total + n));
   const int st = tiler_add_batch(t, d_xyz, (uint32_t)n, stats);
   const hipError_t e = hipStreamSynchronize(c->stream);
@@ -1879,7 +1888,7 @@ int swz_tiler_stage_batch(swz_tiler* t, const double* xyz_host, uint64_t n, cons
   swz_ctx* c = t->c;
   SWZ_HIP(c, hipSetDevice(c->device));
   SWZ_TRY(tiler_guard(t));
-  if (t->finalized) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler: batches cannot be added after finalize");
+  SWZ_TRY(tiler_refuse_batch(t, n));  // (nothing is copied or staged for a batch that tile_staged would refuse)
   if (t->staged_sizes.size() >= 2) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_stage_batch: two batches are already staged");
   if (n && !xyz_host) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_stage_batch: NULL buffer");
   if ((uint64_t)t->staged_total + n > 0xFFFF0000ull) return c->fail(SWZ_ERR_TOO_MANY_POINTS, "more than 2^32-65536 points per tiler");
