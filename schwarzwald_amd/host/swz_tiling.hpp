@@ -272,6 +272,9 @@ public:
   }
   // stored points per export chunk of finalize() (whole node files; at least the largest file)
   void set_export_chunk_points(uint64_t n) { _export_chunk_points = n; }
+  // swz_set_option on the tiler's own context (value NULL removes the switch): the spill and budget options of the
+  // pools (SWZ_TILER_SPILL, SWZ_TILER_DEVICE_BUDGET_MB) are read when a pool grows, so set them before the first batch
+  void set_option(const char* name, const char* value) { _ctx.check(swz_set_option(_ctx.get(), name, value)); }
 
 private:
   struct DeviceBuffer {  // device scratch through the ABI (no HIP headers needed by the host code)
