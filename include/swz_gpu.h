@@ -76,7 +76,10 @@ int swz_set_stream(swz_ctx* ctx, void* hip_stream);
  *   through the exact pass), SWZ_GRID_TABLE_DEPTH, SWZ_JITTER_TABLE=0, SWZ_LEVEL_NODES_SCAN;
  *   MIN_DISTANCE, the path of a level: SWZ_MD_SPARSE_LIMIT, SWZ_MD_KEYS=0, SWZ_MD_KEYS_MIN_CELLS, SWZ_MD_KEYS_BAND >= 0 (a
  *   wider band sends more pairs to the compare on the exact positions), SWZ_SP_FILTER_EPS (1e30: every compare within reach
- *   exact), SWZ_GROUP_JOINT_ROOT=0;
+ *   exact), SWZ_GROUP_JOINT_ROOT=0; how the key sweep numbers its cells: SWZ_MD_DIRECT (1: by their place in the grid
+ *   whatever the occupancy, 0: always the occupied cells compacted), SWZ_MD_DIRECT_MIN_OCCUPANCY (0.5: the estimated share of
+ *   occupied grid cells from which a level is numbered directly), SWZ_MD_DIRECT_MAX_CELLS (the largest grid that is numbered
+ *   directly; default: what fits the free device memory);
  *   the frontier sweeps: SWZ_MD_PATIENT, SWZ_MD_LAZY, SWZ_MD_LAZY_FRAC, SWZ_MD_BIG, SWZ_MD_GROUPS, SWZ_MD_GRID,
  *   SWZ_MD_NBR_GRID, SWZ_MD_BATCH, SWZ_MD_COARSEN, SWZ_MD_COARSEN_MIN, SWZ_MD_FF_MIN, SWZ_MD_NO_DEAD_TEST=1 (blocker scans
  *   without the dead-point test), SWZ_MD_CHAIN, SWZ_MD_KEYS_RG, SWZ_MD_DENSE_MIN;

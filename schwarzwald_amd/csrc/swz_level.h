@@ -195,10 +195,12 @@ bool min_distance_level_uses_keys(const swz_ctx* c, const LevelPlan& plan, const
 // sp.xyz through sp.perm (swz_mdkeys.hip, grid_argmin_keys_kernel)
 bool level_decides_on_keys(const swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp);
 // Frontier sweep on key coordinates for a dense level; *used = false when the level does not qualify.
-// cl: cell levels below the node chosen by the caller; typical_pop: points-weighted mean cell population.
+// cl: cell levels below the node chosen by the caller; typical_pop: points-weighted mean cell population; est_cells: the
+// caller's estimate of the occupied cells at cl, from this call's keys (it decides how the cells are numbered).
 int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp,
                             const LevelBuffers& lb, uint32_t num_nodes, uint32_t sample_nodes, uint32_t sample_points,
-                            const uint32_t* snode_of, int cl, double typical_pop, uint32_t* rounds_out, bool* used,
+                            const uint32_t* snode_of, int cl, double typical_pop, uint32_t est_cells, uint32_t* rounds_out,
+                            bool* used,
                             const MdShardRoot* shard_root = nullptr);
 
 // Property mode on key coordinates in data-parallel rounds (swz_mdrounds.hip): candidates per cell, winners by a hashed

@@ -146,10 +146,17 @@ struct MqArgs {
   uint32_t* counters;
   uint64_t* qpos;         // [m] key coordinates x | y << 21 | z << 42 of the active points
   uint8_t* state;         // [m] QS_*
+  // How the cells are numbered.  Compacted: the occupied cells in Morton order, 0 .. ncells - 1; crel / csnode / gridmap
+  // translate between a cell and its place in the grid.  Direct: the cell IS its place in the grid, id = sample node <<
+  // cpn_shift | cell code (still ascending in Morton order); every per-cell array has sample nodes * cells_per_node
+  // entries, an empty cell has cinfo.x == cinfo.y == 0, is nobody's neighbour and is never queued; the three tables
+  // do not exist (see min_distance_keys_level for which level takes which).
+  uint32_t direct;
+  uint32_t cpn_shift;     // log2(cells_per_node)
   uint2* cinfo;           // [cell] {start, end}
-  uint32_t* crel;         // [cell] cell code inside its node (build time)
-  uint32_t* csnode;       // [cell] index of its node among the sampled nodes
-  uint32_t* gridmap;      // [sample node][cell code] -> cell (build time)
+  uint32_t* crel;         // [cell] cell code inside its node (build time, compacted)
+  uint32_t* csnode;       // [cell] index of its node among the sampled nodes (compacted)
+  uint32_t* gridmap;      // [sample node][cell code] -> cell (build time, compacted)
   uint32_t* qnbr;         // [cell][32]: adjacent cell in direction k = (dx+1)*9 + (dy+1)*3 + (dz+1), 13 = the cell itself
   uint4* rec;             // [cell][2][rg]: header {frontier, accepted, stamp, end} + the first rg-1 accepted points
   float4* ovf;            // accepted point j >= rg-1 of the cell ending at `end`: ovf[end - 1 - (j - (rg-1))]
@@ -324,6 +331,57 @@ struct MqCellBuildG {
   }
 };
 
+// Direct numbering: the cell of a point follows from its own key, so one pass over the keys builds everything per point and
+// the bounds of every occupied cell -- no count, no scan.  A run of equal cell prefixes inside a sampled node is a cell
+// (nodes are prefixes of cells: a run never crosses a node's end); its first point writes the start, its last one the end.
+// cinfo has been zeroed: what no run touches stays {0, 0}, an empty cell.
+// Four consecutive points per thread: 16-byte accesses (vec: the keys are 16-byte aligned; qpos / state always are), the
+// state bytes of the four as one word.
+__global__ __launch_bounds__(256) void mq_direct_build_kernel(MqArgs a, uint32_t vec) {
+  const uint64_t i0 = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 4u;
+  if (i0 >= a.m) return;
+  const uint32_t n = a.m - i0 < 4u ? (uint32_t)(a.m - i0) : 4u;
+  uint64_t key[6];  // [0]: the point in front of the four, [5]: the one behind them (cache hits)
+  uint64_t q[4];
+  if (vec && n == 4u) {
+    const ulonglong2 v0 = *reinterpret_cast<const ulonglong2*>(a.akey + i0), v1 = *reinterpret_cast<const ulonglong2*>(a.akey + i0 + 2);
+    key[1] = v0.x, key[2] = v0.y, key[3] = v1.x, key[4] = v1.y;
+  } else {
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) key[1 + j] = j < n ? a.akey[i0 + j] : 0ull;
+  }
+  key[0] = i0 ? a.akey[i0 - 1u] : 0ull;
+  key[5] = i0 + 4u < a.m ? a.akey[i0 + 4u] : 0ull;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) q[j] = mq_pack(key[1 + j]);
+  if (n == 4u) {
+    ulonglong2 w0, w1;
+    w0.x = q[0], w0.y = q[1], w1.x = q[2], w1.y = q[3];
+    *reinterpret_cast<ulonglong2*>(a.qpos + i0) = w0;
+    *reinterpret_cast<ulonglong2*>(a.qpos + i0 + 2) = w1;
+    *reinterpret_cast<uint32_t*>(a.state + i0) = 0x01010101u * (uint32_t)QS_OPEN;
+  } else {
+    for (uint32_t j = 0; j < n; ++j) {
+      a.qpos[i0 + j] = q[j];
+      a.state[i0 + j] = QS_OPEN;
+    }
+  }
+#pragma unroll
+  for (uint32_t j = 0; j < 4u; ++j) {
+    if (j >= n) break;
+    const uint32_t i = (uint32_t)i0 + j;
+    const uint64_t pre = key[1 + j] >> a.cell_shift;
+    const bool first = i == 0u || (key[j] >> a.cell_shift) != pre;
+    const bool last = i + 1u == a.m || (key[2 + j] >> a.cell_shift) != pre;
+    if (!first && !last) continue;
+    const uint32_t node = a.nid[i];
+    if (!a.all_sampled && a.nmode[node] != MODE_SAMPLE) continue;
+    const uint64_t g = ((uint64_t)(a.all_sampled ? node : a.snode_of[node]) << a.cpn_shift) | (pre & (a.cells_per_node - 1ull));
+    if (first) a.cinfo[g].x = i;
+    if (last) a.cinfo[g].y = i + 1u;
+  }
+}
+
 __global__ __launch_bounds__(256) void mq_cell_end_kernel(MqArgs a, uint32_t ncells) {
   const uint32_t c = blockIdx.x * 256 + threadIdx.x;
   if (c >= ncells) return;
@@ -363,16 +421,26 @@ struct MqStart {
 // cells without an earlier adjacent cell are, and every other cell sleeps on its latest earlier neighbour until that one
 // has decided the given fraction of its points (sleeping on a cell that is not the real blocker is always safe: the cell
 // looks again when it wakes up).
+// Direct numbering: ncells counts the grid's entries.  The neighbour's id is the arithmetic alone, and it exists when its
+// cinfo entry is not empty (a load whose address depends on no other load).  The same lanes write what the sweep expects to
+// find of a new cell -- its two record headers and its stall state (mq_cell_end_kernel does that for compacted cells); an
+// empty cell gets headers that read "at its end" and nothing else.
 __global__ __launch_bounds__(256) void mq_nbr_build_kernel(MqArgs a, uint32_t ncells, MqStart st) {
   for (uint64_t cbase = (uint64_t)blockIdx.x * 8u; cbase < ncells; cbase += (uint64_t)gridDim.x * 8u) {
     const uint32_t c = (uint32_t)cbase + threadIdx.x / 32u;
     const uint32_t k = threadIdx.x & 31u;
-    const bool in = c < ncells;
+    const bool in_grid = c < ncells;
+    bool in = in_grid;
+    if (a.direct && in_grid) {
+      const uint2 ci = a.cinfo[c];
+      if (k < 2u) a.rec[((size_t)c << a.rg2_shift) + k * a.rg] = make_uint4(ci.x, 0u, k, ci.y);
+      in = ci.x != ci.y;
+    }
     uint32_t nb = QNONE;
     if (in && k == 13u) {
       nb = c;
     } else if (in && k < 27u) {
-      const uint32_t rel = a.crel[c];
+      const uint32_t rel = a.direct ? (c & (uint32_t)(a.cells_per_node - 1ull)) : a.crel[c];
       const uint32_t all = (uint32_t)(a.cells_per_node - 1ull);
       const uint32_t mz = all & 0x09249249u, my = mz << 1, mx = mz << 2;
       const uint32_t v[3] = {rel & mx, rel & my, rel & mz};
@@ -403,6 +471,10 @@ __global__ __launch_bounds__(256) void mq_nbr_build_kernel(MqArgs a, uint32_t nc
             const uint32_t id = a.peers.gridmap[owner][nrel];
             if (id != QNONE) nb = ((owner + 1u) << MQ_PEER_SHIFT) | id;
           }
+        } else if (a.direct) {
+          const uint32_t g = (c - rel) | nrel;
+          const uint2 cn = a.cinfo[g];
+          if (cn.x != cn.y) nb = g;
         } else {
           nb = a.gridmap[(uint64_t)a.csnode[c] * a.cells_per_node + nrel];
         }
@@ -422,12 +494,13 @@ __global__ __launch_bounds__(256) void mq_nbr_build_kernel(MqArgs a, uint32_t nc
         a.qst[c] = make_uint4(a.cinfo[c].x, k, bq, 0u);
       }
     }
+    if (a.direct && in_grid && k == 2u && best == 0u) a.qst[c] = make_uint4(QNONE, 0u, 0u, 0u);  // (a cell that starts asleep has its stall on record, above)
     const bool push = in && k == 13u && best == 0u;
     const uint32_t seg = (uint32_t)(cbase >> 3) & (a.nseg - 1u);  // (eight entries per step, spread evenly: a segment cannot overflow)
     if (st.groups == 1u) {
       mq_wave_push(push, c | MQ_WOKEN, st.queue[0] + (size_t)seg * a.segcap, st.qctr[0] + (size_t)seg * 32u);
     } else {
-      const uint32_t g = push ? a.csnode[c] % st.groups : 0u;
+      const uint32_t g = push ? (a.direct ? c >> a.cpn_shift : a.csnode[c]) % st.groups : 0u;
       for (uint32_t gg = 0; gg < st.groups; ++gg)
         mq_wave_push(push && g == gg, c | MQ_WOKEN, st.queue[gg] + (size_t)seg * a.segcap, st.qctr[gg] + (size_t)seg * 32u);
     }
@@ -1271,7 +1344,7 @@ bool min_distance_level_uses_keys(const swz_ctx* c, const LevelPlan& plan, const
 
 int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp, const LevelBuffers& lb,
                             uint32_t nnodes, uint32_t sample_nodes, uint32_t sample_points, const uint32_t* snode_of, int cl,
-                            double typical_pop, uint32_t* rounds_out, bool* used, const MdShardRoot* shard_root) {
+                            double typical_pop, uint32_t est_cells, uint32_t* rounds_out, bool* used, const MdShardRoot* shard_root) {
   *used = false;
   const KeyMetric km = key_metric(c, plan, sp);
   if (!km.ok) return SWZ_OK;
@@ -1293,6 +1366,7 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
   a.counters = lb.counters;
   a.snode_of = snode_of;
   a.cells_per_node = 1ull << (3 * cl);
+  a.cpn_shift = 3u * (uint32_t)cl;
   a.cell_levels = (uint32_t)cl;
   a.peers.shards = sharded ? (uint32_t)shard_root->shards : 1u;
   a.peers.shard = sharded ? (uint32_t)shard_root->shard : 0u;
@@ -1310,18 +1384,6 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
   if (a.cell_bits > 21u) return SWZ_OK;
 
   ProfScope ps(c, "sample_min_distance", (uint64_t)sample_points * 33ull, 1);
-  // cells = runs of the cell prefix inside sampled nodes
-  uint32_t* d_cell_sums = nullptr;
-  SWZ_TRY(fused_scan_sums(c, MqHeadF{a}, m, lb.counters + CTR_NUM_CELLS, "mqc", &d_cell_sums));
-  uint32_t ncells = 0;
-  SWZ_HIP(c, hipMemcpyAsync(&ncells, lb.counters + CTR_NUM_CELLS, 4, hipMemcpyDeviceToHost, c->stream));
-  SWZ_HIP(c, hipStreamSynchronize(c->stream));
-  *used = true;
-  if (ncells == 0) return SWZ_OK;
-  if (ncells >= 0x7FFFFFFFu) {
-    *used = false;
-    return SWZ_OK;
-  }
   // A cell r spacings wide ends with about 0.75 r^3 accepted points: records of 3 or 7 inline ones, the rest in the
   // overflow.  (Small records win well beyond their capacity -- level 1 at 1 B points, cells two spacings wide with ~6
   // accepted points each: 78 ms with records of 3, 84 with records of 7: less to stage, more wavefronts per CU.)
@@ -1329,28 +1391,77 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
   a.rg = (0.75 * r_cell * r_cell * r_cell <= 12.0) ? 4u : 8u;
   a.rg = c->opt_int("SWZ_MD_KEYS_RG", a.rg) >= 8 ? 8u : 4u;
   a.rg2_shift = a.rg == 4u ? 3u : 4u;
+  // How the cells are numbered (MqArgs::direct).  By their place in the grid when most of the grid is occupied -- the
+  // caller's estimate from THIS call's keys (from half of it on) -- and the per-cell arrays of the whole
+  // grid fit what the device has left (plus what the arrays of the level before hold: they are reused).  The joint root
+  // of a sharded batch keeps the compacted cells: its shards publish gridmap to each other.
+  const uint64_t grid_entries = (uint64_t)sample_nodes * a.cells_per_node;
+  {
+    const size_t per_cell = sizeof(uint2) + 32u * 4u + 2u * a.rg * sizeof(uint4) + 32u * 8u + sizeof(uint4) + 5u;
+    uint64_t max_cells = 0x7FFFFFF0ull;
+    if (const char* mc = c->opt("SWZ_MD_DIRECT_MAX_CELLS")) {
+      max_cells = std::min<uint64_t>(max_cells, (uint64_t)std::max(0LL, atoll(mc)));
+    } else {
+      size_t free_b = 0, total_b = 0, held = 0;
+      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+      for (const auto& kv : c->bufs)
+        if (!kv.second.host && kv.first.compare(0, 4, "md_q") == 0) held += kv.second.cap;
+      max_cells = std::min<uint64_t>(max_cells, (uint64_t)((double)(free_b + held) * 0.9 / (double)per_cell));
+    }
+    const double occupancy = (double)est_cells / (double)std::max<uint64_t>(1, grid_entries);
+    bool direct = occupancy >= c->opt_num("SWZ_MD_DIRECT_MIN_OCCUPANCY", 0.5);
+    if (const char* f = c->opt("SWZ_MD_DIRECT")) direct = atoi(f) != 0;  // tests: 1 whatever the occupancy, 0 never
+    a.direct = (direct && !sharded && grid_entries <= max_cells) ? 1u : 0u;
+  }
+  *used = true;
+  uint32_t ncells = 0;  // entries of the per-cell arrays
+  uint32_t* d_cell_sums = nullptr;
+  if (a.direct) {
+    if (sample_points == 0) return SWZ_OK;
+    ncells = (uint32_t)grid_entries;
+  } else {
+    // cells = runs of the cell prefix inside sampled nodes
+    SWZ_TRY(fused_scan_sums(c, MqHeadF{a}, m, lb.counters + CTR_NUM_CELLS, "mqc", &d_cell_sums));
+    SWZ_HIP(c, hipMemcpyAsync(&ncells, lb.counters + CTR_NUM_CELLS, 4, hipMemcpyDeviceToHost, c->stream));
+    SWZ_HIP(c, hipStreamSynchronize(c->stream));
+    if (ncells == 0) return SWZ_OK;
+    if (ncells >= 0x7FFFFFFFu) {
+      *used = false;
+      return SWZ_OK;
+    }
+  }
+  // occupied cells, for the scheduling rules below: counted, or the caller's estimate
+  const uint32_t occ_cells = a.direct ? std::max(1u, std::min<uint32_t>(est_cells, ncells)) : ncells;
 
   SWZ_TRY(c->get(("md_qpos" + sfx).c_str(), (size_t)m, &a.qpos));
   SWZ_TRY(c->get(("md_qstate" + sfx).c_str(), (size_t)m, &a.state));
   SWZ_TRY(c->get(("md_qovf" + sfx).c_str(), (size_t)m, &a.ovf));
   SWZ_TRY(c->get(("md_qcinfo" + sfx).c_str(), (size_t)ncells, &a.cinfo));
-  uint32_t* cellbuf = nullptr;
-  SWZ_TRY(c->get(("md_qcells" + sfx).c_str(), (size_t)ncells * 2, &cellbuf));
-  a.crel = cellbuf;
-  a.csnode = cellbuf + ncells;
+  if (!a.direct) {
+    uint32_t* cellbuf = nullptr;
+    SWZ_TRY(c->get(("md_qcells" + sfx).c_str(), (size_t)ncells * 2, &cellbuf));
+    a.crel = cellbuf;
+    a.csnode = cellbuf + ncells;
+  }
   SWZ_TRY(c->get(("md_qnbr" + sfx).c_str(), (size_t)ncells * 32, &a.qnbr));
   SWZ_TRY(c->get(("md_qrec" + sfx).c_str(), (size_t)ncells * 2 * a.rg, &a.rec));
   SWZ_TRY(c->get(("md_qslot" + sfx).c_str(), (size_t)ncells * 32, &a.slot));
   SWZ_TRY(c->get(("md_qst" + sfx).c_str(), (size_t)ncells, &a.qst));
-  const uint64_t grid_entries = (uint64_t)sample_nodes * a.cells_per_node;
-  SWZ_TRY(c->get(("md_gridmap" + sfx).c_str(), (size_t)grid_entries, &a.gridmap));
-  SWZ_HIP(c, memset_large(a.gridmap, 0xFF, (size_t)grid_entries * 4, c->stream));
+  // (the slots stay a fill of their own: a cell that starts asleep writes into its blocker's row while the table is built)
   SWZ_HIP(c, memset_large(a.slot, 0xFF, (size_t)ncells * 32 * sizeof(unsigned long long), c->stream));
-
-  SWZ_TRY(fused_scan_apply(c, MqHeadF{a}, MqCellBuildG{a}, m, d_cell_sums));
   const uint32_t cb = div_up(ncells, 256);
-  hipLaunchKernelGGL(mq_cell_end_kernel, dim3(cb), dim3(256), 0, c->stream, a, ncells);
-  SWZ_LAUNCH_CHECK(c);
+  if (a.direct) {
+    SWZ_HIP(c, memset_large(a.cinfo, 0, (size_t)ncells * sizeof(uint2), c->stream));
+    hipLaunchKernelGGL(mq_direct_build_kernel, dim3(div_up(m, 1024)), dim3(256), 0, c->stream, a,
+                       ((uintptr_t)a.akey & 15u) == 0 ? 1u : 0u);
+    SWZ_LAUNCH_CHECK(c);
+  } else {
+    SWZ_TRY(c->get(("md_gridmap" + sfx).c_str(), (size_t)grid_entries, &a.gridmap));
+    SWZ_HIP(c, memset_large(a.gridmap, 0xFF, (size_t)grid_entries * 4, c->stream));
+    SWZ_TRY(fused_scan_apply(c, MqHeadF{a}, MqCellBuildG{a}, m, d_cell_sums));
+    hipLaunchKernelGGL(mq_cell_end_kernel, dim3(cb), dim3(256), 0, c->stream, a, ncells);
+    SWZ_LAUNCH_CHECK(c);
+  }
   // From the moment its views are published, a shard that leaves this function early says so in its round word: the
   // higher shards' face cells poll that word and would otherwise spin until their own limits.
   struct WordGuard {
@@ -1418,7 +1529,7 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
     }
   }
   // scheduling: the same rules as the sweep on positions (swz_mindist.hip)
-  const bool many_small = ncells >= (4u << 20) && (double)sample_points / (double)ncells <= 128.0;
+  const bool many_small = occ_cells >= (4u << 20) && (double)sample_points / (double)occ_cells <= 128.0;
   a.patient = (uint32_t)c->opt_int("SWZ_MD_PATIENT", many_small ? 1 : 0);
   const bool lazy = c->opt_on("SWZ_MD_LAZY", true);  // (on keys also for roots of thousands of points per cell: clustered root 99 -> 89 ms)
   a.lazy_frac = (float)c->opt_num("SWZ_MD_LAZY_FRAC", many_small ? 0.5 : 0.0);
@@ -1502,9 +1613,9 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
   }
   const bool dbg = c->opt("SWZ_DEBUG") != nullptr;
   if (dbg)
-    fprintf(stderr, "[swz] MIN_DISTANCE level %d on keys: %u pts in %u nodes, %u cells (cell levels %d), spacing %.1f key cells, band "
+    fprintf(stderr, "[swz] MIN_DISTANCE level %d on keys: %u pts in %u nodes, %u cells%s (cell levels %d), spacing %.1f key cells, band "
                     "[%.0f, %.0f), records of %u, typical cell %.0f pts, lazy %d (%.2f) patient %u groups %u big %d dense cells %u\n",
-            plan.level, sample_points, sample_nodes, ncells, cl, km.T, (double)km.f_lo, (double)km.f_hi, a.rg - 1u, typical_pop, (int)lazy,
+            plan.level, sample_points, sample_nodes, ncells, a.direct ? " of the grid, numbered directly" : "", cl, km.T, (double)km.f_lo, (double)km.f_hi, a.rg - 1u, typical_pop, (int)lazy,
             (double)a.lazy_frac, a.patient, groups, (int)big_cells, ndense);
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (dbg) {

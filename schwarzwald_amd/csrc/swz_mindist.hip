@@ -971,7 +971,7 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
     // The root of a batch sharded over the GPUs of one process (swz_group): every shard sweeps the cells of its own
     // octants, on keys, with the same cells everywhere (the finest ones: what a shard sees of the cloud must not decide).
     bool used = false;
-    SWZ_TRY(min_distance_keys_level(c, plan, as, sp, lb, nnodes, sample_nodes, sample_points, snode, plan.cell_levels_geo, pop[0], rounds_out, &used,
+    SWZ_TRY(min_distance_keys_level(c, plan, as, sp, lb, nnodes, sample_nodes, sample_points, snode, plan.cell_levels_geo, pop[0], occupied[plan.cell_levels_geo], rounds_out, &used,
                                     static_cast<const MdShardRoot*>(c->md_shard_root)));
     if (!used) return c->fail(SWZ_ERR_INTERNAL, "MIN_DISTANCE root of a sharded batch: the joint sweep needs a level that can be decided on keys");
     return SWZ_OK;
@@ -986,7 +986,7 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
     // dense levels whose spacing spans enough key cells: the frontier sweep on key coordinates (swz_mdkeys.hip)
     bool used = false;
     SWZ_TRY(min_distance_keys_level(c, plan, as, sp, lb, nnodes, sample_nodes, sample_points, snode, cl,
-                                    pop[std::min(3, plan.cell_levels_geo - cl)], rounds_out, &used));
+                                    pop[std::min(3, plan.cell_levels_geo - cl)], occupied[cl], rounds_out, &used));
     if (used) return SWZ_OK;
   }
   if (!sp.X) return c->fail(SWZ_ERR_INTERNAL, "MIN_DISTANCE: this level needs the positions in Morton order and they were not gathered");
