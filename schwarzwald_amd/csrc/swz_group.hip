@@ -23,7 +23,7 @@
 #include <vector>
 
 #include "swz_internal.h"
-#include "swz_level.h"
+#include "swz_md.h"
 
 namespace {
 

@@ -1,5 +1,5 @@
 // swz_level.h -- per-level state shared between the level-synchronous tiler (swz_level.hip) and the
-// MIN_DISTANCE dependency sweep (swz_mindist.hip).
+// MIN_DISTANCE samplers (swz_md.h).
 #pragma once
 #include "swz_device.h"
 #include "swz_internal.h"
@@ -133,93 +133,11 @@ int fast_start_level(swz_ctx* c, const uint64_t* d_keys_sorted, uint32_t n, uint
 int fast_prefix_counts(swz_ctx* c, const uint64_t* d_keys_sorted, uint32_t n, uint32_t* counts_host);
 int fast_start_level_from_counts(const uint64_t* counts, uint32_t concurrency);
 
-// MIN_DISTANCE for one level; fills lb.taken for the points of MODE_SAMPLE nodes (take-all points
-// are flagged by the caller).  rounds_out accumulates the dependency rounds executed.
+// MIN_DISTANCE for one level, exact or (plan.md_property) in property mode; fills lb.taken for the points of
+// MODE_SAMPLE nodes (take-all points are flagged by the caller).  rounds_out accumulates the dependency rounds or
+// phases executed.  swz_md.hip decides which algorithm samples the level.
 int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp,
                        const LevelBuffers& lb, uint32_t num_nodes, uint32_t sample_nodes,
                        uint32_t sample_points, uint32_t* rounds_out);
-
-// SWZ_FLAG_MIN_DISTANCE_PROPERTY: coloured cell phases instead of the exact Morton-order greedy (swz_mdprop.hip)
-int min_distance_property_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp,
-                                const LevelBuffers& lb, uint32_t num_nodes, uint32_t sample_nodes,
-                                uint32_t sample_points, uint32_t* phases_out);
-
-// ---- the MIN_DISTANCE root of a batch sharded over several GPUs of ONE process (swz_group)
-// Every shard sweeps the root cells of its own octants at the same time.  Cells only depend on EARLIER adjacent cells,
-// i.e. on cells of the same or of a lower shard: a cell at the face of a lower octant reads the records, key coordinates
-// and state bytes of that shard's adjacent cells through peer access (the halo), as far as that shard's completed rounds
-// have published them, and polls when it has to wait.  Nothing else is exchanged and no shard waits for another's whole
-// root.  What a shard publishes about its root level:
-struct MdPeerView {
-  const uint4* rec = nullptr;        // cell records, [cell][2][rg]
-  const uint64_t* qpos = nullptr;    // key coordinates of its active points
-  const uint8_t* state = nullptr;
-  const float4* ovf = nullptr;
-  const uint32_t* gridmap = nullptr; // [cell code of the root node] -> cell
-  const uint32_t* round_word = nullptr;  // the round its sweep is in: records stamped with an earlier round are complete
-  const uint32_t* perm = nullptr;    // exact positions of its points: xyz[3 * perm[aidx ? aidx[i] : i]]
-  const double* xyz = nullptr;
-  const uint32_t* aidx = nullptr;    // null: the active points are the sorted points (the root of a single batch); a tiler's root
-                                     // level -- batch + cached root file, merged -- has an index into its working arrays
-  uint32_t ncells = 0, rg = 0, cell_shift = 0;
-  uint32_t npoints = 0;              // points of its root level (the readers size their round limit by the lower shards' work too)
-  int status = 0;                    // SWZ_OK, or why this shard cannot take part
-  int entered = 0;                   // the shard's sweep has met the others at the barrier (else its driver does so for it)
-};
-struct MdShardRoot {
-  int shard = 0, shards = 1;
-  MdPeerView* views = nullptr;       // [shards], shared by the group's shards
-  void (*barrier)(void*) = nullptr;  // all shards of the group meet
-  void* barrier_arg = nullptr;
-};
-
-// ---- MIN_DISTANCE on key coordinates (swz_mdkeys.hip) ----------------------------------------------------------
-// The key of a point is its position quantised to 2^-21 of the (cubic) bounds: the integer coordinates of two points
-// bound their distance to +-sqrt(3) key cells, so a compare against the spacing is decided on the keys alone unless the
-// integer distance lies within that band around it; those pairs -- a few in ten thousand at the root, a few per cent of
-// the near pairs at level 3 -- are evaluated on the exact positions with the reference's arithmetic.  The result is
-// therefore the exact one.  KeyMetric holds the thresholds in key cells.
-struct KeyMetric {
-  bool ok = false;     // the level can be decided on keys (cubic bounds, spacing of at least key_min_cells key cells)
-  double T = 0.0;      // spacing in key cells
-  float f_lo = 0.f;    // float squared integer distance <  f_lo: closer than the spacing for sure
-  float f_hi = 0.f;    //                                >= f_hi: at least the spacing apart for sure
-};
-KeyMetric key_metric(const swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp);
-// The caller's index of every active point: perm[aidx[i]] in one array (a streaming pass: aidx ascends), so that the exact
-// compare of a pair costs two dependent loads per point instead of three.  At the root this is perm itself.
-int key_point_ids(swz_ctx* c, const ActiveSet& as, const SortedPoints& sp, const uint32_t** ids);
-// true when min_distance_level will not need sp.X / sp.Y / sp.Z for this level
-bool min_distance_level_uses_keys(const swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp);
-// no sampler of this level reads sp.X / Y / Z: RANDOM_GRID never does, the others decide on key coordinates and look up
-// sp.xyz through sp.perm (swz_mdkeys.hip, grid_argmin_keys_kernel)
-bool level_decides_on_keys(const swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp);
-// Frontier sweep on key coordinates for a dense level; *used = false when the level does not qualify.
-// cl: cell levels below the node chosen by the caller; typical_pop: points-weighted mean cell population; est_cells: the
-// caller's estimate of the occupied cells at cl, from this call's keys (it decides how the cells are numbered).
-int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp,
-                            const LevelBuffers& lb, uint32_t num_nodes, uint32_t sample_nodes, uint32_t sample_points,
-                            const uint32_t* snode_of, int cl, double typical_pop, uint32_t est_cells, uint32_t* rounds_out,
-                            bool* used,
-                            const MdShardRoot* shard_root = nullptr);
-
-// Property mode on key coordinates in data-parallel rounds (swz_mdrounds.hip): candidates per cell, winners by a hashed
-// priority, a kill pass; *used = false when the level does not qualify (then nothing has been decided).
-int min_distance_rounds_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp, const LevelBuffers& lb,
-                              uint32_t num_nodes, uint32_t sample_nodes, uint32_t sample_points, const uint32_t* snode_of, uint32_t* rounds_out,
-                              bool* used);
-
-// Thread-per-point variant for sparse levels (swz_mdsparse.hip); *used = false when the level does not
-// qualify.  snode_of: node -> index among the sampled nodes; occupied[cl]: occupied cells at cell level cl.
-int min_distance_sparse_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp,
-                              const LevelBuffers& lb, const uint32_t* snode_of, bool all_sampled, uint32_t num_nodes,
-                              uint32_t sample_nodes, uint32_t sample_points, const uint32_t occupied[12], uint32_t* rounds_out,
-                              bool* used);
-
-// The same set by blocks of 8^3 cells staged in LDS, blocks in Morton order, decisions in the same launch
-// (swz_mdblock.hip, round 6); *done = false: the level does not qualify or a block did not fit, nothing is lost.
-int min_distance_block_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp, const LevelBuffers& lb,
-                             const uint32_t* snode_of, bool all_sampled, uint32_t num_nodes, uint32_t sample_nodes,
-                             uint32_t sample_points, const uint32_t occupied[12], const KeyMetric& km, bool* done);
 
 }  // namespace swz

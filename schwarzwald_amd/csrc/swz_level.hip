@@ -11,7 +11,7 @@
 #include <cmath>
 #include <vector>
 
-#include "swz_level.h"
+#include "swz_md.h"
 #include "swz_scan.h"
 
 namespace swz {
@@ -1347,12 +1347,8 @@ int level_step(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const Sor
       SWZ_LAUNCH_CHECK(c);
     }
     if (h[CTR_SAMPLE_NODES] > 0) {
-      if (plan.md_property)
-        SWZ_TRY(min_distance_property_level(c, plan, as, sp, lb, h[CTR_NUM_NODES], h[CTR_SAMPLE_NODES],
-                                            h[CTR_SAMPLE_POINTS], &res->md_rounds));
-      else
-        SWZ_TRY(min_distance_level(c, plan, as, sp, lb, h[CTR_NUM_NODES], h[CTR_SAMPLE_NODES], h[CTR_SAMPLE_POINTS],
-                                   &res->md_rounds));
+      SWZ_TRY(min_distance_level(c, plan, as, sp, lb, h[CTR_NUM_NODES], h[CTR_SAMPLE_NODES], h[CTR_SAMPLE_POINTS],
+                                 &res->md_rounds));
     }
   }
 

@@ -34,7 +34,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "swz_level.h"
+#include "swz_md.h"
 #include "swz_scan.h"
 
 namespace swz {
@@ -861,9 +861,13 @@ struct SbInput {
 };
 
 // *done = false: the level does not qualify or a block did not fit -- the caller goes on with another path.
-static int sb_run(swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp, const LevelBuffers& lb, const uint32_t* snode_of,
-                  bool all_sampled, uint32_t sample_nodes, const KeyMetric& km, const SbInput& in, bool* done) {
+static int sb_run(swz_ctx* c, const MdLevel& L, const SbInput& in, bool* done) {
   *done = false;
+  const LevelPlan& plan = L.plan;
+  const SortedPoints& sp = L.sp;
+  const LevelBuffers& lb = L.lb;
+  const KeyMetric& km = L.km;
+  const uint32_t sample_nodes = L.sample_nodes;
   const bool dbg = c->opt("SWZ_DEBUG") != nullptr;
   // cells: as fine as the spacing allows while a block of 8^3 of them still holds a workgroup's worth of points
   int cl = plan.cell_levels_geo;
@@ -914,14 +918,14 @@ static int sb_run(swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp, con
     halo_cap = (uint32_t)std::max(64, atoi(e)) / 16u * 16u;
     caps_forced = true;
   }
-  const uint32_t node_shift = plan.node_shift == 63u ? 63u : plan.node_shift;
+  const uint32_t node_shift = plan.node_shift;
   SbTabArgs t{};
   t.akey = in.akey;
   t.nid = lb.nid;
   t.nmode = lb.nmode;
-  t.snode_of = snode_of;
+  t.snode_of = L.snode_of;
   t.sn_direct = in.sn_direct;
-  t.all_sampled = all_sampled ? 1u : 0u;
+  t.all_sampled = L.all_sampled ? 1u : 0u;
   t.m = in.m;
   SbArgs a{};
   a.akey = in.akey;
@@ -1246,24 +1250,27 @@ __global__ __launch_bounds__(256) void sbi_scatter_kernel(const uint8_t* __restr
 
 // *done = false: not worth it (or a block of the subset did not fit): the whole level is sampled as usual.  Old points that
 // no new point can reach are marked taken either way -- they are in the exact result.
-static int sb_incremental(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp, const LevelBuffers& lb,
-                          const uint32_t* snode_of, bool all_sampled, uint32_t num_nodes, uint32_t sample_nodes, uint32_t sample_points,
-                          const KeyMetric& km, bool* done) {
+static int sb_incremental(swz_ctx* c, const MdLevel& L, bool* done) {
   *done = false;
+  const LevelPlan& plan = L.plan;
+  const ActiveSet& as = L.as;
+  const LevelBuffers& lb = L.lb;
+  const uint32_t* snode_of = L.snode_of;
+  const uint32_t num_nodes = L.num_nodes, sample_nodes = L.sample_nodes, sample_points = L.sample_points;
   const bool dbg = c->opt("SWZ_DEBUG") != nullptr;
   int cl = std::min(plan.cell_levels_geo, 10);
   while (cl > 0 && ((uint64_t)sample_nodes << (3 * cl)) > (1ull << 34)) --cl;  // 2 GB of marks at most; coarser cells mark more
   if (cl < 1) return SWZ_OK;
   const uint64_t nbits = (uint64_t)sample_nodes << (3 * cl);
   const size_t words = (size_t)((nbits + 31ull) / 32ull);
-  const uint32_t node_shift = plan.node_shift == 63u ? 63u : plan.node_shift;
+  const uint32_t node_shift = plan.node_shift;
   SbiArgs a{};
   a.akey = as.akey;
   a.aidx = as.aidx;
   a.nid = lb.nid;
   a.nmode = lb.nmode;
   a.snode_of = snode_of;
-  a.all_sampled = all_sampled ? 1u : 0u;
+  a.all_sampled = L.all_sampled ? 1u : 0u;
   a.m = as.m;
   a.old_lo = as.old_lo;
   a.old_n = as.old_hi - as.old_lo;
@@ -1353,7 +1360,7 @@ static int sb_incremental(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as
   in.spread = 1.0 + 9.0 * std::min(1.0, std::max(0.0, ((double)total - (double)as.new_m) / (double)total));
   in.what = " (what the new points can change)";
   bool ok = false;
-  SWZ_TRY(sb_run(c, plan, sp, lb, snode_of, all_sampled, sample_nodes, km, in, &ok));
+  SWZ_TRY(sb_run(c, L, in, &ok));
   if (!ok) return SWZ_OK;
   hipLaunchKernelGGL(sbi_scatter_kernel, dim3(div_up(total, 256)), dim3(256), 0, c->stream, staken, sidx, total, lb.taken);
   SWZ_LAUNCH_CHECK(c);
@@ -1362,12 +1369,13 @@ static int sb_incremental(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as
 }
 
 // *done = false: the level does not qualify or a block did not fit -- the caller goes on with the thread-per-point path.
-int min_distance_block_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp, const LevelBuffers& lb,
-                             const uint32_t* snode_of, bool all_sampled, uint32_t num_nodes, uint32_t sample_nodes,
-                             uint32_t sample_points, const uint32_t occupied[12], const KeyMetric& km, bool* done) {
+int min_distance_block_level(swz_ctx* c, const MdLevel& L, bool* done) {
   *done = false;
+  const LevelPlan& plan = L.plan;
+  const ActiveSet& as = L.as;
+  const SortedPoints& sp = L.sp;
   if (!c->opt_on("SWZ_SP_BLOCK", true)) return SWZ_OK;
-  if (!km.ok || !sp.xyz || !sp.perm || sp.ghosts) return SWZ_OK;
+  if (!L.km.ok || !sp.xyz || !sp.perm || sp.ghosts) return SWZ_OK;
   if (plan.cell_levels_geo < 3) return SWZ_OK;
   // a batch on top of the files of earlier ones: when those are most of the level, only what the batch can change
   bool inc = as.ckey && as.aidx && as.old_hi > as.old_lo && as.new_key;
@@ -1379,18 +1387,18 @@ int min_distance_block_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet&
   // (... and when the files are big enough for that: one of at most max_points points may come from a node that took everything)
   // (with the node table of the level below a small file can be told from a take-all: then any level of files qualifies)
   if (inc && (double)(as.old_hi - as.old_lo) >= old_share * (double)as.m &&
-      (as.child_nn || (double)(as.old_hi - as.old_lo) >= file_share * (double)plan.max_points * (double)num_nodes)) {
-    SWZ_TRY(sb_incremental(c, plan, as, sp, lb, snode_of, all_sampled, num_nodes, sample_nodes, sample_points, km, done));
+      (as.child_nn || (double)(as.old_hi - as.old_lo) >= file_share * (double)plan.max_points * (double)L.num_nodes)) {
+    SWZ_TRY(sb_incremental(c, L, done));
     if (*done) return SWZ_OK;
   }
   SbInput in;
   in.akey = as.akey;
   in.m = as.m;
   in.aidx = as.aidx;
-  in.taken = lb.taken;
-  in.points = sample_points;
-  in.occupied = occupied;
-  return sb_run(c, plan, sp, lb, snode_of, all_sampled, sample_nodes, km, in, done);
+  in.taken = L.lb.taken;
+  in.points = L.sample_points;
+  in.occupied = L.occupied;
+  return sb_run(c, L, in, done);
 }
 
 }  // namespace swz

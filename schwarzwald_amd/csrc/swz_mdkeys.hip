@@ -33,7 +33,7 @@
 #include <string>
 #include <vector>
 
-#include "swz_level.h"
+#include "swz_md.h"
 #include "swz_scan.h"
 
 namespace swz {
@@ -114,7 +114,7 @@ int key_point_ids(swz_ctx* c, const ActiveSet& as, const SortedPoints& sp, const
 }
 
 // ----------------------------------------------------------------------------- device helpers
-// the root of a batch sharded over the GPUs of one process: what the lower shards publish (swz_level.h, MdPeerView)
+// the root of a batch sharded over the GPUs of one process: what the lower shards publish (swz_md.h, MdPeerView)
 constexpr uint32_t MQ_PEER_SHIFT = 28;          // neighbour id = (shard + 1) << 28 | cell for a cell of another shard
 constexpr uint32_t MQ_ID_MASK = (1u << MQ_PEER_SHIFT) - 1u;
 struct MqPeers {
@@ -1342,11 +1342,17 @@ bool min_distance_level_uses_keys(const swz_ctx* c, const LevelPlan& plan, const
   return key_metric(c, plan, sp).ok;  // (property mode decides on keys as well: swz_mdrounds.hip, or the exact set)
 }
 
-int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp, const LevelBuffers& lb,
-                            uint32_t nnodes, uint32_t sample_nodes, uint32_t sample_points, const uint32_t* snode_of, int cl,
-                            double typical_pop, uint32_t est_cells, uint32_t* rounds_out, bool* used, const MdShardRoot* shard_root) {
+int min_distance_keys_level(swz_ctx* c, const MdLevel& L, int cl, uint32_t* rounds_out, bool* used, const MdShardRoot* shard_root) {
   *used = false;
-  const KeyMetric km = key_metric(c, plan, sp);
+  const LevelPlan& plan = L.plan;
+  const ActiveSet& as = L.as;
+  const SortedPoints& sp = L.sp;
+  const LevelBuffers& lb = L.lb;
+  const KeyMetric& km = L.km;
+  const uint32_t sample_nodes = L.sample_nodes, sample_points = L.sample_points;
+  // the survey's numbers at cl: the points-weighted mean cell population and the estimate of the occupied cells
+  const double typical_pop = L.pop[std::min(3, plan.cell_levels_geo - cl)];
+  const uint32_t est_cells = L.occupied[cl];
   if (!km.ok) return SWZ_OK;
   const bool sharded = shard_root != nullptr && shard_root->shards > 1;
   const std::string sfx = sharded ? "_sr" : "";  // the sharded root's arrays are read by other shards until the batch ends
@@ -1364,18 +1370,18 @@ int min_distance_keys_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& 
   a.ng = sp.ghosts;
   a.taken = lb.taken;
   a.counters = lb.counters;
-  a.snode_of = snode_of;
+  a.snode_of = L.snode_of;
   a.cells_per_node = 1ull << (3 * cl);
   a.cpn_shift = 3u * (uint32_t)cl;
   a.cell_levels = (uint32_t)cl;
   a.peers.shards = sharded ? (uint32_t)shard_root->shards : 1u;
   a.peers.shard = sharded ? (uint32_t)shard_root->shard : 0u;
-  a.cell_shift = (plan.node_shift == 63u ? 63u : plan.node_shift) - 3u * (uint32_t)cl;
+  a.cell_shift = plan.node_shift - 3u * (uint32_t)cl;
   a.cell_bits = a.cell_shift / 3u;
   a.f_lo = km.f_lo;
   a.f_hi = km.f_hi;
   a.sq_spacing = plan.sq_spacing;
-  a.all_sampled = sample_nodes == nnodes ? 1u : 0u;
+  a.all_sampled = L.all_sampled ? 1u : 0u;
   a.no_dead_test = c->opt_on("SWZ_MD_NO_DEAD_TEST", false) ? 1u : 0u;
   a.stats = c->opt("SWZ_MD_STATS") ? 1u : 0u;
   // (measured at 1 B points: 2 cells per chain root / level 0 / level 1 78 / 69 / 96 -> 73 / 62 / 91 ms; longer chains make

@@ -20,7 +20,7 @@
 #include <cmath>
 #include <cstdio>
 
-#include "swz_level.h"
+#include "swz_md.h"
 #include "swz_scan.h"
 
 namespace swz {
@@ -406,203 +406,32 @@ __global__ __launch_bounds__(256) void pm_colour_lists_kernel(PmArgs a, uint32_t
   }
 }
 
-__global__ __launch_bounds__(256) void pm_clear_taken_kernel(const uint32_t* __restrict__ nid, const uint8_t* __restrict__ nmode,
-                                                             uint32_t m, uint8_t* __restrict__ taken) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i < m && nmode[nid[i]] == MODE_SAMPLE) taken[i] = 0;
-}
-__global__ __launch_bounds__(256) void pm_snode_flag_kernel(const uint8_t* __restrict__ nmode, uint32_t nnodes,
-                                                            uint32_t* __restrict__ out) {
-  const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-  if (j < nnodes) out[j] = nmode[j] == MODE_SAMPLE ? 1u : 0u;
-}
-__global__ __launch_bounds__(256) void pm_gather_active_kernel(const uint32_t* __restrict__ aidx, uint32_t m,
-                                                               const double* __restrict__ X, const double* __restrict__ Y,
-                                                               const double* __restrict__ Z, double* __restrict__ ax,
-                                                               double* __restrict__ ay, double* __restrict__ az) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= m) return;
-  const uint32_t s = aidx[i];
-  ax[i] = X[s];
-  ay[i] = Y[s];
-  az[i] = Z[s];
-}
-// occupied cells per candidate cell level (same counting as the exact path's md_cell_hist_kernel)
-__global__ __launch_bounds__(256) void pm_cell_hist_kernel(const uint64_t* __restrict__ akey, const uint32_t* __restrict__ nid,
-                                                           const uint8_t* __restrict__ nmode, uint32_t m, uint32_t node_shift,
-                                                           uint32_t cl_geo, uint32_t skip, uint32_t* __restrict__ hist) {
-  __shared__ uint32_t lh[16];
-  if (threadIdx.x < 16) lh[threadIdx.x] = 0;
-  __syncthreads();
-  uint32_t mine = 0;
-  for (uint64_t i0 = (uint64_t)blockIdx.x * 256u * skip; i0 < m; i0 += (uint64_t)gridDim.x * 256u * skip) {  // every skip-th tile
-    const uint32_t i = (uint32_t)i0 + threadIdx.x;
-    uint32_t bin = 0xFFu;
-    if (i < m && nmode[nid[i]] == MODE_SAMPLE) {
-      if (i == 0 || nid[i - 1] != nid[i]) {
-        bin = 0;
-      } else if (cl_geo) {
-        const uint64_t diff = ((akey[i] ^ akey[i - 1]) >> (node_shift - 3u * cl_geo)) & ((1ull << (3u * cl_geo)) - 1ull);
-        if (diff) bin = cl_geo - (uint32_t)(63 - __clzll((unsigned long long)diff)) / 3u;
-      }
-    }
-    for (uint32_t b = 0; b <= cl_geo; ++b) {
-      const uint32_t cnt = (uint32_t)__popcll(__ballot(bin == b));
-      if (lane_id() == b) mine += cnt;
-    }
-  }
-  if (lane_id() <= cl_geo && mine) atomicAdd(&lh[lane_id()], mine);
-  __syncthreads();
-  if (threadIdx.x < 16 && lh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], lh[threadIdx.x]);
-}
-
-// points-weighted mean cell population at cell level cl_geo (out[0]) and one level coarser (out[1]); out[2] = samples:
-// the population of the cell of every 65536-th point, by binary search for the cell's run in the sorted keys
-__global__ __launch_bounds__(256) void pm_cell_pop_kernel(const uint64_t* __restrict__ akey, const uint32_t* __restrict__ nid,
-                                                          const uint8_t* __restrict__ nmode, uint32_t m, uint32_t node_shift,
-                                                          uint32_t cl_geo, unsigned long long* __restrict__ out) {
-  const uint32_t tsample = blockIdx.x * 256 + threadIdx.x;
-  if (tsample >= 65536u) return;
-  const uint32_t i = (uint32_t)(((uint64_t)tsample * m) / 65536u);
-  if (i >= m || nmode[nid[i]] != MODE_SAMPLE) return;
-  const uint64_t key = akey[i];
-  for (uint32_t k = 0; k <= 1u && k <= cl_geo; ++k) {
-    const uint32_t sh = node_shift - 3u * (cl_geo - k);
-    const uint64_t pre = key >> sh;
-    uint32_t lo = 0, hi = i;
-    while (lo < hi) {
-      const uint32_t mid = lo + (hi - lo) / 2u;
-      if ((akey[mid] >> sh) < pre) lo = mid + 1u; else hi = mid;
-    }
-    const uint32_t first = lo;
-    lo = i;
-    hi = m;
-    while (lo < hi) {
-      const uint32_t mid = lo + (hi - lo) / 2u;
-      if ((akey[mid] >> sh) <= pre) lo = mid + 1u; else hi = mid;
-    }
-    atomicAdd(&out[k], (unsigned long long)(lo - first));
-  }
-  atomicAdd(&out[2], 1ull);
-}
-
-int min_distance_property_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp,
-                                const LevelBuffers& lb, uint32_t nnodes, uint32_t sample_nodes, uint32_t sample_points,
-                                uint32_t* phases_out) {
-  const uint32_t m = as.m;
-  const uint32_t nsh = plan.node_shift;
+// The level's cells are cl levels below its nodes (the dispatcher's choice, swz_md.hip).
+int min_distance_phases_level(swz_ctx* c, const MdLevel& L, int cl, uint32_t* phases_out) {
+  const LevelPlan& plan = L.plan;
+  const LevelBuffers& lb = L.lb;
+  const uint32_t m = L.as.m, sample_nodes = L.sample_nodes, sample_points = L.sample_points;
   const auto wall0 = std::chrono::steady_clock::now();
-  c->next_scratch_epoch();  // what the level before asked for ("md_*", "sp_*", "pm_*") may go if memory runs out
-  uint32_t occupied[12] = {0};
-  bool sampled_hist = false;
-  auto count_cells = [&](bool exact) -> int {
-    uint32_t* d_hist = nullptr;
-    SWZ_TRY(c->get("md_hist", (size_t)16, &d_hist));
-    SWZ_HIP(c, hipMemsetAsync(d_hist, 0, 64, c->stream));
-    // (about 8 M points are looked at on large levels: the counts only steer the choice of path and cell size -- the
-    // coloured phases below size buffers by them and count again, exactly)
-    const uint32_t skip = exact ? 1u : std::max(1u, m >> 23);
-    sampled_hist = skip > 1u;
-    const uint32_t tiles = div_up(m, 256), sampled_tiles = div_up(tiles, skip);
-    hipLaunchKernelGGL(pm_cell_hist_kernel, dim3(std::min<uint32_t>(sampled_tiles, 4096u)), dim3(256), 0, c->stream,
-                       as.akey, lb.nid, lb.nmode, m, nsh, (uint32_t)plan.cell_levels_geo, skip, d_hist);
-    SWZ_LAUNCH_CHECK(c);
-    uint32_t h[16];
-    SWZ_HIP(c, hipMemcpyAsync(h, d_hist, 64, hipMemcpyDeviceToHost, c->stream));
-    SWZ_HIP(c, hipStreamSynchronize(c->stream));
-    const double scale = skip == 1 ? 1.0 : (double)m / (double)std::min<uint64_t>(m, (uint64_t)sampled_tiles * 256u);
-    double run = 0;
-    for (int b = 0; b < 12; ++b) {
-      run += h[b];
-      occupied[b] = (uint32_t)std::min<double>(run * scale, (double)m);
-    }
-    return SWZ_OK;
-  };
-  SWZ_TRY(count_cells(false));
-  // Cell size: coarser cells mean fewer, better filled cells, but every point is tested against the taken points of
-  // 27 cells: keep the expected number of taken points per cell small (<= 8).  A cell of side r spacings holds at
-  // most about 0.75 r^3 points that are pairwise a spacing apart (and never more than it has points).
-  const double node_ext = (plan.root.maxx - plan.root.minx) / std::pow(2.0, plan.level + 1);
-  const double r0 = node_ext / std::pow(2.0, plan.cell_levels_geo) / plan.spacing_node;  // finest cells, in spacings
-  // One wavefront per cell.  Coarser cells are better filled, but a cell of side r spacings can hold about
-  // 0.75 r^3 taken points and every point is tested against those of 27 cells: go one level coarser only when the
-  // finest cells are poorly filled and the coarser ones still hold few taken points WHATEVER their population (real
-  // data is clustered: an average says nothing about the dense parts).
-  int cl = plan.cell_levels_geo;
-  if (cl > 0 && (double)sample_points / (double)std::max(1u, occupied[cl]) < 24.0 && 0.75 * 8.0 * r0 * r0 * r0 <= 48.0) {
-    // ... and only while the TYPICAL point would not sit in an oversized cell afterwards (points-weighted mean
-    // population: a dense blob in a sparse background keeps the plain average low)
-    unsigned long long* d_pop = nullptr;
-    SWZ_TRY(c->get("md_pop", (size_t)8, &d_pop));
-    SWZ_HIP(c, hipMemsetAsync(d_pop, 0, 64, c->stream));
-    hipLaunchKernelGGL(pm_cell_pop_kernel, dim3(256), dim3(256), 0, c->stream, as.akey, lb.nid, lb.nmode, m, nsh,
-                       (uint32_t)plan.cell_levels_geo, d_pop);
-    SWZ_LAUNCH_CHECK(c);
-    unsigned long long hp[3];
-    SWZ_HIP(c, hipMemcpyAsync(hp, d_pop, 24, hipMemcpyDeviceToHost, c->stream));
-    SWZ_HIP(c, hipStreamSynchronize(c->stream));
-    if (hp[2] && (double)hp[1] / (double)hp[2] <= 1024.0) --cl;
-  }
-  while (cl > 0 && (double)sample_nodes * std::pow(8.0, cl) > 2147483648.0) --cl;
-  const double pts_per_cell = (double)sample_points / (double)std::max(1u, occupied[cl]);
+  const double pts_per_cell = (double)sample_points / (double)std::max(1u, L.occupied[cl]);
   const uint64_t cells_per_node = 1ull << (3 * cl);
 
   PmArgs a{};
-  a.akey = as.akey;
+  a.akey = L.as.akey;
   a.m = m;
   a.nid = lb.nid;
   a.nmode = lb.nmode;
   a.nstart = lb.nstart;
-  a.X = sp.X;
-  a.Y = sp.Y;
-  a.Z = sp.Z;
   a.taken = lb.taken;
-  a.cell_shift = nsh - 3u * (uint32_t)cl;
+  a.cell_shift = plan.node_shift - 3u * (uint32_t)cl;
   a.cells_per_node = cells_per_node;
   a.sq_spacing = plan.sq_spacing;
+  a.snode_of = L.snode_of;
 
-  uint32_t* snode = nullptr;
-  SWZ_TRY(c->get("md_snode", (size_t)nnodes, &snode));
-  a.snode_of = snode;
-  hipLaunchKernelGGL(pm_snode_flag_kernel, dim3(div_up(nnodes, 256)), dim3(256), 0, c->stream, lb.nmode, nnodes, snode);
-  SWZ_LAUNCH_CHECK(c);
-  SWZ_TRY(scan_exclusive_u32(c, snode, snode, nnodes, nullptr, "mdn"));
-  {
-    // Sparse levels (about one point per spacing-sized cell or fewer): the exact Morton-order greedy needs only a few
-    // dependent rounds there and one thread per point beats one wavefront per (nearly empty) cell -- the exact set
-    // has the property a fortiori (swz_mdsparse.hip).
-    bool used = false;
-    SWZ_TRY(min_distance_sparse_level(c, plan, as, sp, lb, snode, sample_nodes == nnodes, nnodes, sample_nodes, sample_points, occupied, phases_out, &used));
-    if (used) return SWZ_OK;
-    // it may have given up half way (locally dense data): its decisions are those of ANOTHER priority order.  (A level it
-    // declined at the door -- two or more points per occupied cell, the same test as in swz_mdsparse.hip -- is untouched.)
-    int scl = plan.cell_levels_geo;
-    while (scl > 0 && (double)sample_nodes * std::pow(8.0, scl) > 2147483648.0) --scl;
-    if ((double)sample_points / (double)std::max(1u, occupied[scl]) < c->opt_num("SWZ_MD_SPARSE_LIMIT", 2.0)) {
-      hipLaunchKernelGGL(pm_clear_taken_kernel, dim3(div_up(m, 256)), dim3(256), 0, c->stream, lb.nid, lb.nmode, m, lb.taken);
-      SWZ_LAUNCH_CHECK(c);
-    }
-  }
-  if (key_metric(c, plan, sp).ok) {
-    // On key coordinates (cubic bounds, as the Tiler's are): a maximal independent set grown in data-parallel rounds, no
-    // positions in Morton order, no dependent phases (swz_mdrounds.hip).  Levels it does not take get the exact set
-    // below -- it has the property a fortiori and decides on the keys as well.
-    bool used = false;
-    SWZ_TRY(min_distance_rounds_level(c, plan, as, sp, lb, nnodes, sample_nodes, sample_points, snode, phases_out, &used));
-    if (used) return SWZ_OK;
-    if (!sp.X) return min_distance_level(c, plan, as, sp, lb, nnodes, sample_nodes, sample_points, phases_out);
-  }
-  if (sampled_hist) SWZ_TRY(count_cells(true));  // the coloured phases size their per-cell arrays by these counts
-  if (as.aidx) {  // below the root the survivors are a subsequence: positions into active order
-    double* ax = nullptr;
-    SWZ_TRY(c->get("md_pos", (size_t)m * 4, &ax));
-    hipLaunchKernelGGL(pm_gather_active_kernel, dim3(div_up(m, 256)), dim3(256), 0, c->stream, as.aidx, m, sp.X, sp.Y,
-                       sp.Z, ax, ax + m, ax + 2 * (size_t)m);
-    SWZ_LAUNCH_CHECK(c);
-    a.X = ax;
-    a.Y = ax + m;
-    a.Z = ax + 2 * (size_t)m;
-  }
+  // the per-cell arrays below are sized by the number of occupied cells: the survey's counts are estimates on large levels
+  uint32_t occupied[12];
+  if (L.sampled_hist) SWZ_TRY(md_count_cells_exact(c, L, occupied));
+  else std::copy(L.occupied, L.occupied + 12, occupied);
+  SWZ_TRY(md_active_positions(c, L, 4, &a.X, &a.Y, &a.Z));
   ProfScope ps(c, "sample_min_distance_property", (uint64_t)sample_points * 33ull, 1);
 
   // cells = runs of the cell prefix inside sampled nodes; the scan that numbers them writes their records

@@ -26,7 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "swz_level.h"
+#include "swz_md.h"
 #include "swz_scan.h"
 
 namespace swz {
@@ -638,21 +638,19 @@ struct PrListOfListG {
   }
 };
 
-__global__ __launch_bounds__(256) void pr_snode_flag_kernel(const uint8_t* __restrict__ nmode, uint32_t nnodes, uint32_t* __restrict__ out) {
-  const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-  if (j < nnodes) out[j] = nmode[j] == MODE_SAMPLE ? 1u : 0u;
-}
-
 // One level.  *used = false when the level cannot be decided on keys or its cell grid would be too large.
-int min_distance_rounds_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp, const LevelBuffers& lb,
-                              uint32_t nnodes, uint32_t sample_nodes, uint32_t sample_points, const uint32_t* snode_of, uint32_t* rounds_out,
-                              bool* used) {
+int min_distance_rounds_level(swz_ctx* c, const MdLevel& L, uint32_t* rounds_out, bool* used) {
   *used = false;
-  const KeyMetric km = key_metric(c, plan, sp);
+  const LevelPlan& plan = L.plan;
+  const ActiveSet& as = L.as;
+  const SortedPoints& sp = L.sp;
+  const LevelBuffers& lb = L.lb;
+  const KeyMetric& km = L.km;
+  const uint32_t sample_nodes = L.sample_nodes, sample_points = L.sample_points;
   if (!km.ok || sp.ghosts) return SWZ_OK;
   if (!c->opt_on("SWZ_MD_ROUNDS", true)) return SWZ_OK;
   const uint32_t m = as.m;
-  const uint32_t nsh = plan.node_shift == 63u ? 63u : plan.node_shift;
+  const uint32_t nsh = plan.node_shift;
   // the finest cells the spacing allows give the most candidates per round (measured: coarser cells mean one candidate
   // per LARGER cell and round -- 57 rounds instead of 7)
   const int cl = plan.cell_levels_geo;
@@ -665,8 +663,8 @@ int min_distance_rounds_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet
   a.m = m;
   a.nid = lb.nid;
   a.nmode = lb.nmode;
-  a.snode_of = snode_of;
-  a.all_sampled = sample_nodes == nnodes ? 1u : 0u;
+  a.snode_of = L.snode_of;
+  a.all_sampled = L.all_sampled ? 1u : 0u;
   a.xyz = sp.xyz;
   a.taken = lb.taken;
   a.counters = lb.counters;

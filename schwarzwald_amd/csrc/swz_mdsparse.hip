@@ -30,7 +30,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "swz_level.h"
+#include "swz_md.h"
 
 namespace swz {
 
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void sp_gather_kernel(const uint32_t* __restri
   rec[i] = make_float4((float)(X[s] - nb.minx), (float)(Y[s] - nb.miny), (float)(Z[s] - nb.minz), 0.f);
 }
 
-// Key coordinates as records (swz_level.h, KeyMetric): the differences of integers below 2^21 are exact in float, and
+// Key coordinates as records (swz_md.h, KeyMetric): the differences of integers below 2^21 are exact in float, and
 // the band [f_lo, f_hi) around the spacing holds every pair the quantisation cannot decide.
 // Both in one pass over the keys (round 5: the two kernels above read every key once each, and a memset wrote the state
 // bytes: 15 ms per 1 B-point step for the two sparse levels): record, state byte, and the table entries of the run's ends.
@@ -516,47 +516,28 @@ __global__ __launch_bounds__(256) void sp_round_kernel(SpArgs a, const uint32_t*
 
 __global__ void sp_zero_kernel(uint32_t* p) { *p = 0; }
 
-// positions already in active order (X/Y/Z); snode_of already scanned.  Returns SWZ_OK and sets *used
-// to false when the level does not qualify (the caller then runs the frontier sweep).
-int min_distance_sparse_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp,
-                              const LevelBuffers& lb, const uint32_t* snode_of, bool all_sampled, uint32_t num_nodes,
-                              uint32_t sample_nodes, uint32_t sample_points, const uint32_t occupied[12], uint32_t* rounds_out,
-                              bool* used) {
+// One thread per point on a sparse level (the dispatcher's test, swz_md.hip), cells cl levels below the nodes.  Sets
+// *used to false when it gives up half way (the dispatcher then goes on with a sweep).
+int min_distance_sparse_level(swz_ctx* c, const MdLevel& L, int cl, uint32_t* rounds_out, bool* used) {
   *used = false;
-  int cl = plan.cell_levels_geo;
-  // the table must stay addressable and affordable: at most 2^31 entries
-  while (cl > 0 && (double)sample_nodes * std::pow(8.0, cl) > 2147483648.0) --cl;
-  // points per OCCUPIED cell: clustered data fills a small part of a node's volume
-  const double per_cell = (double)sample_points / (double)std::max(1u, occupied[cl]);
-  const double limit = c->opt_num("SWZ_MD_SPARSE_LIMIT", 2.0);  // per occupied cell; a uniform level with 1.5 points per cell of volume has 1.93
-  if (!(per_cell < limit)) return SWZ_OK;
-  // the root of a sharded batch with ghosts in front, decided on keys: the sweep looks up two position arrays, this path one
-  if (sp.ghosts && plan.level == -1 && !sp.X) return SWZ_OK;
-  const uint32_t m = as.m;
-  const KeyMetric km = key_metric(c, plan, sp);
-  {
-    // round 6: blocks of cells out of LDS, decisions in the same launch (swz_mdblock.hip); levels it cannot take --
-    // no key metric, a block that does not fit its LDS capacity -- go on below as before
-    bool done = false;
-    SWZ_TRY(min_distance_block_level(c, plan, as, sp, lb, snode_of, all_sampled, num_nodes, sample_nodes, sample_points, occupied, km,
-                                     &done));
-    if (done) {
-      if (rounds_out) *rounds_out += 1;
-      *used = true;
-      return SWZ_OK;
-    }
-  }
+  const LevelPlan& plan = L.plan;
+  const ActiveSet& as = L.as;
+  const SortedPoints& sp = L.sp;
+  const LevelBuffers& lb = L.lb;
+  const KeyMetric& km = L.km;
+  const uint32_t m = as.m, sample_nodes = L.sample_nodes, sample_points = L.sample_points;
+  const double per_cell = (double)sample_points / (double)std::max(1u, L.occupied[cl]);  // points per OCCUPIED cell
 
   SpArgs a{};
   a.akey = as.akey;
   a.nid = lb.nid;
   a.nmode = lb.nmode;
-  a.snode_of = snode_of;
-  a.all_sampled = all_sampled ? 1u : 0u;
+  a.snode_of = L.snode_of;
+  a.all_sampled = L.all_sampled ? 1u : 0u;
   a.m = m;
   a.cell_levels = (uint32_t)cl;
   a.cells_per_node = 1ull << (3 * cl);
-  a.cell_shift = (plan.node_shift == 63u ? 63u : plan.node_shift) - 3u * (uint32_t)cl;
+  a.cell_shift = plan.node_shift - 3u * (uint32_t)cl;
   a.sq_spacing = plan.sq_spacing;
   {
     const int sub = std::max(0, std::min(4, 20 - (plan.level + cl)));

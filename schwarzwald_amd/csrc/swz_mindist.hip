@@ -26,7 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "swz_level.h"
+#include "swz_md.h"
 #include "swz_scan.h"
 
 namespace swz {
@@ -99,82 +99,9 @@ struct MdArgs {
 
 __device__ __forceinline__ uint32_t md_spos(const uint32_t* aidx, uint32_t i) { return aidx ? aidx[i] : i; }
 
-__global__ __launch_bounds__(256) void md_node_flag_kernel(const uint8_t* __restrict__ nmode, uint32_t nnodes,
-                                                           uint32_t* __restrict__ out) {
-  const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-  if (j < nnodes) out[j] = nmode[j] == MODE_SAMPLE ? 1u : 0u;
-}
-
 __device__ __forceinline__ bool md_is_head(const MdArgs& a, uint32_t i) {
   if (!a.all_sampled && a.nmode[a.nid[i]] != MODE_SAMPLE) return false;
   return i == 0 || ((a.akey[i] >> a.cell_shift) != (a.akey[i - 1] >> a.cell_shift));
-}
-
-// How many cells are OCCUPIED at every candidate cell level: a point that is not the first of its node is a cell
-// head at cell level cl exactly when its key differs from its predecessor's within the first cl digits below the
-// node prefix.  hist[0] counts the firsts of the sampled nodes, hist[b] the points whose first differing digit is
-// digit b (1-based); occupied(cl) = hist[0] + ... + hist[cl].
-__global__ __launch_bounds__(256) void md_cell_hist_kernel(const uint64_t* __restrict__ akey, const uint32_t* __restrict__ nid,
-                                                           const uint8_t* __restrict__ nmode, uint32_t m, uint32_t node_shift,
-                                                           uint32_t cl_geo, uint32_t skip, uint32_t* __restrict__ hist) {
-  __shared__ uint32_t lh[16];
-  if (threadIdx.x < 16) lh[threadIdx.x] = 0;
-  __syncthreads();
-  uint32_t mine = 0;  // lane b accumulates the wavefront's count of bin b
-  // every skip-th tile of 256 points (the counts only steer the choice of cell size and algorithm: on large levels a
-  // sample of some million points says the same as all of them and saves a pass over the keys)
-  for (uint64_t i0 = (uint64_t)blockIdx.x * skip * 256u; i0 < m; i0 += (uint64_t)gridDim.x * skip * 256u) {
-    const uint32_t i = (uint32_t)i0 + threadIdx.x;
-    uint32_t bin = 0xFFu;
-    if (i0 + threadIdx.x < m && nmode[nid[i]] == MODE_SAMPLE) {
-      if (i == 0 || nid[i - 1] != nid[i]) {
-        bin = 0;
-      } else if (cl_geo) {
-        const uint64_t diff = ((akey[i] ^ akey[i - 1]) >> (node_shift - 3u * cl_geo)) & ((1ull << (3u * cl_geo)) - 1ull);
-        if (diff) bin = cl_geo - (uint32_t)(63 - __clzll((unsigned long long)diff)) / 3u;  // 1 .. cl_geo
-      }
-    }
-    for (uint32_t b = 0; b <= cl_geo; ++b) {
-      const uint32_t cnt = (uint32_t)__popcll(__ballot(bin == b));
-      if (lane_id() == b) mine += cnt;
-    }
-  }
-  if (lane_id() <= cl_geo && mine) atomicAdd(&lh[lane_id()], mine);
-  __syncthreads();
-  if (threadIdx.x < 16 && lh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], lh[threadIdx.x]);
-}
-
-// Points-weighted mean cell population at the cell levels cl_geo, cl_geo-1, -2, -3 (out[0..3] = sums over the
-// samples, out[4] = samples): the population of the cell of every MD_POP_SAMPLES-th point, found by binary search for the
-// cell's run in the sorted keys.  Tells whether the TYPICAL point would sit in an oversized cell after coarsening,
-// which the plain average over cells does not (a dense blob in a sparse background).
-constexpr uint32_t MD_POP_SAMPLES = 1u << 16;
-__global__ __launch_bounds__(256) void md_cell_pop_kernel(const uint64_t* __restrict__ akey, const uint32_t* __restrict__ nid,
-                                                          const uint8_t* __restrict__ nmode, uint32_t m, uint32_t node_shift,
-                                                          uint32_t cl_geo, unsigned long long* __restrict__ out) {
-  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= MD_POP_SAMPLES) return;
-  const uint32_t i = (uint32_t)(((uint64_t)t * m) / MD_POP_SAMPLES);
-  if (i >= m || nmode[nid[i]] != MODE_SAMPLE) return;
-  const uint64_t key = akey[i];
-  for (uint32_t k = 0; k <= 3u && k <= cl_geo; ++k) {
-    const uint32_t sh = node_shift - 3u * (cl_geo - k);
-    const uint64_t pre = key >> sh;
-    uint32_t lo = 0, hi = i;  // first index with prefix >= pre
-    while (lo < hi) {
-      const uint32_t mid = lo + (hi - lo) / 2u;
-      if ((akey[mid] >> sh) < pre) lo = mid + 1u; else hi = mid;
-    }
-    const uint32_t first = lo;
-    lo = i;
-    hi = m;  // first index with prefix > pre
-    while (lo < hi) {
-      const uint32_t mid = lo + (hi - lo) / 2u;
-      if ((akey[mid] >> sh) <= pre) lo = mid + 1u; else hi = mid;
-    }
-    atomicAdd(&out[k], (unsigned long long)(lo - first));
-  }
-  atomicAdd(&out[4], 1ull);
 }
 
 // cells = runs of the cell prefix inside sampled nodes: counted and built by one fused scan (swz_scan.h)
@@ -822,19 +749,6 @@ __global__ __launch_bounds__(256) void md_commit_requeue_kernel(MdArgs a, uint32
   }
 }
 
-__global__ __launch_bounds__(256) void md_gather_active_kernel(const uint32_t* __restrict__ aidx, uint32_t m,
-                                                               const double* __restrict__ X,
-                                                               const double* __restrict__ Y,
-                                                               const double* __restrict__ Z, double* __restrict__ ax,
-                                                               double* __restrict__ ay, double* __restrict__ az) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= m) return;
-  const uint32_t s = aidx[i];
-  ax[i] = X[s];
-  ay[i] = Y[s];
-  az[i] = Z[s];
-}
-
 __global__ __launch_bounds__(256) void md_fill_queue_kernel(MdArgs a, uint32_t n, uint32_t* q, uint32_t* counter) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   md_wave_push(i < n && a.csnode[i] % a.groups == a.group, i, q, counter);
@@ -860,89 +774,29 @@ __global__ __launch_bounds__(256) void md_lazy_start_kernel(MdArgs a, uint32_t n
   md_wave_push(push, c, q, counter);
 }
 
-int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp,
-                       const LevelBuffers& lb, uint32_t nnodes, uint32_t sample_nodes, uint32_t sample_points,
-                       uint32_t* rounds_out) {
-  const uint32_t m = as.m;
-  c->next_scratch_epoch();  // what the level before asked for ("md_*", "sp_*") may go if memory runs out
-
-  // occupied cells at every candidate cell level (one pass over the keys)
-  uint32_t occupied[12] = {0};
-  {
-    uint32_t* d_hist = nullptr;
-    SWZ_TRY(c->get("md_hist", (size_t)16, &d_hist));
-    SWZ_HIP(c, hipMemsetAsync(d_hist, 0, 64, c->stream));
-    const uint32_t nsh = plan.node_shift == 63u ? 63u : plan.node_shift;
-    const uint32_t tiles = div_up(m, 256);
-    const uint32_t skip = std::max(1u, m >> 23);  // about 8 M points are looked at
-    const uint32_t sampled_tiles = div_up(tiles, skip);
-    hipLaunchKernelGGL(md_cell_hist_kernel, dim3(std::min<uint32_t>(sampled_tiles, 4096u)), dim3(256), 0, c->stream, as.akey,
-                       lb.nid, lb.nmode, m, nsh, (uint32_t)plan.cell_levels_geo, skip, d_hist);
-    SWZ_LAUNCH_CHECK(c);
-    SWZ_STAGE(c, "md cell hist");
-    uint32_t h[16];
-    SWZ_HIP(c, hipMemcpyAsync(h, d_hist, 64, hipMemcpyDeviceToHost, c->stream));
-    SWZ_HIP(c, hipStreamSynchronize(c->stream));
-    const double scale = skip == 1 ? 1.0 : (double)m / (double)std::min<uint64_t>(m, (uint64_t)sampled_tiles * 256u);
-    double run = 0;
-    for (int b = 0; b < 12; ++b) {
-      run += h[b];
-      occupied[b] = (uint32_t)std::min<double>(run * scale, (double)m);
-    }
-  }
-  // cell size: as fine as the spacing allows, but coarse enough that an OCCUPIED cell holds >= 8 points on
-  // average (clustered data leaves most of a node empty: the average over the node's volume would make the cells
-  // of a dense sheet or blob far too large) and that the dense [node][cell] lookup table stays affordable
-  int cl = plan.cell_levels_geo;
+// The level's cells are cl levels below its nodes (the dispatcher's choice, swz_md.hip).
+int min_distance_sweep_level(swz_ctx* c, const MdLevel& L, int cl, uint32_t* rounds_out) {
+  const LevelPlan& plan = L.plan;
+  const LevelBuffers& lb = L.lb;
+  const uint32_t m = L.as.m, sample_nodes = L.sample_nodes, sample_points = L.sample_points;
   const double avg = (double)sample_points / (double)sample_nodes;
-  const double per_cell = 8.0;
-  // ... but only while the TYPICAL point would not end up in an oversized cell (points-weighted mean population
-  // after the step <= 160): with mixed densities (a dense blob in a sparse background) the average over the cells
-  // says little, and cells that are too large for the dense part cost far more (long serial activations) than
-  // cells that are too small for the sparse part (more, cheap activations).  Measured on 100 M clustered points:
-  // 11.4 s with the volume average, 0.66 s with this rule; uniform data choose the same cells as before.
-  double pop[4] = {0, 0, 0, 0};  // at cell level cl_geo, cl_geo - 1, - 2, - 3
-  {
-    unsigned long long* d_pop = nullptr;
-    SWZ_TRY(c->get("md_pop", (size_t)8, &d_pop));
-    SWZ_HIP(c, hipMemsetAsync(d_pop, 0, 64, c->stream));
-    const uint32_t nsh = plan.node_shift == 63u ? 63u : plan.node_shift;
-    hipLaunchKernelGGL(md_cell_pop_kernel, dim3(MD_POP_SAMPLES / 256), dim3(256), 0, c->stream, as.akey, lb.nid, lb.nmode, m, nsh,
-                       (uint32_t)plan.cell_levels_geo, d_pop);
-    SWZ_LAUNCH_CHECK(c);
-    SWZ_STAGE(c, "md cell pop");
-    unsigned long long h[5];
-    SWZ_HIP(c, hipMemcpyAsync(h, d_pop, 40, hipMemcpyDeviceToHost, c->stream));
-    SWZ_HIP(c, hipStreamSynchronize(c->stream));
-    for (int k = 0; k < 4; ++k) pop[k] = h[4] ? (double)h[k] / (double)h[4] : 1e30;
-  }
-  const double max_pop = 160.0;
-  while (cl > 0 && plan.cell_levels_geo - cl < 3 && (double)sample_points / (double)std::max(1u, occupied[cl]) < per_cell &&
-         pop[plan.cell_levels_geo - cl + 1] <= max_pop)
-    --cl;
-  // the dense [node][cell] map: at most 2^31 entries (8.6 GB; it is memset once per level, a few ms)
-  while (cl > 0 && (double)sample_nodes * std::pow(8.0, cl) > 2147483648.0) --cl;
-  if (const long coarsen = c->opt_int("SWZ_MD_COARSEN", 0))
-    if (avg / std::pow(8.0, cl) >= c->opt_num("SWZ_MD_COARSEN_MIN", 32.0)) cl = std::max(0, cl - (int)coarsen);
   const uint64_t cells_per_node = 1ull << (3 * cl);
 
   MdArgs a{};
-  a.akey = as.akey;
-  a.aidx = as.aidx;
+  a.akey = L.as.akey;
+  a.aidx = L.as.aidx;
   a.m = m;
   a.nid = lb.nid;
   a.nmode = lb.nmode;
   a.nstart = lb.nstart;
-  a.X = sp.X;
-  a.Y = sp.Y;
-  a.Z = sp.Z;
   a.taken = lb.taken;
   a.counters = lb.counters;
   a.cell_levels = (uint32_t)cl;
   a.cells_per_node = cells_per_node;
-  a.cell_shift = (plan.node_shift == 63u ? 63u : plan.node_shift) - 3u * (uint32_t)cl;
+  a.cell_shift = plan.node_shift - 3u * (uint32_t)cl;
   a.sq_spacing = plan.sq_spacing;
-  a.all_sampled = sample_nodes == nnodes ? 1u : 0u;
+  a.all_sampled = L.all_sampled ? 1u : 0u;
+  a.snode_of = L.snode_of;
   {
     // absolute octree level of a cell is level + cl; up to 4 further levels of the key give the slabs
     const int cell_abs = plan.level + cl;
@@ -961,50 +815,7 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
     a.batch_blockers = (avg / std::pow(8.0, plan.cell_levels_geo) < 0.25) ? 1u : 0u;
   }
 
-  uint32_t* snode = nullptr;
-  SWZ_TRY(c->get("md_snode", (size_t)nnodes, &snode));
-  a.snode_of = snode;
-  hipLaunchKernelGGL(md_node_flag_kernel, dim3(div_up(nnodes, 256)), dim3(256), 0, c->stream, lb.nmode, nnodes, snode);
-  SWZ_LAUNCH_CHECK(c);
-  SWZ_TRY(scan_exclusive_u32(c, snode, snode, nnodes, nullptr, "mdn"));
-  if (c->md_shard_root && plan.level == -1) {
-    // The root of a batch sharded over the GPUs of one process (swz_group): every shard sweeps the cells of its own
-    // octants, on keys, with the same cells everywhere (the finest ones: what a shard sees of the cloud must not decide).
-    bool used = false;
-    SWZ_TRY(min_distance_keys_level(c, plan, as, sp, lb, nnodes, sample_nodes, sample_points, snode, plan.cell_levels_geo, pop[0], occupied[plan.cell_levels_geo], rounds_out, &used,
-                                    static_cast<const MdShardRoot*>(c->md_shard_root)));
-    if (!used) return c->fail(SWZ_ERR_INTERNAL, "MIN_DISTANCE root of a sharded batch: the joint sweep needs a level that can be decided on keys");
-    return SWZ_OK;
-  }
-  {
-    // sparse levels (about one point per spacing-sized cell or fewer): one thread per point
-    bool used = false;
-    SWZ_TRY(min_distance_sparse_level(c, plan, as, sp, lb, snode, sample_nodes == nnodes, nnodes, sample_nodes, sample_points, occupied, rounds_out, &used));
-    if (used) return SWZ_OK;
-  }
-  {
-    // dense levels whose spacing spans enough key cells: the frontier sweep on key coordinates (swz_mdkeys.hip)
-    bool used = false;
-    SWZ_TRY(min_distance_keys_level(c, plan, as, sp, lb, nnodes, sample_nodes, sample_points, snode, cl,
-                                    pop[std::min(3, plan.cell_levels_geo - cl)], occupied[cl], rounds_out, &used));
-    if (used) return SWZ_OK;
-  }
-  if (!sp.X) return c->fail(SWZ_ERR_INTERNAL, "MIN_DISTANCE: this level needs the positions in Morton order and they were not gathered");
-  if (as.aidx) {  // below the root the survivors are a subsequence: bring their positions into active order
-    double *ax = nullptr, *ay = nullptr, *az = nullptr;
-    // the two big per-point buffers are shared with the sparse path (never live at the same time): "md_pos" = x[], y[],
-    // z[] here (24 B per point), {x,y,z,key} records there (32 B), "md_acc" the same sizes.  Each path asks for what it
-    // uses: at 1 B clustered points the 2 x 8 GB between the two decide whether a level with 226 M cells fits
-    SWZ_TRY(c->get("md_pos", (size_t)m * 3, &ax));
-    ay = ax + m;
-    az = ay + m;
-    hipLaunchKernelGGL(md_gather_active_kernel, dim3(div_up(m, 256)), dim3(256), 0, c->stream, as.aidx, m, sp.X, sp.Y,
-                       sp.Z, ax, ay, az);
-    SWZ_LAUNCH_CHECK(c);
-    a.X = ax;
-    a.Y = ay;
-    a.Z = az;
-  }
+  SWZ_TRY(md_active_positions(c, L, 3, &a.X, &a.Y, &a.Z));
   ProfScope ps(c, "sample_min_distance", (uint64_t)sample_points * 33ull, 1);
 
   // cells = runs of the cell prefix inside sampled nodes: count them, size the per-cell arrays, build them
@@ -1025,7 +836,7 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
   SWZ_TRY(c->get("md_cell128", (size_t)ncells, &a.cells));
   SWZ_TRY(c->get("md_nbr_id", (size_t)ncells * 27, &a.nbr_id));
   SWZ_TRY(c->get("md_nbr_slot", (size_t)ncells * 32, &a.nbr_slot));
-  SWZ_TRY(c->get("md_acc", (size_t)m * 3, &a.acc_xyz));  // 3 doubles per point (see md_pos above)
+  SWZ_TRY(c->get("md_acc", (size_t)m * 3, &a.acc_xyz));  // 3 doubles per point (see md_active_positions)
   SWZ_TRY(c->get("md_queue0", (size_t)ncells, &a.queue[0]));
   SWZ_TRY(c->get("md_queue1", (size_t)ncells, &a.queue[1]));
   const uint64_t grid_entries = (uint64_t)sample_nodes * cells_per_node;
@@ -1054,7 +865,7 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
   // decided its first point (1 B points, root: 147 -> 117 ms), throughput-bound ones once half of it is decided
   // -- unless the typical point sits in a very large cell (dense blobs, N x denser roots of sharded batches),
   // where an early wake-up only adds expensive activations
-  const double typical = pop[std::min(3, plan.cell_levels_geo - cl)];
+  const double typical = L.pop[std::min(3, plan.cell_levels_geo - cl)];
   const bool lazy = c->opt_on("SWZ_MD_LAZY", many_small || typical <= 1024.0);
   a.lazy_frac = (float)c->opt_num("SWZ_MD_LAZY_FRAC", many_small ? 0.5 : 0.0);
   // two builds of the sweep: for cells of hundreds of points and more (four chunks per memory round trip in blocker
@@ -1100,8 +911,8 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
   if (dbg)
     fprintf(stderr, "[swz] MIN_DISTANCE level %d starts: %u pts in %u nodes, cell levels %d of %d, %u cells (occupied at the finest: %u), "
                     "points-weighted mean cell population at the finest level and coarser %.0f / %.0f / %.0f / %.0f, lazy %d patient %u\n",
-            plan.level, sample_points, sample_nodes, cl, plan.cell_levels_geo, ncells, occupied[plan.cell_levels_geo], pop[0], pop[1],
-            pop[2], pop[3], (int)lazy, a.patient);
+            plan.level, sample_points, sample_nodes, cl, plan.cell_levels_geo, ncells, L.occupied[plan.cell_levels_geo], L.pop[0], L.pop[1],
+            L.pop[2], L.pop[3], (int)lazy, a.patient);
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (dbg) {
     ev0 = c->take_event();

@@ -24,7 +24,7 @@
 #include <cstring>
 #include <vector>
 
-#include "swz_level.h"
+#include "swz_md.h"
 #include "swz_scan.h"
 
 namespace swz {

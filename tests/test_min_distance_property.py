@@ -1,5 +1,5 @@
-"""MIN_DISTANCE in property mode (SWZ_FLAG_MIN_DISTANCE_PROPERTY, swz_mdprop.hip).  There is no reference result to
-compare with point for point; what must hold is what the sampler is for and what the reference's author tests
+"""MIN_DISTANCE in property mode (SWZ_FLAG_MIN_DISTANCE_PROPERTY: swz_md.hip hands a level to swz_mdrounds.hip or
+swz_mdprop.hip).  There is no reference result to compare with point for point; what must hold is what the sampler is for and what the reference's author tests
 (test/TestTiler.cpp:361-421), with the reference's compare (GridCell.cpp:43-58: (dx*dx + dy*dy) + dz*dz < the
 float-squared spacing, widened to double):
 
