@@ -162,6 +162,12 @@ void swz_ctx::prof_collect() {
   pending.clear();
 }
 
+int swz::read_u32(swz_ctx* c, const uint32_t* d, uint32_t* h) {
+  SWZ_HIP(c, hipMemcpyAsync(h, d, 4, hipMemcpyDeviceToHost, c->stream));
+  SWZ_HIP(c, hipStreamSynchronize(c->stream));
+  return SWZ_OK;
+}
+
 static std::string g_create_error;
 static int check_params(swz_ctx* c, const swz_tile_params* p);
 

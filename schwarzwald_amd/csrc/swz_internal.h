@@ -83,7 +83,7 @@ struct swz_ctx {
   void prof_end(const char* name, uint64_t launches, uint64_t bytes);
   void prof_collect();  // after a stream sync: fold pending events into kstats
   hipEvent_t cur_e0_ = nullptr;
-  void* shard = nullptr;  // swz::ShardState of an open sharded batch (swz_level.hip)
+  void* shard = nullptr;  // swz::ShardState of an open sharded batch (swz_shard.hip)
   const void* md_shard_root = nullptr;  // swz::MdShardRoot while swz_group runs the MIN_DISTANCE root of a sharded batch on all shards at once
   bool md_shard_root_published = false;  // the "md_*_sr" arrays of this context are mapped by other shards: they stay (see get())
   // swz_mdblock.hip, sb_incremental: [sbi_clean_ptr, + sbi_clean_bytes) of the "sbi_bits" buffer is known to be zero
@@ -167,6 +167,9 @@ inline hipError_t memset_large(void* p, int value, size_t bytes, hipStream_t str
   }
   return hipSuccess;
 }
+
+// one device counter to the host: a 4-byte copy and a synchronisation of the context's stream (swz_api.hip)
+int read_u32(swz_ctx* c, const uint32_t* d, uint32_t* h);
 
 // ---- stage entry points (each in its own .hip file) -------------------------------------------
 int encode_device(swz_ctx* c, double* d_xyz, uint32_t n, const double bmin[3], const double bmax[3],

@@ -1,5 +1,6 @@
-// swz_level.h -- per-level state shared between the level-synchronous tiler (swz_level.hip) and the
-// MIN_DISTANCE samplers (swz_md.h).
+// swz_level.h -- the state of one level and the entry points around it: what the drivers of the level loop
+// (swz_session.hip, swz_shard.hip, swz_tiler.hip) hand to level_step (swz_level.hip), and what level_step hands to the
+// level's sampler (swz_grid.hip; MIN_DISTANCE: swz_md.h).
 #pragma once
 #include "swz_device.h"
 #include "swz_internal.h"
@@ -74,6 +75,19 @@ __host__ __device__ inline const double* sorted_point_xyz(const double* xyz, con
                                                           uint32_t s) {
   return (s < ghosts ? ghost_xyz : xyz) + (size_t)perm[s] * 3;
 }
+// ... of sorted point i of a batch, in Morton order or not, to point o of an AoS array
+__device__ __forceinline__ void store_sorted_point(const SortedPoints& sp, uint32_t i, double* __restrict__ out_xyz, uint64_t o) {
+  if (sp.X) {
+    out_xyz[3 * o] = sp.X[i];
+    out_xyz[3 * o + 1] = sp.Y[i];
+    out_xyz[3 * o + 2] = sp.Z[i];
+  } else {  // the positions were never brought into Morton order (the samplers decided on keys)
+    const double* p = sorted_point_xyz(sp.xyz, sp.perm, sp.ghost_xyz, sp.ghosts, i);
+    out_xyz[3 * o] = p[0];
+    out_xyz[3 * o + 1] = p[1];
+    out_xyz[3 * o + 2] = p[2];
+  }
+}
 
 // What the host decides once per level (all float/libm corner cases of the reference live here,
 // evaluated with the host's glibc exactly like the reference evaluates them).
@@ -126,6 +140,8 @@ int required_depth_host(int sampler, int node_level, double root_extent_x, float
 // receives plan.level for the taken points; otherwise only lb.taken is produced.
 int level_step(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp, const LevelBuffers& lb,
                int8_t* level_out, uint64_t* okey, uint32_t* oidx, LevelResult* res);
+// what a kernel of the level raised in CTR_ERROR, in words
+const char* level_error_message(int code);
 // estimate_start_node_level_in_octree (TilingAlgorithms.cpp:1473-1535) of a sorted batch
 int fast_start_level(swz_ctx* c, const uint64_t* d_keys_sorted, uint32_t n, uint32_t concurrency, int* start_level);
 // the same in two steps for a batch that is spread over several GPUs: counts per 6-octant prefix (2^18, host), summed by
@@ -133,6 +149,13 @@ int fast_start_level(swz_ctx* c, const uint64_t* d_keys_sorted, uint32_t n, uint
 int fast_prefix_counts(swz_ctx* c, const uint64_t* d_keys_sorted, uint32_t n, uint32_t* counts_host);
 int fast_start_level_from_counts(const uint64_t* counts, uint32_t concurrency);
 
+// ---- the samplers of a level (called by level_step after the node segmentation; each fills lb.taken) ----------------
+// RANDOM_GRID (swz_grid.hip): the first point of every candidate cell; candidate level -1 (GRID_CENTER's too): of every node.
+int random_grid_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const LevelBuffers& lb);
+// GRID_CENTER / JITTERED (swz_grid.hip): on key coordinates when grid_level_uses_keys, else on sp.X / sp.Y / sp.Z
+int grid_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp, const LevelBuffers& lb);
+// true when grid_level will not need sp.X / sp.Y / sp.Z for this level
+bool grid_level_uses_keys(const swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp);
 // MIN_DISTANCE for one level, exact or (plan.md_property) in property mode; fills lb.taken for the points of
 // MODE_SAMPLE nodes (take-all points are flagged by the caller).  rounds_out accumulates the dependency rounds or
 // phases executed.  swz_md.hip decides which algorithm samples the level.

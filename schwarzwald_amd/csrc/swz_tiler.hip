@@ -11,7 +11,7 @@
 // Here the "files" are a device-resident node store: per octree level the (key, point id) entries of its nodes' files,
 // each file contiguous and in file order, found through a node table (StoreLevel); positions (and attribute columns) of
 // all points ever added live in pools indexed by point id (= running index over all batches).  A batch runs the same
-// level-synchronous loop as a single batch (swz_level.hip); per level the files of the nodes the active set touches are
+// level-synchronous loop as a single batch (swz_session.hip); per level the files of the nodes the active set touches are
 // copied out and merged in, and the level's taken points are appended as those nodes' new files -- carrying the key the
 // reference computes when it reads a file back, so that the re-keying is paid once per stored entry, not per pull.  FAST (TilingAlgorithmV3) later iterations
 // (:1362-1453, 1620-1659: per-thread chunks sorted, split at the start level, k-way merged, earlier chunk first on
@@ -640,7 +640,6 @@ static void store_written_linear(StoreLevel& s, int which, uint32_t cnt, bool re
   s.rekeyed = rekeyed || cnt == 0;
 }
 
-static int read_u32(swz_ctx* c, const uint32_t* d, uint32_t* h);
 static int table_reserve(swz_ctx* c, StoreLevel& s, int level_index, int which, size_t count) {
   // (part of the store: placed like its sides -- SWZ_TILER_SPILL=host leaves nothing of a tiler on the device)
   const std::string sfx = std::to_string(level_index) + "_" + std::to_string(which);
@@ -803,12 +802,6 @@ static int merge_pairs(swz_ctx* c, const uint64_t* k1, const uint32_t* v1, uint3
     hipLaunchKernelGGL(tl_merge_rank_kernel<true>, dim3(div_up(n2, TL_MERGE_TILE)), dim3(256), 0, c->stream, k2, v2, n2, k1, n1, sh, base2, ok, ov);
     SWZ_LAUNCH_CHECK(c);
   }
-  return SWZ_OK;
-}
-
-static int read_u32(swz_ctx* c, const uint32_t* d, uint32_t* h) {
-  SWZ_HIP(c, hipMemcpyAsync(h, d, 4, hipMemcpyDeviceToHost, c->stream));
-  SWZ_HIP(c, hipStreamSynchronize(c->stream));
   return SWZ_OK;
 }
 

@@ -1,4 +1,4 @@
-"""GRID_CENTER / JITTERED decided on key coordinates (grid_argmin_keys_kernel, swz_level.hip) against the CPU oracle.
+"""GRID_CENTER / JITTERED decided on key coordinates (grid_argmin_keys_kernel, swz_grid.hip) against the CPU oracle.
 
 Per grid cell the point with the smallest upper bound of its distance to the target wins outright when every other
 point's lower bound is larger; the runs that leaves undecided are repeated with the reference's arithmetic on the original

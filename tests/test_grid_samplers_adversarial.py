@@ -587,12 +587,12 @@ def test_las_surface_is_quantised_at_utm_offsets():
 
 
 def test_tile_sizes_are_what_the_edge_family_aims_at():
-    text = open(os.path.join(ROOT, "schwarzwald_amd", "csrc", "swz_level.hip")).read()
+    text = open(os.path.join(ROOT, "schwarzwald_amd", "csrc", "swz_grid.hip")).read()
     v = {}
     for short in ("GA_THREADS", "GA_IPT", "GAK_IPT"):
         name = "SWZ_" + short   # (compile-time constants, not options: test_abi_and_host.py looks for quoted option names)
         m = re.search(r"#ifndef %s\s*\n#define %s (\d+)" % (name, name), text)
-        assert m, "swz_level.hip no longer defines %s: tests/test_grid_samplers_adversarial.py must learn the tile sizes anew" % name
+        assert m, "swz_grid.hip no longer defines %s: tests/test_grid_samplers_adversarial.py must learn the tile sizes anew" % name
         v[short] = int(m.group(1))
     keys, positions = v["GA_THREADS"] * v["GAK_IPT"], v["GA_THREADS"] * v["GA_IPT"]
     assert (keys, positions) == (KEY_TILE, POS_TILE), (
