@@ -96,6 +96,10 @@ __device__ __forceinline__ uint32_t sb_expand3(uint32_t v) {  // 10 bits -> ever
   v = (v | (v << 2)) & 0x09249249u;
   return v;
 }
+// "does any lane ...".  Cheap when p is ONE compare -- the compare then writes the lanes' answers where the branch reads
+// them; a predicate combined from several (a && b, a flag carried round a loop) is first turned into 0 / 1 per lane and
+// compared again.  The search loop below is written so that every vote on its path is of the first kind.
+__device__ __forceinline__ bool sb_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 __device__ __forceinline__ uint32_t sb_load_word(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // LDS states are read while other wavefronts of the workgroup write them, without a barrier in between
 __device__ __forceinline__ uint32_t sb_lds_state(const uint8_t* st, uint32_t q) {
@@ -197,8 +201,12 @@ __device__ __forceinline__ uint64_t sb_make_point(const SbArgs& a, const SbBlock
 __device__ __forceinline__ uint32_t sb_halo_slot(const SbLds& l, uint32_t j) {
   uint32_t lo = 0;
 #pragma unroll
-  for (uint32_t step = 128u; step; step >>= 1)
-    if (lo + step <= 216u && l.soff[lo + step] <= j) lo += step;
+  for (uint32_t step = 128u; step; step >>= 1) {
+    // (a probe beyond the table reads [216] = total > j and answers "no": a select, where "lo + step <= 216 &&" was a branch
+    // on the execution mask per step)
+    const uint32_t probe = min(lo + step, 216u);
+    lo += l.soff[probe] <= j ? step : 0u;
+  }
   return lo;
 }
 // active index of staged point q (a halo point's is looked up: only polls and compares on the original positions want it)
@@ -300,27 +308,36 @@ __device__ __forceinline__ SbOwn sb_own_point(const SbArgs& a, const SbLds& l, c
   p.corner = (ix - 1u) + 10u * (iy - 1u) + 100u * (iz - 1u);
   return p;
 }
-// squared distance of own point p to staged point word o: closer than the spacing for sure / possibly
+// squared distance of own point p to staged point word o: closer than the spacing for sure / possibly.  A lane without a
+// candidate (valid = false) compares against a bound of zero: "possibly" stays ONE compare (sb_any), and the distance is
+// computed by every lane (selecting the distance instead makes the compiler branch around the read and the arithmetic).
 template <bool WIDE>
-__device__ __forceinline__ void sb_compare(const SbArgs& a, const SbOwn& p, uint64_t o, bool& sure, bool& maybe) {
+__device__ __forceinline__ void sb_compare(const SbArgs& a, const SbOwn& p, uint64_t o, bool valid, bool& sure, bool& maybe) {
   if (WIDE) {
     uint32_t vx, vy, vz;
     sb_unpack(o, vx, vy, vz);
     const float ddx = p.fx - (float)vx, ddy = p.fy - (float)vy, ddz = p.fz - (float)vz;
     const float d2 = ddx * ddx + ddy * ddy + ddz * ddz;
     sure = d2 < a.f_lo;
-    maybe = d2 < a.f_hi;
+    maybe = d2 < (valid ? a.f_hi : 0.f);
   } else {
     const uint32_t lo = (uint32_t)o, hi = (uint32_t)(o >> 32);
     const int ddx = (int)p.ux - (int)(lo & 0xFFFFu), ddy = (int)p.uy - (int)(lo >> 16), ddz = (int)p.uz - (int)(hi & 0xFFFFu);
     const uint32_t d2 = (uint32_t)(__mul24(ddx, ddx) + __mul24(ddy, ddy) + __mul24(ddz, ddz));  // < 3 * 2^26: adjacent cells
     sure = d2 < a.i_lo;
-    maybe = d2 < a.i_hi;
+    maybe = d2 < (valid ? a.i_hi : 0u);
   }
 }
-__device__ __forceinline__ uint32_t sb_cell_offset(uint32_t b) {  // bit of the 27-cell mask -> offset in the cell index
-  const uint32_t dz = (b * 57u) >> 9, rem = b - 9u * dz, dy = (rem * 11u) >> 5, dx = rem - 3u * dy;
-  return dx + 10u * dy + 100u * dz;
+// bit b = dx + 3 dy + 9 dz of the 27-cell mask -> offset dx + 10 dy + 100 dz in the cell index = b + 7 (b / 3) + 70 (b / 9);
+// both quotients out of one 24-bit multiply: b * 11 >> 5 in the low half, b * 57 >> 9 in the high one (b < 27)
+__device__ __forceinline__ uint32_t sb_cell_offset(uint32_t b) {
+  const uint32_t x = (uint32_t)__mul24((int)b, (int)((57u << 16) | 11u));
+  return b + 7u * ((x >> 5) & 15u) + 70u * (x >> 25);
+}
+// Where the entry of the first cell of mask lies, seen from the corner of the 27 cells.  No cell left: the last of the 27,
+// an entry like any other that nobody uses -- every lane computes, nothing is branched around or selected.
+__device__ __forceinline__ uint32_t sb_next_entry(uint32_t corner, uint32_t mask) {
+  return corner + sb_cell_offset((uint32_t)__builtin_ctz(mask | (1u << 26)));
 }
 
 // Visits every EARLIER staged point closer than the spacing to own point j.  f(q) returns false to stop.  (The general
@@ -342,7 +359,7 @@ __device__ __forceinline__ void sb_visit(const SbArgs& a, const SbLds& l, const 
       if (q >= e) continue;
     }
     bool sure, maybe;
-    sb_compare<WIDE>(a, p, l.pts[q], sure, maybe);
+    sb_compare<WIDE>(a, p, l.pts[q], true, sure, maybe);
     if (maybe) {
       if (sure || sb_exact_near(a, k.first + j, sb_active_index(l, k, q))) {
         if (!f(q)) return;
@@ -352,7 +369,7 @@ __device__ __forceinline__ void sb_visit(const SbArgs& a, const SbLds& l, const 
   }
 }
 
-// The search of own point j (lanes without a point: active = false): its earlier neighbours go to mine[] (the first
+// The search of own point j (lanes without a point: have = false): its earlier neighbours go to mine[] (the first
 // SB_K), *cnt counts them -- whatever their state: the states are looked at after the loop.  One loop over all candidates
 // of the point -- a lane either takes its next cell or tests its next candidate, so the wavefront runs as long as its
 // busiest lane has candidates, not 27 x the fullest cell -- written without divergent branches: every lane executes every
@@ -361,38 +378,36 @@ __device__ __forceinline__ void sb_visit(const SbArgs& a, const SbLds& l, const 
 // bound.)  A wavefront issues an instruction every four cycles at best and every LDS read it waits for costs ~100 more, so
 // a step is kept short and has ONE read on its critical path: the candidate; the entry of the lane's next cell is requested
 // a step ahead and the neighbours' states are not read here at all.
+// A lane is busy while it has a candidate (q < e) or a cell (mask) left: no flag is carried round the loop, and what the
+// wavefront votes on -- go on?  any pair within the spacing? -- are single compares (sb_any).
 // Pairs inside the quantisation band go to the wavefront's pending list.
 template <bool WIDE>
-__device__ __forceinline__ void sb_search(const SbArgs& a, const SbLds& l, const SbBlock& k, uint32_t j, bool active, uint16_t* mine,
+__device__ __forceinline__ void sb_search(const SbArgs& a, const SbLds& l, const SbBlock& k, uint32_t j, bool have, uint16_t* mine,
                                           uint32_t* pend, uint32_t* cnt_out, uint32_t* steps) {
-  const SbOwn p = sb_own_point<WIDE>(a, l, k, active ? j : 0u);
-  uint32_t mask = active ? p.mask : 0u;
+  const SbOwn p = sb_own_point<WIDE>(a, l, k, have ? j : 0u);
+  uint32_t mask = have ? p.mask : 0u;
   uint32_t q = 0, e = 0, cnt = 0;
-  uint32_t ne2 = l.cse[mask ? p.corner + sb_cell_offset((uint32_t)__ffs((int)mask) - 1u) : 0u];  // the first cell's entry
-  while (__ballot(active)) {
+  uint32_t ne2 = l.cse[sb_next_entry(p.corner, mask)];  // the first cell's entry
+  while ((__builtin_amdgcn_ballot_w64(q < e) | __builtin_amdgcn_ballot_w64(mask != 0u)) != 0ull) {
     ++*steps;
     // lanes whose cell is used up take their next one (its entry is here already) and ask for the one after it
-    const bool need = active && q >= e;
-    const bool fetch = need && mask != 0u;
+    const bool fetch = q >= e && mask != 0u;
     const uint32_t s2 = ne2 & 0xFFFFu, t2 = ne2 >> 16;
     const uint32_t t3 = s2 < k.n_own ? min(t2, j) : t2;  // a cell of the block itself: earlier points only
     mask = fetch ? (mask & (mask - 1u)) : mask;
     q = fetch ? s2 : q;
     e = fetch ? t3 : e;
-    active = active && !(need && !fetch);
-    if (__ballot(fetch)) {
-      const uint32_t nxt = l.cse[(fetch && mask) ? p.corner + sb_cell_offset((uint32_t)__ffs((int)mask) - 1u) : 0u];
-      ne2 = fetch ? nxt : ne2;
-    }
+    // (every step: some lane of 64 takes a cell in nearly every step, and a vote and a branch around the read cost more than it)
+    const uint32_t nxt = l.cse[sb_next_entry(p.corner, mask)];
+    ne2 = fetch ? nxt : ne2;
     // lanes that have a candidate test it
-    const bool valid = active && q < e;
+    const bool valid = q < e;
     bool sure, maybe;
-    sb_compare<WIDE>(a, p, l.pts[valid ? q : 0u], sure, maybe);
-    maybe = maybe && valid;
-    if (__ballot(maybe)) {
+    sb_compare<WIDE>(a, p, l.pts[valid ? q : 0u], valid, sure, maybe);
+    if (sb_any(maybe)) {
       const bool band = maybe && !sure;
       bool near = maybe && sure;
-      if (__ballot(band)) {
+      if (sb_any(band)) {
         if (band) {
           const uint32_t slot = atomicAdd(&pend[SB_PEND], 1u);
           if (slot < (uint32_t)SB_PEND) pend[slot] = (j << 16) | q;
@@ -422,7 +437,10 @@ template <bool WIDE>
 __global__ __launch_bounds__(SB_THREADS, SB_MINW) void sb_block_kernel(SbArgs a) {
   extern __shared__ __align__(16) unsigned char sb_smem[];
   const SbLds l = sb_carve(sb_smem, a.own_cap, a.halo_cap);
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  // (read from the first lane: the compiler then knows that a wavefront's share of the block [ja, jb), its loops over it and
+  // its pending list are the same in every lane, and keeps them in scalar registers and scalar branches)
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
   const uint32_t nb_per_node = 1u << (3u * (a.cl - 3u));
   const uint32_t gmax = 1u << (a.cl - 1u);
   const uint64_t gran_per_node = 1ull << (3u * (a.cl - 1u));
@@ -668,7 +686,7 @@ __global__ __launch_bounds__(SB_THREADS, SB_MINW) void sb_block_kernel(SbArgs a)
         const bool have = j < jb;
         uint32_t cur = have ? sb_lds_state(l.st, j) : (uint32_t)SB_R;  // this lane's state as the other lanes see it
         const bool und = have && cur == SB_U;
-        if (!__ballot(und)) continue;
+        if (!sb_any(und)) continue;
         // the recorded neighbours: those among the 64 points of this round are read from the lanes' registers (shuffles,
         // below), the others -- earlier rounds, other wavefronts, the halo -- from the LDS states, once per pass
         static_assert(SB_K == 4, "four two-byte entries = one eight-byte load");
@@ -720,7 +738,7 @@ __global__ __launch_bounds__(SB_THREADS, SB_MINW) void sb_block_kernel(SbArgs a)
               changed = true;
             }
           }
-          if (!__ballot(changed)) break;
+          if (!sb_any(changed)) break;
         }
         if (und && cur == SB_U && cnt > (uint32_t)SB_K && !ext_u && !in_u_last) {
           // more neighbours than were recorded, and the recorded ones have all been rejected: search again (rare)
@@ -743,7 +761,7 @@ __global__ __launch_bounds__(SB_THREADS, SB_MINW) void sb_block_kernel(SbArgs a)
           remaining = true;
         }
       }
-      const bool any_progress = __ballot(progress) != 0, any_remaining = __ballot(remaining) != 0;
+      const bool any_progress = sb_any(progress), any_remaining = sb_any(remaining);
       if (lane == 0) ++my_iters;
       to_publish |= any_progress;
       if (any_progress && any_remaining && !poll) continue;  // the chains inside the wavefront's own points first
@@ -763,7 +781,7 @@ __global__ __launch_bounds__(SB_THREADS, SB_MINW) void sb_block_kernel(SbArgs a)
       }
       // nothing decided in this pass: the wavefront waits for other wavefronts of its workgroup (their decisions show up in
       // the LDS states) or for earlier blocks (the next pass asks the state array: a global round trip)
-      poll = __ballot(halo_wait) != 0;
+      poll = sb_any(halo_wait);
       ++idle;
       if (lane == 0) ++my_waits;
       if (idle > 1u) __builtin_amdgcn_s_sleep(4);
@@ -825,26 +843,44 @@ struct SbTabArgs {
   uint64_t gran_per_node;
   uint2* gtab;
 };
-__device__ __forceinline__ uint64_t sb_granule_of(const SbTabArgs& t, uint32_t i) {  // ~0: the point's node is not sampled
-  uint32_t sn;
-  if (t.sn_direct) {
-    sn = t.sn_direct[i];
+// A run of equal key >> gran_shift inside a sampled node is a granule (nodes are prefixes of granules: a run never crosses a
+// node's end); its first point writes the start, its last one the end.  Four consecutive points per thread: the keys in
+// 16-byte loads (vec: they are 16-byte aligned), the neighbours' keys once (cache hits), and the point's node -- nid, nmode,
+// snode_of, or sn_direct -- looked up only where a run begins or ends.
+__global__ __launch_bounds__(256) void sb_table_kernel(SbTabArgs t, uint32_t vec) {
+  const uint64_t i0 = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 4u;
+  if (i0 >= t.m) return;
+  const uint32_t n = t.m - i0 < 4u ? (uint32_t)(t.m - i0) : 4u;
+  uint64_t key[6];  // [0]: the point in front of the four, [5]: the one behind them
+  if (vec && n == 4u) {
+    const ulonglong2 v0 = *reinterpret_cast<const ulonglong2*>(t.akey + i0), v1 = *reinterpret_cast<const ulonglong2*>(t.akey + i0 + 2);
+    key[1] = v0.x, key[2] = v0.y, key[3] = v1.x, key[4] = v1.y;
   } else {
-    const uint32_t node = t.nid[i];
-    if (!t.all_sampled && t.nmode[node] != MODE_SAMPLE) return ~0ull;
-    sn = t.all_sampled ? node : t.snode_of[node];
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) key[1 + j] = j < n ? t.akey[i0 + j] : 0ull;
   }
-  return (uint64_t)sn * t.gran_per_node + ((t.akey[i] >> t.gran_shift) & (t.gran_per_node - 1ull));
-}
-__global__ __launch_bounds__(256) void sb_table_kernel(SbTabArgs t) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= t.m) return;
-  const uint64_t g = sb_granule_of(t, i);
-  if (g == ~0ull) return;
-  const bool head = i == 0 || sb_granule_of(t, i - 1) != g;
-  const bool tail = i + 1 == t.m || sb_granule_of(t, i + 1) != g;
-  if (head) t.gtab[g].x = i;
-  if (tail) t.gtab[g].y = i + 1u;
+  key[0] = i0 ? t.akey[i0 - 1u] : 0ull;
+  key[5] = i0 + 4u < t.m ? t.akey[i0 + 4u] : 0ull;
+#pragma unroll
+  for (uint32_t j = 0; j < 4u; ++j) {
+    if (j >= n) break;
+    const uint32_t i = (uint32_t)i0 + j;
+    const uint64_t pre = key[1 + j] >> t.gran_shift;
+    const bool head = i == 0u || (key[j] >> t.gran_shift) != pre;
+    const bool tail = i + 1u == t.m || (key[2 + j] >> t.gran_shift) != pre;
+    if (!head && !tail) continue;
+    uint32_t sn;
+    if (t.sn_direct) {
+      sn = t.sn_direct[i];
+    } else {
+      const uint32_t node = t.nid[i];
+      if (!t.all_sampled && t.nmode[node] != MODE_SAMPLE) continue;  // the point's node is not sampled
+      sn = t.all_sampled ? node : t.snode_of[node];
+    }
+    const uint64_t g = (uint64_t)sn * t.gran_per_node + (pre & (t.gran_per_node - 1ull));
+    if (head) t.gtab[g].x = i;
+    if (tail) t.gtab[g].y = i + 1u;
+  }
 }
 
 // What one run of the block kernel works on: the level's active points, or the subset of them that new points can change.
@@ -978,7 +1014,7 @@ static int sb_run(swz_ctx* c, const MdLevel& L, const SbInput& in, bool* done) {
     SWZ_HIP(c, memset_large(t.gtab, 0, (size_t)entries * sizeof(uint2), c->stream));
     SWZ_HIP(c, hipMemsetAsync(a.st2, 0, ((size_t)in.m / 16 + 2) * sizeof(uint32_t), c->stream));
     SWZ_HIP(c, hipMemsetAsync(a.ctr, 0, (size_t)(SB_NC * SB_CTR_STRIDE + SBW_COUNT) * sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(sb_table_kernel, dim3(div_up(in.m, 256)), dim3(256), 0, c->stream, t);
+    hipLaunchKernelGGL(sb_table_kernel, dim3(div_up(in.m, 1024)), dim3(256), 0, c->stream, t, ((uintptr_t)t.akey & 15u) == 0 ? 1u : 0u);
     SWZ_LAUNCH_CHECK(c);
     // (every time: the attribute belongs to the function on the CURRENT device, and a process may drive several)
     const bool wide = a.cell_bits > 12u || c->opt_on("SWZ_SP_BLOCK_WIDE", false);  // a region of ten cells must fit sixteen bits
