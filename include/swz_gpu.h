@@ -312,6 +312,69 @@ int swz_tileset_build(uint64_t num_nodes, const int8_t* node_level, const uint64
                       const double root_max[3], float spacing_at_root, const double global_offset[3], uint64_t max_out,
                       swz_tileset_node* out, uint64_t* num_out);
 
+/* ---- 3D Tiles node files and tileset JSON: Cesium3DTilesPersistence, the reference's default persistence
+ * (executable/main.cpp:241-242; core/io/Cesium3DTilesPersistence.cpp:53-210, core/io/PNTSWriter.cpp:109-264).
+ * A "<name>.pnts" file is a 28-byte header ("pnts", u32 version 1, u32 byteLength, u32 JSON length, u32 binary length,
+ * u32 0, u32 0), the feature-table JSON {POINTS_LENGTH, RTC_CENTER, then {"byteOffset"} per array} padded with spaces to a
+ * multiple of 8 counted from the start of the JSON (PNTSWriter.cpp:241-258), and the feature-table binary, the BODY: every
+ * array at the running offset rounded up to its alignment, the whole zero-padded to a multiple of 8 (:198-213).
+ * supported_output_attributes() is Position, RGB, Intensity: POSITION 3 x f32 (alignment 4; the PointBuffer's positions
+ * narrowed with static_cast<float>, NOT shifted by RTC_CENTER, which only carries the persistence's global_offset), RGB
+ * 3 x u8 (1), INTENSITY u16 (2).  The reference iterates an unordered_set, so it defines no order of the arrays; here it is
+ * POSITION, RGB, INTENSITY, and the JSON carries every offset.  `mask` says which arrays besides POSITION a file holds.
+ * Numbers in JSON are written in the shortest text that parses back to the same double.  rapidjson's Grisu2 does not always
+ * find the shortest form, so a file agrees with the reference's in every parsed value and in every byte of the binary, but
+ * not necessarily in the length of the JSON text (the spelling of a number is no part of either format).
+ * --calculate-rgb-from (RGBFromIntensityAttribute, PNTSWriter.cpp:507-527): with a mapping RGB is the grey value of the
+ * point's intensity (LINEAR: intensity >> 8; LOG: (uint8_t)(255 * logf(intensity + 1.f) / log(65535.)), a float numerator
+ * divided in double), written whether or not the batch has a colour column, and only if it has intensities.  The 65 536 grey
+ * values are evaluated once, on the host, with the host's libm (like swz_required_morton_index_depth).
+ *   swz_pnts_layout (host): size and offset of every node's body in one contiguous IMAGE (bodies in table order, each a
+ *     multiple of 8; a node of count 0 has size 0), the offsets of the RGB and intensity arrays inside a body (0 when absent),
+ *     and the image's total size.  Any output may be NULL.
+ *   swz_pnts_pack_device: writes the image of a node table into d_image_out (device, 8-byte aligned, image_bytes >= the
+ *     layout's total) in one pass: the permuted gather (row i = row d_perm[d_order[i]] of d_xyz and of the columns of d_in,
+ *     composed as in swz_gather_payload_device; d_order NULL = identity, what a tiler's export ids need), the narrowing, the
+ *     colour mapping and the layout, padding included -- no byte of the image depends on what the buffer held, the caller
+ *     need not clear it.  node_offset / node_count (host) are rows of the gathered order.  SWZ_ERR_BAD_ARG before anything
+ *     is launched for: offsets that do not ascend, ranges that overlap or pass n, a mask that names an absent column, a
+ *     mapping without the intensity column, n above 2^32 - 65536.  n == 0 or no nodes is valid and launches nothing.
+ *   swz_pnts_write_node: one file from a packed body (count == 0 writes nothing, like swz_bin_write_node); rtc_center NULL
+ *     = zeros.  swz_pnts_write_node_rows: the same file from unpacked rows (double positions + columns, what a PointsSink
+ *     receives), converted on the host.  swz_pnts_persist_nodes: one file "r" + octant digits + ".pnts" per node of a table
+ *     out of a HOST copy of the image, written by the pool of host threads of swz_bin_persist_nodes.
+ *   swz_pnts_read_header / swz_pnts_read_node: retrieve_points.  Positions come back as the stored floats widened to double
+ *     (the format is lossy), RGB and intensity into the non-NULL columns if the file has them.  The arrays are found through
+ *     the offsets in the file's JSON, whatever their order.  SWZ_ERR_BAD_ARG, without reading outside the file, for a short
+ *     file, a wrong magic, lengths that do not add up, an array that passes the binary, a JSON that cannot be read.
+ *   swz_tileset_write: the JSON files of swz_tileset_build's output (write_tilesets, Cesium3DTilesPersistence.cpp:173-210;
+ *     writeTilesetJSON, core/io/TileSetWriter.cpp:42-210): "<name>.json" per is_tileset_root entry with asset.version "0.0",
+ *     the entry's geometricError and its tile as root.  A tile holds boundingVolume.box = [centre, then the FULL extent on the
+ *     diagonal] (boundingBoxFromAABB, core/pointcloud/Tileset.cpp:94-118: not halved), geometricError, refine "ADD",
+ *     content.uri and children (by octant); three levels below the file's root the uri is "<name>.json" and there are no
+ *     children, everywhere else "<name>.pnts" -- for ancestors without a file of their own too, as setup_tileset does.
+ *     Compact, no whitespace.
+ * The host functions need no GPU; their ctx only carries the error text and may be NULL. */
+enum { SWZ_PNTS_RGB = 1u << SWZ_ATTR_RGB, SWZ_PNTS_INTENSITY = 1u << SWZ_ATTR_INTENSITY };
+enum { SWZ_PNTS_RGB_FROM_COLOR = 0, SWZ_PNTS_RGB_FROM_INTENSITY_LINEAR = 1, SWZ_PNTS_RGB_FROM_INTENSITY_LOG = 2 };
+int swz_pnts_layout(uint64_t num_nodes, const uint64_t* node_count, uint32_t mask, int rgb_mapping, uint64_t* body_offset_out,
+                    uint64_t* body_size_out, uint64_t* rgb_offset_out, uint64_t* intensity_offset_out, uint64_t* total_out);
+int swz_pnts_pack_device(swz_ctx* ctx, const uint32_t* d_perm, const uint32_t* d_order, uint64_t n, const double* d_xyz,
+                         const swz_attribute_columns* d_in, uint64_t num_nodes, const uint64_t* node_offset,
+                         const uint64_t* node_count, uint32_t mask, int rgb_mapping, void* d_image_out, uint64_t image_bytes);
+int swz_pnts_write_node(swz_ctx* ctx, const char* path, uint64_t count, const void* body, uint64_t body_bytes, uint32_t mask,
+                        const double rtc_center[3]);
+int swz_pnts_write_node_rows(swz_ctx* ctx, const char* path, uint64_t count, const double* xyz,
+                             const swz_attribute_columns* columns, uint32_t mask, int rgb_mapping, const double rtc_center[3]);
+int swz_pnts_persist_nodes(swz_ctx* ctx, const char* dir, uint64_t num_nodes, const int8_t* node_level, const uint64_t* node_key,
+                           const uint64_t* node_count, const void* image, uint64_t image_bytes, uint32_t mask,
+                           const double rtc_center[3]);
+int swz_pnts_read_header(swz_ctx* ctx, const char* path, uint64_t* count_out, uint32_t* mask_out, double rtc_center_out[3]);
+int swz_pnts_read_node(swz_ctx* ctx, const char* path, double* xyz_out, const swz_attribute_columns* columns_out);
+/* one value of the grey table (0 for SWZ_PNTS_RGB_FROM_COLOR) */
+uint8_t swz_pnts_rgb_from_intensity(int rgb_mapping, uint16_t intensity);
+int swz_tileset_write(swz_ctx* ctx, const swz_tileset_node* nodes, uint64_t num, const char* dir);
+
 /* ---- LAS point records -> positions + attribute columns: the step right in
  * front of the path.  The reference reads points through LASzip into a laszip_point and converts them in
  * position_from_las_point (core/io/LASFile.cpp:79-94: offset + X * scale per axis, then clamped into the

@@ -236,6 +236,101 @@ def bin_read_node(path, compressed=False):
     return xyz, keep
 
 
+# 3D Tiles node files (include/swz_gpu.h, swz_pnts_*): the arrays a .pnts file may hold besides POSITION, and how RGB is made
+PNTS_RGB, PNTS_INTENSITY = 1 << 0, 1 << 2
+RGB_FROM_COLOR, RGB_FROM_INTENSITY_LINEAR, RGB_FROM_INTENSITY_LOG = 0, 1, 2
+
+
+def _pnts_mask(attrs):
+    """("rgb", "intensity") or a mask  =>  mask"""
+    if isinstance(attrs, (int, np.integer)):
+        return int(attrs)
+    mask = 0
+    for name in attrs or ():
+        if name not in ("rgb", "intensity"):
+            raise ValueError("a .pnts file holds rgb and intensity besides the positions, not %r" % (name,))
+        mask |= PNTS_RGB if name == "rgb" else PNTS_INTENSITY
+    return mask
+
+
+def pnts_layout(counts, attrs=(), rgb_from=RGB_FROM_COLOR):
+    """swz_pnts_layout: where every node's .pnts body lies in one contiguous image.  Returns a dict of per-node arrays
+    offset / size / rgb_offset / intensity_offset and the image's total size."""
+    cnt = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    m = cnt.shape[0]
+    out = {k: np.empty(m, dtype=np.uint64) for k in ("offset", "size", "rgb_offset", "intensity_offset")}
+    total = C.c_uint64()
+    st = load_library().swz_pnts_layout(m, cnt.ctypes.data_as(_u64p), _pnts_mask(attrs), int(rgb_from),
+                                        out["offset"].ctypes.data_as(_u64p), out["size"].ctypes.data_as(_u64p),
+                                        out["rgb_offset"].ctypes.data_as(_u64p), out["intensity_offset"].ctypes.data_as(_u64p),
+                                        C.byref(total))
+    if st != 0:
+        raise SwzError(st, "swz_pnts_layout failed")
+    out["total"] = int(total.value)
+    return out
+
+
+def pnts_rgb_from_intensity(rgb_from, intensity):
+    """One value of the grey table of --calculate-rgb-from (PNTSWriter.cpp:507-527)."""
+    return int(load_library().swz_pnts_rgb_from_intensity(int(rgb_from), int(intensity)))
+
+
+def pnts_write_node(path, count, body, attrs=(), rtc_center=None):
+    """One .pnts file from a packed body (a slice of the image pnts_pack_device wrote; host only)."""
+    b = np.ascontiguousarray(body, dtype=np.uint8).reshape(-1)
+    rtc = _vec3(rtc_center) if rtc_center is not None else None
+    st = load_library().swz_pnts_write_node(None, os.fsencode(path), int(count), b.ctypes.data, b.shape[0], _pnts_mask(attrs), rtc)
+    if st != 0:
+        raise SwzError(st, "swz_pnts_write_node(%s) failed" % path)
+
+
+def pnts_write_node_rows(path, xyz, attrs=None, write=None, rgb_from=RGB_FROM_COLOR, rtc_center=None):
+    """The same file from unpacked rows: double positions plus the columns of attrs (dict name -> array), converted on the
+    host.  write: the arrays to put into the file (default: what attrs holds of rgb / intensity)."""
+    x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    cols, keep = _host_columns(attrs, x.shape[0])
+    if write is None:
+        write = [k for k in ("rgb", "intensity") if k in (attrs or {})]
+    rtc = _vec3(rtc_center) if rtc_center is not None else None
+    st = load_library().swz_pnts_write_node_rows(None, os.fsencode(path), x.shape[0], x.ctypes.data_as(_dp), C.byref(cols),
+                                                 _pnts_mask(write), int(rgb_from), rtc)
+    if st != 0:
+        raise SwzError(st, "swz_pnts_write_node_rows(%s) failed" % path)
+
+
+def pnts_read_node(path):
+    """retrieve_points of a .pnts file: (xyz as float64 of the stored floats, dict of rgb / intensity if present, RTC_CENTER)."""
+    L = load_library()
+    mask, count, rtc = C.c_uint32(), C.c_uint64(), (C.c_double * 3)()
+    st = L.swz_pnts_read_header(None, os.fsencode(path), C.byref(count), C.byref(mask), rtc)
+    if st != 0:
+        raise SwzError(st, "swz_pnts_read_header(%s) failed" % path)
+    n = int(count.value)
+    xyz = np.empty((n, 3), dtype=np.float64)
+    out = {}
+    if mask.value & PNTS_RGB:
+        out["rgb"] = np.empty((n, 3), dtype=np.uint8)
+    if mask.value & PNTS_INTENSITY:
+        out["intensity"] = np.empty(n, dtype=np.uint16)
+    cols, keep = _host_columns(out, n)
+    st = L.swz_pnts_read_node(None, os.fsencode(path), xyz.ctypes.data_as(_dp), C.byref(cols))
+    if st != 0:
+        raise SwzError(st, "swz_pnts_read_node(%s) failed" % path)
+    return xyz, keep, list(rtc)
+
+
+def tileset_write(tiles, directory):
+    """swz_tileset_write: the tileset JSON files of tileset_build's output (the list of dicts it returns)."""
+    buf = (_TilesetNode * max(len(tiles), 1))()
+    for t, d in zip(buf, tiles):
+        t.level, t.key, t.has_content, t.is_tileset_root = d["level"], d["key"], int(d["has_content"]), int(d["is_tileset_root"])
+        t.num_children, t.parent, t.first_child, t.geometric_error = d["num_children"], d["parent"], d["first_child"], d["geometric_error"]
+        t.bounds_min, t.bounds_max = _vec3(d["bounds_min"]), _vec3(d["bounds_max"])
+    st = load_library().swz_tileset_write(None, buf, len(tiles), os.fsencode(directory))
+    if st != 0:
+        raise SwzError(st, "swz_tileset_write(%s) failed" % directory)
+
+
 def library_path():
     return os.environ.get("SWZ_GPU_LIBRARY", os.path.join(_HERE, "lib", "libswz_gpu.so"))
 
@@ -325,6 +420,20 @@ def load_library():
     L.swz_tileset_build.argtypes = [C.c_uint64, _i8p, _u64p, _dp, _dp, C.c_float, _dp, C.c_uint64,
                                     C.POINTER(_TilesetNode), _u64p]
     L.swz_tileset_build.restype = C.c_int
+    L.swz_pnts_layout.argtypes = [C.c_uint64, _u64p, C.c_uint32, C.c_int, _u64p, _u64p, _u64p, _u64p, _u64p]
+    L.swz_pnts_pack_device.argtypes = [vp, vp, vp, C.c_uint64, vp, cols, C.c_uint64, _u64p, _u64p, C.c_uint32, C.c_int, vp,
+                                       C.c_uint64]
+    L.swz_pnts_write_node.argtypes = [vp, C.c_char_p, C.c_uint64, vp, C.c_uint64, C.c_uint32, _dp]
+    L.swz_pnts_write_node_rows.argtypes = [vp, C.c_char_p, C.c_uint64, _dp, cols, C.c_uint32, C.c_int, _dp]
+    L.swz_pnts_persist_nodes.argtypes = [vp, C.c_char_p, C.c_uint64, _i8p, _u64p, _u64p, vp, C.c_uint64, C.c_uint32, _dp]
+    L.swz_pnts_read_header.argtypes = [vp, C.c_char_p, _u64p, _u32p, _dp]
+    L.swz_pnts_read_node.argtypes = [vp, C.c_char_p, _dp, cols]
+    L.swz_pnts_rgb_from_intensity.argtypes = [C.c_int, C.c_uint16]
+    L.swz_pnts_rgb_from_intensity.restype = C.c_uint8
+    L.swz_tileset_write.argtypes = [vp, C.POINTER(_TilesetNode), C.c_uint64, C.c_char_p]
+    for name in ("swz_pnts_layout", "swz_pnts_pack_device", "swz_pnts_write_node", "swz_pnts_write_node_rows",
+                 "swz_pnts_persist_nodes", "swz_pnts_read_header", "swz_pnts_read_node", "swz_tileset_write"):
+        getattr(L, name).restype = C.c_int
     L.swz_las_decode_device.argtypes = [vp, vp, C.c_uint64, C.POINTER(_LasLayout), vp, cols]
     L.swz_partition_by_octant_device.argtypes = [vp, vp, C.c_uint64, vp, _u64p]
     L.swz_shard_begin_device.argtypes = [vp, vp, C.c_uint64, _dp, _dp, C.POINTER(_TileParams), C.POINTER(_ShardInfo),
@@ -629,6 +738,27 @@ class Context:
                                                     nk.ctypes.data_as(_u64p), no.ctypes.data_as(_u64p),
                                                     nc.ctypes.data_as(_u64p), x.ctypes.data_as(_dp), C.byref(cols),
                                                     int(bool(compressed))))
+
+    def pnts_pack_device(self, d_perm, d_order, n, d_xyz, d_attrs, nodes, d_image, image_bytes, attrs=(), rgb_from=RGB_FROM_COLOR):
+        """swz_pnts_pack_device: the .pnts bodies of all nodes of a table, laid out as pnts_layout says, written into
+        d_image (device, image_bytes bytes) in one pass.  d_order None = identity (a tiler's export ids as d_perm)."""
+        cin = device_columns(d_attrs)
+        no = np.ascontiguousarray(nodes["offset"], dtype=np.uint64)
+        nc = np.ascontiguousarray(nodes["count"], dtype=np.uint64)
+        self._check(self._lib.swz_pnts_pack_device(self._ctx, C.c_void_p(d_perm), C.c_void_p(d_order), int(n), C.c_void_p(d_xyz),
+                                                   C.byref(cin), nc.shape[0], no.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p),
+                                                   _pnts_mask(attrs), int(rgb_from), C.c_void_p(d_image), int(image_bytes)))
+
+    def pnts_persist_nodes(self, directory, nodes, image, attrs=(), rtc_center=None):
+        """One .pnts file per node of a node table out of a host copy of the image pnts_pack_device wrote."""
+        img = np.ascontiguousarray(image, dtype=np.uint8).reshape(-1)
+        nl = np.ascontiguousarray(nodes["level"], dtype=np.int8)
+        nk = np.ascontiguousarray(nodes["key"], dtype=np.uint64)
+        nc = np.ascontiguousarray(nodes["count"], dtype=np.uint64)
+        rtc = _vec3(rtc_center) if rtc_center is not None else None
+        self._check(self._lib.swz_pnts_persist_nodes(self._ctx, os.fsencode(directory), nl.shape[0], nl.ctypes.data_as(_i8p),
+                                                     nk.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p), img.ctypes.data, img.shape[0],
+                                                     _pnts_mask(attrs), rtc))
 
     # ------------------------------------------------------------------ sharded batches (one context per GPU)
     def partition_by_octant_device(self, d_keys, n, d_perm):

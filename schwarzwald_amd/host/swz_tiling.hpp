@@ -176,6 +176,87 @@ struct PointsSink {
   }
 };
 
+// Cesium3DTilesPersistence (core/io/Cesium3DTilesPersistence.cpp:53-210), the reference's default persistence, as a sink:
+// every node becomes "<work_dir>/<name>.pnts" (swz_pnts_write_node_rows: positions narrowed to float and not shifted,
+// RTC_CENTER = global_offset; RGB and intensity when the rows carry them), the sink remembers the names it wrote, and
+// write_tilesets() -- called by the destructor if nobody did, like the reference's -- writes the tileset JSON files of
+// those nodes and their ancestors (swz_tileset_build + swz_tileset_write).  rgb_mapping: --calculate-rgb-from
+// (SWZ_PNTS_RGB_FROM_*): with a mapping RGB is the grey value of the intensity, written only if the rows have intensities.
+// persist_points receives ids and positions only, so its files hold POSITION alone.
+class Cesium3DTilesSink : public PointsSink {
+public:
+  Cesium3DTilesSink(std::string work_dir, const AABB& root_bounds, float spacing_at_root, Vector3d global_offset = {},
+                    int rgb_mapping = SWZ_PNTS_RGB_FROM_COLOR)
+    : _work_dir(std::move(work_dir)), _root_bounds(root_bounds), _spacing_at_root(spacing_at_root),
+      _offset{global_offset.x, global_offset.y, global_offset.z}, _rgb_mapping(rgb_mapping) {}
+  ~Cesium3DTilesSink() override {
+    if (!_tilesets_written) {
+      try {
+        write_tilesets();
+      } catch (...) {  // a destructor reports nothing; call write_tilesets() to see the error
+      }
+    }
+  }
+  Cesium3DTilesSink(const Cesium3DTilesSink&) = delete;
+  Cesium3DTilesSink& operator=(const Cesium3DTilesSink&) = delete;
+
+  void persist_points(const uint32_t* ids_begin, const uint32_t* ids_end, const double* positions, const AABB& node_bounds,
+                      const std::string& node_name) override {
+    persist_rows(static_cast<size_t>(ids_end - ids_begin), positions, swz_attribute_columns{}, node_bounds, node_name);
+  }
+  void persist_rows(size_t count, const double* positions, const swz_attribute_columns& attributes, const AABB&,
+                    const std::string& node_name) override {
+    if (count == 0) throw std::runtime_error{"persist_points requires a non-empty range"};  // Cesium3DTilesPersistence.cpp:58-60
+    const bool has_intensity = attributes.column[SWZ_ATTR_INTENSITY] != nullptr;
+    const bool mapped = _rgb_mapping != SWZ_PNTS_RGB_FROM_COLOR;
+    uint32_t mask = has_intensity ? SWZ_PNTS_INTENSITY : 0u;
+    if (mapped ? has_intensity : attributes.column[SWZ_ATTR_RGB] != nullptr) mask |= SWZ_PNTS_RGB;
+    const std::string path = _work_dir + "/" + node_name + ".pnts";
+    if (swz_pnts_write_node_rows(nullptr, path.c_str(), count, positions, &attributes, mask,
+                                 (mapped && has_intensity) ? _rgb_mapping : SWZ_PNTS_RGB_FROM_COLOR, _offset) != SWZ_OK)
+      throw std::runtime_error{"Could not write .pnts file \"" + path + "\""};
+    _node_names.push_back(node_name);
+  }
+
+  // the names of the nodes written so far, in the order they arrived
+  const std::vector<std::string>& node_names() const { return _node_names; }
+
+  void write_tilesets() {
+    _tilesets_written = true;
+    if (_node_names.empty()) return;
+    std::vector<int8_t> level(_node_names.size());
+    std::vector<uint64_t> key(_node_names.size());
+    for (size_t j = 0; j < _node_names.size(); ++j) {  // "r" + octant digits
+      const std::string& name = _node_names[j];
+      if (name.empty() || name[0] != 'r' || name.size() > MortonIndex64Levels + 1)
+        throw std::runtime_error{"not a node name: \"" + name + "\""};
+      level[j] = static_cast<int8_t>(static_cast<int>(name.size()) - 2);
+      for (size_t l = 1; l < name.size(); ++l) {
+        if (name[l] < '0' || name[l] > '7') throw std::runtime_error{"not a node name: \"" + name + "\""};
+        key[j] |= static_cast<uint64_t>(name[l] - '0') << ((MortonIndex64Levels - l) * 3);
+      }
+    }
+    const double mn[3] = {_root_bounds.min.x, _root_bounds.min.y, _root_bounds.min.z};
+    const double mx[3] = {_root_bounds.max.x, _root_bounds.max.y, _root_bounds.max.z};
+    uint64_t num = 0;
+    if (swz_tileset_build(level.size(), level.data(), key.data(), mn, mx, _spacing_at_root, _offset, 0, nullptr, &num) != SWZ_OK)
+      throw std::runtime_error{"swz_tileset_build failed"};
+    std::vector<swz_tileset_node> tiles(num);
+    if (swz_tileset_build(level.size(), level.data(), key.data(), mn, mx, _spacing_at_root, _offset, num, tiles.data(), &num) != SWZ_OK ||
+        swz_tileset_write(nullptr, tiles.data(), num, _work_dir.c_str()) != SWZ_OK)
+      throw std::runtime_error{"Error writing tileset JSON to \"" + _work_dir + "\""};
+  }
+
+private:
+  std::string _work_dir;
+  AABB _root_bounds;
+  float _spacing_at_root;
+  double _offset[3];
+  int _rgb_mapping;
+  std::vector<std::string> _node_names;
+  bool _tilesets_written = false;
+};
+
 // The shape of TilingAlgorithmBase (core/tiling/TilingAlgorithms.h:70-116): one object per Tiler, fed one batch at
 // a time (Tiler.cpp:509-510), finalize() once at the end.  tile_batch() is what the single task emitted by
 // build_execution_graph() runs.  Unlike the reference, which rewrites the files of every node a batch reaches
