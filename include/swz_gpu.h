@@ -411,7 +411,8 @@ int swz_las_decode_device(swz_ctx* ctx, const uint8_t* d_records, uint64_t n, co
  * process); the exchange itself (RCCL all-to-all) is done by the host driver, the library provides
  * the device-side pieces:
  *   swz_partition_by_octant_device: perm groups point indices by octant 0..7 (stable inside an
- *     octant); counts_out[o] = points of octant o.
+ *     octant); counts_out[o] = points of octant o.  Drivers may rely on the order (octant, original
+ *     index): the key bits below the octant play no part, and points of equal key keep their index order.
  *   swz_shard_begin_device: indexes + sorts the shard's points (d_xyz_local stays referenced until
  *     swz_shard_finish_device returns and may be clamped in place) and samples the ROOT node, whose
  *     take-all/sample decision uses shard->global_points.  For MIN_DISTANCE the root couples the

@@ -221,8 +221,9 @@ int shard_fast_root_candidates_device(swz_ctx* c, uint64_t* d_keys_out, double* 
 int shard_fast_set_root_device(swz_ctx* c, const uint8_t* d_taken);
 int shard_fast_finish_device(swz_ctx* c, uint64_t* d_keys_out, uint32_t* d_perm_out, int8_t* d_level_out, uint32_t* d_dup_out,
                              swz_tile_stats* stats);
-// One radix pass on the top key digit: perm groups the points by octant (stable); octants (host)
-// receives the eight counts.
+// One radix pass on the octant (key bits 60..62): perm groups the points by octant (stable); octants (host)
+// receives the eight counts.  Callers may rely on the order (octant, original index): points of equal key keep
+// their index order.
 int partition_top_digit(swz_ctx* c, const uint64_t* d_keys, uint32_t n, uint32_t* d_perm_out, uint64_t octants[8]);
 // Stable partition by the top byte of the keys: d_perm_out[i] = index of the i-th element, starts[d] = first
 // position of byte value d.

@@ -733,7 +733,8 @@ __global__ __launch_bounds__(RADIX) void digit_starts_kernel(const uint32_t* __r
   out[threadIdx.x] = offs[(uint64_t)threadIdx.x * ntiles];
 }
 
-int partition_by_top_byte(swz_ctx* c, const uint64_t* d_keys, uint32_t n, uint32_t* d_perm_out, uint32_t starts[256]) {
+// one stable pass on the digit (key >> shift) & 255: histogram, scan, scatter of the identity permutation
+static int partition_by_digit(swz_ctx* c, const uint64_t* d_keys, uint32_t n, int shift, uint32_t* d_perm_out, uint32_t starts[256]) {
   static_assert(RADIX == 256, "one radix digit is one byte");
   for (int d = 0; d < RADIX; ++d) starts[d] = 0;
   if (n == 0) return SWZ_OK;
@@ -743,7 +744,6 @@ int partition_by_top_byte(swz_ctx* c, const uint64_t* d_keys, uint32_t n, uint32
   SWZ_TRY(c->get("radix_hist", (size_t)ntiles * RADIX, &d_hist));
   SWZ_TRY(c->get("part_starts", (size_t)RADIX, &d_starts));
   SWZ_TRY(c->get("part_keys", (size_t)n, &d_keys_tmp));
-  const int shift = 64 - RADIX_BITS;
   hipLaunchKernelGGL(radix_hist_kernel, dim3(ntiles), dim3(RS_THREADS), 0, c->stream, d_keys, n, shift, d_hist, ntiles);
   SWZ_LAUNCH_CHECK(c);
   SWZ_TRY(scan_exclusive_u32(c, d_hist, d_hist, (uint64_t)ntiles * RADIX, nullptr, "radix"));
@@ -757,14 +757,18 @@ int partition_by_top_byte(swz_ctx* c, const uint64_t* d_keys, uint32_t n, uint32
   return SWZ_OK;
 }
 
-// the octant (key bits 60..62) is the top digit's bits below the unused bit 63
+int partition_by_top_byte(swz_ctx* c, const uint64_t* d_keys, uint32_t n, uint32_t* d_perm_out, uint32_t starts[256]) {
+  return partition_by_digit(c, d_keys, n, 64 - RADIX_BITS, d_perm_out, starts);
+}
+
+// the octant is key bits 60..62 (bit 63 is unused): the digit at shift 60 is the octant itself, so the order is
+// (octant, original index) whatever the bits below say
 int partition_top_digit(swz_ctx* c, const uint64_t* d_keys, uint32_t n, uint32_t* d_perm_out, uint64_t octants[8]) {
   for (int o = 0; o < 8; ++o) octants[o] = 0;
   if (n == 0) return SWZ_OK;
   uint32_t starts[RADIX];
-  SWZ_TRY(partition_by_top_byte(c, d_keys, n, d_perm_out, starts));
-  for (int d = 0; d < RADIX; ++d)
-    octants[(d >> (RADIX_BITS - 4)) & 7] += (uint64_t)((d == RADIX - 1 ? n : starts[d + 1]) - starts[d]);
+  SWZ_TRY(partition_by_digit(c, d_keys, n, 60, d_perm_out, starts));
+  for (int d = 0; d < RADIX; ++d) octants[d & 7] += (uint64_t)((d == RADIX - 1 ? n : starts[d + 1]) - starts[d]);
   return SWZ_OK;
 }
 
