@@ -168,8 +168,17 @@ int swz::read_u32(swz_ctx* c, const uint32_t* d, uint32_t* h) {
   return SWZ_OK;
 }
 
+int swz::check_params(swz_ctx* c, const swz_tile_params* p) {
+  if (!p) return c->fail(SWZ_ERR_BAD_ARG, "params must not be NULL");
+  if (p->sampler < SWZ_RANDOM_GRID || p->sampler > SWZ_JITTERED) return c->fail(SWZ_ERR_BAD_ARG, "unknown sampler");
+  if (p->strategy != SWZ_ACCURATE && p->strategy != SWZ_FAST) return c->fail(SWZ_ERR_BAD_ARG, "unknown strategy");
+  if (!(p->spacing_at_root > 0.f)) return c->fail(SWZ_ERR_BAD_ARG, "spacing_at_root must be > 0");
+  if (p->strategy == SWZ_FAST && p->fast_concurrency == 0)
+    return c->fail(SWZ_ERR_BAD_ARG, "FAST needs fast_concurrency >= 1");
+  return SWZ_OK;
+}
+
 static std::string g_create_error;
-static int check_params(swz_ctx* c, const swz_tile_params* p);
 
 namespace {
 
@@ -291,6 +300,61 @@ int swz_release_workspace(swz_ctx* c) {
 
 uint64_t swz_workspace_bytes(const swz_ctx* c) { return c ? c->held_bytes() : 0; }
 
+// ---- memory the callers hold themselves: pinned host buffers, device buffers, copies between them
+int swz_host_alloc_pinned(uint64_t bytes, void** out) {
+  if (!out) return SWZ_ERR_BAD_ARG;
+  *out = nullptr;
+  return hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault) == hipSuccess ? SWZ_OK : SWZ_ERR_HIP;
+}
+int swz_host_free_pinned(void* p) { return (!p || hipHostFree(p) == hipSuccess) ? SWZ_OK : SWZ_ERR_HIP; }
+
+int swz_device_alloc(uint64_t bytes, void** d_out) {
+  if (!d_out) return SWZ_ERR_BAD_ARG;
+  *d_out = nullptr;
+  return hipMalloc(d_out, bytes ? bytes : 1) == hipSuccess ? SWZ_OK : SWZ_ERR_HIP;
+}
+int swz_device_alloc_on(swz_ctx* c, uint64_t bytes, void** d_out) {
+  if (!c || !d_out) return SWZ_ERR_BAD_ARG;
+  *d_out = nullptr;
+  SWZ_HIP(c, hipSetDevice(c->device));
+  SWZ_HIP(c, hipMalloc(d_out, bytes ? bytes : 1));
+  return SWZ_OK;
+}
+int swz_device_free(void* d_ptr) { return (!d_ptr || hipFree(d_ptr) == hipSuccess) ? SWZ_OK : SWZ_ERR_HIP; }
+// (a pointer the library hands out may be a spilled pool: page-locked HOST memory mapped into the device's address space)
+static bool is_mapped_host_memory(const void* p) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return at.type == hipMemoryTypeHost;
+}
+int swz_copy_to_host(swz_ctx* c, void* dst_host, const void* d_src, uint64_t bytes) {
+  if (!c) return SWZ_ERR_BAD_ARG;
+  SWZ_HIP(c, hipSetDevice(c->device));
+  if (bytes && is_mapped_host_memory(d_src)) {
+    SWZ_HIP(c, hipStreamSynchronize(c->stream));
+    std::memcpy(dst_host, d_src, bytes);
+    return SWZ_OK;
+  }
+  if (bytes) SWZ_HIP(c, hipMemcpyAsync(dst_host, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
+  SWZ_HIP(c, hipStreamSynchronize(c->stream));
+  return SWZ_OK;
+}
+int swz_copy_to_device(swz_ctx* c, void* d_dst, const void* src_host, uint64_t bytes) {
+  if (!c) return SWZ_ERR_BAD_ARG;
+  SWZ_HIP(c, hipSetDevice(c->device));
+  if (bytes && is_mapped_host_memory(d_dst)) {
+    SWZ_HIP(c, hipStreamSynchronize(c->stream));
+    std::memcpy(d_dst, src_host, bytes);
+    return SWZ_OK;
+  }
+  if (bytes) SWZ_HIP(c, hipMemcpyAsync(d_dst, src_host, bytes, hipMemcpyHostToDevice, c->stream));
+  SWZ_HIP(c, hipStreamSynchronize(c->stream));
+  return SWZ_OK;
+}
+
 int swz_profile_enable(swz_ctx* c, int enabled) {
   if (!c) return SWZ_ERR_BAD_ARG;
   c->profile = enabled != 0;
@@ -364,13 +428,8 @@ int swz_sort_by_key_device(swz_ctx* c, const uint64_t* d_keys, uint64_t n, uint3
   SWZ_TRY(c->get("sort_keys_b", (size_t)n, &kin));
   SWZ_TRY(c->get("sort_vals_b", (size_t)n, &vtmp));
   if (!kout) SWZ_TRY(c->get("sort_keys_a", (size_t)n, &kout));
-  if (swz::radix_result_in_second()) {
-    SWZ_HIP(c, hipMemcpyAsync(kin, d_keys, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
-    SWZ_TRY(swz::radix_sort_pairs(c, kin, vtmp, kout, d_perm_out, (uint32_t)n, true));
-  } else {
-    SWZ_HIP(c, hipMemcpyAsync(kout, d_keys, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
-    SWZ_TRY(swz::radix_sort_pairs(c, kout, d_perm_out, kin, vtmp, (uint32_t)n, true));
-  }
+  SWZ_HIP(c, hipMemcpyAsync(kin, d_keys, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
+  SWZ_TRY(swz::radix_sort_pairs(c, kin, vtmp, kout, d_perm_out, (uint32_t)n, true));
   return sync(c);
 }
 
@@ -386,13 +445,8 @@ int swz_sort_by_key(swz_ctx* c, const uint64_t* keys, uint64_t n, uint32_t* perm
   SWZ_TRY(c->get("sort_keys_b", (size_t)n, &kb));
   SWZ_TRY(c->get("sort_vals_a", (size_t)n, &va));
   SWZ_TRY(c->get("sort_vals_b", (size_t)n, &vb));
-  if (swz::radix_result_in_second()) {
-    SWZ_TRY(upload(c, kb, keys, (size_t)n * 8));
-    SWZ_TRY(swz::radix_sort_pairs(c, kb, vb, ka, va, (uint32_t)n, true));
-  } else {
-    SWZ_TRY(upload(c, ka, keys, (size_t)n * 8));
-    SWZ_TRY(swz::radix_sort_pairs(c, ka, va, kb, vb, (uint32_t)n, true));
-  }
+  SWZ_TRY(upload(c, kb, keys, (size_t)n * 8));
+  SWZ_TRY(swz::radix_sort_pairs(c, kb, vb, ka, va, (uint32_t)n, true));
   SWZ_TRY(download(c, perm_out, va, (size_t)n * 4));
   if (keys_sorted_out) SWZ_TRY(download(c, keys_sorted_out, ka, (size_t)n * 8));
   return sync(c);
@@ -408,16 +462,6 @@ int swz_generate_uniform_device(swz_ctx* c, uint64_t seed, uint64_t first_point,
 }
 
 // ------------------------------------------------------------------------------ tile
-static int check_params(swz_ctx* c, const swz_tile_params* p) {
-  if (!p) return c->fail(SWZ_ERR_BAD_ARG, "params must not be NULL");
-  if (p->sampler < SWZ_RANDOM_GRID || p->sampler > SWZ_JITTERED) return c->fail(SWZ_ERR_BAD_ARG, "unknown sampler");
-  if (p->strategy != SWZ_ACCURATE && p->strategy != SWZ_FAST) return c->fail(SWZ_ERR_BAD_ARG, "unknown strategy");
-  if (!(p->spacing_at_root > 0.f)) return c->fail(SWZ_ERR_BAD_ARG, "spacing_at_root must be > 0");
-  if (p->strategy == SWZ_FAST && p->fast_concurrency == 0)
-    return c->fail(SWZ_ERR_BAD_ARG, "FAST needs fast_concurrency >= 1");
-  return SWZ_OK;
-}
-
 int swz_tile_device(swz_ctx* c, double* d_xyz, uint64_t n, const double bmin[3], const double bmax[3],
                     const swz_tile_params* params, uint64_t* d_keys_out, uint32_t* d_perm_out, int8_t* d_level_out,
                     uint32_t* d_dup_mask_out, swz_tile_stats* stats) {
@@ -426,7 +470,7 @@ int swz_tile_device(swz_ctx* c, double* d_xyz, uint64_t n, const double bmin[3],
   if (c->opt("SWZ_SYNC_ENTRY")) SWZ_HIP(c, hipDeviceSynchronize());
   SWZ_TRY(check_n(c, n));
   SWZ_TRY(check_bounds(c, bmin, bmax));
-  SWZ_TRY(check_params(c, params));
+  SWZ_TRY(swz::check_params(c, params));
   if (stats) std::memset(stats, 0, sizeof(*stats));
   if (stats) {
     stats->max_level = -1;
@@ -448,7 +492,7 @@ int swz_tile(swz_ctx* c, double* xyz, uint64_t n, const double bmin[3], const do
   SWZ_HIP(c, hipSetDevice(c->device));
   SWZ_TRY(check_n(c, n));
   SWZ_TRY(check_bounds(c, bmin, bmax));
-  SWZ_TRY(check_params(c, params));
+  SWZ_TRY(swz::check_params(c, params));
   if (stats) {
     std::memset(stats, 0, sizeof(*stats));
     stats->max_level = -1;
@@ -499,7 +543,7 @@ int swz_shard_presort_device(swz_ctx* c, const double* d_xyz_local, uint64_t n, 
   SWZ_HIP(c, hipSetDevice(c->device));
   SWZ_TRY(check_n(c, n + ghost_capacity));
   SWZ_TRY(check_bounds(c, bmin, bmax));
-  SWZ_TRY(check_params(c, params));
+  SWZ_TRY(swz::check_params(c, params));
   if (n && !d_xyz_local) return c->fail(SWZ_ERR_BAD_ARG, "swz_shard_presort_device: NULL buffer");
   if (n == 0) return SWZ_OK;  // a shard without points (its octants are empty) has nothing to prepare
   int st = swz::shard_presort_device(c, d_xyz_local, (uint32_t)n, bmin, bmax, *params, (uint32_t)ghost_capacity);
@@ -515,7 +559,7 @@ int swz_shard_begin_device(swz_ctx* c, const double* d_xyz_local, uint64_t n, co
   if (!shard) return c->fail(SWZ_ERR_BAD_ARG, "shard info must not be NULL");
   SWZ_TRY(check_n(c, n + shard->num_ghosts));
   SWZ_TRY(check_bounds(c, bmin, bmax));
-  SWZ_TRY(check_params(c, params));
+  SWZ_TRY(swz::check_params(c, params));
   if ((n && !d_xyz_local) || (shard->num_ghosts && !shard->d_ghost_xyz))
     return c->fail(SWZ_ERR_BAD_ARG, "swz_shard_begin_device: NULL buffer");
   if (num_root_taken_out) *num_root_taken_out = 0;
@@ -559,7 +603,7 @@ int swz_shard_fast_begin_device(swz_ctx* c, const double* d_xyz_local, uint64_t 
   SWZ_HIP(c, hipSetDevice(c->device));
   SWZ_TRY(check_n(c, n));
   SWZ_TRY(check_bounds(c, bmin, bmax));
-  SWZ_TRY(check_params(c, params));
+  SWZ_TRY(swz::check_params(c, params));
   if ((n && !d_xyz_local) || !prefix_counts_out) return c->fail(SWZ_ERR_BAD_ARG, "swz_shard_fast_begin_device: NULL buffer");
   int st = swz::shard_fast_begin_device(c, d_xyz_local, (uint32_t)n, bmin, bmax, *params, prefix_counts_out);
   int st2 = sync(c);

@@ -175,13 +175,15 @@ int read_u32(swz_ctx* c, const uint32_t* d, uint32_t* h);
 int encode_device(swz_ctx* c, double* d_xyz, uint32_t n, const double bmin[3], const double bmax[3],
                   uint64_t* d_keys);
 int generate_uniform_device(swz_ctx* c, uint64_t seed, uint64_t first, uint64_t n, double* d_xyz);
+// what every entry point that takes swz_tile_params refuses (swz_api.hip)
+int check_params(swz_ctx* c, const swz_tile_params* p);
 
-// Stable LSD radix sort of (key, value) pairs.  The keys in the FIRST pair (d_keys_in, and
-// d_vals_tmp unless vals_identity) are the input; both pairs are clobbered by the ping-pong and the
-// sorted result ends in the first pair for an even number of passes, in the second pair for an odd
-// one (radix_result_in_second()).  With vals_identity the first pass synthesises value = element
-// index instead of reading the values.
-bool radix_result_in_second();
+// Stable LSD radix sort of (key, value) pairs.  The input goes in the FIRST pair: the keys in d_keys_in and, unless
+// vals_identity, the values in d_vals_tmp (with vals_identity the first pass synthesises value = element index instead of
+// reading them).  The sorted result comes out in the SECOND pair (d_keys_out, d_vals_out), on every path: the hybrid
+// moves the data an odd number of times (4 or 6 passes and the run pass); the plain eight passes -- small inputs, 2^30
+// points and more, keys with long runs of equal top bits -- end in the first pair and are copied over.  Both pairs are
+// clobbered.
 int radix_sort_pairs(swz_ctx* c, uint64_t* d_keys_in, uint32_t* d_vals_tmp, uint64_t* d_keys_out,
                      uint32_t* d_vals_out, uint32_t n, bool vals_identity);
 

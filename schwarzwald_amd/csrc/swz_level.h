@@ -1,5 +1,5 @@
 // swz_level.h -- the state of one level and the entry points around it: what the drivers of the level loop
-// (swz_session.hip, swz_shard.hip, swz_tiler.hip) hand to level_step (swz_level.hip), and what level_step hands to the
+// (swz_session.hip, swz_shard.hip, swz_tlevel.hip) hand to level_step (swz_level.hip), and what level_step hands to the
 // level's sampler (swz_grid.hip; MIN_DISTANCE: swz_md.h).
 #pragma once
 #include "swz_device.h"
@@ -33,7 +33,7 @@ struct ActiveSet {
   const uint64_t* akey = nullptr;  // key of every active point
   const uint32_t* aidx = nullptr;  // its position in the fully sorted arrays (X/Y/Z/level)
   uint32_t m = 0;
-  // multi-batch tiling (swz_tiler.hip): the keys of the points earlier batches persisted in the nodes of this level
+  // multi-batch tiling (swz_tlevel.hip): the keys of the points earlier batches persisted in the nodes of this level
   // that the active set touches, ascending by node prefix.  A node that has some is sampled with
   // SamplingBehaviour::AlwaysAdhereToMinSpacing (tile_internal_node, TilingAlgorithms.cpp:272-275).
   const uint64_t* ckey = nullptr;

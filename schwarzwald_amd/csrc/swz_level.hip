@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void node_fill_kernel(const uint32_t* __restri
     }
     return lo - 1u;
   };
-  if (tid < 2) {  // (two lanes of one wavefront: see tl_merge_rank_kernel, swz_tiler.hip)
+  if (tid < 2) {  // (two lanes of one wavefront: see tl_merge_rank_kernel, swz_tlevel.hip)
     const uint32_t r = node_of(tid ? last : i0);
     if (tid) s_hi = r; else s_lo = r;
   }

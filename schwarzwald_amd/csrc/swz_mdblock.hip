@@ -1084,7 +1084,7 @@ static int sb_run(swz_ctx* c, const MdLevel& L, const SbInput& in, bool* done) {
 }
 
 // ----------------------------------------------------------------------------- multi-batch tiling: only what new points can change
-// A batch of a multi-batch tiling (swz_tiler.hip) merges its points with the files earlier batches left in the nodes it
+// A batch of a multi-batch tiling (swz_tlevel.hip) merges its points with the files earlier batches left in the nodes it
 // touches and samples the union (tile_node, TilingAlgorithms.cpp:421-442).  The entries of a file that holds more than
 // max_points points are what THIS sampler accepted at THIS spacing in an earlier batch -- a node takes everything only
 // while it holds no file and at most max_points points (TilingAlgorithms.cpp:272-275, Sampling.h:201-208) --, so any two

@@ -61,14 +61,10 @@ int session_prepare(swz_ctx* c, TileSession& t, double* d_xyz, uint32_t n, const
   uint32_t* vals_b = nullptr;
   SWZ_TRY(c->get("sort_keys_b", (size_t)n, &keys_b));
   SWZ_TRY(c->get("sort_vals_b", (size_t)n, &vals_b));
-  if (radix_result_in_second()) {  // place the input so that the sorted result lands in the output buffers
-    SWZ_TRY(encode_device(c, d_xyz, n, bmin, bmax, keys_b));
-    SWZ_STAGE(c, "encode");
-    SWZ_TRY(radix_sort_pairs(c, keys_b, vals_b, out.keys, out.perm, n, true));
-  } else {
-    SWZ_TRY(encode_device(c, d_xyz, n, bmin, bmax, out.keys));
-    SWZ_TRY(radix_sort_pairs(c, out.keys, out.perm, keys_b, vals_b, n, true));
-  }
+  // (encoded into the sort's first pair: the sorted result lands in the output buffers)
+  SWZ_TRY(encode_device(c, d_xyz, n, bmin, bmax, keys_b));
+  SWZ_STAGE(c, "encode");
+  SWZ_TRY(radix_sort_pairs(c, keys_b, vals_b, out.keys, out.perm, n, true));
   // The positions in Morton order (SoA).  RANDOM_GRID decides on the keys alone.  MIN_DISTANCE decides on the key
   // coordinates and looks up the pairs inside the quantisation band through the permutation (swz_mdkeys.hip): there
   // the gather is put off until a level asks for it (session_need_positions) -- for cubic bounds and exact mode that is

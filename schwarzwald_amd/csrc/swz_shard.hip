@@ -109,13 +109,8 @@ static int shard_attach_ghosts(swz_ctx* c, ShardState* s, const double* d_ghost_
     uint64_t* gk = t.keys - g;
     uint32_t* gp = t.perm - g;
     double* gx = const_cast<double*>(d_ghost_xyz);  // inside the bounds already: the clamp of the encode is a no-op
-    if (radix_result_in_second()) {
-      SWZ_TRY(encode_device(c, gx, g, t.bmin, t.bmax, tmpk));
-      SWZ_TRY(radix_sort_pairs(c, tmpk, tmpv, gk, gp, g, true));
-    } else {
-      SWZ_TRY(encode_device(c, gx, g, t.bmin, t.bmax, gk));
-      SWZ_TRY(radix_sort_pairs(c, gk, gp, tmpk, tmpv, g, true));
-    }
+    SWZ_TRY(encode_device(c, gx, g, t.bmin, t.bmax, tmpk));
+    SWZ_TRY(radix_sort_pairs(c, tmpk, tmpv, gk, gp, g, true));
     if (t.sp.X) SWZ_TRY(gather_positions(c, d_ghost_xyz, gp, g, const_cast<double*>(t.sp.X) - g, const_cast<double*>(t.sp.Y) - g,
                                          const_cast<double*>(t.sp.Z) - g));
     SWZ_HIP(c, hipMemsetAsync(t.level - g, 0x80, (size_t)g, c->stream));

@@ -580,11 +580,6 @@ __global__ __launch_bounds__(256) void radix_copy_pairs_kernel(const uint64_t* _
   }
 }
 
-// The sorted pairs always end in the SECOND buffer pair: the hybrid moves the data an odd number of times (4 or 6 passes
-// and the run pass); the plain eight passes end in the first pair and are copied over (small inputs, 2^30 points and
-// more, keys with long runs of equal top bits).
-bool radix_result_in_second() { return true; }
-
 static int radix_lsd_passes(swz_ctx* c, uint64_t*& kin, uint32_t*& vin, uint64_t*& kout, uint32_t*& vout, uint32_t n, int first_pass,
                             int last_pass, bool first_synthesises_values, uint32_t* d_ghist, uint32_t* d_status, uint32_t* d_ticket) {
   const uint32_t ntiles = div_up(n, RS_TILE);

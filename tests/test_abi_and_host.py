@@ -59,6 +59,25 @@ def test_jitter_tables_are_identical_in_product_and_checker():
         assert sorted(nums[r * 64:(r + 1) * 64]) == list(range(1, 65))
 
 
+def test_makefile_lists_every_source_and_header():
+    """bench.py's source hash globs csrc/ while the build reads the Makefile's lists: a .hip missing from SRCS is not
+    compiled (at best the link fails), a header missing from HDRS silently drops out of the rebuild dependencies."""
+    csrc = os.path.join(ROOT, "schwarzwald_amd", "csrc")
+    make = open(os.path.join(csrc, "Makefile")).read()
+
+    def listed(var):
+        m = re.search(r"^%s\s*:=\s*(.*)$" % var, make, flags=re.M)
+        assert m, "the Makefile sets no %s" % var
+        return sorted(m.group(1).split())
+
+    on_disk = sorted(os.listdir(csrc))
+    assert listed("SRCS") == [f for f in on_disk if f.endswith(".hip")]
+    assert len(listed("SRCS")) >= 10
+    headers = [f for f in on_disk if f.endswith((".h", ".inc"))]
+    assert sorted(h for h in listed("HDRS") if "/" not in h) == headers
+    assert "../../include/swz_gpu.h" in listed("HDRS")
+
+
 def test_spacing_from_diagonal_matches_reference_value():
     import schwarzwald_amd as swz
     s = swz.spacing_from_diagonal([0, 0, 0], [1, 1, 1], 250)

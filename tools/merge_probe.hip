@@ -1,4 +1,4 @@
-// tools/merge_probe.hip -- a stand-alone copy of tl_merge_rank_kernel (schwarzwald_amd/csrc/swz_tiler.hip) against std::merge:
+// tools/merge_probe.hip -- a stand-alone copy of tl_merge_rank_kernel (schwarzwald_amd/csrc/swz_tlevel.hip) against std::merge:
 // what found the wrong ranks of its first four-elements-per-thread version.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DIPT=4 tools/merge_probe.hip -o /tmp/merge_probe && /tmp/merge_probe
 // -DBRACKET_ON_THREAD_64 restores the bracket searches on threads 0 and 64 (the second one alone in its wavefront: hipcc 7.2
