@@ -405,6 +405,103 @@ typedef struct {
 int swz_las_decode_device(swz_ctx* ctx, const uint8_t* d_records, uint64_t n, const swz_las_layout* layout,
                           double* d_xyz_out, const swz_attribute_columns* d_out);
 
+/* ---- LAS node files and Entwine (EPT) output: LASPersistence and EntwinePersistence, --output-format LAS / ENTWINE_LAS
+ * (executable/main.cpp:421-428; core/io/LASPersistence.cpp:16-271, core/io/EntwinePersistence.cpp:31-130, 197-333).  LAZ is
+ * LASzip's compression and is not written.
+ * A node file is a LAS 1.2 file: the 227-byte public header, no VLRs, then `count` point records of format (gps times ? 1
+ * : 0) + (colours ? 2 : 0), 20 + 8 * gps + 6 * rgb bytes each (the record of formats 0-3 as swz_las_decode_device states it).
+ * The header as the reference sets it (LASPersistence.cpp:113-136): number of point records = count, by return {count, 0,
+ * 0, 0, 0}, version 1.2, generating software "pointcloud_tiler", header size = offset to point data = 227, the offsets = the
+ * NODE BOX minimum, max/min x, y, z = the node box (the box handed to persist_points, not the extent of the points), one
+ * scale for the three axes.  Everything else is what a fresh laszip_header happens to hold, and those bytes are NOT pinned
+ * against LASzip: file source id, global encoding, GUID, system identifier, creation day and year are written as zeros, the
+ * software string is padded with zeros.
+ * Records: X = I32_QUANTIZE((x - offset) / scale) with I32_QUANTIZE(n) = n >= 0 ? (int32)(n + 0.5) : (int32)(n - 0.5)
+ * (laszip_set_coordinates: a double subtraction, a division, an addition, not contracted, then truncation); intensity u16;
+ * return number & 7 | (number of returns & 7) << 3 | (scan direction flag & 1) << 6 | (edge of flight line & 1) << 7;
+ * classification & 31 (the flag bits zero); scan angle rank i8; user data u8; point source id u16; gps time f64 (formats 1,
+ * 3); R, G, B as u8 << 8 in u16 (formats 2, 3; LASPersistence.cpp:215-217).  `mask` is a bit set over SWZ_ATTR_*: the
+ * columns that are written; an attribute outside it is 0 like an untouched laszip_point.  Bit SWZ_ATTR_NORMAL is accepted and
+ * ignored: normals are in supported_output_attributes(), but no LAS field takes them.  OURS, not the reference's: its
+ * (int32) cast of a quotient outside int32 is undefined behaviour; here it saturates to INT32_MIN / INT32_MAX, and NaN
+ * becomes 0.
+ *   swz_las_scale_from_bounds: compute_las_scale_from_bounds (:16-28) on the box diagonal d: d > 1e6 -> 0.01, d > 1 -> 0.001,
+ *     else 0.0001.  The writers take any finite positive scale.
+ *   swz_las_record_layout: point format (0-3) and record bytes of a mask; SWZ_ERR_BAD_ARG for a bit above SWZ_ATTR_COUNT.
+ *   swz_las_image_layout (host): the IMAGE holds the point records of every node in table order; each body is count x
+ *     record bytes rounded up to a multiple of 8 (the padding is part of the image, not of the file), a node of count 0 has
+ *     size 0.  Any output may be NULL.  SWZ_ERR_BAD_ARG for a count above 2^32 - 1 (the header's u32).
+ *   swz_las_pack_device: writes the image of a node table into d_image_out (device, 8-byte aligned, image_bytes >= the
+ *     layout's total) in one kernel: the permuted gather (row i = row d_perm[d_order[i]] of d_xyz and of the columns of
+ *     d_in; d_order NULL = identity), the quantisation against node k's node_las_offset[3 k ..] and node_las_scale[k] (the
+ *     box minimum of swz_node_bounds and the scale rule), the bit packing, the colour shift, the interleaved records and the
+ *     zero padding -- no byte of the image depends on what the buffer held.  SWZ_ERR_BAD_ARG before anything is launched
+ *     for: offsets that do not ascend, ranges that overlap or pass n, a mask that names an absent column or a bit that does
+ *     not exist, n above 2^32 - 65536, an image that is too small or not 8-byte aligned, a scale that is not finite and
+ *     positive, an offset that is not finite.  n == 0 or no nodes is valid and launches nothing.  swz_las_pack_tile: the
+ *     stored rows one workgroup takes (tests place their edge cases by it).
+ *   swz_las_write_node: header + count x record bytes of a packed body; count == 0 writes nothing (LASPersistence would
+ *     write an empty file, EntwinePersistence returns before it does).  swz_las_write_node_rows: the same file from unpacked
+ *     rows (what a PointsSink receives), converted on the host with the identical arithmetic.  Both refuse a box or scale
+ *     that is not finite (scale: and positive) and a count above 2^32 - 1.
+ *   swz_las_persist_nodes: one file per node of a table out of a HOST copy of the image, written by the pool of host threads
+ *     of swz_bin_persist_nodes; node_box_min / node_box_max hold 3 doubles per node, node_scale one.  naming: "r" + octant
+ *     digits + ".las" (SWZ_LAS_NAMING_POTREE) or "D-X-Y-Z.las" (SWZ_LAS_NAMING_ENTWINE).
+ *   swz_las_read_header / swz_las_read_node: retrieve_points for formats 0-3.  Positions are offset + X * scale clamped into
+ *     the header's box (position_from_las_point, core/io/LASFile.cpp:79-94), RGB is >> 8, the non-NULL columns are filled
+ *     (0 where the format lacks the attribute).  Any output of read_header may be NULL.  SWZ_ERR_BAD_ARG, without reading
+ *     outside the file, for a short file, a wrong signature, a header size or data offset that passes the file, a record
+ *     length below the format's, a format above 3 (swz_las_decode_device decodes those), a count whose records pass the end.
+ *   swz_ept_create_dirs: dir, dir/ept-data, dir/ept-hierarchy, dir/ept-sources (existing ones are kept).
+ *   swz_ept_hierarchy_write: the files dir/ept-hierarchy/<D-X-Y-Z>.json of create_hierarchy_files (:51-130), split every 5
+ *     levels: a node belongs to the file of its nearest ancestor-or-self whose depth is a multiple of 5, an object
+ *     {"D-X-Y-Z": count, ...}; a subtree root carries its count in its own file and -1 in the file of the subtree root above
+ *     it, up to 0-0-0-0, whether or not those ancestors are in the table.  Nodes of count 0 are skipped.  Compact; members
+ *     ordered by (depth, Morton index) -- the reference iterates unordered maps, the order is no part of the format.
+ *   swz_ept_json_write: ept.json of write_ept_json (:197-269) with the members bounds, boundsConforming, dataType "las",
+ *     hierarchyType "json", points, schema, span, srs {authority, horizontal, wkt}, version, in this order.  The schema
+ *     (point_attributes_to_ept_schema, :132-194) is X, Y, Z (the only entries with "offset" 0 and "scale" 1), then the
+ *     attributes of attribute_mask by SWZ_ATTR_* -- the reference iterates an unordered set; entries are {name, size, type}.
+ *     Numbers are written like swz_tileset_write writes them; a NULL string is "".
+ * The host functions need no GPU; their ctx only carries the error text and may be NULL. */
+enum { SWZ_LAS_NAMING_POTREE = 0, SWZ_LAS_NAMING_ENTWINE = 1 };
+typedef struct {
+  double bounds_min[3], bounds_max[3];         /* the cubic root box */
+  double conforming_min[3], conforming_max[3]; /* the box of the points */
+  uint64_t points;
+  uint32_t attribute_mask;                     /* bits SWZ_ATTR_*; the position is always part of the schema */
+  uint32_t reserved;
+  double span;
+  const char* srs_authority;
+  const char* srs_horizontal;
+  const char* srs_wkt;
+  const char* version;
+} swz_ept_json;
+double swz_las_scale_from_bounds(const double box_min[3], const double box_max[3]);
+int swz_las_record_layout(uint32_t mask, uint32_t* point_format_out, uint32_t* record_bytes_out);
+int swz_las_image_layout(uint64_t num_nodes, const uint64_t* node_count, uint32_t mask, uint64_t* body_offset_out,
+                         uint64_t* body_size_out, uint64_t* total_out);
+uint32_t swz_las_pack_tile(void);
+int swz_las_pack_device(swz_ctx* ctx, const uint32_t* d_perm, const uint32_t* d_order, uint64_t n, const double* d_xyz,
+                        const swz_attribute_columns* d_in, uint64_t num_nodes, const uint64_t* node_offset,
+                        const uint64_t* node_count, const double* node_las_offset, const double* node_las_scale, uint32_t mask,
+                        void* d_image_out, uint64_t image_bytes);
+int swz_las_write_node(swz_ctx* ctx, const char* path, uint64_t count, const void* body, uint32_t mask, const double box_min[3],
+                       const double box_max[3], double scale);
+int swz_las_write_node_rows(swz_ctx* ctx, const char* path, uint64_t count, const double* xyz,
+                            const swz_attribute_columns* columns, uint32_t mask, const double box_min[3], const double box_max[3],
+                            double scale);
+int swz_las_persist_nodes(swz_ctx* ctx, const char* dir, uint64_t num_nodes, const int8_t* node_level, const uint64_t* node_key,
+                          const uint64_t* node_count, const double* node_box_min, const double* node_box_max,
+                          const double* node_scale, const void* image, uint64_t image_bytes, uint32_t mask, int naming);
+int swz_las_read_header(swz_ctx* ctx, const char* path, uint64_t* count_out, uint32_t* point_format_out,
+                        uint32_t* record_bytes_out, uint32_t* offset_to_point_data_out, swz_las_layout* layout_out);
+int swz_las_read_node(swz_ctx* ctx, const char* path, double* xyz_out, const swz_attribute_columns* columns_out);
+int swz_ept_create_dirs(swz_ctx* ctx, const char* dir);
+int swz_ept_hierarchy_write(swz_ctx* ctx, const char* dir, uint64_t num_nodes, const int8_t* node_level,
+                            const uint64_t* node_key, const uint64_t* node_count);
+int swz_ept_json_write(swz_ctx* ctx, const char* path, const swz_ept_json* ept);
+
 /* ---- multi-GPU sharding: one context per GPU, points owned by their top
  * Morton bits (level-0 octant, MortonIndex::get_octant_at_level(0), MortonIndex.h:133-138), so every
  * node at level >= 0 lives on exactly one GPU.  The reference has no counterpart (it is a single

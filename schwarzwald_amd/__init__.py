@@ -11,9 +11,13 @@ from .api import (ACCURATE, FLAG_MIN_DISTANCE_PROPERTY, ALWAYS_ADHERE_TO_MIN_SPA
                   node_from_entwine_name, node_geometric_error, node_name, node_name_entwine,
                   spacing_from_diagonal, Tiler, pinned_empty, tileset_build, tileset_write, pnts_layout, pnts_write_node,
                   pnts_write_node_rows, pnts_read_node, pnts_rgb_from_intensity, PNTS_RGB, PNTS_INTENSITY, RGB_FROM_COLOR,
-                  RGB_FROM_INTENSITY_LINEAR, RGB_FROM_INTENSITY_LOG)
+                  RGB_FROM_INTENSITY_LINEAR, RGB_FROM_INTENSITY_LOG, LAS_NAMING_POTREE, LAS_NAMING_ENTWINE, las_scale_from_bounds,
+                  las_record_layout, las_pack_tile, las_image_layout, las_write_node, las_write_node_rows, las_persist_nodes,
+                  las_read_header, las_read_node, ept_create_dirs, ept_hierarchy_write, ept_json_write)
 
-__all__ = ["tileset_write", "pnts_layout", "pnts_write_node", "pnts_write_node_rows", "pnts_read_node", "pnts_rgb_from_intensity",
+__all__ = ["LAS_NAMING_POTREE", "LAS_NAMING_ENTWINE", "las_scale_from_bounds", "las_record_layout", "las_pack_tile", "las_image_layout",
+           "las_write_node", "las_write_node_rows", "las_persist_nodes", "las_read_header", "las_read_node", "ept_create_dirs",
+           "ept_hierarchy_write", "ept_json_write", "tileset_write", "pnts_layout", "pnts_write_node", "pnts_write_node_rows", "pnts_read_node", "pnts_rgb_from_intensity",
            "PNTS_RGB", "PNTS_INTENSITY", "RGB_FROM_COLOR", "RGB_FROM_INTENSITY_LINEAR", "RGB_FROM_INTENSITY_LOG",
            "tileset_build","FLAG_MIN_DISTANCE_PROPERTY", "Context", "Tiler", "pinned_empty", "SwzError", "TileParams", "TileResult", "load_library", "library_path", "SAMPLERS",
            "RANDOM_GRID", "GRID_CENTER", "MIN_DISTANCE", "JITTERED", "ACCURATE", "FAST",

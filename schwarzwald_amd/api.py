@@ -331,6 +331,167 @@ def tileset_write(tiles, directory):
         raise SwzError(st, "swz_tileset_write(%s) failed" % directory)
 
 
+# LAS node files and Entwine metadata (include/swz_gpu.h, swz_las_* / swz_ept_*)
+LAS_NAMING_POTREE, LAS_NAMING_ENTWINE = 0, 1
+
+
+class _EptJson(C.Structure):
+    _fields_ = [("bounds_min", C.c_double * 3), ("bounds_max", C.c_double * 3), ("conforming_min", C.c_double * 3),
+                ("conforming_max", C.c_double * 3), ("points", C.c_uint64), ("attribute_mask", C.c_uint32),
+                ("reserved", C.c_uint32), ("span", C.c_double), ("srs_authority", C.c_char_p), ("srs_horizontal", C.c_char_p),
+                ("srs_wkt", C.c_char_p), ("version", C.c_char_p)]
+
+
+def _las_mask(attrs):
+    """names of ATTRIBUTES or a mask  =>  mask over the attribute indices"""
+    if isinstance(attrs, (int, np.integer)):
+        return int(attrs)
+    mask = 0
+    for name in attrs or ():
+        mask |= 1 << ATTRIBUTES[name][0]
+    return mask
+
+
+def las_scale_from_bounds(bmin, bmax):
+    """compute_las_scale_from_bounds (LASPersistence.cpp:16-28): the scale of a node file from the node box."""
+    return float(load_library().swz_las_scale_from_bounds(_vec3(bmin), _vec3(bmax)))
+
+
+def las_record_layout(attrs=()):
+    """(point format 0-3, record bytes) of the records a mask writes."""
+    fmt, rb = C.c_uint32(), C.c_uint32()
+    st = load_library().swz_las_record_layout(_las_mask(attrs), C.byref(fmt), C.byref(rb))
+    if st != 0:
+        raise SwzError(st, "swz_las_record_layout failed")
+    return int(fmt.value), int(rb.value)
+
+
+def las_pack_tile():
+    """The stored rows one workgroup of las_pack_device takes."""
+    return int(load_library().swz_las_pack_tile())
+
+
+def las_image_layout(counts, attrs=()):
+    """swz_las_image_layout: where every node's point records lie in one contiguous image.  Returns a dict of the per-node
+    arrays offset / size and the image's total size."""
+    cnt = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    m = cnt.shape[0]
+    out = {k: np.empty(m, dtype=np.uint64) for k in ("offset", "size")}
+    total = C.c_uint64()
+    st = load_library().swz_las_image_layout(m, cnt.ctypes.data_as(_u64p), _las_mask(attrs), out["offset"].ctypes.data_as(_u64p),
+                                             out["size"].ctypes.data_as(_u64p), C.byref(total))
+    if st != 0:
+        raise SwzError(st, "swz_las_image_layout failed")
+    out["total"] = int(total.value)
+    return out
+
+
+def las_write_node(path, count, body, attrs, box_min, box_max, scale):
+    """One LAS 1.2 node file from packed records (a slice of the image las_pack_device wrote; host only)."""
+    b = np.ascontiguousarray(body, dtype=np.uint8).reshape(-1)
+    fmt, rb = las_record_layout(attrs)
+    if b.shape[0] < int(count) * rb:
+        raise ValueError("the body holds %d bytes, %d records of %d need more" % (b.shape[0], count, rb))
+    st = load_library().swz_las_write_node(None, os.fsencode(path), int(count), b.ctypes.data, _las_mask(attrs), _vec3(box_min),
+                                           _vec3(box_max), float(scale))
+    if st != 0:
+        raise SwzError(st, "swz_las_write_node(%s) failed" % path)
+
+
+def las_write_node_rows(path, xyz, attrs, box_min, box_max, scale, write=None):
+    """The same file from unpacked rows: double positions plus the columns of attrs (dict name -> array), converted on the
+    host.  write: the columns to put into the records (default: all of attrs)."""
+    x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    cols, keep = _host_columns(attrs, x.shape[0])
+    if write is None:
+        write = list(attrs or {})
+    st = load_library().swz_las_write_node_rows(None, os.fsencode(path), x.shape[0], x.ctypes.data_as(_dp), C.byref(cols),
+                                                _las_mask(write), _vec3(box_min), _vec3(box_max), float(scale))
+    if st != 0:
+        raise SwzError(st, "swz_las_write_node_rows(%s) failed" % path)
+
+
+def las_read_header(path):
+    """Header of a LAS node file: dict of count, point_format, record_bytes, offset_to_point_data, scale, offset, min, max."""
+    count, fmt, rb, at, lay = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint32(), _LasLayout()
+    st = load_library().swz_las_read_header(None, os.fsencode(path), C.byref(count), C.byref(fmt), C.byref(rb), C.byref(at),
+                                            C.byref(lay))
+    if st != 0:
+        raise SwzError(st, "swz_las_read_header(%s) failed" % path)
+    return dict(count=int(count.value), point_format=int(fmt.value), record_bytes=int(rb.value), offset_to_point_data=int(at.value),
+                scale=list(lay.scale), offset=list(lay.offset), min=list(lay.min), max=list(lay.max))
+
+
+def las_read_node(path):
+    """retrieve_points of a LAS node file (formats 0-3): (xyz, dict of every attribute column a LAS record carries)."""
+    head = las_read_header(path)
+    n = head["count"]
+    xyz = np.empty((n, 3), dtype=np.float64)
+    out = {}
+    for name, (idx, dt, width) in ATTRIBUTES.items():
+        if name == "normal" or (name == "gps_time" and not head["point_format"] & 1) or (name == "rgb" and not head["point_format"] & 2):
+            continue
+        out[name] = np.empty((n, width) if width > 1 else n, dtype=dt)
+    cols, keep = _host_columns(out, n)
+    st = load_library().swz_las_read_node(None, os.fsencode(path), xyz.ctypes.data_as(_dp), C.byref(cols))
+    if st != 0:
+        raise SwzError(st, "swz_las_read_node(%s) failed" % path)
+    return xyz, keep
+
+
+def las_persist_nodes(directory, nodes, image, attrs, box_min, box_max, scale, naming=LAS_NAMING_POTREE, ctx=None):
+    """One LAS file per node of a node table out of a host copy of the image las_pack_device wrote.  box_min / box_max
+    (num_nodes x 3) and scale (num_nodes) are the nodes' boxes and scales; naming: LAS_NAMING_POTREE or LAS_NAMING_ENTWINE."""
+    img = np.ascontiguousarray(image, dtype=np.uint8).reshape(-1)
+    nl = np.ascontiguousarray(nodes["level"], dtype=np.int8)
+    nk = np.ascontiguousarray(nodes["key"], dtype=np.uint64)
+    nc = np.ascontiguousarray(nodes["count"], dtype=np.uint64)
+    mn = np.ascontiguousarray(box_min, dtype=np.float64).reshape(-1, 3)
+    mx = np.ascontiguousarray(box_max, dtype=np.float64).reshape(-1, 3)
+    sc = np.ascontiguousarray(scale, dtype=np.float64).reshape(-1)
+    if not (mn.shape[0] == mx.shape[0] == sc.shape[0] == nl.shape[0] == nk.shape[0] == nc.shape[0]):
+        raise ValueError("the node table, the boxes and the scales differ in length")
+    L = load_library()
+    st = L.swz_las_persist_nodes(ctx, os.fsencode(directory), nl.shape[0], nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p),
+                                 nc.ctypes.data_as(_u64p), mn.ctypes.data_as(_dp), mx.ctypes.data_as(_dp), sc.ctypes.data_as(_dp),
+                                 img.ctypes.data, img.shape[0], _las_mask(attrs), int(naming))
+    if st != 0:
+        raise SwzError(st, (L.swz_last_error(ctx) or b"").decode() if ctx else "swz_las_persist_nodes(%s) failed" % directory)
+
+
+def ept_create_dirs(directory):
+    """ept-data, ept-hierarchy and ept-sources under directory (create_ept_folder_structure)."""
+    st = load_library().swz_ept_create_dirs(None, os.fsencode(directory))
+    if st != 0:
+        raise SwzError(st, "swz_ept_create_dirs(%s) failed" % directory)
+
+
+def ept_hierarchy_write(directory, nodes):
+    """swz_ept_hierarchy_write: directory/ept-hierarchy/*.json of a node table (dict of level / key / count)."""
+    nl = np.ascontiguousarray(nodes["level"], dtype=np.int8)
+    nk = np.ascontiguousarray(nodes["key"], dtype=np.uint64)
+    nc = np.ascontiguousarray(nodes["count"], dtype=np.uint64)
+    if not (nl.shape[0] == nk.shape[0] == nc.shape[0]):
+        raise ValueError("the columns of the node table differ in length")
+    st = load_library().swz_ept_hierarchy_write(None, os.fsencode(directory), nl.shape[0], nl.ctypes.data_as(_i8p),
+                                                nk.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p))
+    if st != 0:
+        raise SwzError(st, "swz_ept_hierarchy_write(%s) failed" % directory)
+
+
+def ept_json_write(path, bounds, conforming_bounds, points, attrs=(), span=0.0, srs=None, version=""):
+    """swz_ept_json_write: ept.json.  bounds / conforming_bounds: (min, max); attrs: the attributes of the schema besides
+    the position; srs: dict of authority / horizontal / wkt."""
+    srs = srs or {}
+    e = _EptJson(_vec3(bounds[0]), _vec3(bounds[1]), _vec3(conforming_bounds[0]), _vec3(conforming_bounds[1]), int(points),
+                 _las_mask(attrs), 0, float(span), srs.get("authority", "").encode(), srs.get("horizontal", "").encode(),
+                 srs.get("wkt", "").encode(), version.encode())
+    st = load_library().swz_ept_json_write(None, os.fsencode(path), C.byref(e))
+    if st != 0:
+        raise SwzError(st, "swz_ept_json_write(%s) failed" % path)
+
+
+
 def library_path():
     return os.environ.get("SWZ_GPU_LIBRARY", os.path.join(_HERE, "lib", "libswz_gpu.so"))
 
@@ -435,6 +596,26 @@ def load_library():
                  "swz_pnts_persist_nodes", "swz_pnts_read_header", "swz_pnts_read_node", "swz_tileset_write"):
         getattr(L, name).restype = C.c_int
     L.swz_las_decode_device.argtypes = [vp, vp, C.c_uint64, C.POINTER(_LasLayout), vp, cols]
+    L.swz_las_scale_from_bounds.argtypes = [_dp, _dp]
+    L.swz_las_scale_from_bounds.restype = C.c_double
+    L.swz_las_record_layout.argtypes = [C.c_uint32, _u32p, _u32p]
+    L.swz_las_image_layout.argtypes = [C.c_uint64, _u64p, C.c_uint32, _u64p, _u64p, _u64p]
+    L.swz_las_pack_tile.argtypes = []
+    L.swz_las_pack_tile.restype = C.c_uint32
+    L.swz_las_pack_device.argtypes = [vp, vp, vp, C.c_uint64, vp, cols, C.c_uint64, _u64p, _u64p, _dp, _dp, C.c_uint32, vp, C.c_uint64]
+    L.swz_las_write_node.argtypes = [vp, C.c_char_p, C.c_uint64, vp, C.c_uint32, _dp, _dp, C.c_double]
+    L.swz_las_write_node_rows.argtypes = [vp, C.c_char_p, C.c_uint64, _dp, cols, C.c_uint32, _dp, _dp, C.c_double]
+    L.swz_las_persist_nodes.argtypes = [vp, C.c_char_p, C.c_uint64, _i8p, _u64p, _u64p, _dp, _dp, _dp, vp, C.c_uint64, C.c_uint32,
+                                        C.c_int]
+    L.swz_las_read_header.argtypes = [vp, C.c_char_p, _u64p, _u32p, _u32p, _u32p, C.POINTER(_LasLayout)]
+    L.swz_las_read_node.argtypes = [vp, C.c_char_p, _dp, cols]
+    L.swz_ept_create_dirs.argtypes = [vp, C.c_char_p]
+    L.swz_ept_hierarchy_write.argtypes = [vp, C.c_char_p, C.c_uint64, _i8p, _u64p, _u64p]
+    L.swz_ept_json_write.argtypes = [vp, C.c_char_p, C.POINTER(_EptJson)]
+    for name in ("swz_las_record_layout", "swz_las_image_layout", "swz_las_pack_device", "swz_las_write_node", "swz_las_write_node_rows",
+                 "swz_las_persist_nodes", "swz_las_read_header", "swz_las_read_node", "swz_ept_create_dirs", "swz_ept_hierarchy_write",
+                 "swz_ept_json_write"):
+        getattr(L, name).restype = C.c_int
     L.swz_partition_by_octant_device.argtypes = [vp, vp, C.c_uint64, vp, _u64p]
     L.swz_shard_begin_device.argtypes = [vp, vp, C.c_uint64, _dp, _dp, C.POINTER(_TileParams), C.POINTER(_ShardInfo),
                                          _u64p]
@@ -759,6 +940,26 @@ class Context:
         self._check(self._lib.swz_pnts_persist_nodes(self._ctx, os.fsencode(directory), nl.shape[0], nl.ctypes.data_as(_i8p),
                                                      nk.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p), img.ctypes.data, img.shape[0],
                                                      _pnts_mask(attrs), rtc))
+
+    def las_pack_device(self, d_perm, d_order, n, d_xyz, d_attrs, nodes, las_offset, las_scale, d_image, image_bytes, attrs=()):
+        """swz_las_pack_device: the LAS point records of all nodes of a table, laid out as las_image_layout says, written
+        into d_image (device, image_bytes bytes) by one kernel.  las_offset (num_nodes x 3) and las_scale (num_nodes): the
+        box minimum and the scale of every node.  d_order None = identity (a tiler's export ids as d_perm)."""
+        cin = device_columns(d_attrs)
+        no = np.ascontiguousarray(nodes["offset"], dtype=np.uint64)
+        nc = np.ascontiguousarray(nodes["count"], dtype=np.uint64)
+        lo = np.ascontiguousarray(las_offset, dtype=np.float64).reshape(-1, 3)
+        ls = np.ascontiguousarray(las_scale, dtype=np.float64).reshape(-1)
+        if not (no.shape[0] == nc.shape[0] == lo.shape[0] == ls.shape[0]):
+            raise ValueError("the node table, the offsets and the scales differ in length")
+        self._check(self._lib.swz_las_pack_device(self._ctx, C.c_void_p(d_perm), C.c_void_p(d_order), int(n), C.c_void_p(d_xyz),
+                                                  C.byref(cin), nc.shape[0], no.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p),
+                                                  lo.ctypes.data_as(_dp), ls.ctypes.data_as(_dp), _las_mask(attrs), C.c_void_p(d_image),
+                                                  int(image_bytes)))
+
+    def las_persist_nodes(self, directory, nodes, image, attrs, box_min, box_max, scale, naming=LAS_NAMING_POTREE):
+        """las_persist_nodes with this context's writer threads and error text."""
+        las_persist_nodes(directory, nodes, image, attrs, box_min, box_max, scale, naming, ctx=self._ctx)
 
     # ------------------------------------------------------------------ sharded batches (one context per GPU)
     def partition_by_octant_device(self, d_keys, n, d_perm):

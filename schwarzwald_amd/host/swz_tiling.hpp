@@ -25,9 +25,11 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/swz_gpu.h"
@@ -255,6 +257,106 @@ private:
   int _rgb_mapping;
   std::vector<std::string> _node_names;
   bool _tilesets_written = false;
+};
+
+// "r" + octant digits (TilingAlgorithms.cpp:139) -> (node level, Morton key); throws for anything else
+inline void node_from_potree_name(const std::string& name, int8_t* level, uint64_t* key) {
+  if (name.empty() || name[0] != 'r' || name.size() > MortonIndex64Levels + 1)
+    throw std::runtime_error{"not a node name: \"" + name + "\""};
+  *level = static_cast<int8_t>(static_cast<int>(name.size()) - 2);
+  *key = 0;
+  for (size_t l = 1; l < name.size(); ++l) {
+    if (name[l] < '0' || name[l] > '7') throw std::runtime_error{"not a node name: \"" + name + "\""};
+    *key |= static_cast<uint64_t>(name[l] - '0') << ((MortonIndex64Levels - l) * 3);
+  }
+}
+
+// LASPersistence (core/io/LASPersistence.cpp:69-271) as a sink: every node becomes "<work_dir>/<name>.las", a LAS 1.2 file
+// whose offsets and box are node_bounds and whose scale is compute_las_scale_from_bounds of them (swz_las_write_node_rows).
+// The records carry every attribute column the rows have; persist_points receives ids and positions only, so its files are
+// point format 0 with zero attributes.  An empty range: the reference writes a file of a header and no records, this sink
+// writes nothing and does not throw.
+class LASSink : public PointsSink {
+public:
+  explicit LASSink(std::string work_dir) : _work_dir(std::move(work_dir)) {}
+
+  void persist_points(const uint32_t* ids_begin, const uint32_t* ids_end, const double* positions, const AABB& node_bounds,
+                      const std::string& node_name) override {
+    persist_rows(static_cast<size_t>(ids_end - ids_begin), positions, swz_attribute_columns{}, node_bounds, node_name);
+  }
+  void persist_rows(size_t count, const double* positions, const swz_attribute_columns& attributes, const AABB& node_bounds,
+                    const std::string& node_name) override {
+    write_las(_work_dir + "/" + node_name + ".las", count, positions, attributes, node_bounds);
+  }
+
+protected:
+  static void write_las(const std::string& path, size_t count, const double* positions, const swz_attribute_columns& attributes,
+                        const AABB& b) {
+    if (count == 0) return;
+    uint32_t mask = 0;
+    for (int a = 0; a < SWZ_ATTR_COUNT; ++a)
+      if (attributes.column[a]) mask |= 1u << a;
+    const double mn[3] = {b.min.x, b.min.y, b.min.z}, mx[3] = {b.max.x, b.max.y, b.max.z};
+    if (swz_las_write_node_rows(nullptr, path.c_str(), count, positions, &attributes, mask, mn, mx, swz_las_scale_from_bounds(mn, mx)) !=
+        SWZ_OK)
+      throw std::runtime_error{"Could not write LAS file \"" + path + "\""};
+  }
+  std::string _work_dir;
+};
+
+// EntwinePersistence (core/io/EntwinePersistence.cpp:271-333) as a sink: the constructor creates ept-data, ept-hierarchy and
+// ept-sources under work_dir; every non-empty node becomes "ept-data/<D-X-Y-Z>.las" (the Potree name converted) through the
+// LAS writer and its count is recorded; finish() -- called by the destructor if nobody did, where the reference writes them
+// -- writes the ept-hierarchy files (swz_ept_hierarchy_write).  An empty range returns silently, like the reference.
+// ept.json is the caller's (swz_ept_json_write), as it is the reference's tiler process's.
+class EntwineSink : public LASSink {
+public:
+  explicit EntwineSink(std::string work_dir) : LASSink(std::move(work_dir)) {
+    if (swz_ept_create_dirs(nullptr, _work_dir.c_str()) != SWZ_OK)
+      throw std::runtime_error{"Could not create the ept directories under \"" + _work_dir + "\""};
+  }
+  ~EntwineSink() override {
+    if (!_finished) {
+      try {
+        finish();
+      } catch (...) {  // a destructor reports nothing; call finish() to see the error
+      }
+    }
+  }
+  EntwineSink(const EntwineSink&) = delete;
+  EntwineSink& operator=(const EntwineSink&) = delete;
+
+  void persist_rows(size_t count, const double* positions, const swz_attribute_columns& attributes, const AABB& node_bounds,
+                    const std::string& node_name) override {
+    if (count == 0) return;  // EntwinePersistence.cpp:297-298
+    int8_t level = 0;
+    uint64_t key = 0;
+    node_from_potree_name(node_name, &level, &key);
+    char name[72];
+    if (swz_node_name_entwine(level, key, name) != SWZ_OK) throw std::runtime_error{"not a node name: \"" + node_name + "\""};
+    write_las(_work_dir + "/ept-data/" + name + ".las", count, positions, attributes, node_bounds);
+    _counts[{level, key}] = count;  // a node persisted again replaces its file and its count
+  }
+
+  // number of nodes recorded so far
+  size_t num_nodes() const { return _counts.size(); }
+
+  void finish() {
+    _finished = true;
+    std::vector<int8_t> level;
+    std::vector<uint64_t> key, count;
+    for (const auto& kv : _counts) {
+      level.push_back(kv.first.first);
+      key.push_back(kv.first.second);
+      count.push_back(kv.second);
+    }
+    if (swz_ept_hierarchy_write(nullptr, _work_dir.c_str(), level.size(), level.data(), key.data(), count.data()) != SWZ_OK)
+      throw std::runtime_error{"Could not write hierarchy file under \"" + _work_dir + "\""};
+  }
+
+private:
+  std::map<std::pair<int8_t, uint64_t>, uint64_t> _counts;
+  bool _finished = false;
 };
 
 // The shape of TilingAlgorithmBase (core/tiling/TilingAlgorithms.h:70-116): one object per Tiler, fed one batch at
