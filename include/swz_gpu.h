@@ -42,8 +42,16 @@ enum {
 };
 
 /* --sampling values, TilerProcess::make_sampling_strategy (core/process/TilerProcess.cpp:491-516)
- * -> Sampling.h:187-308 / :314-416 / :421-471 / :598-759 */
-enum { SWZ_RANDOM_GRID = 0, SWZ_GRID_CENTER = 1, SWZ_MIN_DISTANCE = 2, SWZ_JITTERED = 3 };
+ * -> Sampling.h:187-308 / :314-416 / :421-471 / :598-759 / :477-542.
+ * MIN_DISTANCE_FAST is AdaptivePoissonDiskSampling with the densities of the command line (TilerProcess.cpp:500-508): a
+ * sampled node offers only every n-th point of its Morton-ordered range, counted from its own first point, to MIN_DISTANCE's
+ * greedy test (n = swz_min_distance_fast_stride); the others are passed down unexamined.  A node whose candidate level is -1
+ * keeps its first point only.  Not with SWZ_FLAG_MIN_DISTANCE_PROPERTY and not on the sharded entry points (swz_shard_*,
+ * swz_tiler_shard_*, swz_group_*): both return SWZ_ERR_BAD_ARG. */
+enum { SWZ_RANDOM_GRID = 0, SWZ_GRID_CENTER = 1, SWZ_MIN_DISTANCE = 2, SWZ_JITTERED = 3, SWZ_MIN_DISTANCE_FAST = 4 };
+/* The n of MIN_DISTANCE_FAST at a node level (relative to the root, -1 = the root): (uint32_t)std::round(1 / density) with
+ * density 0.25f below level 0, 0.5f below level 1, else 1.f -- 4, 2, 1.  Host arithmetic only; the one place that decides n. */
+int32_t swz_min_distance_fast_stride(int32_t node_level);
 /* SamplingBehaviour, Sampling.h:170-181 */
 enum { SWZ_TAKE_ALL_WHEN_COUNT_BELOW_MAX_POINTS = 0, SWZ_ALWAYS_ADHERE_TO_MIN_SPACING = 1 };
 /* --tiling-strategy values, executable/main.cpp:484-497 -> TilingAlgorithmV1 / V3 */

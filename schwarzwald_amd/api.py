@@ -13,6 +13,11 @@ import numpy as np
 RANDOM_GRID, GRID_CENTER, MIN_DISTANCE, JITTERED = 0, 1, 2, 3
 SAMPLERS = {"RANDOM_GRID": RANDOM_GRID, "GRID_CENTER": GRID_CENTER, "MIN_DISTANCE": MIN_DISTANCE,
             "JITTERED": JITTERED}
+# MIN_DISTANCE_FAST (AdaptivePoissonDiskSampling): every n-th point of a node through MIN_DISTANCE's greedy test,
+# n = min_distance_fast_stride(node level).  ALL_SAMPLERS holds the five --sampling names; SAMPLERS stays the four that every
+# entry point, sharded or not, takes.
+MIN_DISTANCE_FAST = 4
+ALL_SAMPLERS = dict(SAMPLERS, MIN_DISTANCE_FAST=MIN_DISTANCE_FAST)
 TAKE_ALL_WHEN_COUNT_BELOW_MAX_POINTS, ALWAYS_ADHERE_TO_MIN_SPACING = 0, 1
 ACCURATE, FAST = 0, 1
 ERR_BAD_ARG = 2
@@ -178,6 +183,14 @@ def required_morton_index_depth(sampler, node_level, root_min, root_max, spacing
     L.swz_required_morton_index_depth.argtypes = [C.c_int, C.c_int32, _dp, _dp, C.c_float]
     return int(L.swz_required_morton_index_depth(int(sampler), int(node_level), _vec3(root_min), _vec3(root_max),
                                                  C.c_float(spacing_at_root)))
+
+
+def min_distance_fast_stride(node_level):
+    """The n of MIN_DISTANCE_FAST at a node level (-1 = the root): 4, 2, then 1 (swz_min_distance_fast_stride)."""
+    L = load_library()
+    L.swz_min_distance_fast_stride.restype = C.c_int32
+    L.swz_min_distance_fast_stride.argtypes = [C.c_int32]
+    return int(L.swz_min_distance_fast_stride(int(node_level)))
 
 
 class _TilesetNode(C.Structure):

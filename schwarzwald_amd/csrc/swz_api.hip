@@ -170,12 +170,21 @@ int swz::read_u32(swz_ctx* c, const uint32_t* d, uint32_t* h) {
 
 int swz::check_params(swz_ctx* c, const swz_tile_params* p) {
   if (!p) return c->fail(SWZ_ERR_BAD_ARG, "params must not be NULL");
-  if (p->sampler < SWZ_RANDOM_GRID || p->sampler > SWZ_JITTERED) return c->fail(SWZ_ERR_BAD_ARG, "unknown sampler");
+  if (p->sampler < SWZ_RANDOM_GRID || p->sampler > SWZ_MIN_DISTANCE_FAST) return c->fail(SWZ_ERR_BAD_ARG, "unknown sampler");
+  if (p->sampler == SWZ_MIN_DISTANCE_FAST && (p->flags & SWZ_FLAG_MIN_DISTANCE_PROPERTY))
+    return c->fail(SWZ_ERR_BAD_ARG, "SWZ_FLAG_MIN_DISTANCE_PROPERTY with MIN_DISTANCE_FAST: the property mode's order is not defined for "
+                                    "a sampler that offers only every n-th point of a node");
   if (p->strategy != SWZ_ACCURATE && p->strategy != SWZ_FAST) return c->fail(SWZ_ERR_BAD_ARG, "unknown strategy");
   if (!(p->spacing_at_root > 0.f)) return c->fail(SWZ_ERR_BAD_ARG, "spacing_at_root must be > 0");
   if (p->strategy == SWZ_FAST && p->fast_concurrency == 0)
     return c->fail(SWZ_ERR_BAD_ARG, "FAST needs fast_concurrency >= 1");
   return SWZ_OK;
+}
+
+const char* swz::sharded_sampler_refusal(int sampler) {
+  if (sampler != SWZ_MIN_DISTANCE_FAST) return nullptr;
+  return "MIN_DISTANCE_FAST cannot be sharded: the root offers every fourth point of ITS Morton-ordered range, counted across the "
+         "shards' octants, and a shard does not know how many points the lower shards hold in front of its own";
 }
 
 static std::string g_create_error;
@@ -544,6 +553,7 @@ int swz_shard_presort_device(swz_ctx* c, const double* d_xyz_local, uint64_t n, 
   SWZ_TRY(check_n(c, n + ghost_capacity));
   SWZ_TRY(check_bounds(c, bmin, bmax));
   SWZ_TRY(swz::check_params(c, params));
+  if (const char* why = swz::sharded_sampler_refusal(params->sampler)) return c->fail(SWZ_ERR_BAD_ARG, why);
   if (n && !d_xyz_local) return c->fail(SWZ_ERR_BAD_ARG, "swz_shard_presort_device: NULL buffer");
   if (n == 0) return SWZ_OK;  // a shard without points (its octants are empty) has nothing to prepare
   int st = swz::shard_presort_device(c, d_xyz_local, (uint32_t)n, bmin, bmax, *params, (uint32_t)ghost_capacity);
@@ -560,6 +570,7 @@ int swz_shard_begin_device(swz_ctx* c, const double* d_xyz_local, uint64_t n, co
   SWZ_TRY(check_n(c, n + shard->num_ghosts));
   SWZ_TRY(check_bounds(c, bmin, bmax));
   SWZ_TRY(swz::check_params(c, params));
+  if (const char* why = swz::sharded_sampler_refusal(params->sampler)) return c->fail(SWZ_ERR_BAD_ARG, why);
   if ((n && !d_xyz_local) || (shard->num_ghosts && !shard->d_ghost_xyz))
     return c->fail(SWZ_ERR_BAD_ARG, "swz_shard_begin_device: NULL buffer");
   if (num_root_taken_out) *num_root_taken_out = 0;
@@ -604,6 +615,7 @@ int swz_shard_fast_begin_device(swz_ctx* c, const double* d_xyz_local, uint64_t 
   SWZ_TRY(check_n(c, n));
   SWZ_TRY(check_bounds(c, bmin, bmax));
   SWZ_TRY(swz::check_params(c, params));
+  if (const char* why = swz::sharded_sampler_refusal(params->sampler)) return c->fail(SWZ_ERR_BAD_ARG, why);
   if ((n && !d_xyz_local) || !prefix_counts_out) return c->fail(SWZ_ERR_BAD_ARG, "swz_shard_fast_begin_device: NULL buffer");
   int st = swz::shard_fast_begin_device(c, d_xyz_local, (uint32_t)n, bmin, bmax, *params, prefix_counts_out);
   int st2 = sync(c);
@@ -652,7 +664,7 @@ int swz_sample_points(swz_ctx* c, int sampler, uint64_t max_points_per_node, con
   SWZ_TRY(check_n(c, n));
   SWZ_TRY(check_n(c, num_points));
   SWZ_TRY(check_bounds(c, root_min, root_max));
-  if (sampler < SWZ_RANDOM_GRID || sampler > SWZ_JITTERED) return c->fail(SWZ_ERR_BAD_ARG, "unknown sampler");
+  if (sampler < SWZ_RANDOM_GRID || sampler > SWZ_MIN_DISTANCE_FAST) return c->fail(SWZ_ERR_BAD_ARG, "unknown sampler");
   if (node_level < -1 || node_level > 20) return c->fail(SWZ_ERR_BAD_ARG, "node_level out of range");
   if (num_taken_out) *num_taken_out = 0;
   if (n == 0) return SWZ_OK;
@@ -689,7 +701,7 @@ int swz_sample_points_device(swz_ctx* c, int sampler, uint64_t max_points_per_no
   SWZ_TRY(check_n(c, n));
   SWZ_TRY(check_n(c, num_points));
   SWZ_TRY(check_bounds(c, root_min, root_max));
-  if (sampler < SWZ_RANDOM_GRID || sampler > SWZ_JITTERED) return c->fail(SWZ_ERR_BAD_ARG, "unknown sampler");
+  if (sampler < SWZ_RANDOM_GRID || sampler > SWZ_MIN_DISTANCE_FAST) return c->fail(SWZ_ERR_BAD_ARG, "unknown sampler");
   if (node_level < -1 || node_level > 20) return c->fail(SWZ_ERR_BAD_ARG, "node_level out of range");
   if (num_taken_out) *num_taken_out = 0;
   if (n == 0) return SWZ_OK;

@@ -762,6 +762,10 @@ int swz_group_tile(swz_group* g, double* const* d_xyz, const swz_attribute_colum
     g->err = "unknown strategy";
     return SWZ_ERR_BAD_ARG;
   }
+  if (const char* why = swz::sharded_sampler_refusal(params->sampler)) {
+    g->err = why;
+    return SWZ_ERR_BAD_ARG;
+  }
   if (d_attrs)
     for (int r = 1; r < g->n; ++r)
       for (int t = 0; t < SWZ_ATTR_COUNT; ++t)
@@ -802,6 +806,10 @@ int swz_group_tiler_open(swz_group* g, const double bmin[3], const double bmax[3
   if (!g || !bmin || !bmax || !params) return SWZ_ERR_BAD_ARG;
   if (!g->tiler.empty()) {
     g->err = "swz_group_tiler_open: a data set is open already (swz_group_tiler_close)";
+    return SWZ_ERR_BAD_ARG;
+  }
+  if (const char* why = swz::sharded_sampler_refusal(params->sampler)) {
+    g->err = why;
     return SWZ_ERR_BAD_ARG;
   }
   g->fast_start = -1;

@@ -177,6 +177,8 @@ int encode_device(swz_ctx* c, double* d_xyz, uint32_t n, const double bmin[3], c
 int generate_uniform_device(swz_ctx* c, uint64_t seed, uint64_t first, uint64_t n, double* d_xyz);
 // what every entry point that takes swz_tile_params refuses (swz_api.hip)
 int check_params(swz_ctx* c, const swz_tile_params* p);
+// ... and what the sharded entry points refuse on top of that; nullptr: the sampler may be sharded
+const char* sharded_sampler_refusal(int sampler);
 
 // Stable LSD radix sort of (key, value) pairs.  The input goes in the FIRST pair: the keys in d_keys_in and, unless
 // vals_identity, the values in d_vals_tmp (with vals_identity the first pass synthesises value = element index instead of

@@ -9,6 +9,9 @@ namespace swz {
 
 enum : uint8_t { MODE_TAKE_ALL = 0, MODE_SAMPLE = 1 };
 
+// the samplers that run the greedy minimum-distance test (MIN_DISTANCE_FAST: on every n-th point of a node, swz_mdfast.hip)
+inline bool greedy_sampler(int sampler) { return sampler == SWZ_MIN_DISTANCE || sampler == SWZ_MIN_DISTANCE_FAST; }
+
 // device counters of one level iteration
 enum {
   CTR_NUM_NODES = 0,     // nodes at this level
@@ -101,7 +104,7 @@ struct LevelPlan {
   bool reroot = false;       // sampling this level would need Morton re-rooting
   bool md_property = false;  // MIN_DISTANCE: SWZ_FLAG_MIN_DISTANCE_PROPERTY (swz_mdprop.hip)
   Box root;
-  // RANDOM_GRID / GRID_CENTER: candidate_level_in_octree (Sampling.h:223-229); -1 = first point only
+  // RANDOM_GRID / GRID_CENTER / MIN_DISTANCE_FAST: candidate_level_in_octree (Sampling.h:223-229); -1 = first point only
   int cand = -1;
   // JITTERED / MIN_DISTANCE
   double spacing_node = 0.0; // spacing_at_root / pow(2, level + 1)
@@ -150,7 +153,8 @@ int fast_prefix_counts(swz_ctx* c, const uint64_t* d_keys_sorted, uint32_t n, ui
 int fast_start_level_from_counts(const uint64_t* counts, uint32_t concurrency);
 
 // ---- the samplers of a level (called by level_step after the node segmentation; each fills lb.taken) ----------------
-// RANDOM_GRID (swz_grid.hip): the first point of every candidate cell; candidate level -1 (GRID_CENTER's too): of every node.
+// RANDOM_GRID (swz_grid.hip): the first point of every candidate cell; candidate level -1 (GRID_CENTER's and
+// MIN_DISTANCE_FAST's too): of every node.
 int random_grid_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const LevelBuffers& lb);
 // GRID_CENTER / JITTERED (swz_grid.hip): on key coordinates when grid_level_uses_keys, else on sp.X / sp.Y / sp.Z
 int grid_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp, const LevelBuffers& lb);
@@ -162,5 +166,10 @@ bool grid_level_uses_keys(const swz_ctx* c, const LevelPlan& plan, const SortedP
 int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp,
                        const LevelBuffers& lb, uint32_t num_nodes, uint32_t sample_nodes,
                        uint32_t sample_points, uint32_t* rounds_out);
+// MIN_DISTANCE_FAST on a level whose stride is above one (swz_mdfast.hip): the candidates -- every stride-th point of every
+// MODE_SAMPLE node, counted from the node's first -- as an active set of their own through min_distance_level, the decisions
+// scattered back into lb.taken (zero for the points of sampled nodes on entry).
+int min_distance_fast_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp, const LevelBuffers& lb,
+                            uint32_t stride, uint32_t num_nodes, uint32_t sample_nodes, uint32_t* rounds_out);
 
 }  // namespace swz

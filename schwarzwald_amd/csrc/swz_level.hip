@@ -1,6 +1,6 @@
 // swz_level.hip -- one level of the level-synchronous octree tiling: node segmentation (K3), the level's sampler,
 // stream compaction (K5), and the host's plan of a level.  The grid samplers live in swz_grid.hip, MIN_DISTANCE behind
-// swz_md.hip; the drivers that loop over the levels in swz_session.hip, swz_shard.hip and swz_tiler.hip.
+// swz_md.hip (MIN_DISTANCE_FAST: swz_mdfast.hip in front of it); the drivers that loop over the levels in swz_session.hip, swz_shard.hip and swz_tiler.hip.
 //
 // The reference recurses top-down per node (TilingAlgorithmBase::do_tiling_for_node /
 // tile_node / tile_internal_node, core/tiling/TilingAlgorithms.cpp:499-561, 351-492, 247-349): sample
@@ -252,6 +252,7 @@ int required_depth_host(int sampler, int node_level, double root_extent_x, float
     case SWZ_GRID_CENTER:
       return node_level_to_sample_from_host(root_extent_x, root_max_spacing, node_level);
     case SWZ_MIN_DISTANCE:
+    case SWZ_MIN_DISTANCE_FAST:  // (Sampling.cpp:45-47)
       return node_level;
     default: {
       const auto spacing_at_this_node = root_max_spacing / std::pow(2, node_level + 1);
@@ -316,7 +317,7 @@ LevelPlan make_plan(int level, int sampler, uint64_t max_points, float spacing_a
 
 bool level_decides_on_keys(const swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp) {
   if (plan.sampler == SWZ_RANDOM_GRID) return true;
-  if (plan.sampler == SWZ_MIN_DISTANCE) return min_distance_level_uses_keys(c, plan, sp);
+  if (greedy_sampler(plan.sampler)) return min_distance_level_uses_keys(c, plan, sp);
   return grid_level_uses_keys(c, plan, sp);
 }
 
@@ -348,7 +349,7 @@ int level_step(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const Sor
       // (node ids: zeros -- unless the one node is going to be sampled and the sampler is one that then never looks, see
       // node_fill_kernel)
       const bool sampled_for_sure = !plan.terminal && (plan.force_sample || (uint64_t)m > plan.max_points);
-      if (plan.sampler == SWZ_MIN_DISTANCE || !sampled_for_sure)
+      if (greedy_sampler(plan.sampler) || !sampled_for_sure)
         SWZ_HIP(c, hipMemsetAsync(lb.nid, 0, (size_t)m * sizeof(uint32_t), c->stream));
       hipLaunchKernelGGL(single_node_kernel, dim3(1), dim3(1), 0, c->stream, lb.nstart, lb.counters + CTR_NUM_NODES, m);
       SWZ_LAUNCH_CHECK(c);
@@ -371,7 +372,7 @@ int level_step(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const Sor
     SWZ_LAUNCH_CHECK(c);
     if (fill_after_modes) {  // the node id per point, from the node starts (MIN_DISTANCE reads it on every level)
       hipLaunchKernelGGL(node_fill_kernel, dim3(div_up(m, NF_TILE)), dim3(256), 0, c->stream, lb.nstart, lb.counters, m, lb.nid,
-                         plan.sampler == SWZ_MIN_DISTANCE ? 0 : 1);
+                         greedy_sampler(plan.sampler) ? 0 : 1);
       SWZ_LAUNCH_CHECK(c);
     }
   }
@@ -381,7 +382,10 @@ int level_step(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const Sor
     SWZ_TRY(random_grid_level(c, plan, as, lb));
   } else if (plan.sampler == SWZ_GRID_CENTER || plan.sampler == SWZ_JITTERED) {
     SWZ_TRY(grid_level(c, plan, as, sp, lb));
-  } else {  // MIN_DISTANCE
+  } else if (plan.sampler == SWZ_MIN_DISTANCE_FAST && plan.cand < 0) {
+    // AdaptivePoissonDiskSampling, Sampling.h:510-512: "just take the first point" of every sampled node, no sweep
+    SWZ_TRY(random_grid_level(c, plan, as, lb));
+  } else {  // MIN_DISTANCE; MIN_DISTANCE_FAST: the same on every n-th point of a node
     SWZ_HIP(c, hipMemsetAsync(lb.taken, 0, m, c->stream));
     uint32_t h[CTR_COUNT];
     SWZ_HIP(c, hipMemcpyAsync(h, lb.counters, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -391,7 +395,10 @@ int level_step(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const Sor
       hipLaunchKernelGGL(take_all_kernel, dim3(nb), dim3(256), 0, c->stream, m, lb.nid, lb.nmode, lb.taken);
       SWZ_LAUNCH_CHECK(c);
     }
-    if (h[CTR_SAMPLE_NODES] > 0) {
+    const uint32_t stride = plan.sampler == SWZ_MIN_DISTANCE_FAST ? (uint32_t)swz_min_distance_fast_stride(plan.level) : 1u;
+    if (h[CTR_SAMPLE_NODES] > 0 && stride > 1u) {
+      SWZ_TRY(min_distance_fast_level(c, plan, as, sp, lb, stride, h[CTR_NUM_NODES], h[CTR_SAMPLE_NODES], &res->md_rounds));
+    } else if (h[CTR_SAMPLE_NODES] > 0) {
       SWZ_TRY(min_distance_level(c, plan, as, sp, lb, h[CTR_NUM_NODES], h[CTR_SAMPLE_NODES], h[CTR_SAMPLE_POINTS],
                                  &res->md_rounds));
     }

@@ -340,7 +340,7 @@ int sample_points_device(swz_ctx* c, int sampler, uint64_t max_points, const uin
   // RANDOM_GRID and GRID_CENTER never look at node_key: the whole range is "the node" (count, candidate level from
   // node_level; the reference's own test samples a range spanning all octants at node level 0,
   // test/TestOctreeIndexing.cpp:169-252).  MIN_DISTANCE and JITTERED take the node's box from node_key.
-  const bool uses_node_key = sampler == SWZ_MIN_DISTANCE || sampler == SWZ_JITTERED;
+  const bool uses_node_key = greedy_sampler(sampler) || sampler == SWZ_JITTERED;
   if (node_level >= 0 && uses_node_key) {
     uint32_t* d_bad = nullptr;
     SWZ_TRY(c->get("lvl_counters", (size_t)CTR_COUNT, &d_bad));

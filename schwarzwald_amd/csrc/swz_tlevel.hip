@@ -440,7 +440,7 @@ static int level_merge(swz_tiler* t, BatchWork& w, const LevelPlan& plan, const 
     ms->old_hi = p.pull_lo + nc;
     ms->new_key = as.akey;
     ms->new_m = as.m;
-    if (plan.sampler == SWZ_MIN_DISTANCE && !plan.terminal && plan.level + 2 < 22) {
+    if (greedy_sampler(plan.sampler) && !plan.terminal && plan.level + 2 < 22) {
       StoreLevel& below = t->lv[plan.level + 2];
       if (below.cnt) {  // (the table this batch's next level asks for anyway)
         SWZ_TRY(store_table(c, below, plan.level + 2));

@@ -59,14 +59,27 @@ enum class TilingStrategy { Accurate, Fast };
 struct SamplingStrategy {
   int kind;  // SWZ_RANDOM_GRID ...
   size_t max_points_per_node;
+  // SWZ_MIN_DISTANCE_FAST (AdaptivePoissonDiskSampling): the share of a node's points that is examined, per node level.  The
+  // library samples with the command line's densities and no others (swz_min_distance_fast_stride); this is their record.
+  float (*density_per_level)(int32_t) = nullptr;
 };
-// make_sampling_strategy_from_name -- core/tiling/Sampling.h:774-791 (MIN_DISTANCE_FAST is out of scope)
+// the densities TilerProcess::make_sampling_strategy attaches (TilerProcess.cpp:502-508): 0.25f, 0.5f, then 1.f
+inline float min_distance_fast_density(int32_t node_level) { return 1.f / static_cast<float>(swz_min_distance_fast_stride(node_level)); }
+// make_sampling_strategy_from_name -- core/tiling/Sampling.h:774-791 (no MIN_DISTANCE_FAST: like the reference's, this
+// factory has no densities to build the adaptive sampler with; see make_sampling_strategy)
 inline SamplingStrategy make_sampling_strategy_from_name(const std::string& name, size_t max_points_per_node) {
   if (name == "RANDOM_GRID") return {SWZ_RANDOM_GRID, max_points_per_node};
   if (name == "GRID_CENTER") return {SWZ_GRID_CENTER, max_points_per_node};
   if (name == "MIN_DISTANCE") return {SWZ_MIN_DISTANCE, max_points_per_node};
   if (name == "JITTERED") return {SWZ_JITTERED, max_points_per_node};
   throw std::runtime_error{"Unrecognized sampling strategy name \"" + name + "\""};
+}
+// TilerProcess::make_sampling_strategy -- core/process/TilerProcess.cpp:491-516: the five --sampling names
+inline SamplingStrategy make_sampling_strategy(const std::string& name, size_t max_points_per_node) {
+  if (name == "MIN_DISTANCE_FAST") return {SWZ_MIN_DISTANCE_FAST, max_points_per_node, &min_distance_fast_density};
+  if (name == "RANDOM_GRID" || name == "GRID_CENTER" || name == "MIN_DISTANCE" || name == "JITTERED")
+    return make_sampling_strategy_from_name(name, max_points_per_node);
+  throw std::invalid_argument{"Unrecognized sampling strategy " + name};
 }
 
 struct TilerMetaParameters {  // core/process/Tiler.h:64-75

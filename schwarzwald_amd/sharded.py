@@ -222,10 +222,18 @@ def _joint_root_step(ctx, rank, world, group, gather, begin, failure):
     return result
 
 
+def _refuse_unshardable(params):
+    # (like the library's own sharded entry points: swz_shard_*, swz_tiler_shard_*, swz_group_*)
+    if params.sampler == api.MIN_DISTANCE_FAST:
+        raise api.SwzError(api.ERR_BAD_ARG, "MIN_DISTANCE_FAST cannot be sharded: the root offers every fourth point of its "
+                           "Morton-ordered range, counted across the ranks' octants")
+
+
 class ShardedTiler:
     """Tiles one batch whose points are spread over the ranks of a process group."""
 
     def __init__(self, ctx, device, bmin, bmax, params, group=None):
+        _refuse_unshardable(params)
         self.ctx, self.device, self.bmin, self.bmax, self.params, self.group = ctx, device, bmin, bmax, params, group
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
@@ -524,6 +532,7 @@ class ShardedBatchTiler:
     and, without communication, the levels below it."""
 
     def __init__(self, ctx, device, bmin, bmax, params, group=None, capacity_hint=0):
+        _refuse_unshardable(params)
         self.ctx, self.device, self.bmin, self.bmax, self.params, self.group = ctx, device, bmin, bmax, params, group
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
