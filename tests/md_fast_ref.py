@@ -151,13 +151,21 @@ def files_table(files):
 
 
 class MultiBatch:
-    """ACCURATE over several batches (MBTiler): files[(level, key)] = global ids in file order."""
+    """ACCURATE over several batches (MBTiler): files[(level, key)] = global ids in file order.  With start_level = S > 0 the
+    batches of a FAST tiler (MBTiler::add_batch): every batch is split at its start nodes (node level S - 1), each of which
+    is tiled like a root; reconstruct_files(files, xyz, ..., S - 1) then is the finalize.
 
-    def __init__(self, bmin, bmax, max_points, spacing_at_root, max_depth=100):
+    A file whose re-keyed points are no longer ascending ends the comparison with the library (which sorts them, where the
+    reference merges them as they are): by default that is an assertion; with count_unsorted=True such nodes are counted in
+    unsorted_cached_nodes instead (like the oracle's counter), and files is not to be trusted when the count is not zero."""
+
+    def __init__(self, bmin, bmax, max_points, spacing_at_root, max_depth=100, start_level=0, count_unsorted=False):
         self.bmin, self.bmax, self.max_points, self.spacing, self.max_depth = list(bmin), list(bmax), max_points, spacing_at_root, max_depth
+        self.start_level, self.count_unsorted = int(start_level), count_unsorted
         self.xyz = np.zeros((0, 3))
         self.files = {}
         self.points_visited = 0
+        self.unsorted_cached_nodes = 0
 
     def add_batch(self, batch):
         batch = np.ascontiguousarray(batch, dtype=np.float64).reshape(-1, 3)
@@ -167,13 +175,22 @@ class MultiBatch:
         if len(keys) == 0:
             return
         perm = O.sort_by_key(keys)
-        self._node(keys[perm], (perm + base).astype(np.uint32), 0, -1)
+        skeys, ids = keys[perm], (perm + base).astype(np.uint32)
+        if self.start_level <= 0:
+            self._node(skeys, ids, 0, -1)
+            return
+        sh = np.uint64(3 * (LEVELS - self.start_level))
+        prefix = skeys >> sh
+        heads = np.flatnonzero(np.concatenate([[True], prefix[1:] != prefix[:-1]]))
+        for b, e in zip(heads, np.concatenate([heads[1:], [len(skeys)]])):
+            self._node(skeys[b:e], ids[b:e], int(prefix[b]) << int(sh), self.start_level - 1)
 
     def _node(self, keys, ids, node_key, node_level):
         cached = np.asarray(self.files.get((node_level, node_key), []), dtype=np.uint32)
         ckeys = _rekey(cached, self.xyz, node_key, node_level, self.bmin, self.bmax) if len(cached) else np.zeros(0, np.uint64)
-        if len(ckeys) > 1:
-            assert np.all(ckeys[1:] >= ckeys[:-1]), "a file read back out of order: choose another input"
+        if len(ckeys) > 1 and not np.all(ckeys[1:] >= ckeys[:-1]):
+            assert self.count_unsorted, "a file read back out of order: choose another input"
+            self.unsorted_cached_nodes += 1
         self.points_visited += len(keys) + len(cached)
         max_level = min(LEVELS - 1, self.max_depth)
         if node_level >= max_level:  # terminal: new ++ cached
@@ -190,10 +207,11 @@ class MultiBatch:
             self._node(rk[b:e], ri[b:e], int(node_key) | (o << _shift(node_level + 1)), node_level + 1)
 
 
-def reconstruct_files(files, xyz, bmin, bmax, max_points, spacing_at_root, lowest_given_level):
+def reconstruct_files(files, xyz, bmin, bmax, max_points, spacing_at_root, lowest_given_level, unsorted=None):
     """FAST finalize on node files: files holds the levels >= lowest_given_level (node level; ids into xyz, clamped
     positions); the levels above are rebuilt, deepest first, from the children's files in octant order, keyed against the
-    root bounds, with AlwaysAdhereToMinSpacing.  Returns files with the rebuilt levels added."""
+    root bounds, with AlwaysAdhereToMinSpacing.  Returns files with the rebuilt levels added.  unsorted: a list that receives
+    the parents whose children's files are out of order (instead of the assertion; the result is then not to be trusted)."""
     out = {k: list(v) for k, v in files.items() if k[0] >= lowest_given_level}
     for lv in range(lowest_given_level, -1, -1):  # children at node level lv (lv + 1 octants), parents at lv - 1
         child_shift = _shift(lv)
@@ -203,7 +221,9 @@ def reconstruct_files(files, xyz, bmin, bmax, max_points, spacing_at_root, lowes
             ids = [i for o in range(8) for i in out.get((lv, node_key | (o << child_shift)), [])]
             ids = np.asarray(ids, dtype=np.uint32)
             keys, _ = O.index_points(xyz[ids], bmin, bmax)
-            assert np.all(keys[1:] >= keys[:-1]), "children's files out of order inside a parent: choose another input"
+            if not np.all(keys[1:] >= keys[:-1]):
+                assert unsorted is not None, "children's files out of order inside a parent: choose another input"
+                unsorted.append((lv - 1, node_key))
             t = sample_points(max_points, keys, ids, xyz, node_key, lv - 1, bmin, bmax, spacing_at_root, O.ALWAYS_ADHERE).astype(bool)
             out[(lv - 1, node_key)] = list(ids[t])
     return out
