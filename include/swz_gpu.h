@@ -79,7 +79,8 @@ int swz_set_stream(swz_ctx* ctx, void* hip_stream);
  *   kind), SWZ_POISON=<byte> and SWZ_POISON_ONLY=<part of a buffer name> (fill new workspace memory),
  *   SWZ_BIN_WRITER_THREADS (host threads that write node files).
  * - Switches that only force a path, a schedule or a capacity -- the samplers' results stay what they are:
- *   sort: SWZ_SORT_ONESWEEP=0, SWZ_SORT_HYBRID_MIN_N, SWZ_SORT_HYBRID_TOP, SWZ_SORT_FIX_SHORT, SWZ_SORT_FIX_LONG;
+ *   sort: SWZ_SORT_ONESWEEP=0, SWZ_SORT_HYBRID_MIN_N, SWZ_SORT_HYBRID_TOP, SWZ_SORT_FIX_SHORT, SWZ_SORT_FIX_LONG,
+ *   SWZ_SORT_WIDE_MIN_N (keys from which a scatter pass takes its 8192-key tile);
  *   GRID_CENTER / JITTERED: SWZ_GRID_KEYS=0, SWZ_GRID_KEYS_SLACK >= 0 (a large one sends every run of more than one point
  *   through the exact pass), SWZ_GRID_TABLE_DEPTH, SWZ_JITTER_TABLE=0, SWZ_LEVEL_NODES_SCAN;
  *   MIN_DISTANCE, the path of a level: SWZ_MD_SPARSE_LIMIT, SWZ_MD_KEYS=0, SWZ_MD_KEYS_MIN_CELLS, SWZ_MD_KEYS_BAND >= 0 (a

@@ -319,42 +319,61 @@ __global__ __launch_bounds__(RADIX) void radix_gscan_kernel(uint32_t* __restrict
   hrow[threadIdx.x] = ex;
 }
 
-__global__ __launch_bounds__(RS_THREADS) void radix_onesweep_kernel(const uint64_t* __restrict__ keys_in,
-                                                                    const uint32_t* __restrict__ vals_in,
-                                                                    uint64_t* __restrict__ keys_out,
-                                                                    uint32_t* __restrict__ vals_out, uint32_t n, int shift,
-                                                                    const uint32_t* __restrict__ gstart /*[256]*/,
-                                                                    uint32_t* __restrict__ status /*[ntiles][256]*/,
-                                                                    uint32_t* __restrict__ ticket) {
-  // 52 KB of LDS: three workgroups per CU (the per-wave counters fit 16 bits: a wave holds 1024 keys)
-  __shared__ uint16_t whist[RS_WAVES][RADIX];
+// The scatter kernel of a pass comes in two shapes, chosen from n on the host (os_wide):
+//   256 threads x 16 keys = 4096 keys per tile, keys and values exchanged through LDS images of their own (52 KB, three
+//     workgroups per CU);
+//   512 threads x 16 keys = 8192 keys per tile: a digit run of the tile is twice as long (32 keys = 256 B on a uniform
+//     digit instead of 128 B), half the status words and look-backs per key.  Keys and values go through the SAME 64 KB
+//     image one after the other (69 KB: two workgroups = sixteen wavefronts per CU).
+// Digit d belongs to thread d of the workgroup in either shape (the threads from 256 up own none).
+constexpr int OS_KPT = 16;                    // keys per thread; a wavefront holds 1024 consecutive keys (16-bit counters)
+constexpr int OS_WAVE_SPAN = WAVE * OS_KPT;
+constexpr int OS_THREADS_SMALL = 256, OS_THREADS_WIDE = 512;
+constexpr int OS_TILE_SMALL = OS_THREADS_SMALL * OS_KPT, OS_TILE_WIDE = OS_THREADS_WIDE * OS_KPT;
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void radix_onesweep_kernel(const uint64_t* __restrict__ keys_in,
+                                                                 const uint32_t* __restrict__ vals_in,
+                                                                 uint64_t* __restrict__ keys_out,
+                                                                 uint32_t* __restrict__ vals_out, uint32_t n, int shift,
+                                                                 const uint32_t* __restrict__ gstart /*[256]*/,
+                                                                 uint32_t* __restrict__ status /*[ntiles][256]*/,
+                                                                 uint32_t* __restrict__ ticket) {
+  constexpr int TILE = THREADS * OS_KPT, WAVES = THREADS / WAVE;
+  constexpr bool SHARE = THREADS > OS_THREADS_SMALL;  // values through the keys' image, after the keys have left it
+  static_assert(THREADS >= RADIX && OS_WAVE_SPAN <= 65535, "one thread per digit; a wave's digit count fits 16 bits");
+  __shared__ uint16_t whist[WAVES][RADIX];
   __shared__ uint32_t doff[RADIX];  // start of the digit's run inside the tile, later: global start minus that
-  __shared__ uint32_t scan_lds[RS_WAVES];
-  __shared__ uint64_t xkeys[RS_TILE];
-  __shared__ uint32_t xvals[RS_TILE];
+  __shared__ uint32_t scan_lds[WAVES];
+  // one raw image, two typed views: the values follow the keys (own image) or take their place once they have left (shared)
+  __shared__ __attribute__((aligned(16))) unsigned char image[SHARE ? TILE * sizeof(uint64_t) : TILE * (sizeof(uint64_t) + sizeof(uint32_t))];
   __shared__ uint32_t s_tile;
+  uint64_t* const xkeys = reinterpret_cast<uint64_t*>(image);
+  uint32_t* const xvals = reinterpret_cast<uint32_t*>(image + (SHARE ? 0 : TILE * sizeof(uint64_t)));
 
   const uint32_t tid = threadIdx.x, w = tid / WAVE, l = lane_id();
+  const bool owner = tid < (uint32_t)RADIX;  // of digit tid
   if (tid == 0) s_tile = atomicAdd(ticket, (uint32_t)OS_BATCH);
   __syncthreads();
   const uint32_t tile0 = s_tile;
-  const uint32_t ntiles = div_up_dev(n, RS_TILE);
+  const uint32_t ntiles = div_up_dev(n, TILE);
   uint32_t carry = 0;  // digit tid: keys with this digit in all tiles in front of the current one
   for (uint32_t b = 0; b < (uint32_t)OS_BATCH; ++b) {
     const uint32_t tile = tile0 + b;
     if (tile >= ntiles) break;
-#pragma unroll
-    for (int i = 0; i < RS_WAVES; ++i) whist[i][tid] = 0;
+    for (uint32_t i = tid; i < (uint32_t)(WAVES * RADIX); i += THREADS) (&whist[0][0])[i] = 0;
     __syncthreads();
-    const uint64_t tile_base = (uint64_t)tile * RS_TILE;
-    const uint32_t tile_n = (uint32_t)((n - tile_base) < (uint64_t)RS_TILE ? (n - tile_base) : RS_TILE);
+    const uint64_t tile_base = (uint64_t)tile * TILE;
+    const uint32_t tile_n = (uint32_t)((n - tile_base) < (uint64_t)TILE ? (n - tile_base) : TILE);
 
-    uint64_t key[RS_KPT];
-    uint32_t val[RS_KPT];
-    uint32_t rank[RS_KPT];
+    // wave-blocked arrangement: item k of lane l is element w*1024 + k*64 + l of the tile: the order is (wave, item, lane)
+    auto elem = [&](int k) -> uint32_t { return w * OS_WAVE_SPAN + (uint32_t)k * WAVE + l; };
+    uint64_t key[OS_KPT];
+    uint32_t val[OS_KPT];
+    uint32_t rank[OS_KPT];
 #pragma unroll
-    for (int k = 0; k < RS_KPT; ++k) {
-      const uint32_t e = w * RS_WAVE_SPAN + k * WAVE + l;
+    for (int k = 0; k < OS_KPT; ++k) {
+      const uint32_t e = elem(k);
       if (e < tile_n) {
         key[k] = keys_in[tile_base + e];
         val[k] = vals_in ? vals_in[tile_base + e] : (uint32_t)(tile_base + e);
@@ -363,11 +382,12 @@ __global__ __launch_bounds__(RS_THREADS) void radix_onesweep_kernel(const uint64
         val[k] = 0;
       }
     }
+    // rank of every key among the equal-digit keys of its own wave, in (item, lane) order.  The per-wave counters are
+    // read and written by different lanes in successive items: volatile keeps every access a real, in-order LDS operation.
     volatile uint16_t* wh = whist[w];
 #pragma unroll
-    for (int k = 0; k < RS_KPT; ++k) {
-      const uint32_t e = w * RS_WAVE_SPAN + k * WAVE + l;
-      const bool ok = e < tile_n;
+    for (int k = 0; k < OS_KPT; ++k) {
+      const bool ok = elem(k) < tile_n;
       const uint64_t valid = __ballot(ok);
       const uint32_t d = (uint32_t)(key[k] >> shift) & (RADIX - 1);
       const uint64_t peers = match_digit(d, valid);
@@ -388,37 +408,38 @@ __global__ __launch_bounds__(RS_THREADS) void radix_onesweep_kernel(const uint64
 
     // thread tid owns digit tid: exclusive prefix over the waves, the tile's count of the digit
     uint32_t cnt = 0;
+    if (owner) {
 #pragma unroll
-    for (int i = 0; i < RS_WAVES; ++i) {
-      const uint32_t t = whist[i][tid];
-      whist[i][tid] = (uint16_t)cnt;
-      cnt += t;
+      for (int i = 0; i < WAVES; ++i) {
+        const uint32_t t = whist[i][tid];
+        whist[i][tid] = (uint16_t)cnt;
+        cnt += t;
+      }
     }
     uint32_t* my_status = status + (size_t)tile * RADIX + tid;
-    const bool look_back = b == 0 && tile > 0;  // the tiles in front belong to other workgroups
+    const bool look_back = owner && b == 0 && tile > 0;  // the tiles in front belong to other workgroups
     uint32_t look = 0;
     if (look_back) {
       // publish the tile's own count right away: later tiles can walk over it while this one is still busy; and take
       // a first look at the tile in front: by the time the exchange below is done its answer has arrived
       __hip_atomic_store(my_status, OS_FLAG_LOCAL | cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       look = __hip_atomic_load(status + (size_t)(tile - 1) * RADIX + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
+    } else if (owner) {
       __hip_atomic_store(my_status, OS_FLAG_INCL | (carry + cnt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     uint32_t total;
-    const uint32_t ds = block_excl_sum<RS_THREADS>(cnt, scan_lds, total);
-    doff[tid] = ds;
+    const uint32_t ds = block_excl_sum<THREADS>(cnt, scan_lds, total);
+    if (owner) doff[tid] = ds;
     __syncthreads();
 
-    // exchange through LDS: position inside the digit-sorted tile
+    // exchange through LDS: position inside the digit-sorted tile (kept in rank[] for the values of the shared image)
 #pragma unroll
-    for (int k = 0; k < RS_KPT; ++k) {
-      const uint32_t e = w * RS_WAVE_SPAN + k * WAVE + l;
-      if (e < tile_n) {
+    for (int k = 0; k < OS_KPT; ++k) {
+      if (elem(k) < tile_n) {
         const uint32_t d = (uint32_t)(key[k] >> shift) & (RADIX - 1);
         const uint32_t p = doff[d] + whist[w][d] + rank[k];
         xkeys[p] = key[k];
-        xvals[p] = val[k];
+        if constexpr (SHARE) rank[k] = p; else xvals[p] = val[k];
       }
     }
 
@@ -438,19 +459,42 @@ __global__ __launch_bounds__(RS_THREADS) void radix_onesweep_kernel(const uint64
       __hip_atomic_store(my_status, OS_FLAG_INCL | (carry + cnt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();  // every thread has read doff for the exchange
-    doff[tid] = gstart[tid] + carry - ds;
+    if (owner) doff[tid] = gstart[tid] + carry - ds;
     __syncthreads();
 
     // contiguous stores per digit run
+    if constexpr (SHARE) {
+      uint32_t dst[OS_KPT];
 #pragma unroll
-    for (int k = 0; k < RS_KPT; ++k) {
-      const uint32_t j = k * RS_THREADS + tid;
-      if (j < tile_n) {
-        const uint64_t kk = xkeys[j];
-        const uint32_t d = (uint32_t)(kk >> shift) & (RADIX - 1);
-        const uint32_t dst = doff[d] + j;
-        keys_out[dst] = kk;
-        vals_out[dst] = xvals[j];
+      for (int k = 0; k < OS_KPT; ++k) {
+        const uint32_t j = k * THREADS + tid;
+        if (j < tile_n) {
+          const uint64_t kk = xkeys[j];
+          dst[k] = doff[(uint32_t)(kk >> shift) & (RADIX - 1)] + j;
+          keys_out[dst[k]] = kk;
+        }
+      }
+      __syncthreads();  // the keys have left the image
+#pragma unroll
+      for (int k = 0; k < OS_KPT; ++k)
+        if (elem(k) < tile_n) xvals[rank[k]] = val[k];
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < OS_KPT; ++k) {
+        const uint32_t j = k * THREADS + tid;
+        if (j < tile_n) vals_out[dst[k]] = xvals[j];
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < OS_KPT; ++k) {
+        const uint32_t j = k * THREADS + tid;
+        if (j < tile_n) {
+          const uint64_t kk = xkeys[j];
+          const uint32_t d = (uint32_t)(kk >> shift) & (RADIX - 1);
+          const uint32_t dst = doff[d] + j;
+          keys_out[dst] = kk;
+          vals_out[dst] = xvals[j];
+        }
       }
     }
     carry += cnt;
@@ -580,16 +624,27 @@ __global__ __launch_bounds__(256) void radix_copy_pairs_kernel(const uint64_t* _
   }
 }
 
+// The 8192-key shape is taken from OS_WIDE_MIN_N keys on (SWZ_SORT_WIDE_MIN_N moves the threshold).  Measured against the
+// 4096-key shape (EXPERIMENTS R10.1): 4 % slower at 2^20 keys, 11 % faster at 2^21, 19 % at 2^22, 7 % at 10 M, 16 % at
+// 100 M, 22 % at 1 B.  The threshold is the state the library was verified in; 2^21 is where the large tile starts to pay.
+constexpr uint32_t OS_WIDE_MIN_N = 1u << 23;
+static bool os_wide(swz_ctx* c, uint32_t n) { return n >= (uint32_t)c->opt_int("SWZ_SORT_WIDE_MIN_N", OS_WIDE_MIN_N); }
+
 static int radix_lsd_passes(swz_ctx* c, uint64_t*& kin, uint32_t*& vin, uint64_t*& kout, uint32_t*& vout, uint32_t n, int first_pass,
                             int last_pass, bool first_synthesises_values, uint32_t* d_ghist, uint32_t* d_status, uint32_t* d_ticket) {
-  const uint32_t ntiles = div_up(n, RS_TILE);
+  const bool wide = os_wide(c, n);
+  const uint32_t ntiles = div_up(n, wide ? OS_TILE_WIDE : OS_TILE_SMALL);  // (never more than the status buffer's div_up(n, OS_TILE_SMALL))
   SWZ_HIP(c, hipMemsetAsync(d_ticket, 0, sizeof(uint32_t) * RADIX_PASSES, c->stream));
   for (int pass = first_pass; pass <= last_pass; ++pass) {
     ProfScope ps(c, "radix_scatter", (uint64_t)n * 24ull);
     SWZ_HIP(c, hipMemsetAsync(d_status, 0, (size_t)ntiles * RADIX * sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(radix_onesweep_kernel, dim3(div_up(ntiles, OS_BATCH)), dim3(RS_THREADS), 0, c->stream, kin,
-                       (pass == first_pass && first_synthesises_values) ? (const uint32_t*)nullptr : vin, kout, vout, n,
-                       pass * RADIX_BITS, d_ghist + pass * RADIX, d_status, d_ticket + pass);
+    const uint32_t* vals = (pass == first_pass && first_synthesises_values) ? (const uint32_t*)nullptr : vin;
+    if (wide)
+      hipLaunchKernelGGL(radix_onesweep_kernel<OS_THREADS_WIDE>, dim3(div_up(ntiles, OS_BATCH)), dim3(OS_THREADS_WIDE), 0, c->stream,
+                         kin, vals, kout, vout, n, pass * RADIX_BITS, d_ghist + pass * RADIX, d_status, d_ticket + pass);
+    else
+      hipLaunchKernelGGL(radix_onesweep_kernel<OS_THREADS_SMALL>, dim3(div_up(ntiles, OS_BATCH)), dim3(OS_THREADS_SMALL), 0, c->stream,
+                         kin, vals, kout, vout, n, pass * RADIX_BITS, d_ghist + pass * RADIX, d_status, d_ticket + pass);
     SWZ_LAUNCH_CHECK(c);
     std::swap(kin, kout);
     std::swap(vin, vout);
@@ -615,10 +670,9 @@ int radix_sort_pairs(swz_ctx* c, uint64_t* d_keys_in, uint32_t* d_vals_tmp, uint
   uint64_t* kout = d_keys_out;
   uint32_t* vout = d_vals_out;
   if (n < (1u << 30) && c->opt_on("SWZ_SORT_ONESWEEP", true)) {
-    static_assert(RADIX == RS_THREADS, "one thread per digit");
     uint32_t *d_ghist = nullptr, *d_status = nullptr, *d_ticket = nullptr;
     SWZ_TRY(c->get("radix_ghist", (size_t)RADIX_PASSES * RADIX, &d_ghist));
-    SWZ_TRY(c->get("radix_status", (size_t)ntiles * RADIX, &d_status));
+    SWZ_TRY(c->get("radix_status", (size_t)div_up(n, OS_TILE_SMALL) * RADIX, &d_status));  // the small shape's tile count: the most either shape needs
     SWZ_TRY(c->get("radix_ticket", (size_t)RADIX_PASSES, &d_ticket));
     // the digit histograms of the whole input, for the digits from `first` up
     auto global_histograms = [&](int first) -> int {

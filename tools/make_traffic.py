@@ -41,7 +41,8 @@ else:
 # (templated kernels are listed as "void swz::md_sweep_kernel<1, false>"; the fused cell scan belongs to the class too)
 # (round 6: the sparse levels run sb_block_kernel / sb_table_kernel, swz_mdblock.hip)
 md_k, md_b = bytes_of(lambda k: "swz::md_" in k or "swz::sp_" in k or "swz::sb_" in k or "swz::mq_" in k or "swz::CellHeadF" in k or "swz::MqHeadF" in k)
-rs_k, rs_b = bytes_of(lambda k: k in ("swz::radix_scatter_kernel", "swz::radix_onesweep_kernel"))
+# (the one-sweep kernel is a template: "void swz::radix_onesweep_kernel<512>")
+rs_k, rs_b = bytes_of(lambda k: k == "swz::radix_scatter_kernel" or "swz::radix_onesweep_kernel" in k)
 # launches of the scatter kernel in the profiled step: the passes over the whole input (the eight tiny passes that sort
 # the sample which picks the number of top digits do not count)
 rs_disp = sum(fetch.get(k, (0, 0))[0] for k in rs_k)
