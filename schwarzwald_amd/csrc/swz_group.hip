@@ -436,6 +436,7 @@ void shard_thread(ShardCall a) {
   const bool sequential_root = a.params->sampler == SWZ_MIN_DISTANCE && global_points > a.params->max_points_per_node;
   uint64_t taken = 0;
   g->root_taken_count[r] = 0;
+  bool in_turns = false;
   if (!sequential_root) {
     swz_shard_info info{global_points, nullptr, 0};
     GRP_TRY(swz_shard_begin_device(c, recv, m, a.bmin, a.bmax, a.params, &info, &taken));
@@ -452,7 +453,9 @@ void shard_thread(ShardCall a) {
     c->md_shard_root = &sr;
     c->md_shard_root_published = true;  // the higher shards read this root's "md_*_sr" arrays until the barrier at the end of the batch
     swz_shard_info info{global_points, nullptr, 0};
-    if (m) GRP_TRY(swz_shard_begin_device(c, recv, m, a.bmin, a.bmax, a.params, &info, &taken));
+    // (a shard whose octants are empty -- flat terrain in a cubic box -- opens its batch all the same: swz_shard_finish_device
+    // below pairs up with it; it never reaches the sweep, so the group meets the others for it)
+    GRP_TRY(swz_shard_begin_device(c, recv, m, a.bmin, a.bmax, a.params, &info, &taken));
     c->md_shard_root = nullptr;
     if (!g->views[r].entered) {  // no points here, or the call failed before its sweep met the others: meet them for it
       g->views[r].ncells = 0;
@@ -466,6 +469,10 @@ void shard_thread(ShardCall a) {
       std::unique_lock<std::mutex> lk(g->turn_m);
       g->turn_cv.wait(lk, [&] { return g->turn == r; });
     }
+    // (the stamps of a root taken in turns say so: "root begun" when the turn has come, "root done" before it is passed on,
+    // so that no shard's root begins before the lower shard's is done -- tests/test_shard_seams.py tells the paths apart by it)
+    in_turns = true;
+    stamp(1);
     // ghosts: what the root took on all lower shards, right in front of the received points
     uint64_t gh = 0;
     for (int s = 0; s < r; ++s) gh += g->root_taken_count[s];
@@ -485,6 +492,7 @@ void shard_thread(ShardCall a) {
     if (taken) GRP_TRY(swz_shard_root_taken_device(c, mine));
     g->root_taken[r] = mine;
     g->root_taken_count[r] = ok ? taken : 0;
+    stamp(2);  // (both calls above return with the stream idle)
     {
       std::lock_guard<std::mutex> lk(g->turn_m);
       g->turn = r + 1;
@@ -494,7 +502,7 @@ void shard_thread(ShardCall a) {
 
   // 4. everything below the root is local
   GRP_HIP(hipStreamSynchronize(c->stream));
-  stamp(2);
+  if (!in_turns) stamp(2);
   uint64_t* okeys = nullptr;
   uint32_t* operm = nullptr;
   int8_t* olevel = nullptr;
