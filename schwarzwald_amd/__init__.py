@@ -7,7 +7,7 @@ multi-GPU sharding driver; there is no CPU implementation in the product.
 """
 from .api import (ACCURATE, FLAG_MIN_DISTANCE_PROPERTY, ALWAYS_ADHERE_TO_MIN_SPACING, FAST, GRID_CENTER, JITTERED, MIN_DISTANCE, RANDOM_GRID,
                   SAMPLERS, ALL_SAMPLERS, MIN_DISTANCE_FAST, min_distance_fast_stride, TAKE_ALL_WHEN_COUNT_BELOW_MAX_POINTS, Context, SwzError, TileParams, TileResult,
-                  ATTRIBUTES, bin_read_node, bin_write_node, library_path, load_library, node_bounds,
+                  ATTRIBUTES, bin_read_node, bin_write_node, bin_persist_nodes, library_path, load_library, node_bounds,
                   node_from_entwine_name, node_geometric_error, node_name, node_name_entwine,
                   spacing_from_diagonal, Tiler, pinned_empty, tileset_build, tileset_write, pnts_layout, pnts_write_node,
                   pnts_write_node_rows, pnts_read_node, pnts_rgb_from_intensity, PNTS_RGB, PNTS_INTENSITY, RGB_FROM_COLOR,
@@ -22,5 +22,5 @@ __all__ = ["LAS_NAMING_POTREE", "LAS_NAMING_ENTWINE", "las_scale_from_bounds", "
            "tileset_build","FLAG_MIN_DISTANCE_PROPERTY", "Context", "Tiler", "pinned_empty", "SwzError", "TileParams", "TileResult", "load_library", "library_path", "SAMPLERS",
            "RANDOM_GRID", "GRID_CENTER", "MIN_DISTANCE", "JITTERED", "ACCURATE", "FAST",
            "MIN_DISTANCE_FAST", "ALL_SAMPLERS", "min_distance_fast_stride",
-           "TAKE_ALL_WHEN_COUNT_BELOW_MAX_POINTS", "ALWAYS_ADHERE_TO_MIN_SPACING", "spacing_from_diagonal", "ATTRIBUTES", "bin_write_node", "bin_read_node",
+           "TAKE_ALL_WHEN_COUNT_BELOW_MAX_POINTS", "ALWAYS_ADHERE_TO_MIN_SPACING", "spacing_from_diagonal", "ATTRIBUTES", "bin_write_node", "bin_read_node", "bin_persist_nodes",
            "node_name", "node_name_entwine", "node_from_entwine_name", "node_bounds", "node_geometric_error"]

@@ -139,6 +139,14 @@ def device_columns(ptrs):
     return cols
 
 
+_NODE_DTYPES = dict(level=np.int8, key=np.uint64, offset=np.uint64, count=np.uint64)
+
+
+def _node_columns(nodes, *names):
+    """The named columns of a node table (dict of level / key / offset / count) as the contiguous arrays the library reads."""
+    return [np.ascontiguousarray(nodes[k], dtype=_NODE_DTYPES[k]) for k in names]
+
+
 def node_name(level, key):
     """"r" + octant digits of a node (TilingAlgorithms.cpp:139)."""
     buf = C.create_string_buffer(24)
@@ -452,13 +460,24 @@ def las_read_node(path):
     return xyz, keep
 
 
+def bin_persist_nodes(directory, nodes, xyz, attrs=None, compressed=False, ctx=None):
+    """One BinaryPersistence file per node of a node table from the gathered (host) payload (host only, no GPU needed)."""
+    x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    cols, keep = _host_columns(attrs, x.shape[0])
+    nl, nk, no, nc = _node_columns(nodes, "level", "key", "offset", "count")
+    L = load_library()
+    st = L.swz_bin_persist_nodes(ctx, os.fsencode(directory), nl.shape[0], nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p),
+                                 no.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p), x.ctypes.data_as(_dp), C.byref(cols),
+                                 int(bool(compressed)))
+    if st != 0:
+        raise SwzError(st, (L.swz_last_error(ctx) or b"").decode() if ctx else "swz_bin_persist_nodes(%s) failed" % directory)
+
+
 def las_persist_nodes(directory, nodes, image, attrs, box_min, box_max, scale, naming=LAS_NAMING_POTREE, ctx=None):
     """One LAS file per node of a node table out of a host copy of the image las_pack_device wrote.  box_min / box_max
     (num_nodes x 3) and scale (num_nodes) are the nodes' boxes and scales; naming: LAS_NAMING_POTREE or LAS_NAMING_ENTWINE."""
     img = np.ascontiguousarray(image, dtype=np.uint8).reshape(-1)
-    nl = np.ascontiguousarray(nodes["level"], dtype=np.int8)
-    nk = np.ascontiguousarray(nodes["key"], dtype=np.uint64)
-    nc = np.ascontiguousarray(nodes["count"], dtype=np.uint64)
+    nl, nk, nc = _node_columns(nodes, "level", "key", "count")
     mn = np.ascontiguousarray(box_min, dtype=np.float64).reshape(-1, 3)
     mx = np.ascontiguousarray(box_max, dtype=np.float64).reshape(-1, 3)
     sc = np.ascontiguousarray(scale, dtype=np.float64).reshape(-1)
@@ -481,9 +500,7 @@ def ept_create_dirs(directory):
 
 def ept_hierarchy_write(directory, nodes):
     """swz_ept_hierarchy_write: directory/ept-hierarchy/*.json of a node table (dict of level / key / count)."""
-    nl = np.ascontiguousarray(nodes["level"], dtype=np.int8)
-    nk = np.ascontiguousarray(nodes["key"], dtype=np.uint64)
-    nc = np.ascontiguousarray(nodes["count"], dtype=np.uint64)
+    nl, nk, nc = _node_columns(nodes, "level", "key", "count")
     if not (nl.shape[0] == nk.shape[0] == nc.shape[0]):
         raise ValueError("the columns of the node table differ in length")
     st = load_library().swz_ept_hierarchy_write(None, os.fsencode(directory), nl.shape[0], nl.ctypes.data_as(_i8p),
@@ -921,24 +938,14 @@ class Context:
                                                     C.c_void_p(d_xyz), C.byref(cols)))
 
     def bin_persist_nodes(self, directory, nodes, xyz, attrs=None, compressed=False):
-        """One BinaryPersistence file per node of a node table from the gathered (host) payload."""
-        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        cols, keep = _host_columns(attrs, x.shape[0])
-        nl = np.ascontiguousarray(nodes["level"], dtype=np.int8)
-        nk = np.ascontiguousarray(nodes["key"], dtype=np.uint64)
-        no = np.ascontiguousarray(nodes["offset"], dtype=np.uint64)
-        nc = np.ascontiguousarray(nodes["count"], dtype=np.uint64)
-        self._check(self._lib.swz_bin_persist_nodes(self._ctx, os.fsencode(directory), nl.shape[0], nl.ctypes.data_as(_i8p),
-                                                    nk.ctypes.data_as(_u64p), no.ctypes.data_as(_u64p),
-                                                    nc.ctypes.data_as(_u64p), x.ctypes.data_as(_dp), C.byref(cols),
-                                                    int(bool(compressed))))
+        """bin_persist_nodes with this context's writer threads and error text."""
+        bin_persist_nodes(directory, nodes, xyz, attrs, compressed, ctx=self._ctx)
 
     def pnts_pack_device(self, d_perm, d_order, n, d_xyz, d_attrs, nodes, d_image, image_bytes, attrs=(), rgb_from=RGB_FROM_COLOR):
         """swz_pnts_pack_device: the .pnts bodies of all nodes of a table, laid out as pnts_layout says, written into
         d_image (device, image_bytes bytes) in one pass.  d_order None = identity (a tiler's export ids as d_perm)."""
         cin = device_columns(d_attrs)
-        no = np.ascontiguousarray(nodes["offset"], dtype=np.uint64)
-        nc = np.ascontiguousarray(nodes["count"], dtype=np.uint64)
+        no, nc = _node_columns(nodes, "offset", "count")
         self._check(self._lib.swz_pnts_pack_device(self._ctx, C.c_void_p(d_perm), C.c_void_p(d_order), int(n), C.c_void_p(d_xyz),
                                                    C.byref(cin), nc.shape[0], no.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p),
                                                    _pnts_mask(attrs), int(rgb_from), C.c_void_p(d_image), int(image_bytes)))
@@ -946,9 +953,7 @@ class Context:
     def pnts_persist_nodes(self, directory, nodes, image, attrs=(), rtc_center=None):
         """One .pnts file per node of a node table out of a host copy of the image pnts_pack_device wrote."""
         img = np.ascontiguousarray(image, dtype=np.uint8).reshape(-1)
-        nl = np.ascontiguousarray(nodes["level"], dtype=np.int8)
-        nk = np.ascontiguousarray(nodes["key"], dtype=np.uint64)
-        nc = np.ascontiguousarray(nodes["count"], dtype=np.uint64)
+        nl, nk, nc = _node_columns(nodes, "level", "key", "count")
         rtc = _vec3(rtc_center) if rtc_center is not None else None
         self._check(self._lib.swz_pnts_persist_nodes(self._ctx, os.fsencode(directory), nl.shape[0], nl.ctypes.data_as(_i8p),
                                                      nk.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p), img.ctypes.data, img.shape[0],
@@ -959,8 +964,7 @@ class Context:
         into d_image (device, image_bytes bytes) by one kernel.  las_offset (num_nodes x 3) and las_scale (num_nodes): the
         box minimum and the scale of every node.  d_order None = identity (a tiler's export ids as d_perm)."""
         cin = device_columns(d_attrs)
-        no = np.ascontiguousarray(nodes["offset"], dtype=np.uint64)
-        nc = np.ascontiguousarray(nodes["count"], dtype=np.uint64)
+        no, nc = _node_columns(nodes, "offset", "count")
         lo = np.ascontiguousarray(las_offset, dtype=np.float64).reshape(-1, 3)
         ls = np.ascontiguousarray(las_scale, dtype=np.float64).reshape(-1)
         if not (no.shape[0] == nc.shape[0] == lo.shape[0] == ls.shape[0]):

@@ -25,6 +25,7 @@
 #include "swz_internal.h"
 #include "swz_device.h"
 #include "swz_hostio.h"
+#include "swz_nodepack.h"
 
 namespace swz {
 
@@ -118,7 +119,7 @@ __host__ __device__ inline void las_compose(uint32_t rec[9], const double p[3], 
 constexpr int LAS_TILE = 256;                 // stored rows per block, one per thread
 constexpr uint32_t LAS_STAGE = 34 * LAS_TILE;  // bytes of LDS the records pass through
 
-struct LasNode {  // the nodes that hold points, by ascending first row
+struct LasNode {  // an entry of the pack table (swz_nodepack.h)
   uint32_t start, count;
   uint64_t base;  // of the body in the image, a multiple of 8
   double offset[3];
@@ -137,7 +138,7 @@ struct LasPackArgs {
 };
 
 // One block takes LAS_TILE consecutive stored rows.  It finds the node of its first row with one binary search in the table
-// and walks forward from there (a tile holds at most LAS_TILE nodes: they are not empty), like pnts_pack_kernel.  The bodies
+// and walks forward from there (swz_nodepack.h).  The bodies
 // of consecutive nodes of the table lie one behind the other, so whatever the block's rows hold -- parts of nodes, whole nodes
 // with their padding, rows of no node in between -- their bytes are ONE range [lo, hi) of the image, every byte of which is
 // this block's and nobody else's.  Each lane loads its row (scattered reads), composes the record in registers and puts it
@@ -159,13 +160,7 @@ __global__ __launch_bounds__(LAS_TILE) void las_pack_kernel(LasPackArgs a) {
   const uint32_t r0 = blockIdx.x * (uint32_t)LAS_TILE;
   const uint32_t r1 = (uint32_t)min((uint64_t)r0 + LAS_TILE, (uint64_t)a.n);
 
-  // the last node that starts at or before r0 (the first node when there is none)
-  uint32_t lo = 0, hi = a.num_nodes;
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (a.nodes[mid].start <= r0) lo = mid + 1; else hi = mid;
-  }
-  const uint32_t k0 = lo ? lo - 1 : 0;
+  const uint32_t k0 = pack_first_node(a.nodes, a.num_nodes, r0);
   // Offsets in the image are kept as 32-bit distances from an ANCHOR just in front of the block's range: where node k0's
   // rows in front of the tile end, rounded down to 8.  The base of node k0 itself may lie 2^32 bytes and more in front of
   // it; its distance and RB * (row in the node) wrap, their sum -- a place inside the range -- does not.
@@ -175,31 +170,19 @@ __global__ __launch_bounds__(LAS_TILE) void las_pack_kernel(LasPackArgs a) {
     const uint32_t before = nd->start < r0 ? min(r0 - nd->start, nd->count) : 0u;
     anchor = nd->base + (((uint64_t)RB * before) & ~7ull);
   }
-  {
-    uint32_t st = 0xFFFFFFFFu, cn = 0, rel = 0;  // (a row number is below 2^32 - 65536: the filler sorts behind every row)
-    if ((uint64_t)k0 + t < a.num_nodes) {
-      const LasNode* nd = a.nodes + k0 + t;
-      if (nd->start < r1) {
-        st = nd->start;
-        cn = nd->count;
-        rel = (uint32_t)(nd->base - anchor);
-      }
-    }
-    s_start[t] = st;
-    s_count[t] = cn;
-    s_rel[t] = rel;
-  }
+  const LasNode* const listed = pack_fill_window(a.nodes, a.num_nodes, k0, r1, s_start, s_count);
+  s_rel[t] = listed ? (uint32_t)(listed->base - anchor) : 0u;
   __syncthreads();
 
   // the block's range of the image, relative to the anchor: from the first listed node that reaches into the tile ...
-  const uint32_t first = (s_start[0] != 0xFFFFFFFFu && s_start[0] + s_count[0] > r0) ? 0u : 1u;
-  if (first >= (uint32_t)LAS_TILE || s_start[first] == 0xFFFFFFFFu) return;  // no row of the tile is in a node
+  const uint32_t first = (s_start[0] != PACK_FILLER && s_start[0] + s_count[0] > r0) ? 0u : 1u;
+  if (first >= (uint32_t)LAS_TILE || s_start[first] == PACK_FILLER) return;  // no row of the tile is in a node
   const uint32_t range_lo = s_rel[first] + (s_start[first] < r0 ? RB * (r0 - s_start[first]) : 0u);
   // ... to the last one (entries are valid up to the first filler)
   uint32_t l = first, h = LAS_TILE;
   while (l < h) {
     const uint32_t mid = (l + h) / 2;
-    if (s_start[mid] != 0xFFFFFFFFu) l = mid + 1; else h = mid;
+    if (s_start[mid] != PACK_FILLER) l = mid + 1; else h = mid;
   }
   const uint32_t last = l - 1;
   const uint32_t last_rows = min(s_count[last], r1 - s_start[last]);
@@ -207,25 +190,13 @@ __global__ __launch_bounds__(LAS_TILE) void las_pack_kernel(LasPackArgs a) {
   const uint32_t mirror_lo = range_lo & ~3u;  // what LDS byte 0 of the first window stands for
 
   const uint32_t r = r0 + t;
-  uint32_t e = 0;
-  bool in_node = false;
-  if (r < r1) {
-    uint32_t l2 = 0, h2 = LAS_TILE;
-    while (l2 < h2) {
-      const uint32_t mid = (l2 + h2) / 2;
-      if (s_start[mid] <= r) l2 = mid + 1; else h2 = mid;
-    }
-    if (l2) {
-      e = l2 - 1;
-      in_node = r - s_start[e] < s_count[e];
-    }
-  }
+  uint32_t e;
+  const bool in_node = pack_row_node<LAS_TILE>(s_start, s_count, r, r1, &e);
   uint32_t rec[9];
   uint32_t at = 0, pad_halves = 0;  // where the record lies in the range, and the zeros behind it
   if (in_node) {
-    const uint32_t src = a.perm[a.order ? a.order[r] : r];
-    const double* p = a.xyz + (size_t)src * 3;
-    const double pos[3] = {p[0], p[1], p[2]};
+    double pos[3];
+    const uint32_t src = pack_source_row(a.perm, a.order, a.xyz, r, pos);
     const LasNode* nd = a.nodes + k0 + e;
     const double off[3] = {nd->offset[0], nd->offset[1], nd->offset[2]};
     las_compose<FORMAT>(rec, pos, a.cols, src, off, nd->scale);
@@ -274,12 +245,6 @@ __global__ __launch_bounds__(LAS_TILE) void las_pack_kernel(LasPackArgs a) {
 }
 
 // ---------------------------------------------------------------------------------- host helpers
-static int fail(swz_ctx* c, int code, const std::string& msg) {
-  if (c) return c->fail(code, msg.c_str());
-  return code;
-}
-
-static bool finite3(const double v[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 static bool scale_ok(double s) { return std::isfinite(s) && s > 0; }
 
 static int check_mask(swz_ctx* c, const char* who, const swz_attribute_columns* cols, uint32_t mask) {
@@ -335,19 +300,7 @@ static int las_write_file(const char* path, uint64_t count, const void* body, ui
                           const double box_max[3], double scale, std::string* err) {
   unsigned char h[LAS_HEADER_BYTES];
   las_header(h, count, format, box_min, box_max, scale);
-  FILE* f = fopen(path, "wb");
-  if (!f) {
-    *err = std::string("cannot write ") + path;
-    return SWZ_ERR_BAD_ARG;
-  }
-  const size_t bytes = (size_t)(count * las_record_bytes(format));
-  bool ok = fwrite(h, 1, sizeof(h), f) == sizeof(h) && fwrite(body, 1, bytes, f) == bytes;
-  ok = (fclose(f) == 0) && ok;
-  if (!ok) {
-    *err = std::string("short write to ") + path;
-    return SWZ_ERR_INTERNAL;
-  }
-  return SWZ_OK;
+  return write_file(path, {{h, sizeof(h)}, {body, (size_t)(count * las_record_bytes(format))}}, err);
 }
 
 static int check_file_args(swz_ctx* c, const char* who, uint64_t count, const double box_min[3], const double box_max[3], double scale) {
@@ -378,12 +331,7 @@ struct LasFile {
 };
 
 static int las_parse(swz_ctx* c, const char* path, LasFile* f) {
-  FILE* fp = fopen(path, "rb");
-  if (!fp) return fail(c, SWZ_ERR_BAD_ARG, std::string("cannot open ") + path);
-  unsigned char tmp[1 << 16];
-  size_t got;
-  while ((got = fread(tmp, 1, sizeof(tmp), fp)) > 0) f->data.insert(f->data.end(), tmp, tmp + got);
-  fclose(fp);
+  SWZ_TRY(read_whole_file(c, path, &f->data));
   const std::string where = std::string(" in ") + path;
   const unsigned char* h = f->data.data();
   const uint64_t size = f->data.size();
@@ -415,21 +363,6 @@ static int make_dir(const std::string& path) {
   if (mkdir(path.c_str(), 0777) == 0) return 0;
   struct stat st;
   return (stat(path.c_str(), &st) == 0 && S_ISDIR(st.st_mode)) ? 0 : -1;
-}
-
-static int write_text(const std::string& path, const std::string& s, std::string* err) {
-  FILE* f = fopen(path.c_str(), "wb");
-  if (!f) {
-    *err = "cannot write " + path;
-    return SWZ_ERR_BAD_ARG;
-  }
-  bool ok = fwrite(s.data(), 1, s.size(), f) == s.size();
-  ok = (fclose(f) == 0) && ok;
-  if (!ok) {
-    *err = "short write to " + path;
-    return SWZ_ERR_INTERNAL;
-  }
-  return SWZ_OK;
 }
 
 static void put_string(std::string& s, const char* text) {
@@ -515,45 +448,34 @@ int swz_las_pack_device(swz_ctx* c, const uint32_t* d_perm, const uint32_t* d_or
   if (num_nodes && (!node_offset || !node_count || !node_las_offset || !node_las_scale))
     return c->fail(SWZ_ERR_BAD_ARG, "swz_las_pack_device: NULL node table");
   const uint32_t format = las_format(mask), rb = las_record_bytes(format);
-  std::vector<LasNode> table;
-  uint64_t at = 0, prev_offset = 0, prev_end = 0;
-  for (uint64_t k = 0; k < num_nodes; ++k) {
-    const uint64_t off = node_offset[k], cnt = node_count[k];
-    if (off < prev_offset) return c->fail(SWZ_ERR_BAD_ARG, "swz_las_pack_device: node offsets are not ascending");
-    prev_offset = off;
-    if (!scale_ok(node_las_scale[k])) return c->fail(SWZ_ERR_BAD_ARG, "swz_las_pack_device: a scale is not finite and positive");
-    if (!finite3(node_las_offset + 3 * k)) return c->fail(SWZ_ERR_BAD_ARG, "swz_las_pack_device: an offset is not finite");
-    if (cnt == 0) continue;
-    if (off < prev_end) return c->fail(SWZ_ERR_BAD_ARG, "swz_las_pack_device: node ranges overlap");
-    if (off > n || cnt > n - off) return c->fail(SWZ_ERR_BAD_ARG, "swz_las_pack_device: a node range passes the last row");
-    prev_end = off + cnt;
-    LasNode nd;
-    nd.start = (uint32_t)off;
-    nd.count = (uint32_t)cnt;
-    nd.base = at;
-    for (int a = 0; a < 3; ++a) nd.offset[a] = node_las_offset[3 * k + a];
-    nd.scale = node_las_scale[k];
-    table.push_back(nd);
-    at += las_body_size(cnt, rb);
-  }
-  if (at > image_bytes) return c->fail(SWZ_ERR_BAD_ARG, "swz_las_pack_device: the image buffer is smaller than swz_las_image_layout's total");
-  if (table.empty()) return SWZ_OK;  // n == 0, no nodes, or only empty ones: nothing to write
-  if (!d_perm || !d_xyz || !d_image_out) return c->fail(SWZ_ERR_BAD_ARG, "swz_las_pack_device: NULL buffer");
-  if (((uintptr_t)d_image_out & 7u) != 0) return c->fail(SWZ_ERR_BAD_ARG, "swz_las_pack_device: the image must be 8-byte aligned");
-  SWZ_HIP(c, hipSetDevice(c->device));
+  const PackNames names{"swz_las_pack_device", "swz_las_image_layout", "las_nodes"};
+  PackTable<LasNode> table;
+  SWZ_TRY(pack_build_table(
+    c, names, n, num_nodes, node_offset, node_count,
+    [&](uint64_t k, LasNode* nd) -> const char* {
+      if (!scale_ok(node_las_scale[k])) return "a scale is not finite and positive";
+      if (!finite3(node_las_offset + 3 * k)) return "an offset is not finite";
+      for (int a = 0; a < 3; ++a) nd->offset[a] = node_las_offset[3 * k + a];
+      nd->scale = node_las_scale[k];
+      return nullptr;
+    },
+    [&](uint64_t cnt, uint64_t* bytes) -> const char* {
+      *bytes = las_body_size(cnt, rb);
+      return nullptr;
+    },
+    &table));
+  const uint64_t at = table.image_bytes, prev_end = table.prev_end;
 
   LasPackArgs a{};
+  SWZ_TRY(pack_upload_table(c, names, table, d_perm, d_xyz, d_image_out, image_bytes, &a.nodes));
+  if (!a.nodes) return SWZ_OK;
   a.perm = d_perm;
   a.order = d_order;
   a.n = (uint32_t)n;
   a.xyz = d_xyz;
   a.cols = las_columns(d_in, mask);
   a.image = static_cast<uint8_t*>(d_image_out);
-  a.num_nodes = (uint32_t)table.size();
-  LasNode* d_nodes = nullptr;
-  SWZ_TRY(c->get("las_nodes", table.size(), &d_nodes));
-  SWZ_HIP(c, hipMemcpyAsync(d_nodes, table.data(), table.size() * sizeof(LasNode), hipMemcpyHostToDevice, c->stream));
-  a.nodes = d_nodes;
+  a.num_nodes = (uint32_t)table.nodes.size();
   {
     uint64_t row = 24;
     for (int k = 0; k < SWZ_ATTR_COUNT; ++k)
@@ -727,7 +649,7 @@ int swz_ept_hierarchy_write(swz_ctx* c, const char* dir, uint64_t num_nodes, con
       s += "\"" + ept_name(entry.first) + "\":" + std::to_string(entry.second);
     }
     s += "}";
-    return write_text(std::string(dir) + "/ept-hierarchy/" + ept_name(list[k]->first) + ".json", s, err);
+    return write_file(std::string(dir) + "/ept-hierarchy/" + ept_name(list[k]->first) + ".json", {{s.data(), s.size()}}, err);
   }, &first_err);
   return st == SWZ_OK ? SWZ_OK : fail(c, st, first_err);
 }
@@ -787,7 +709,7 @@ int swz_ept_json_write(swz_ctx* c, const char* path, const swz_ept_json* ept) {
   put_string(s, ept->version);
   s += "}";
   std::string err;
-  const int st = write_text(path, s, &err);
+  const int st = write_file(path, {{s.data(), s.size()}}, &err);
   return st == SWZ_OK ? SWZ_OK : fail(c, st, err);
 }
 

@@ -7,15 +7,13 @@
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
-#include <atomic>
 #include <map>
-#include <mutex>
-#include <thread>
 #include <string>
 #include <vector>
 
 #include "swz_internal.h"
 #include "swz_device.h"
+#include "swz_hostio.h"
 
 namespace swz {
 
@@ -100,31 +98,14 @@ static void launch_gather(swz_ctx* c, const void* in, const uint32_t* src, uint3
 }
 
 // ---------------------------------------------------------------------------------- node files
-struct ByteSink {
-  std::vector<unsigned char> buf;
-  void put(const void* p, size_t n) {
-    const unsigned char* b = (const unsigned char*)p;
-    buf.insert(buf.end(), b, b + n);
-  }
-};
-
-static int fail(swz_ctx* c, int code, const std::string& msg) {
-  if (c) return c->fail(code, msg.c_str());
-  return code;
-}
-
 static int read_file(swz_ctx* c, const char* path, int compressed, std::vector<unsigned char>& out, size_t want_at_most) {
-  FILE* f = fopen(path, "rb");
-  if (!f) return fail(c, SWZ_ERR_BAD_ARG, std::string("cannot open ") + path);
   std::vector<unsigned char> raw;
-  unsigned char tmp[1 << 16];
-  size_t got;
-  while ((got = fread(tmp, 1, sizeof(tmp), f)) > 0) raw.insert(raw.end(), tmp, tmp + got);
-  fclose(f);
+  SWZ_TRY(read_whole_file(c, path, &raw));
   if (!compressed) {
     out.swap(raw);
     return SWZ_OK;
   }
+  unsigned char tmp[1 << 16];
   z_stream zs;
   memset(&zs, 0, sizeof(zs));
   if (inflateInit(&zs) != Z_OK) return fail(c, SWZ_ERR_INTERNAL, "inflateInit failed");
@@ -380,39 +361,23 @@ static int bin_write_node_impl(const char* path, uint64_t count, const double* x
   uint32_t bitmask = 0;
   for (int a = 0; a < SWZ_ATTR_COUNT; ++a)
     if (columns && columns->column[a]) bitmask |= 1u << a;
-  FILE* f = fopen(path, "wb");
-  if (!f) {
-    *err = std::string("cannot write ") + path;
-    return SWZ_ERR_BAD_ARG;
+  // (the pieces go out as they lie in the caller's arrays: a node file is its header and slices of the columns)
+  std::vector<FilePiece> pieces = {{&bitmask, 4}, {&count, 8}, {xyz, (size_t)count * 24}};
+  for (int k = 0; k < SWZ_ATTR_COUNT; ++k) {
+    const int a = FILE_ORDER[k];
+    if (bitmask & (1u << a)) pieces.push_back({columns->column[a], (size_t)count * ATTR_BYTES[a]});
   }
-  bool ok = true;
-  if (!compressed) {
-    // (the pieces go out as they lie in the caller's arrays: a node file is its header and slices of the columns)
-    ok = fwrite(&bitmask, 1, 4, f) == 4 && fwrite(&count, 1, 8, f) == 8 && fwrite(xyz, 24, (size_t)count, f) == (size_t)count;
-    for (int k = 0; k < SWZ_ATTR_COUNT && ok; ++k) {
-      const int a = FILE_ORDER[k];
-      if (bitmask & (1u << a)) ok = fwrite(columns->column[a], ATTR_BYTES[a], (size_t)count, f) == (size_t)count;
-    }
-  } else {
-    ByteSink sink;
-    sink.put(&bitmask, 4);
-    sink.put(&count, 8);
-    sink.put(xyz, (size_t)count * 24);
-    for (int k = 0; k < SWZ_ATTR_COUNT; ++k) {
-      const int a = FILE_ORDER[k];
-      if (bitmask & (1u << a)) sink.put(columns->column[a], (size_t)count * ATTR_BYTES[a]);
-    }
-    uLongf cap = compressBound((uLong)sink.buf.size());
-    std::vector<unsigned char> z(cap);
-    ok = compress2(z.data(), &cap, sink.buf.data(), (uLong)sink.buf.size(), Z_BEST_SPEED) == Z_OK &&
-         fwrite(z.data(), 1, cap, f) == cap;
-  }
-  ok = (fclose(f) == 0) && ok;
-  if (!ok) {
-    *err = std::string("short write to ") + path;
-    return SWZ_ERR_INTERNAL;
-  }
-  return SWZ_OK;
+  if (!compressed) return write_file(path, pieces, err);
+  std::vector<unsigned char> plain;
+  for (const FilePiece& p : pieces) plain.insert(plain.end(), (const unsigned char*)p.data, (const unsigned char*)p.data + p.bytes);
+  uLongf cap = compressBound((uLong)plain.size());
+  std::vector<unsigned char> z(cap);
+  // (a stream zlib could not make leaves an empty file and is reported like a write that failed)
+  const bool packed = compress2(z.data(), &cap, plain.data(), (uLong)plain.size(), Z_BEST_SPEED) == Z_OK;
+  const int st = write_file(path, {{z.data(), packed ? (size_t)cap : 0}}, err);
+  if (st != SWZ_OK || packed) return st;
+  *err = std::string("short write to ") + path;
+  return SWZ_ERR_INTERNAL;
 }
 
 extern "C" {
@@ -473,49 +438,20 @@ int swz_bin_persist_nodes(swz_ctx* c, const char* dir, uint64_t num_nodes, const
     char name[24];
     if (swz_node_name(node_level[k], node_key[k], name) != SWZ_OK) return fail(c, SWZ_ERR_BAD_ARG, "bad node level");
   }
-  // The files are independent: a few host threads take the nodes by ticket (the reference persists its nodes from the
-  // tasks of its tiling graph, TilingAlgorithms.cpp:330-334).  One thread wrote 2.7 GB/s -- a hundredth of what the device
-  // hands over.  SWZ_BIN_WRITER_THREADS: the number of threads (default: the host's, at most 32).
-  unsigned threads = std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
-  if (c) threads = (unsigned)std::max(1L, c->opt_int("SWZ_BIN_WRITER_THREADS", threads));
-  threads = (unsigned)std::min<uint64_t>(threads, std::max<uint64_t>(num_nodes, 1));
-  std::atomic<uint64_t> next{0};
-  std::atomic<int> status{SWZ_OK};
-  std::mutex err_m;
   std::string first_err;
-  auto work = [&]() {
-    for (;;) {
-      const uint64_t k = next.fetch_add(1);
-      if (k >= num_nodes || status.load() != SWZ_OK) return;
-      if (node_count[k] == 0) continue;  // persist_points returns before opening the file
-      char name[24];
-      (void)swz_node_name(node_level[k], node_key[k], name);
-      const std::string path = std::string(dir) + "/" + name + (compressed ? ".binz" : ".bin");
-      swz_attribute_columns cols;
-      for (int a = 0; a < SWZ_ATTR_COUNT; ++a)
-        cols.column[a] = (columns && columns->column[a])
-                           ? (void*)((unsigned char*)columns->column[a] + (size_t)node_offset[k] * ATTR_BYTES[a])
-                           : nullptr;
-      std::string err;
-      const int st = bin_write_node_impl(path.c_str(), node_count[k], xyz + (size_t)node_offset[k] * 3, &cols, compressed, &err);
-      if (st != SWZ_OK) {
-        std::lock_guard<std::mutex> lk(err_m);
-        if (status.load() == SWZ_OK) {
-          first_err = err;
-          status.store(st);
-        }
-        return;
-      }
-    }
-  };
-  if (threads <= 1) {
-    work();
-  } else {
-    std::vector<std::thread> pool;
-    for (unsigned t = 0; t < threads; ++t) pool.emplace_back(work);
-    for (auto& t : pool) t.join();
-  }
-  return status.load() == SWZ_OK ? SWZ_OK : fail(c, status.load(), first_err);
+  const int st = run_tickets(c, num_nodes, [&](uint64_t k, std::string* err) {
+    if (node_count[k] == 0) return (int)SWZ_OK;  // persist_points returns before opening the file
+    char name[24];
+    (void)swz_node_name(node_level[k], node_key[k], name);
+    const std::string path = std::string(dir) + "/" + name + (compressed ? ".binz" : ".bin");
+    swz_attribute_columns cols;
+    for (int a = 0; a < SWZ_ATTR_COUNT; ++a)
+      cols.column[a] = (columns && columns->column[a])
+                         ? (void*)((unsigned char*)columns->column[a] + (size_t)node_offset[k] * ATTR_BYTES[a])
+                         : nullptr;
+    return bin_write_node_impl(path.c_str(), node_count[k], xyz + (size_t)node_offset[k] * 3, &cols, compressed, err);
+  }, &first_err);
+  return st == SWZ_OK ? SWZ_OK : fail(c, st, first_err);
 }
 
 }  // extern "C"

@@ -12,7 +12,6 @@
 // rapidjson does not always find the shortest form (Grisu2), so a file agrees with the reference's in every parsed value and
 // in every byte of the binary, but not necessarily in the length of the JSON text; the spelling of a number is no part of
 // either format.
-#include <atomic>
 #include <charconv>
 #include <cmath>
 #include <cstdio>
@@ -20,12 +19,12 @@
 #include <algorithm>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "swz_internal.h"
 #include "swz_device.h"
 #include "swz_hostio.h"
+#include "swz_nodepack.h"
 
 namespace swz {
 
@@ -84,7 +83,7 @@ static const uint8_t* grey_table(int mapping) {
 // ---------------------------------------------------------------------------------- the pack kernel
 constexpr int PNTS_TILE = 256;  // stored rows per block, one per thread
 
-struct PntsNode {  // the nodes that hold points, by ascending first row
+struct PntsNode {  // an entry of the pack table (swz_nodepack.h)
   uint32_t start, count;
   uint64_t base;  // of the body in the image, a multiple of 8
 };
@@ -133,8 +132,8 @@ __device__ __forceinline__ void pnts_emit_bytes(uint8_t* __restrict__ body, cons
 }
 
 // One block takes PNTS_TILE consecutive stored rows.  It finds the node of its first row with one binary search in the
-// table, walks forward from there (a tile holds at most PNTS_TILE nodes: they are not empty), loads its rows -- scattered
-// 24-byte position reads, the narrowing is the plain cast (round to nearest even) -- into LDS and writes from there:
+// table, walks forward from there (swz_nodepack.h), loads its rows -- scattered 24-byte position reads, the narrowing is
+// the plain cast (round to nearest even) -- into LDS and writes from there:
 // positions as dwords in the order of the image, the 3- and 2-byte rows as aligned dwords put together from LDS.
 __global__ __launch_bounds__(PNTS_TILE) void pnts_pack_kernel(PntsPackArgs a) {
   __shared__ uint32_t s_start[PNTS_TILE];
@@ -148,52 +147,21 @@ __global__ __launch_bounds__(PNTS_TILE) void pnts_pack_kernel(PntsPackArgs a) {
   const uint32_t r0 = blockIdx.x * (uint32_t)PNTS_TILE;
   const uint32_t r1 = (uint32_t)min((uint64_t)r0 + PNTS_TILE, (uint64_t)a.n);
 
-  // the last node that starts at or before r0 (the first node when there is none)
-  uint32_t lo = 0, hi = a.num_nodes;
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (a.nodes[mid].start <= r0) lo = mid + 1; else hi = mid;
-  }
-  const uint32_t k0 = lo ? lo - 1 : 0;
-  {
-    uint32_t st = 0xFFFFFFFFu, cn = 0;  // (a row number is below 2^32 - 65536: the filler sorts behind every row)
-    uint64_t bs = 0;
-    if ((uint64_t)k0 + t < a.num_nodes) {
-      const PntsNode nd = a.nodes[k0 + t];
-      if (nd.start < r1) {
-        st = nd.start;
-        cn = nd.count;
-        bs = nd.base;
-      }
-    }
-    s_start[t] = st;
-    s_count[t] = cn;
-    s_base[t] = bs;
-  }
+  const uint32_t k0 = pack_first_node(a.nodes, a.num_nodes, r0);
+  const PntsNode* const listed = pack_fill_window(a.nodes, a.num_nodes, k0, r1, s_start, s_count);
+  s_base[t] = listed ? listed->base : 0ull;
   __syncthreads();
 
   const uint32_t r = r0 + t;
-  uint32_t e = 0;
-  bool in_node = false;
-  if (r < r1) {
-    uint32_t l = 0, h = PNTS_TILE;
-    while (l < h) {
-      const uint32_t mid = (l + h) / 2;
-      if (s_start[mid] <= r) l = mid + 1; else h = mid;
-    }
-    if (l) {
-      e = l - 1;
-      in_node = r - s_start[e] < s_count[e];
-    }
-  }
+  uint32_t e;
+  const bool in_node = pack_row_node<PNTS_TILE>(s_start, s_count, r, r1, &e);
   uint8_t* const rgb_bytes = reinterpret_cast<uint8_t*>(s_rgb);
   if (in_node) {
-    const uint32_t src = a.perm[a.order ? a.order[r] : r];
-    const double* p = a.xyz + (size_t)src * 3;
-    const double x = p[0], y = p[1], z = p[2];
-    s_pos[3 * t + 0] = __float_as_uint((float)x);
-    s_pos[3 * t + 1] = __float_as_uint((float)y);
-    s_pos[3 * t + 2] = __float_as_uint((float)z);
+    double pos[3];
+    const uint32_t src = pack_source_row(a.perm, a.order, a.xyz, r, pos);
+    s_pos[3 * t + 0] = __float_as_uint((float)pos[0]);
+    s_pos[3 * t + 1] = __float_as_uint((float)pos[1]);
+    s_pos[3 * t + 2] = __float_as_uint((float)pos[2]);
     uint16_t in = 0;
     if (a.intensity) in = a.intensity[src];
     if (a.mask & SWZ_PNTS_RGB) {
@@ -242,17 +210,10 @@ __global__ __launch_bounds__(PNTS_TILE) void pnts_pack_kernel(PntsPackArgs a) {
 }
 
 // ---------------------------------------------------------------------------------- host helpers
-static int fail(swz_ctx* c, int code, const std::string& msg) {
-  if (c) return c->fail(code, msg.c_str());
-  return code;
-}
-
 static bool mask_ok(uint32_t mask) { return (mask & ~PNTS_MASK_ALL) == 0; }
 static bool mapping_ok(int m) {
   return m == SWZ_PNTS_RGB_FROM_COLOR || m == SWZ_PNTS_RGB_FROM_INTENSITY_LINEAR || m == SWZ_PNTS_RGB_FROM_INTENSITY_LOG;
 }
-
-static bool finite3(const double v[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
 // header + feature-table JSON of a node file (PNTSWriter::flush / createFeatureTableBlob, PNTSWriter.cpp:109-264)
 static std::string pnts_file_head(uint64_t count, uint32_t mask, const double rtc[3], uint64_t body_bytes) {
@@ -276,18 +237,7 @@ static std::string pnts_file_head(uint64_t count, uint32_t mask, const double rt
 static int pnts_write_file(const char* path, uint64_t count, const void* body, uint64_t body_bytes, uint32_t mask, const double rtc[3],
                            std::string* err) {
   const std::string head = pnts_file_head(count, mask, rtc, body_bytes);
-  FILE* f = fopen(path, "wb");
-  if (!f) {
-    *err = std::string("cannot write ") + path;
-    return SWZ_ERR_BAD_ARG;
-  }
-  bool ok = fwrite(head.data(), 1, head.size(), f) == head.size() && fwrite(body, 1, (size_t)body_bytes, f) == (size_t)body_bytes;
-  ok = (fclose(f) == 0) && ok;
-  if (!ok) {
-    *err = std::string("short write to ") + path;
-    return SWZ_ERR_INTERNAL;
-  }
-  return SWZ_OK;
+  return write_file(path, {{head.data(), head.size()}, {body, (size_t)body_bytes}}, err);
 }
 
 static int check_columns(swz_ctx* c, const char* who, const swz_attribute_columns* cols, uint32_t mask, int mapping) {
@@ -417,12 +367,7 @@ static bool offset_ok(double v, uint64_t bytes, uint64_t binary_bytes, uint64_t*
 }
 
 static int pnts_parse(swz_ctx* c, const char* path, PntsFile* f) {
-  FILE* fp = fopen(path, "rb");
-  if (!fp) return fail(c, SWZ_ERR_BAD_ARG, std::string("cannot open ") + path);
-  unsigned char tmp[1 << 16];
-  size_t got;
-  while ((got = fread(tmp, 1, sizeof(tmp), fp)) > 0) f->data.insert(f->data.end(), tmp, tmp + got);
-  fclose(fp);
+  SWZ_TRY(read_whole_file(c, path, &f->data));
   const std::string where = std::string(" in ") + path;
   if (f->data.size() < 28) return fail(c, SWZ_ERR_BAD_ARG, "shorter than a .pnts header" + where);
   if (memcmp(f->data.data(), "pnts", 4) != 0) return fail(c, SWZ_ERR_BAD_ARG, "not a .pnts file (magic)" + where);
@@ -564,27 +509,21 @@ int swz_pnts_pack_device(swz_ctx* c, const uint32_t* d_perm, const uint32_t* d_o
   if (n > PNTS_MAX_POINTS) return c->fail(SWZ_ERR_BAD_ARG, "swz_pnts_pack_device: more than 2^32-65536 rows");
   SWZ_TRY(check_columns(c, "swz_pnts_pack_device", d_in, mask, rgb_mapping));
   if (num_nodes && (!node_offset || !node_count)) return c->fail(SWZ_ERR_BAD_ARG, "swz_pnts_pack_device: NULL node table");
-  std::vector<PntsNode> table;
-  uint64_t at = 0, prev_offset = 0, prev_end = 0;
-  for (uint64_t k = 0; k < num_nodes; ++k) {
-    const uint64_t off = node_offset[k], cnt = node_count[k];
-    if (off < prev_offset) return c->fail(SWZ_ERR_BAD_ARG, "swz_pnts_pack_device: node offsets are not ascending");
-    prev_offset = off;
-    if (cnt == 0) continue;
-    if (off < prev_end) return c->fail(SWZ_ERR_BAD_ARG, "swz_pnts_pack_device: node ranges overlap");
-    if (off > n || cnt > n - off) return c->fail(SWZ_ERR_BAD_ARG, "swz_pnts_pack_device: a node range passes the last row");
-    if (cnt > PNTS_MAX_BODY / 17) return c->fail(SWZ_ERR_BAD_ARG, "swz_pnts_pack_device: a node too large for a .pnts file");
-    prev_end = off + cnt;
-    table.push_back({(uint32_t)off, (uint32_t)cnt, at});
-    at += pnts_body<uint64_t>(cnt, mask).size;
-  }
-  if (at > image_bytes) return c->fail(SWZ_ERR_BAD_ARG, "swz_pnts_pack_device: the image buffer is smaller than swz_pnts_layout's total");
-  if (table.empty()) return SWZ_OK;  // n == 0, no nodes, or only empty ones: nothing to write
-  if (!d_perm || !d_xyz || !d_image_out) return c->fail(SWZ_ERR_BAD_ARG, "swz_pnts_pack_device: NULL buffer");
-  if (((uintptr_t)d_image_out & 7u) != 0) return c->fail(SWZ_ERR_BAD_ARG, "swz_pnts_pack_device: the image must be 8-byte aligned");
-  SWZ_HIP(c, hipSetDevice(c->device));
+  const PackNames names{"swz_pnts_pack_device", "swz_pnts_layout", "pnts_nodes"};
+  PackTable<PntsNode> table;
+  SWZ_TRY(pack_build_table(
+    c, names, n, num_nodes, node_offset, node_count, [](uint64_t, PntsNode*) -> const char* { return nullptr; },
+    [&](uint64_t cnt, uint64_t* bytes) -> const char* {
+      if (cnt > PNTS_MAX_BODY / 17) return "a node too large for a .pnts file";
+      *bytes = pnts_body<uint64_t>(cnt, mask).size;
+      return nullptr;
+    },
+    &table));
+  const uint64_t at = table.image_bytes, prev_end = table.prev_end;
 
   PntsPackArgs a{};
+  SWZ_TRY(pack_upload_table(c, names, table, d_perm, d_xyz, d_image_out, image_bytes, &a.nodes));
+  if (!a.nodes) return SWZ_OK;
   a.perm = d_perm;
   a.order = d_order;
   a.n = (uint32_t)n;
@@ -593,11 +532,7 @@ int swz_pnts_pack_device(swz_ctx* c, const uint32_t* d_perm, const uint32_t* d_o
   a.intensity = static_cast<const uint16_t*>(d_in ? d_in->column[SWZ_ATTR_INTENSITY] : nullptr);
   a.mask = mask;
   a.image = static_cast<uint8_t*>(d_image_out);
-  a.num_nodes = (uint32_t)table.size();
-  PntsNode* d_nodes = nullptr;
-  SWZ_TRY(c->get("pnts_nodes", table.size(), &d_nodes));
-  SWZ_HIP(c, hipMemcpyAsync(d_nodes, table.data(), table.size() * sizeof(PntsNode), hipMemcpyHostToDevice, c->stream));
-  a.nodes = d_nodes;
+  a.num_nodes = (uint32_t)table.nodes.size();
   if ((mask & SWZ_PNTS_RGB) && rgb_mapping != SWZ_PNTS_RGB_FROM_COLOR) {
     // (64 KiB per call: the workspace may have been released since the last one)
     uint8_t* d_grey = nullptr;
@@ -742,18 +677,7 @@ int swz_tileset_write(swz_ctx* c, const swz_tileset_node* nodes, uint64_t num, c
     char name[24];
     (void)swz_node_name(t.level, t.key, name);
     const std::string path = std::string(dir) + "/" + name + ".json";
-    FILE* f = fopen(path.c_str(), "wb");
-    if (!f) {
-      *err = "cannot write " + path;
-      return (int)SWZ_ERR_BAD_ARG;
-    }
-    bool ok = fwrite(s.data(), 1, s.size(), f) == s.size();
-    ok = (fclose(f) == 0) && ok;
-    if (!ok) {
-      *err = "short write to " + path;
-      return (int)SWZ_ERR_INTERNAL;
-    }
-    return (int)SWZ_OK;
+    return write_file(path, {{s.data(), s.size()}}, err);
   }, &first_err);
   return st == SWZ_OK ? SWZ_OK : fail(c, st, first_err);
 }

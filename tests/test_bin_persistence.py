@@ -136,6 +136,46 @@ def test_node_files_of_a_batch_written_by_several_threads(tmp_path):
     assert run(tmp_path / "does" / "not" / "exist") != 0
 
 
+def _persist_table(rng, counts):
+    counts = np.asarray(counts, dtype=np.uint64)
+    n = int(counts.sum())
+    nodes = dict(level=np.full(len(counts), 2, dtype=np.int8), key=np.arange(len(counts), dtype=np.uint64) << np.uint64(54),
+                 offset=np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.uint64), count=counts)
+    return nodes, rng.random((n, 3)), _attributes(rng, n, ["rgb", "intensity"])
+
+
+@pytest.mark.parametrize("threads", [None, pytest.param(1, marks=pytest.mark.gpu)])
+def test_persist_nodes_into_a_missing_directory_raises(tmp_path, threads):
+    """The first file that cannot be opened ends the writer threads (all of them fail here, at once) and comes back as ONE
+    error: with the default number of threads and with a single one, which takes the path without a pool.  The number of
+    threads is an option of a context, and a context exists only on a device; without one the call needs no GPU."""
+    import contextlib
+    import schwarzwald_amd as swz
+    from schwarzwald_amd import api
+    nodes, xyz, attrs = _persist_table(np.random.default_rng(31), [3, 0, 5, 1] * 10)
+    with (swz.Context(0) if threads else contextlib.nullcontext()) as ctx:
+        if ctx:
+            ctx.set_option("SWZ_BIN_WRITER_THREADS", threads)
+        persist = ctx.bin_persist_nodes if ctx else api.bin_persist_nodes
+        for compressed in (False, True):
+            with pytest.raises(swz.SwzError) as e:
+                persist(str(tmp_path / "does" / "not" / "exist"), nodes, xyz, attrs, compressed=compressed)
+            assert e.value.code == 2   # SWZ_ERR_BAD_ARG: the file could not be opened
+    assert list(tmp_path.iterdir()) == []
+
+
+def test_persist_nodes_of_a_table_of_empty_nodes_writes_nothing(tmp_path):
+    """Empty nodes have no file, so a table of nothing else touches no file at all -- not even a directory that does not
+    exist is an error then."""
+    from schwarzwald_amd import api
+    rng = np.random.default_rng(32)
+    nodes = _persist_table(rng, [0, 0, 0])[0]
+    xyz, attrs = rng.random((4, 3)), _attributes(rng, 4, ["rgb", "intensity"])   # rows of no node
+    api.bin_persist_nodes(str(tmp_path), nodes, xyz, attrs)
+    api.bin_persist_nodes(str(tmp_path / "missing"), nodes, xyz, attrs, compressed=True)
+    assert list(tmp_path.iterdir()) == []
+
+
 def test_empty_node_writes_no_file_and_names(tmp_path):
     import schwarzwald_amd as swz
     swz.bin_write_node(str(tmp_path / "none.bin"), np.empty((0, 3)))

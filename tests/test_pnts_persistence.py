@@ -434,6 +434,35 @@ def test_gpu_pack_handles_gaps_a_short_table_and_nothing_to_do(packed_inputs):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("names", [MASKS[0], MASKS[3]])
+def test_gpu_pack_tiles_of_one_point_nodes(packed_inputs, names):
+    """Every row a node of its own: a block lists as many nodes as it has rows, the whole window of its table; the nine
+    two-point nodes shift the node boundaries against the block edges from the middle of the first block on."""
+    import torch
+    import schwarzwald_amd as swz
+    P = packed_inputs
+    d = P["d"]
+    T = 256  # rows per block of the pack kernel
+    counts = np.ones(2 * T + 3, np.uint64)
+    counts[T // 2:T // 2 + 9] = 2
+    offsets = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.uint64)
+    n = int(counts.sum())
+    rows = P["perm"][:n]
+    total = swz.pnts_layout(counts, names)["total"]
+    want = _expected_image(counts, offsets, P["xyz"][rows], P["rgb"][rows], P["intensity"][rows], names)
+    assert len(want) == total
+    with swz.Context(0) as ctx:
+        buf = torch.full((total + 2 * GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()
+        attrs = {"rgb": d["rgb"].data_ptr(), "intensity": d["intensity"].data_ptr()}
+        ctx.pnts_pack_device(d["perm"].data_ptr(), None, n, d["xyz"].data_ptr(), attrs, dict(offset=offsets, count=counts),
+                             buf.data_ptr() + GUARD, total, attrs=names)
+        got = buf.cpu().numpy()
+    assert np.all(got[:GUARD] == 0xA5) and np.all(got[GUARD + total:] == 0xA5)
+    assert got[GUARD:GUARD + total].tobytes() == want
+
+
+@pytest.mark.gpu
 def test_gpu_pack_refuses_bad_tables_before_anything_is_launched(packed_inputs):
     import torch
     import schwarzwald_amd as swz
