@@ -103,7 +103,8 @@ int swz_set_stream(swz_ctx* ctx, void* hip_stream);
  *   property mode (SWZ_FLAG_MIN_DISTANCE_PROPERTY): SWZ_MD_ROUNDS=0, SWZ_MD_ROUNDS_LIST=0, SWZ_MD_ROUNDS_CELL_LISTS=0,
  *   SWZ_MD_ROUNDS_BLOCK=0, SWZ_MD_ROUNDS_BLOCK_MIN_POP, SWZ_MD_ROUNDS_WLIST_MIN_POP -- the set keeps the mode's properties
  *   on every path; which set it is may depend on the path a level takes;
- *   the tiler's memory: SWZ_TILER_SPILL=off|host, SWZ_TILER_DEVICE_BUDGET_MB.
+ *   the tiler's memory: SWZ_TILER_SPILL=off|host, SWZ_TILER_DEVICE_BUDGET_MB; SWZ_OUTPUT_CHUNK_POINTS (stored points per
+ *   chunk of swz_tiler_write_output when its parameters say 0; default 16 Mi).
  * - Switches that can make a call FAIL: SWZ_MD_TIME_LIMIT and SWZ_MD_ROUND_LIMIT (a MIN_DISTANCE level that exceeds them is
  *   abandoned with an error), SWZ_SP_BLOCK_TIMEOUT_MS (default 10 000: how long a wavefront waits for an earlier block;
  *   when it expires the call returns SWZ_ERR_INTERNAL, nothing is restarted), SWZ_FAIL_ALLOC=<buffer name, or prefix*>
@@ -282,6 +283,31 @@ int swz_bin_read_node(swz_ctx* ctx, const char* path, int compressed, double* xy
 int swz_bin_persist_nodes(swz_ctx* ctx, const char* dir, uint64_t num_nodes, const int8_t* node_level,
                           const uint64_t* node_key, const uint64_t* node_offset, const uint64_t* node_count,
                           const double* xyz, const swz_attribute_columns* columns, int compressed);
+/* BIN node files packed on the device, like swz_pnts_pack_device and swz_las_pack_device below.  A node's BODY is its whole
+ * uncompressed file: the 12 bytes of mask and count, count x 24 bytes of positions, the arrays of `mask` in file order, no
+ * padding inside.  The IMAGE holds the bodies in table order; every body starts on a multiple of 8, the bytes up to the next
+ * multiple of 8 are zeros and no part of the file.  A node of count 0 has no file and size 0.
+ *   swz_bin_layout (host): offset and size (a multiple of 8) of every body in the image, the size of every file, the image's
+ *     total size.  Any output may be NULL.  SWZ_ERR_BAD_ARG for a mask bit that does not exist or a count above 2^32 - 65536.
+ *   swz_bin_pack_device: writes the image of a node table into d_image_out (device, 8-byte aligned, image_bytes >= the
+ *     layout's total) with one kernel: the permuted gather (row i = row d_perm[d_order[i]] of d_xyz and of the columns of
+ *     d_in; d_order NULL = identity, what a tiler's export ids need) and the layout, headers and padding included -- no byte
+ *     of the image depends on what the buffer held.  node_offset / node_count (host) are rows of the gathered order.
+ *     SWZ_ERR_BAD_ARG before anything is launched for: offsets that do not ascend, ranges that overlap or pass n, a mask that
+ *     names an absent column or a bit that does not exist, n above 2^32 - 65536, an image that is too small or not 8-byte
+ *     aligned.  n == 0 or no nodes is valid and launches nothing.  swz_bin_pack_tile: the stored rows one workgroup takes.
+ *   swz_bin_persist_nodes_image: one file "r" + octant digits + ".bin" per node of a table out of a HOST copy of the image,
+ *     a verbatim slice of it; compressed != 0: that slice as one zlib stream, level 1, ".binz", the way swz_bin_write_node
+ *     compresses.  Written by the pool of host threads of swz_bin_persist_nodes. */
+int swz_bin_layout(uint64_t num_nodes, const uint64_t* node_count, uint32_t mask, uint64_t* body_offset_out,
+                   uint64_t* body_size_out, uint64_t* file_size_out, uint64_t* total_out);
+uint32_t swz_bin_pack_tile(void);
+int swz_bin_pack_device(swz_ctx* ctx, const uint32_t* d_perm, const uint32_t* d_order, uint64_t n, const double* d_xyz,
+                        const swz_attribute_columns* d_in, uint64_t num_nodes, const uint64_t* node_offset,
+                        const uint64_t* node_count, uint32_t mask, void* d_image_out, uint64_t image_bytes);
+int swz_bin_persist_nodes_image(swz_ctx* ctx, const char* dir, uint64_t num_nodes, const int8_t* node_level,
+                                const uint64_t* node_key, const uint64_t* node_count, const void* image, uint64_t image_bytes,
+                                uint32_t mask, int compressed);
 /* "r" + octant digits of a node; name_out must hold 23 bytes */
 int swz_node_name(int8_t node_level, uint64_t node_key, char* name_out);
 
@@ -674,6 +700,48 @@ int swz_tile_nodes_end_device(swz_ctx* ctx, uint64_t* d_keys_out, uint32_t* d_id
                               uint64_t* node_count_out);
 /* the pools by point id: positions (num_points x 3, clamped) and the attribute columns staged so far */
 int swz_tiler_pools_device(swz_tiler* tiler, const double** d_xyz_out, swz_attribute_columns* d_attrs_out);
+/* ---- the node files of a tiler, written in ONE call, in any of the reference's uncompressed output formats (--output-format
+ * BIN, BINZ, 3DTILES, LAS, ENTWINE_LAS; executable/main.cpp:421-428) with the attribute columns the batches carried.
+ * Precondition: that of swz_tiler_export_device -- the tiler is not poisoned and no batch is staged or open; the files are
+ * the node store's as it stands, so a data set is written after swz_tiler_finalize.  The tiler stays usable, a failed write
+ * does not poison it.
+ *   Files: node k of swz_tiler_node_table becomes dir/<swz_node_name>.bin | .binz | .pnts | .las, or
+ *     dir/ept-data/<swz_node_name_entwine>.las; boxes are swz_node_bounds of the tiler's root box, a LAS file's offset is its
+ *     box minimum and its scale swz_las_scale_from_bounds of its box -- what TilingAlgorithmGPU::finalize and the sinks of
+ *     schwarzwald_amd/host/swz_tiling.hpp compute.  dir is created when it does not exist (one level).
+ *   attribute_mask: the columns to write, a subset of what the batches carried.  3DTILES writes RGB and INTENSITY of it and
+ *     ignores the rest, like Cesium3DTilesSink: with an rgb_mapping RGB is the grey value of the intensity.
+ *   Metadata, at the end: 3DTILES swz_tileset_build + swz_tileset_write (global_offset: RTC_CENTER and the boxes' shift);
+ *     ENTWINE_LAS swz_ept_create_dirs first, swz_ept_hierarchy_write last, and ept.json from `ept` unless it is NULL.
+ *   Streaming: the ids of all files are exported once (4 bytes per stored point); the node table is cut into chunks of
+ *     whole consecutive nodes of at most chunk_points stored points (0: option SWZ_OUTPUT_CHUNK_POINTS, else 16 Mi; never
+ *     less than the largest node); per chunk the format's pack kernel writes the chunk's image from the pools (spilled ones
+ *     are read in place) into one of two device buffers, a copy stream moves it into one of two page-locked host buffers,
+ *     and the writer threads (SWZ_BIN_WRITER_THREADS) write chunk k's files while chunk k + 1 is packed and copied.  Device
+ *     and host hold two chunk images at most, whatever the size of the data set.
+ *   SWZ_ERR_BAD_ARG before anything is written for: an unknown format, a mask that names a column the pools do not have, an
+ *     rgb_mapping without intensities in the mask, a global_offset that is not finite, a dir that cannot be created.  A file
+ *     that cannot be written stops the stream after the running chunk and is reported by name.
+ *   stats (may be NULL): pack_ms is the time in the pack calls, copy_ms the copy stream's, write_ms the writer threads',
+ *     each summed over the chunks; wall_ms the whole call; bytes_written the chunk images that went into files. */
+enum { SWZ_OUT_BIN = 0, SWZ_OUT_BINZ = 1, SWZ_OUT_3DTILES = 2, SWZ_OUT_LAS = 3, SWZ_OUT_ENTWINE_LAS = 4 };
+typedef struct {
+  int format;
+  uint32_t attribute_mask;   /* bits SWZ_ATTR_*, a subset of what the batches carried */
+  int rgb_mapping;           /* 3DTILES only: SWZ_PNTS_RGB_FROM_* */
+  double global_offset[3];   /* 3DTILES: RTC_CENTER / the tileset boxes */
+  uint64_t chunk_points;     /* 0 = default */
+  const swz_ept_json* ept;   /* ENTWINE_LAS: NULL = do not write ept.json */
+} swz_output_params;
+typedef struct {
+  uint64_t nodes, stored_points, bytes_written, chunks;
+  double pack_ms, copy_ms, write_ms, wall_ms;
+} swz_output_stats;
+int swz_tiler_write_output(swz_tiler* tiler, const char* dir, const swz_output_params* params, swz_output_stats* stats);
+/* The chunks swz_tiler_write_output cuts a node table into (host): chunk j holds the nodes [first_node_out[j],
+ * first_node_out[j + 1]); first_node_out takes up to max_chunks + 1 entries and may be NULL (then only *num_chunks_out). */
+int swz_output_chunks(uint64_t num_nodes, const uint64_t* node_count, uint64_t chunk_points, uint64_t max_chunks,
+                      uint64_t* first_node_out, uint64_t* num_chunks_out);
 /* ---- one tiler per GPU of a multi-GPU run (BASELINE config 5: sharded + multi-batch).  Points are owned by their
  * level-0 octant as in swz_shard_* above; every shard keeps the subtrees of its octants and ITS part of the root's
  * file.  Per batch, after the exchange of the batch's points (and attribute columns) by octant:

@@ -473,6 +473,68 @@ def bin_persist_nodes(directory, nodes, xyz, attrs=None, compressed=False, ctx=N
         raise SwzError(st, (L.swz_last_error(ctx) or b"").decode() if ctx else "swz_bin_persist_nodes(%s) failed" % directory)
 
 
+def bin_pack_tile():
+    """The stored rows one workgroup of bin_pack_device takes."""
+    return int(load_library().swz_bin_pack_tile())
+
+
+def bin_layout(counts, attrs=()):
+    """swz_bin_layout: where every node's BIN file lies in one contiguous image.  Returns a dict of the per-node arrays
+    offset / size (of the body, a multiple of 8) / file_size and the image's total size."""
+    cnt = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    m = cnt.shape[0]
+    out = {k: np.empty(m, dtype=np.uint64) for k in ("offset", "size", "file_size")}
+    total = C.c_uint64()
+    st = load_library().swz_bin_layout(m, cnt.ctypes.data_as(_u64p), _las_mask(attrs), out["offset"].ctypes.data_as(_u64p),
+                                       out["size"].ctypes.data_as(_u64p), out["file_size"].ctypes.data_as(_u64p), C.byref(total))
+    if st != 0:
+        raise SwzError(st, "swz_bin_layout failed")
+    out["total"] = int(total.value)
+    return out
+
+
+def bin_persist_nodes_image(directory, nodes, image, attrs=(), compressed=False, ctx=None):
+    """One BIN (.binz: zlib) file per node of a node table out of a host copy of the image bin_pack_device wrote."""
+    img = np.ascontiguousarray(image, dtype=np.uint8).reshape(-1)
+    nl, nk, nc = _node_columns(nodes, "level", "key", "count")
+    if not (nl.shape[0] == nk.shape[0] == nc.shape[0]):
+        raise ValueError("the columns of the node table differ in length")
+    L = load_library()
+    st = L.swz_bin_persist_nodes_image(ctx, os.fsencode(directory), nl.shape[0], nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p),
+                                       nc.ctypes.data_as(_u64p), img.ctypes.data, img.shape[0], _las_mask(attrs),
+                                       int(bool(compressed)))
+    if st != 0:
+        raise SwzError(st, (L.swz_last_error(ctx) or b"").decode() if ctx else "swz_bin_persist_nodes_image(%s) failed" % directory)
+
+
+# swz_tiler_write_output: the formats, its parameters and what it reports
+OUTPUT_FORMATS = {"BIN": 0, "BINZ": 1, "3DTILES": 2, "LAS": 3, "ENTWINE_LAS": 4}
+
+
+class _OutputParams(C.Structure):
+    _fields_ = [("format", C.c_int), ("attribute_mask", C.c_uint32), ("rgb_mapping", C.c_int), ("global_offset", C.c_double * 3),
+                ("chunk_points", C.c_uint64), ("ept", C.POINTER(_EptJson))]
+
+
+class _OutputStats(C.Structure):
+    _fields_ = [("nodes", C.c_uint64), ("stored_points", C.c_uint64), ("bytes_written", C.c_uint64), ("chunks", C.c_uint64),
+                ("pack_ms", C.c_double), ("copy_ms", C.c_double), ("write_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+def output_chunks(counts, chunk_points):
+    """swz_output_chunks: the first node of every chunk write_output cuts a node table into, and one entry past the last."""
+    cnt = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    num = C.c_uint64()
+    L = load_library()
+    if L.swz_output_chunks(cnt.shape[0], cnt.ctypes.data_as(_u64p), int(chunk_points), 0, None, C.byref(num)) != 0:
+        raise ValueError("bad node table")
+    first = np.zeros(int(num.value) + 1, dtype=np.uint64)
+    if L.swz_output_chunks(cnt.shape[0], cnt.ctypes.data_as(_u64p), int(chunk_points), int(num.value), first.ctypes.data_as(_u64p),
+                           C.byref(num)) != 0:
+        raise ValueError("bad node table")
+    return first
+
+
 def las_persist_nodes(directory, nodes, image, attrs, box_min, box_max, scale, naming=LAS_NAMING_POTREE, ctx=None):
     """One LAS file per node of a node table out of a host copy of the image las_pack_device wrote.  box_min / box_max
     (num_nodes x 3) and scale (num_nodes) are the nodes' boxes and scales; naming: LAS_NAMING_POTREE or LAS_NAMING_ENTWINE."""
@@ -602,6 +664,16 @@ def load_library():
     L.swz_bin_read_header.argtypes = [vp, C.c_char_p, C.c_int, _u32p, _u64p]
     L.swz_bin_read_node.argtypes = [vp, C.c_char_p, C.c_int, _dp, cols]
     L.swz_bin_persist_nodes.argtypes = [vp, C.c_char_p, C.c_uint64, _i8p, _u64p, _u64p, _u64p, _dp, cols, C.c_int]
+    L.swz_bin_layout.argtypes = [C.c_uint64, _u64p, C.c_uint32, _u64p, _u64p, _u64p, _u64p]
+    L.swz_bin_pack_tile.argtypes = []
+    L.swz_bin_pack_tile.restype = C.c_uint32
+    L.swz_bin_pack_device.argtypes = [vp, vp, vp, C.c_uint64, vp, cols, C.c_uint64, _u64p, _u64p, C.c_uint32, vp, C.c_uint64]
+    L.swz_bin_persist_nodes_image.argtypes = [vp, C.c_char_p, C.c_uint64, _i8p, _u64p, _u64p, vp, C.c_uint64, C.c_uint32, C.c_int]
+    L.swz_tiler_write_output.argtypes = [vp, C.c_char_p, C.POINTER(_OutputParams), C.POINTER(_OutputStats)]
+    L.swz_output_chunks.argtypes = [C.c_uint64, _u64p, C.c_uint64, C.c_uint64, _u64p, _u64p]
+    for name in ("swz_bin_layout", "swz_bin_pack_device", "swz_bin_persist_nodes_image", "swz_tiler_write_output",
+                 "swz_output_chunks"):
+        getattr(L, name).restype = C.c_int
     L.swz_node_name.argtypes = [C.c_int8, C.c_uint64, C.c_char_p]
     L.swz_node_name_entwine.argtypes = [C.c_int8, C.c_uint64, C.c_char_p]
     L.swz_node_from_entwine_name.argtypes = [C.c_char_p, _i8p, _u64p]
@@ -941,6 +1013,19 @@ class Context:
         """bin_persist_nodes with this context's writer threads and error text."""
         bin_persist_nodes(directory, nodes, xyz, attrs, compressed, ctx=self._ctx)
 
+    def bin_pack_device(self, d_perm, d_order, n, d_xyz, d_attrs, nodes, d_image, image_bytes, attrs=()):
+        """swz_bin_pack_device: the BIN files of all nodes of a table, laid out as bin_layout says, written into d_image
+        (device, image_bytes bytes) by one kernel.  d_order None = identity (a tiler's export ids as d_perm)."""
+        cin = device_columns(d_attrs)
+        no, nc = _node_columns(nodes, "offset", "count")
+        self._check(self._lib.swz_bin_pack_device(self._ctx, C.c_void_p(d_perm), C.c_void_p(d_order), int(n), C.c_void_p(d_xyz),
+                                                  C.byref(cin), nc.shape[0], no.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p),
+                                                  _las_mask(attrs), C.c_void_p(d_image), int(image_bytes)))
+
+    def bin_persist_nodes_image(self, directory, nodes, image, attrs=(), compressed=False):
+        """bin_persist_nodes_image with this context's writer threads and error text."""
+        bin_persist_nodes_image(directory, nodes, image, attrs, compressed, ctx=self._ctx)
+
     def pnts_pack_device(self, d_perm, d_order, n, d_xyz, d_attrs, nodes, d_image, image_bytes, attrs=(), rgb_from=RGB_FROM_COLOR):
         """swz_pnts_pack_device: the .pnts bodies of all nodes of a table, laid out as pnts_layout says, written into
         d_image (device, image_bytes bytes) in one pass.  d_order None = identity (a tiler's export ids as d_perm)."""
@@ -1259,6 +1344,27 @@ class Tiler:
 
     def level_positions_device(self, level, d_xyz_out):
         self._ctx._check(self._lib.swz_tiler_level_positions_device(self._t, int(level), C.c_void_p(d_xyz_out)))
+
+    def write_output(self, directory, format, attrs=(), rgb_from=RGB_FROM_COLOR, global_offset=None, chunk_points=0, ept=None):
+        """swz_tiler_write_output: every node file of the tiler, and the format's metadata, into directory.  format: a key of
+        OUTPUT_FORMATS; attrs: the attribute columns to write (names or a mask), a subset of what the batches carried;
+        rgb_from / global_offset: 3DTILES; chunk_points: stored points per chunk (0 = default); ept: ENTWINE_LAS, the keyword
+        arguments of ept_json_write as a dict (bounds, conforming_bounds, points, ...) or None for no ept.json.  Returns the
+        stats as a dict (nodes, stored_points, bytes_written, chunks, pack_ms, copy_ms, write_ms, wall_ms)."""
+        fmt = OUTPUT_FORMATS[format] if isinstance(format, str) else int(format)
+        p = _OutputParams(fmt, _las_mask(attrs), int(rgb_from), _vec3(global_offset if global_offset is not None else (0, 0, 0)),
+                          int(chunk_points), None)
+        keep = None
+        if ept is not None:
+            srs = ept.get("srs") or {}
+            keep = _EptJson(_vec3(ept["bounds"][0]), _vec3(ept["bounds"][1]), _vec3(ept["conforming_bounds"][0]),
+                            _vec3(ept["conforming_bounds"][1]), int(ept["points"]), _las_mask(ept.get("attrs", ())), 0,
+                            float(ept.get("span", 0.0)), srs.get("authority", "").encode(), srs.get("horizontal", "").encode(),
+                            srs.get("wkt", "").encode(), ept.get("version", "").encode())
+            p.ept = C.pointer(keep)
+        stats = _OutputStats()
+        self._ctx._check(self._lib.swz_tiler_write_output(self._t, os.fsencode(directory), C.byref(p), C.byref(stats)))
+        return {k: getattr(stats, k) for k, _ in _OutputStats._fields_}
 
     def pools_device(self):
         """(device pointer of the clamped positions by point id, dict name -> device pointer of the attribute pools)"""

@@ -1,8 +1,12 @@
-// swz_hostio.h -- what the host side of the node-file writers shares (swz_payload.hip, swz_pnts.hip, swz_las.hip): errors
-// with or without a context, whole files in and out, numbers in JSON text and the pool of writer threads.
+// swz_hostio.h -- what the host side of the node-file writers shares (swz_payload.hip, swz_binpack.hip, swz_pnts.hip,
+// swz_las.hip, swz_toutput.hip): errors with or without a context, whole files in and out, numbers in JSON text, the pool
+// of writer threads and the attribute arrays of a BIN node file.
 #pragma once
 
+#include <zlib.h>
+
 #include <atomic>
+#include <chrono>
 #include <charconv>
 #include <cmath>
 #include <cstdio>
@@ -21,6 +25,13 @@ inline int fail(swz_ctx* c, int code, const std::string& msg) {
   if (c) return c->fail(code, msg.c_str());
   return code;
 }
+
+static const uint32_t ATTR_BYTES[SWZ_ATTR_COUNT] = {3, 12, 2, 1, 1, 8, 1, 1, 2, 1, 1, 1};
+// order of the attribute arrays in a node file (BinaryPersistence.h:120-190: bit 10 before bit 9)
+static const int FILE_ORDER[SWZ_ATTR_COUNT] = {SWZ_ATTR_RGB, SWZ_ATTR_NORMAL, SWZ_ATTR_INTENSITY, SWZ_ATTR_CLASSIFICATION,
+                                               SWZ_ATTR_EDGE_OF_FLIGHT_LINE, SWZ_ATTR_GPS_TIME, SWZ_ATTR_NUMBER_OF_RETURNS,
+                                               SWZ_ATTR_RETURN_NUMBER, SWZ_ATTR_POINT_SOURCE_ID, SWZ_ATTR_SCAN_ANGLE_RANK,
+                                               SWZ_ATTR_SCAN_DIRECTION_FLAG, SWZ_ATTR_USER_DATA};
 
 inline bool finite3(const double v[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
@@ -54,6 +65,18 @@ inline int write_file(const std::string& path, const std::vector<FilePiece>& pie
     return SWZ_ERR_INTERNAL;
   }
   return SWZ_OK;
+}
+
+// the same bytes as ONE zlib stream, level 1 (BinaryPersistence's .binz).  A stream zlib could not make leaves an empty file
+// and is reported like a write that failed.
+inline int write_file_zlib(const std::string& path, const void* data, size_t bytes, std::string* err) {
+  uLongf cap = compressBound((uLong)bytes);
+  std::vector<unsigned char> z(cap);
+  const bool packed = compress2(z.data(), &cap, static_cast<const Bytef*>(data), (uLong)bytes, Z_BEST_SPEED) == Z_OK;
+  const int st = write_file(path, {{z.data(), packed ? (size_t)cap : 0}}, err);
+  if (st != SWZ_OK || packed) return st;
+  *err = "short write to " + path;
+  return SWZ_ERR_INTERNAL;
 }
 
 inline void put_number(std::string& s, double v) {
@@ -103,5 +126,66 @@ inline int run_tickets(swz_ctx* c, uint64_t num, F&& item, std::string* first_er
   }
   return status.load();
 }
+
+// The same pool, started and joined in two steps: the caller goes on (packs and copies the next chunk of a tiler's output,
+// swz_toutput.hip) while the items are worked off.  As many threads as run_tickets would take, never the caller's own.
+class TicketRun {
+public:
+  TicketRun() = default;
+  TicketRun(const TicketRun&) = delete;
+  TicketRun& operator=(const TicketRun&) = delete;
+  ~TicketRun() { (void)wait(nullptr, nullptr); }
+
+  template <typename F>
+  void start(swz_ctx* c, uint64_t num, F item) {
+    unsigned threads = std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
+    if (c) threads = (unsigned)std::max(1L, c->opt_int("SWZ_BIN_WRITER_THREADS", threads));
+    threads = (unsigned)std::min<uint64_t>(threads, std::max<uint64_t>(num, 1));
+    next_.store(0);
+    status_.store(SWZ_OK);
+    err_.clear();
+    begin_ = std::chrono::steady_clock::now();
+    busy_ms_ = 0.0;
+    for (unsigned t = 0; t < threads; ++t)
+      pool_.emplace_back([this, num, item]() {
+        for (;;) {
+          const uint64_t k = next_.fetch_add(1);
+          if (k >= num || status_.load() != SWZ_OK) break;
+          std::string err;
+          const int st = item(k, &err);
+          if (st != SWZ_OK) {
+            std::lock_guard<std::mutex> lk(m_);
+            if (status_.load() == SWZ_OK) {
+              err_ = err;
+              status_.store(st);
+            }
+            break;
+          }
+        }
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - begin_).count();
+        std::lock_guard<std::mutex> lk(m_);
+        busy_ms_ = std::max(busy_ms_, ms);
+      });
+  }
+  bool running() const { return !pool_.empty(); }
+  // joins; the status of the first item that failed and its text; *busy_ms: from start() to the last thread's end
+  int wait(std::string* first_err, double* busy_ms) {
+    for (auto& t : pool_) t.join();
+    const bool ran = !pool_.empty();
+    pool_.clear();
+    if (first_err && status_.load() != SWZ_OK) *first_err = err_;
+    if (busy_ms) *busy_ms = ran ? busy_ms_ : 0.0;
+    return status_.load();
+  }
+
+private:
+  std::vector<std::thread> pool_;
+  std::atomic<uint64_t> next_{0};
+  std::atomic<int> status_{SWZ_OK};
+  std::mutex m_;
+  std::string err_;
+  std::chrono::steady_clock::time_point begin_;
+  double busy_ms_ = 0.0;
+};
 
 }  // namespace swz

@@ -1,8 +1,6 @@
 // swz_payload.hip -- node lists on the device, the permuted payload gather, and BinaryPersistence node files
 // (reference: core/io/BinaryPersistence.h:45-193, BinaryPersistence.cpp:200-375,
 // core/tiling/TilingAlgorithms.cpp:139, 232-236).
-#include <zlib.h>
-
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -17,13 +15,7 @@
 
 namespace swz {
 
-static const uint32_t ATTR_BYTES[SWZ_ATTR_COUNT] = {3, 12, 2, 1, 1, 8, 1, 1, 2, 1, 1, 1};
-// order of the attribute arrays in a node file (BinaryPersistence.h:120-190: bit 10 before bit 9)
-static const int FILE_ORDER[SWZ_ATTR_COUNT] = {SWZ_ATTR_RGB, SWZ_ATTR_NORMAL, SWZ_ATTR_INTENSITY, SWZ_ATTR_CLASSIFICATION,
-                                               SWZ_ATTR_EDGE_OF_FLIGHT_LINE, SWZ_ATTR_GPS_TIME, SWZ_ATTR_NUMBER_OF_RETURNS,
-                                               SWZ_ATTR_RETURN_NUMBER, SWZ_ATTR_POINT_SOURCE_ID, SWZ_ATTR_SCAN_ANGLE_RANK,
-                                               SWZ_ATTR_SCAN_DIRECTION_FLAG, SWZ_ATTR_USER_DATA};
-
+// (ATTR_BYTES and FILE_ORDER, the attribute arrays of a node file: swz_hostio.h)
 // ---------------------------------------------------------------------------------- node lists
 __global__ __launch_bounds__(256) void level_key_kernel(const int8_t* __restrict__ level, uint32_t n, uint64_t* __restrict__ out,
                                                         uint32_t* __restrict__ bad) {
@@ -370,14 +362,7 @@ static int bin_write_node_impl(const char* path, uint64_t count, const double* x
   if (!compressed) return write_file(path, pieces, err);
   std::vector<unsigned char> plain;
   for (const FilePiece& p : pieces) plain.insert(plain.end(), (const unsigned char*)p.data, (const unsigned char*)p.data + p.bytes);
-  uLongf cap = compressBound((uLong)plain.size());
-  std::vector<unsigned char> z(cap);
-  // (a stream zlib could not make leaves an empty file and is reported like a write that failed)
-  const bool packed = compress2(z.data(), &cap, plain.data(), (uLong)plain.size(), Z_BEST_SPEED) == Z_OK;
-  const int st = write_file(path, {{z.data(), packed ? (size_t)cap : 0}}, err);
-  if (st != SWZ_OK || packed) return st;
-  *err = std::string("short write to ") + path;
-  return SWZ_ERR_INTERNAL;
+  return write_file_zlib(path, plain.data(), plain.size(), err);
 }
 
 extern "C" {

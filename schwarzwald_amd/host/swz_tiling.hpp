@@ -16,7 +16,7 @@
 //   sample_points                    Sampling.h:799-821       sample_points (returns the partition point)
 //   TilerMetaParameters              process/Tiler.h:64-75    TilerMetaParameters
 //   PointsPersistence::persist_points io/PointsPersistence.h  PointsSink::persist_points
-//   TilingAlgorithmBase              TilingAlgorithms.h:70    TilingAlgorithmGPU::tile_batch / finalize
+//   TilingAlgorithmBase              TilingAlgorithms.h:70    TilingAlgorithmGPU::tile_batch / finalize / write_output
 //   get_octant_bounds                OctreeAlgorithms.cpp:3   get_octant_bounds
 //
 // Errors: every failing ABI call becomes std::runtime_error carrying swz_last_error(), the way the
@@ -389,8 +389,34 @@ public:
 
   // positions: n x 3 doubles of this batch (host memory; pinned memory makes the copy asynchronous);
   // bounds: the octree's (cubic) root bounds, the same for every batch
-  swz_tile_stats tile_batch(const double* positions, size_t n, const AABB& bounds) {
-    if (_finalized) throw std::runtime_error{"TilingAlgorithmGPU: tile_batch after finalize"};
+  swz_tile_stats tile_batch(const double* positions, size_t n, const AABB& bounds) { return tile_batch(positions, nullptr, n, bounds); }
+  // ... with the batch's attribute columns (host memory, n rows each; the same set for every batch): they go into the
+  // tiler's pools and come out in the files of write_output()
+  swz_tile_stats tile_batch(const double* positions, const swz_attribute_columns& attributes, size_t n, const AABB& bounds) {
+    return tile_batch(positions, &attributes, n, bounds);
+  }
+
+  // The node files and the format's metadata under `dir`, written by the library in one call (swz_tiler_write_output): packed
+  // on the device straight from the pools, with the attribute columns of params.attribute_mask, chunk by chunk while the
+  // chunk before is being written -- what replaces the hand-off of every node to a PointsSink.  Finalizes the tiler if
+  // finalize() has not; the persistence given to the constructor is not involved.
+  swz_output_stats write_output(const std::string& dir, const swz_output_params& params) {
+    if (!_tiler) throw std::runtime_error{"TilingAlgorithmGPU: write_output before the first batch"};
+    finalize_tiler();
+    swz_output_stats stats{};
+    _ctx.check(swz_tiler_write_output(_tiler, dir.c_str(), &params, &stats));
+    return stats;
+  }
+
+private:
+  void finalize_tiler() {
+    if (_tiler_finalized) return;
+    swz_tile_stats stats{};
+    _ctx.check(swz_tiler_finalize(_tiler, &stats));
+    _tiler_finalized = true;
+  }
+  swz_tile_stats tile_batch(const double* positions, const swz_attribute_columns* attributes, size_t n, const AABB& bounds) {
+    if (_finalized || _tiler_finalized) throw std::runtime_error{"TilingAlgorithmGPU: tile_batch after finalize"};
     if (!_tiler) {
       swz_tile_params p{};
       p.sampler = _sampling_strategy.kind;
@@ -404,17 +430,18 @@ public:
       _bounds = bounds;
     }
     swz_tile_stats stats{};
-    _ctx.check(swz_tiler_add_batch(_tiler, positions, n, nullptr, &stats));
+    _ctx.check(swz_tiler_add_batch(_tiler, positions, n, attributes, &stats));
     return stats;
   }
+
+public:
 
   // TilingAlgorithmBase::finalize (FAST: reconstruct_left_out_nodes), then every node file goes to the persistence.
   // Returns the number of nodes persisted.
   size_t finalize(const AABB&) {
     if (!_tiler || _finalized) return 0;
     _finalized = true;
-    swz_tile_stats stats{};
-    _ctx.check(swz_tiler_finalize(_tiler, &stats));
+    finalize_tiler();
     swz_tiler_info info{};
     _ctx.check(swz_tiler_get_info(_tiler, &info));
     const uint64_t ns = info.num_stored, nn = info.num_nodes;
@@ -487,7 +514,8 @@ private:
   TilerMetaParameters _meta;
   swz_tiler* _tiler = nullptr;
   AABB _bounds;
-  bool _finalized = false;
+  bool _finalized = false;        // finalize() has handed the files to the persistence
+  bool _tiler_finalized = false;  // swz_tiler_finalize has run (finalize() or write_output())
   uint64_t _export_chunk_points = 16u << 20;
 };
 
