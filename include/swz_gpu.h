@@ -77,7 +77,8 @@ int swz_set_stream(swz_ctx* ctx, void* hip_stream);
  * - Diagnostics: SWZ_DEBUG (per-level lines on stderr), SWZ_TRACE (synchronise and report after every stage),
  *   SWZ_SYNC_ENTRY (synchronise the device when swz_tile_device starts), SWZ_MD_STATS (count the key sweep's activations by
  *   kind), SWZ_POISON=<byte> and SWZ_POISON_ONLY=<part of a buffer name> (fill new workspace memory),
- *   SWZ_BIN_WRITER_THREADS (host threads that write node files).
+ *   SWZ_BIN_WRITER_THREADS (host threads that write node files), SWZ_INPUT_READER_THREADS (host threads that read the
+ *   LAS files of swz_tiler_add_las_files).
  * - Switches that only force a path, a schedule or a capacity -- the samplers' results stay what they are:
  *   sort: SWZ_SORT_ONESWEEP=0, SWZ_SORT_HYBRID_MIN_N, SWZ_SORT_HYBRID_TOP, SWZ_SORT_FIX_SHORT, SWZ_SORT_FIX_LONG,
  *   SWZ_SORT_WIDE_MIN_N (keys from which a scatter pass takes its 8192-key tile);
@@ -742,6 +743,110 @@ int swz_tiler_write_output(swz_tiler* tiler, const char* dir, const swz_output_p
  * first_node_out[j + 1]); first_node_out takes up to max_chunks + 1 entries and may be NULL (then only *num_chunks_out). */
 int swz_output_chunks(uint64_t num_nodes, const uint64_t* node_count, uint64_t chunk_points, uint64_t max_chunks,
                       uint64_t* first_node_out, uint64_t* num_chunks_out);
+/* ---- a data set of uncompressed LAS files read in ONE call: the input side of swz_tiler_write_output.  What the reference
+ * does in TilerProcess::prepare / calculate_dataset_metadata (core/process/TilerProcess.cpp:250-390, 570-600) and
+ * MultiReaderPointSource, for files that need neither a PROJ transformation nor LASzip ("LAZ is not read").
+ *   swz_las_scan_files (host, no GPU; ctx only carries the error text and may be NULL): parses the LAS 1.0 - 1.4 public
+ *     header of every file, little-endian, without reading past the file.  Per file (files_out, may be NULL): the point count
+ *     -- the legacy u32, or the LAS 1.4 extended u64 count when the legacy one is 0 or the point format is >= 6
+ *     (LASFile::size, core/io/LASFile.cpp:268-276) --, the swz_las_layout, the offset to the point data, the SWZ_ATTR_* the
+ *     file has by the rules of las_file_has_attribute (LASFile.cpp:415-445, as written: GPS time is credited to formats 1
+ *     and 3 only, colours to 2, 3, 5, 7, 8, 10, normals to none) and a status.  The data set: the total point count, the
+ *     union of the headers' boxes (get_bounds_from_las_header, :402-406; every readable file, an empty one included, as
+ *     DatasetMetadata::add_file_metadata does), that box made cubic exactly as AABB::makeCubic computes it
+ *     (core/math/AABB.h:50-70: centre = min + extent / 2, then -+ the largest extent / 2 -- bit for bit), the cubic box at
+ *     the origin (cubic min / max minus the cubic box's own centre, core/pointcloud/FileStats.cpp:30-37), that centre, and
+ *     the attributes common to all readable files.
+ *     SWZ_ERR_BAD_ARG, naming the file, for: a file that cannot be opened, a short file or a wrong signature, a point format
+ *     above 10, a record length below the format's, an offset to the point data or count x record length that passes the
+ *     end of the file, a compressed file (bit 7 of the point format or a LASzip VLR).  With SWZ_LAS_SCAN_SKIP_UNREADABLE
+ *     such a file gets count 0 and its status instead (IgnoreErrors::InaccessibleFiles) and takes no part in the data set.
+ *     No points at all: SWZ_ERR_BAD_ARG ("Found no points to process", TilerProcess.cpp:587-589).
+ *   swz_input_batches (host): the cuts of the data set into batches, as swz_output_chunks does for output.  Batches are
+ *     runs of batch_points consecutive points of the files concatenated in the given order (a batch of the reference is
+ *     internal_cache_size points of the concatenated sources); batch j holds the points [first_point_out[j],
+ *     first_point_out[j + 1]); first_point_out takes up to max_batches + 1 entries and may be NULL (then only
+ *     *num_batches_out).  A tail of fewer than min_last points is folded into the batch before it -- min_last is
+ *     fast_concurrency under SWZ_FAST, which refuses a shorter batch, and 0 otherwise.  The folding is OURS: the
+ *     reference's reader threads define no batch order.  SWZ_ERR_BAD_ARG for batch_points 0, a data set of fewer than
+ *     min_last points, and max_batches too small.
+ *   swz_las_decode_segments_device: one kernel for a batch that spans files.  d_raw holds raw point records; segment s is
+ *     count records of layout.record_bytes each, the first at byte byte_offset of d_raw, decoded into the output rows
+ *     [first_row, first_row + count).  d_raw, the byte offsets and the record lengths have ANY alignment and parity.  A
+ *     workgroup takes swz_las_input_tile() consecutive rows, whatever segments they belong to (it finds them in a table in
+ *     LDS), loads the aligned words that cover its records into LDS -- whole words only where they lie inside
+ *     [d_raw, d_raw + raw_bytes), single bytes at the two ends -- and unpacks from there; a tile whose records span more
+ *     than swz_las_input_tile() x 96 bytes (records longer than 96 bytes, or gaps between segments) is read directly.  The
+ *     field mapping is swz_las_decode_device's.  shift_center (NULL = none): after the clamp into the header box every
+ *     axis becomes (double)(float)(p - centre), the 3D Tiles transformation of TilerProcess::make_tiler
+ *     (TilerProcess.cpp:552-559).  Columns absent from d_out are skipped, d_xyz_out may be NULL.
+ *     SWZ_ERR_BAD_ARG before anything is launched for: rows that do not ascend contiguously from 0, a segment whose
+ *     records pass raw_bytes, a format above 10 or a record length below the format's, more than 2^32 - 65536 points, a
+ *     centre that is not finite.  Zero segments or zero points launches nothing.
+ *   swz_tiler_add_las_files: scans the headers, refuses what can be refused, then streams the files through the tiler.
+ *     params: batch_points (0 = 10 M, the reference's --internal-cache-size), attribute_mask (a subset of the data set's
+ *     common mask; ~0u = all of it; bit SWZ_ATTR_NORMAL is refused), shift_to_center (positions become (double)(float)(p -
+ *     the cubic box's centre): the tiler's root box must then be the box at the origin), flags (SWZ_LAS_SCAN_*).  Point ids
+ *     are the input order: file by file, record by record.  SWZ_ERR_BAD_ARG when the tiler's root box does not contain the
+ *     data set's (shifted) tight box -- up to 4 ulp of the coordinates: makeCubic's own box can miss its tight box by one,
+ *     and what lies outside by a rounding is clamped by the indexing as in the reference --, when the mask is not the one the tiler's first batch fixed, when batches are staged
+ *     or open; SWZ_ERR_TOO_MANY_POINTS before anything is read.  The pools are reserved once for the total
+ *     (swz_tiler_reserve), so nothing grows while a batch is in flight.  Per batch: reader threads (option
+ *     SWZ_INPUT_READER_THREADS; default: the host's, at most 32) pread the raw record ranges of the batch's segments back to
+ *     back into one of TWO page-locked buffers, the tiler's copy stream moves the buffer into one of two device buffers
+ *     and decodes it there with the segment kernel STRAIGHT into the pool rows of the batch (positions and the masked
+ *     columns, spilled pools included), and the batch is tiled as swz_tiler_tile_staged does -- read, copy and decode of
+ *     batch k + 1 run beside the tiling of batch k.  Host and device hold two raw batch images at most, whatever the size
+ *     of the data set.  A read that fails stops the stream after the running batch and is reported by the file's name.  A
+ *     failure before the first batch leaves the tiler untouched, a later one poisons it as a failed staged batch does.
+ *     The call does not finalize.  stats (may be NULL): read_ms the reader threads', copy_ms and decode_ms the copy
+ *     stream's, tile_ms the tiling calls', wait_ms the time tiling waited for its input, each summed over the batches. */
+enum { SWZ_LAS_FILE_OK = 0, SWZ_LAS_FILE_UNREADABLE = 1, SWZ_LAS_FILE_BAD_HEADER = 2, SWZ_LAS_FILE_COMPRESSED = 3 };
+#define SWZ_LAS_SCAN_SKIP_UNREADABLE 1u
+typedef struct {
+  uint64_t point_count;
+  uint64_t offset_to_point_data;
+  swz_las_layout layout;
+  uint32_t attribute_mask; /* bits SWZ_ATTR_* */
+  int32_t status;          /* SWZ_LAS_FILE_* */
+} swz_las_file_info;
+typedef struct {
+  uint64_t total_points;
+  uint64_t readable_files;
+  double tight_min[3], tight_max[3];
+  double cubic_min[3], cubic_max[3];
+  double origin_min[3], origin_max[3]; /* the cubic box at the origin */
+  double center[3];                    /* the cubic box's centre: what shift_to_center subtracts */
+  uint32_t attribute_mask;             /* common to all readable files */
+  uint32_t reserved;
+} swz_las_dataset;
+int swz_las_scan_files(swz_ctx* ctx, const char* const* paths, uint64_t num_files, uint32_t flags,
+                       swz_las_file_info* files_out, swz_las_dataset* dataset_out);
+int swz_input_batches(uint64_t num_files, const uint64_t* file_count, uint64_t batch_points, uint64_t min_last,
+                      uint64_t max_batches, uint64_t* first_point_out, uint64_t* num_batches_out);
+typedef struct {
+  uint64_t first_row;   /* output row of the segment's first record */
+  uint64_t count;       /* records */
+  uint64_t byte_offset; /* of the first record in d_raw */
+  swz_las_layout layout;
+} swz_las_segment;
+uint32_t swz_las_input_tile(void); /* points one workgroup takes; tests place their edges by it */
+int swz_las_decode_segments_device(swz_ctx* ctx, const uint8_t* d_raw, uint64_t raw_bytes, uint64_t num_segments,
+                                   const swz_las_segment* segments /* host */, const double shift_center[3] /* or NULL */,
+                                   double* d_xyz_out, const swz_attribute_columns* d_out);
+typedef struct {
+  uint64_t batch_points;   /* 0 = 10 M */
+  uint32_t attribute_mask; /* bits SWZ_ATTR_*; ~0u = every attribute the files have in common */
+  uint32_t shift_to_center;
+  uint32_t flags;          /* SWZ_LAS_SCAN_* */
+  uint32_t reserved;
+} swz_input_params;
+typedef struct {
+  uint64_t files, points, batches, bytes_read;
+  double read_ms, copy_ms, decode_ms, tile_ms, wait_ms, wall_ms;
+} swz_input_stats;
+int swz_tiler_add_las_files(swz_tiler* tiler, const char* const* paths, uint64_t num_files, const swz_input_params* params,
+                            swz_input_stats* stats);
 /* ---- one tiler per GPU of a multi-GPU run (BASELINE config 5: sharded + multi-batch).  Points are owned by their
  * level-0 octant as in swz_shard_* above; every shard keeps the subtrees of its octants and ITS part of the root's
  * file.  Per batch, after the exchange of the batch's points (and attribute columns) by octant:

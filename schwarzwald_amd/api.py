@@ -584,6 +584,95 @@ def ept_json_write(path, bounds, conforming_bounds, points, attrs=(), span=0.0, 
 
 
 
+LAS_FILE_OK, LAS_FILE_UNREADABLE, LAS_FILE_BAD_HEADER, LAS_FILE_COMPRESSED = 0, 1, 2, 3
+LAS_SCAN_SKIP_UNREADABLE = 1
+
+
+class _LasFileInfo(C.Structure):
+    _fields_ = [("point_count", C.c_uint64), ("offset_to_point_data", C.c_uint64), ("layout", _LasLayout),
+                ("attribute_mask", C.c_uint32), ("status", C.c_int32)]
+
+
+class _LasDataset(C.Structure):
+    _fields_ = [("total_points", C.c_uint64), ("readable_files", C.c_uint64), ("tight_min", C.c_double * 3),
+                ("tight_max", C.c_double * 3), ("cubic_min", C.c_double * 3), ("cubic_max", C.c_double * 3),
+                ("origin_min", C.c_double * 3), ("origin_max", C.c_double * 3), ("center", C.c_double * 3),
+                ("attribute_mask", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _LasSegment(C.Structure):
+    _fields_ = [("first_row", C.c_uint64), ("count", C.c_uint64), ("byte_offset", C.c_uint64), ("layout", _LasLayout)]
+
+
+class _InputParams(C.Structure):
+    _fields_ = [("batch_points", C.c_uint64), ("attribute_mask", C.c_uint32), ("shift_to_center", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _InputStats(C.Structure):
+    _fields_ = [("files", C.c_uint64), ("points", C.c_uint64), ("batches", C.c_uint64), ("bytes_read", C.c_uint64),
+                ("read_ms", C.c_double), ("copy_ms", C.c_double), ("decode_ms", C.c_double), ("tile_ms", C.c_double),
+                ("wait_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+def _path_array(paths):
+    enc = [os.fsencode(p) for p in paths]
+    return (C.c_char_p * max(len(enc), 1))(*enc), len(enc)
+
+
+def attribute_names(mask):
+    """the names of ATTRIBUTES whose bits are set in mask"""
+    return [name for name, (idx, _, _) in ATTRIBUTES.items() if int(mask) >> idx & 1]
+
+
+def las_scan_files(paths, skip_unreadable=False, ctx=None):
+    """swz_las_scan_files: the headers of a data set of uncompressed LAS files (host only).  Returns (files, dataset):
+    files is a list of dicts (count, offset_to_point_data, point_format, record_bytes, scale, offset, min, max, attrs,
+    status), dataset a dict (total_points, readable_files, tight / cubic / origin boxes as (min, max) of float64 arrays,
+    center, attrs: the names common to all readable files, attribute_mask)."""
+    arr, n = _path_array(paths)
+    infos = (_LasFileInfo * max(n, 1))()
+    ds = _LasDataset()
+    L = load_library()
+    st = L.swz_las_scan_files(ctx, arr, n, LAS_SCAN_SKIP_UNREADABLE if skip_unreadable else 0, infos, C.byref(ds))
+    if st != 0:
+        raise SwzError(st, L.swz_last_error(ctx).decode() if ctx else "swz_las_scan_files failed")
+    files = []
+    for i in range(n):
+        f, lay = infos[i], infos[i].layout
+        files.append(dict(count=int(f.point_count), offset_to_point_data=int(f.offset_to_point_data),
+                          point_format=int(lay.point_format), record_bytes=int(lay.record_bytes), scale=list(lay.scale),
+                          offset=list(lay.offset), min=list(lay.min), max=list(lay.max),
+                          attrs=attribute_names(f.attribute_mask), attribute_mask=int(f.attribute_mask), status=int(f.status)))
+    vec = lambda v: np.array(list(v), dtype=np.float64)
+    dataset = dict(total_points=int(ds.total_points), readable_files=int(ds.readable_files),
+                   tight=(vec(ds.tight_min), vec(ds.tight_max)), cubic=(vec(ds.cubic_min), vec(ds.cubic_max)),
+                   origin=(vec(ds.origin_min), vec(ds.origin_max)), center=vec(ds.center),
+                   attrs=attribute_names(ds.attribute_mask), attribute_mask=int(ds.attribute_mask))
+    return files, dataset
+
+
+def input_batches(file_counts, batch_points, min_last=0):
+    """swz_input_batches: the first point of every batch of the concatenated files, and the total as the last entry."""
+    cnt = np.ascontiguousarray(file_counts, dtype=np.uint64).reshape(-1)
+    num = C.c_uint64()
+    L = load_library()
+    st = L.swz_input_batches(cnt.shape[0], cnt.ctypes.data_as(_u64p), int(batch_points), int(min_last), 0, None, C.byref(num))
+    if st != 0:
+        raise SwzError(st, "swz_input_batches failed")
+    first = np.empty(int(num.value) + 1, dtype=np.uint64)
+    st = L.swz_input_batches(cnt.shape[0], cnt.ctypes.data_as(_u64p), int(batch_points), int(min_last), int(num.value),
+                             first.ctypes.data_as(_u64p), C.byref(num))
+    if st != 0:
+        raise SwzError(st, "swz_input_batches failed")
+    return first
+
+
+def las_input_tile():
+    """The points one workgroup of las_decode_segments_device takes."""
+    return int(load_library().swz_las_input_tile())
+
+
 def library_path():
     return os.environ.get("SWZ_GPU_LIBRARY", os.path.join(_HERE, "lib", "libswz_gpu.so"))
 
@@ -698,6 +787,14 @@ def load_library():
                  "swz_pnts_persist_nodes", "swz_pnts_read_header", "swz_pnts_read_node", "swz_tileset_write"):
         getattr(L, name).restype = C.c_int
     L.swz_las_decode_device.argtypes = [vp, vp, C.c_uint64, C.POINTER(_LasLayout), vp, cols]
+    L.swz_las_scan_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.c_uint32, C.POINTER(_LasFileInfo), C.POINTER(_LasDataset)]
+    L.swz_input_batches.argtypes = [C.c_uint64, _u64p, C.c_uint64, C.c_uint64, C.c_uint64, _u64p, _u64p]
+    L.swz_las_input_tile.argtypes = []
+    L.swz_las_input_tile.restype = C.c_uint32
+    L.swz_las_decode_segments_device.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(_LasSegment), _dp, vp, cols]
+    L.swz_tiler_add_las_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(_InputParams), C.POINTER(_InputStats)]
+    for name in ("swz_las_scan_files", "swz_input_batches", "swz_las_decode_segments_device", "swz_tiler_add_las_files"):
+        getattr(L, name).restype = C.c_int
     L.swz_las_scale_from_bounds.argtypes = [_dp, _dp]
     L.swz_las_scale_from_bounds.restype = C.c_double
     L.swz_las_record_layout.argtypes = [C.c_uint32, _u32p, _u32p]
@@ -1008,6 +1105,20 @@ class Context:
         cols = device_columns(d_attrs)
         self._check(self._lib.swz_las_decode_device(self._ctx, C.c_void_p(d_records), int(n), C.byref(lay),
                                                     C.c_void_p(d_xyz), C.byref(cols)))
+
+    def las_decode_segments_device(self, d_raw, raw_bytes, segments, d_xyz, d_attrs=None, shift_center=None):
+        """swz_las_decode_segments_device: raw point records of several files (device memory, any alignment) -> positions and
+        attribute columns in one launch.  segments: dicts of first_row, count, byte_offset, scale, offset, min, max,
+        point_format, record_bytes (the keys of a las_scan_files entry)."""
+        segs = (_LasSegment * max(len(segments), 1))()
+        for i, g in enumerate(segments):
+            segs[i] = _LasSegment(int(g["first_row"]), int(g["count"]), int(g["byte_offset"]),
+                                  _LasLayout(_vec3(g["scale"]), _vec3(g["offset"]), _vec3(g["min"]), _vec3(g["max"]),
+                                             int(g["point_format"]), int(g["record_bytes"])))
+        cols = device_columns(d_attrs)
+        center = None if shift_center is None else _vec3(shift_center)
+        self._check(self._lib.swz_las_decode_segments_device(self._ctx, C.c_void_p(d_raw), int(raw_bytes), len(segments), segs, center,
+                                                             C.c_void_p(d_xyz), C.byref(cols)))
 
     def bin_persist_nodes(self, directory, nodes, xyz, attrs=None, compressed=False):
         """bin_persist_nodes with this context's writer threads and error text."""
@@ -1365,6 +1476,18 @@ class Tiler:
         stats = _OutputStats()
         self._ctx._check(self._lib.swz_tiler_write_output(self._t, os.fsencode(directory), C.byref(p), C.byref(stats)))
         return {k: getattr(stats, k) for k, _ in _OutputStats._fields_}
+
+    def add_las_files(self, paths, batch_points=0, attrs=None, shift_to_center=False, skip_unreadable=False):
+        """swz_tiler_add_las_files: a data set of uncompressed LAS files read, decoded on the device straight into the pools
+        and tiled, batch after batch.  attrs: the attribute columns to carry (names or a mask; None = all the files have in
+        common); batch_points 0 = 10 M.  Does not finalize.  Returns the stats as a dict (files, points, batches, bytes_read,
+        read_ms, copy_ms, decode_ms, tile_ms, wait_ms, wall_ms)."""
+        arr, n = _path_array(paths)
+        mask = 0xFFFFFFFF if attrs is None else _las_mask(attrs)
+        p = _InputParams(int(batch_points), mask, 1 if shift_to_center else 0, LAS_SCAN_SKIP_UNREADABLE if skip_unreadable else 0, 0)
+        stats = _InputStats()
+        self._ctx._check(self._lib.swz_tiler_add_las_files(self._t, arr, n, C.byref(p), C.byref(stats)))
+        return {k: getattr(stats, k) for k, _ in _InputStats._fields_}
 
     def pools_device(self):
         """(device pointer of the clamped positions by point id, dict name -> device pointer of the attribute pools)"""

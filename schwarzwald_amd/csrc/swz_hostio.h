@@ -136,10 +136,12 @@ public:
   TicketRun& operator=(const TicketRun&) = delete;
   ~TicketRun() { (void)wait(nullptr, nullptr); }
 
+  // want_threads > 0: that many threads (a caller with an option of its own: the readers of swz_tinput.hip)
   template <typename F>
-  void start(swz_ctx* c, uint64_t num, F item) {
+  void start(swz_ctx* c, uint64_t num, F item, long want_threads = 0) {
     unsigned threads = std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
-    if (c) threads = (unsigned)std::max(1L, c->opt_int("SWZ_BIN_WRITER_THREADS", threads));
+    if (want_threads > 0) threads = (unsigned)want_threads;
+    else if (c) threads = (unsigned)std::max(1L, c->opt_int("SWZ_BIN_WRITER_THREADS", threads));
     threads = (unsigned)std::min<uint64_t>(threads, std::max<uint64_t>(num, 1));
     next_.store(0);
     status_.store(SWZ_OK);

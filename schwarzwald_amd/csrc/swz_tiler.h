@@ -5,6 +5,8 @@
 //   swz_tlevel.hip   one level of a batch: pull, merge, sample, store
 //   swz_treroot.hip  re-rooting
 //   swz_tiler.hip    the batch life cycle, FAST finalize, the node table and the C ABI
+//   swz_toutput.hip  the node files written in one call
+//   swz_tinput.hip   a data set of LAS files read in one call
 #pragma once
 #include <string>
 #include <vector>
@@ -104,6 +106,10 @@ struct swz_tiler {
   uint32_t acc_rounds = 0, acc_levels = 0;
   int acc_max_level = -1;
 };
+
+// swz_tiler.hip: what every call of the tiler's API starts with -- SWZ_ERR_TILER_FAILED for a poisoned tiler, else a new
+// scratch epoch (swz_tinput.hip's call is one of them)
+int tiler_guard(swz_tiler* t);
 
 namespace swz {
 

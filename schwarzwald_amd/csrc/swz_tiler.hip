@@ -30,7 +30,7 @@
 
 #include "swz_tiler.h"
 
-static int tiler_guard(swz_tiler* t) {
+int tiler_guard(swz_tiler* t) {
   // (every call of the tiler's API starts a scratch epoch: what earlier calls asked for and nothing holds on to -- level
   // scratch, and the per-batch "tl_*" buffers once no batch is open -- may be freed when the device runs out of memory)
   if (!t->failed) {

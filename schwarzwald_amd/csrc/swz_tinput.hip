@@ -1,0 +1,706 @@
+// swz_tinput.hip -- a data set of uncompressed LAS files read in one call (swz_tiler_add_las_files), the input side of
+// swz_toutput.hip: the headers are scanned on the host (swz_las_scan_files: what TilerProcess::prepare and
+// calculate_dataset_metadata do, core/process/TilerProcess.cpp:250-390), the concatenated files are cut into batches
+// (swz_input_batches), and while batch k is tiled the reader threads pread the raw records of batch k + 1 into a page-locked
+// buffer, the tiler's copy stream moves them to the device and ONE kernel decodes them straight into the pool rows of the
+// batch (swz_las_decode_segments_device's kernel).
+//
+// The kernel.  A batch is a run of points of the concatenated files, so its raw image holds SEGMENTS: records of several
+// files, each with its own scale, offset, box, point format and record length, one behind the other.  The point data of a
+// file starts at byte 227, 235 or 375 plus its VLRs and record lengths with extra bytes are odd, so neither a segment nor a
+// record is 4-byte aligned.  One workgroup takes LASIN_TILE consecutive output rows, whatever segments they belong to:
+// it finds the segment of its first row with one binary search in the table, puts the first rows of the LASIN_TILE segments
+// from there on into LDS (a tile of one-point files spans that many), and every lane finds its own segment there.  The byte
+// range the tile's records cover is loaded into LDS as the aligned dwords that cover it, consecutive lanes consecutive
+// dwords; a dword that does not lie wholly inside [raw, raw + raw_bytes) is put together from the bytes that do.  The
+// records are then unpacked at byte granularity from LDS (las_unpack, swz_lasrec.h).  A tile whose range is longer than the
+// stage -- records of more than LASIN_MAX_RECORD bytes, or segments that do not lie back to back -- reads its records
+// directly.
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <cerrno>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "swz_tiler.h"
+#include "swz_hostio.h"
+#include "swz_lasrec.h"
+
+namespace swz {
+
+constexpr uint32_t LASIN_TILE = 256;                             // output rows per workgroup, one per thread
+constexpr uint32_t LASIN_MAX_RECORD = 96;                        // a tile of records up to this length is staged
+constexpr uint32_t LASIN_STAGE = LASIN_TILE * LASIN_MAX_RECORD;  // bytes of LDS the records pass through
+constexpr uint64_t LASIN_MAX_POINTS = 0xFFFFFFFFull - 65535ull;  // the library's limit of points per batch (2^32 - 65536)
+constexpr uint64_t INPUT_BATCH_POINTS = 10000000;                // --internal-cache-size, executable/main.cpp:233-236
+constexpr uint64_t READ_PIECE = 8ull << 20;                      // bytes one reader thread takes at a time
+constexpr uint32_t LAS_MASK_ALWAYS =
+  (1u << SWZ_ATTR_INTENSITY) | (1u << SWZ_ATTR_CLASSIFICATION) | (1u << SWZ_ATTR_EDGE_OF_FLIGHT_LINE) |
+  (1u << SWZ_ATTR_NUMBER_OF_RETURNS) | (1u << SWZ_ATTR_RETURN_NUMBER) | (1u << SWZ_ATTR_POINT_SOURCE_ID) |
+  (1u << SWZ_ATTR_SCAN_DIRECTION_FLAG) | (1u << SWZ_ATTR_SCAN_ANGLE_RANK) | (1u << SWZ_ATTR_USER_DATA);
+
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// ---------------------------------------------------------------------------------- the segment kernel
+struct LasSegArgs {
+  const uint8_t* raw;
+  uint64_t raw_bytes;
+  const swz_las_segment* segs;  // the segments that hold points; first_row ascends, every row belongs to exactly one
+  uint32_t num_segs;
+  uint32_t n;                   // rows
+  double* xyz;
+  void* col[SWZ_ATTR_COUNT];
+  bool shift;
+  double center[3];
+};
+
+__global__ __launch_bounds__(LASIN_TILE) void las_segments_kernel(LasSegArgs a) {
+  __shared__ uint32_t s_first[LASIN_TILE];  // first rows of the segments k0 .. k0 + LASIN_TILE - 1 (past the table: no row)
+  __shared__ unsigned long long s_lo, s_hi;  // the byte range of the tile's records in raw
+  __shared__ uint32_t s_stage[LASIN_STAGE / 4 + 2];
+  const uint32_t t = threadIdx.x;
+  const uint32_t r0 = blockIdx.x * LASIN_TILE;
+  const uint32_t r1 = (uint32_t)min((uint64_t)r0 + LASIN_TILE, (uint64_t)a.n);
+
+  // the segment of the tile's first row: the last one that begins at or before it (segment 0 begins at row 0)
+  uint32_t k0 = 0;
+  for (uint32_t hi = a.num_segs; hi - k0 > 1;) {
+    const uint32_t mid = k0 + (hi - k0) / 2;
+    if ((uint32_t)a.segs[mid].first_row <= r0) k0 = mid; else hi = mid;
+  }
+  s_first[t] = (k0 + t < a.num_segs) ? (uint32_t)a.segs[k0 + t].first_row : 0xFFFFFFFFu;
+  if (t == 0) {
+    s_lo = ~0ull;
+    s_hi = 0ull;
+  }
+  __syncthreads();
+
+  // this lane's row: its segment (every segment holds a point, so the tile's rows lie in the LASIN_TILE segments listed),
+  // its record, and the layout it is unpacked with
+  const uint32_t r = r0 + t;
+  const bool live = r < r1;
+  LasArgs la{};
+  uint64_t start = 0;
+  if (live) {
+    uint32_t e = 0;
+    for (uint32_t hi = LASIN_TILE; hi - e > 1;) {
+      const uint32_t mid = e + (hi - e) / 2;
+      if (s_first[mid] <= r) e = mid; else hi = mid;
+    }
+    const swz_las_segment* sg = a.segs + k0 + e;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      la.scale[k] = sg->layout.scale[k];
+      la.offset[k] = sg->layout.offset[k];
+      la.mn[k] = sg->layout.min[k];
+      la.mx[k] = sg->layout.max[k];
+      la.center[k] = a.center[k];
+    }
+    la.format = sg->layout.point_format;
+    la.record_bytes = sg->layout.record_bytes;
+    la.xyz = a.xyz;
+#pragma unroll
+    for (int k = 0; k < SWZ_ATTR_COUNT; ++k) la.col[k] = a.col[k];
+    la.shift = a.shift;
+    start = sg->byte_offset + (uint64_t)(r - s_first[e]) * la.record_bytes;
+    atomicMin(&s_lo, (unsigned long long)start);
+    atomicMax(&s_hi, (unsigned long long)(start + la.record_bytes));
+  }
+  __syncthreads();
+
+  // The covering aligned dwords of [s_lo, s_hi): alignment is that of the ADDRESS, raw itself may lie anywhere.
+  const uintptr_t raw_begin = (uintptr_t)a.raw, raw_end = raw_begin + a.raw_bytes;
+  const uintptr_t word0 = (raw_begin + (uintptr_t)s_lo) & ~(uintptr_t)3;
+  const uint64_t span = (raw_begin + (uintptr_t)s_hi) - word0;
+  if (span <= (uint64_t)LASIN_STAGE + 4u) {  // (block-uniform)
+    for (uint32_t w = t; 4ull * w < span; w += LASIN_TILE) {
+      const uintptr_t at = word0 + 4u * (uintptr_t)w;
+      uint32_t v;
+      if (at >= raw_begin && at + 4u <= raw_end) {
+        v = *reinterpret_cast<const uint32_t*>(at);
+      } else {  // the first or the last dword of the buffer: only the bytes inside it
+        v = 0;
+        for (uint32_t b = 0; b < 4u; ++b)
+          if (at + b >= raw_begin && at + b < raw_end) v |= (uint32_t)*reinterpret_cast<const uint8_t*>(at + b) << (8u * b);
+      }
+      s_stage[w] = v;
+    }
+    __syncthreads();
+    if (live) las_unpack(la, reinterpret_cast<const uint8_t*>(s_stage) + (size_t)((raw_begin + start) - word0), r);
+  } else if (live) {
+    las_unpack(la, a.raw + start, r);
+  }
+}
+
+// ---------------------------------------------------------------------------------- what the two entry points share
+// the segments that hold points, checked: rows contiguous from 0, records inside raw_bytes, formats and record lengths
+static int check_segments(swz_ctx* c, const char* who, uint64_t raw_bytes, uint64_t num_segments, const swz_las_segment* segments,
+                          std::vector<swz_las_segment>* kept, uint64_t* rows_out) {
+  auto refuse = [&](const std::string& what) { return c->fail(SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
+  if (num_segments && !segments) return refuse("NULL segments");
+  uint64_t rows = 0;
+  for (uint64_t s = 0; s < num_segments; ++s) {
+    const swz_las_segment& sg = segments[s];
+    if (sg.first_row != rows) return refuse("the rows of the segments must ascend contiguously from 0");
+    if (sg.layout.point_format > 10) return refuse("LAS point data record formats 0-10 are decoded");
+    if (sg.layout.record_bytes < las_format_bytes(sg.layout.point_format)) return refuse("record length shorter than the point format");
+    if (sg.count > LASIN_MAX_POINTS || rows + sg.count > LASIN_MAX_POINTS) return refuse("more than 2^32-65536 points");
+    if (sg.byte_offset > raw_bytes || sg.count > (raw_bytes - sg.byte_offset) / sg.layout.record_bytes)
+      return refuse("the records of a segment pass raw_bytes");
+    rows += sg.count;
+    if (sg.count) kept->push_back(sg);
+  }
+  *rows_out = rows;
+  return SWZ_OK;
+}
+
+static uint64_t decode_bytes(const std::vector<swz_las_segment>& segs, const double* d_xyz, const swz_attribute_columns* d_out,
+                             uint32_t mask) {
+  uint64_t row = d_xyz ? 24 : 0, bytes = 0;
+  for (int k = 0; k < SWZ_ATTR_COUNT; ++k)
+    if (k != SWZ_ATTR_NORMAL && ((mask >> k) & 1u) && d_out && d_out->column[k]) row += ATTR_BYTES[k];
+  for (const swz_las_segment& sg : segs) bytes += sg.count * (sg.layout.record_bytes + row);
+  return bytes;
+}
+
+// launches the kernel on `stream`; d_table holds num_segs checked segments with points.  No synchronisation.
+static int launch_segments(swz_ctx* c, hipStream_t stream, const uint8_t* d_raw, uint64_t raw_bytes, const swz_las_segment* d_table,
+                           uint32_t num_segs, uint32_t rows, const double* shift_center, double* d_xyz_out,
+                           const swz_attribute_columns* d_out, uint32_t mask) {
+  LasSegArgs a{};
+  a.raw = d_raw;
+  a.raw_bytes = raw_bytes;
+  a.segs = d_table;
+  a.num_segs = num_segs;
+  a.n = rows;
+  a.xyz = d_xyz_out;
+  for (int k = 0; k < SWZ_ATTR_COUNT; ++k)  // LAS points carry no normals
+    a.col[k] = (d_out && k != SWZ_ATTR_NORMAL && ((mask >> k) & 1u)) ? d_out->column[k] : nullptr;
+  a.shift = shift_center != nullptr;
+  for (int k = 0; k < 3; ++k) a.center[k] = shift_center ? shift_center[k] : 0.0;
+  hipLaunchKernelGGL(las_segments_kernel, dim3(div_up(rows, LASIN_TILE)), dim3(LASIN_TILE), 0, stream, a);
+  SWZ_LAUNCH_CHECK(c);
+  return SWZ_OK;
+}
+
+// ---------------------------------------------------------------------------------- the headers
+static uint32_t get_u16(const unsigned char* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
+static uint32_t get_u32(const unsigned char* p) { return get_u16(p) | (get_u16(p + 2) << 16); }
+static uint64_t get_u64(const unsigned char* p) { return (uint64_t)get_u32(p) | ((uint64_t)get_u32(p + 4) << 32); }
+static double get_f64(const unsigned char* p) {
+  double v;
+  memcpy(&v, p, 8);
+  return v;
+}
+
+// `bytes` bytes at `offset` of the file, all of them or an error
+static bool pread_all(int fd, void* dst, uint64_t bytes, uint64_t offset) {
+  unsigned char* out = static_cast<unsigned char*>(dst);
+  while (bytes) {
+    const ssize_t got = pread(fd, out, (size_t)std::min<uint64_t>(bytes, 1ull << 30), (off_t)offset);
+    if (got < 0 && errno == EINTR) continue;
+    if (got <= 0) return false;
+    out += got;
+    offset += (uint64_t)got;
+    bytes -= (uint64_t)got;
+  }
+  return true;
+}
+
+struct Fd {
+  int fd = -1;
+  ~Fd() {
+    if (fd >= 0) (void)close(fd);
+  }
+};
+
+// the public header block of one file (LAS 1.0 - 1.4); SWZ_LAS_FILE_* and, unless OK, the reason
+static int scan_one(const char* path, swz_las_file_info* info, std::string* why) {
+  *info = swz_las_file_info{};
+  Fd f;
+  f.fd = open(path, O_RDONLY | O_CLOEXEC);
+  struct stat st;
+  if (f.fd < 0 || fstat(f.fd, &st) != 0 || !S_ISREG(st.st_mode)) {
+    *why = "cannot open";
+    return SWZ_LAS_FILE_UNREADABLE;
+  }
+  const uint64_t size = (uint64_t)st.st_size;
+  unsigned char h[375];
+  const uint64_t have = std::min<uint64_t>(size, sizeof(h));
+  if (have < 227 || !pread_all(f.fd, h, have, 0)) {
+    *why = "shorter than a LAS header";
+    return SWZ_LAS_FILE_BAD_HEADER;
+  }
+  if (memcmp(h, "LASF", 4) != 0) {
+    *why = "not a LAS file (signature)";
+    return SWZ_LAS_FILE_BAD_HEADER;
+  }
+  const uint32_t major = h[24], minor = h[25];
+  const uint64_t header_size = get_u16(h + 94), data_at = get_u32(h + 96);
+  const uint64_t need = (major == 1 && minor >= 4) ? 375 : ((major == 1 && minor == 3) ? 235 : 227);
+  if (header_size < need || header_size > size) {
+    *why = "the header is shorter than its version's, or passes the file";
+    return SWZ_LAS_FILE_BAD_HEADER;
+  }
+  if (data_at < header_size || data_at > size) {
+    *why = "the offset to the point data passes the file";
+    return SWZ_LAS_FILE_BAD_HEADER;
+  }
+  const uint32_t format = h[104], rb = get_u16(h + 105);
+  if (format & 0x80u) {
+    *why = "compressed point data (LAZ is not read)";
+    return SWZ_LAS_FILE_COMPRESSED;
+  }
+  if (format > 10) {
+    *why = "point data record format above 10";
+    return SWZ_LAS_FILE_BAD_HEADER;
+  }
+  if (rb < las_format_bytes(format)) {
+    *why = "the record length is below the format's";
+    return SWZ_LAS_FILE_BAD_HEADER;
+  }
+  // the variable length records between the header and the point data: LASzip's marks a compressed file
+  uint64_t at = header_size;
+  for (uint32_t v = 0, num = get_u32(h + 100); v < num && at + 54 <= data_at; ++v) {
+    unsigned char vlr[54];
+    if (!pread_all(f.fd, vlr, sizeof(vlr), at)) break;
+    if (memcmp(vlr + 2, "laszip encoded", 14) == 0 && get_u16(vlr + 18) == 22204) {
+      *why = "a LASzip VLR (LAZ is not read)";
+      return SWZ_LAS_FILE_COMPRESSED;
+    }
+    at += 54 + (uint64_t)get_u16(vlr + 20);
+  }
+  uint64_t count = get_u32(h + 107);
+  if (major == 1 && minor >= 4 && (count == 0 || format >= 6)) count = get_u64(h + 247);
+  if (count > (size - data_at) / rb) {
+    *why = "the point records pass the end of the file";
+    return SWZ_LAS_FILE_BAD_HEADER;
+  }
+  info->point_count = count;
+  info->offset_to_point_data = data_at;
+  for (int k = 0; k < 3; ++k) {
+    info->layout.scale[k] = get_f64(h + 131 + 8 * k);
+    info->layout.offset[k] = get_f64(h + 155 + 8 * k);
+    info->layout.max[k] = get_f64(h + 179 + 16 * k);  // max x, min x, max y, min y, max z, min z
+    info->layout.min[k] = get_f64(h + 187 + 16 * k);
+  }
+  info->layout.point_format = format;
+  info->layout.record_bytes = rb;
+  // las_file_has_attribute (LASFile.cpp:415-445), as written
+  uint32_t mask = LAS_MASK_ALWAYS;
+  if (format == 2 || format == 3 || format == 5 || format == 7 || format == 8 || format == 10) mask |= 1u << SWZ_ATTR_RGB;
+  if (format == 1 || format == 3) mask |= 1u << SWZ_ATTR_GPS_TIME;
+  info->attribute_mask = mask;
+  return SWZ_LAS_FILE_OK;
+}
+
+// ---------------------------------------------------------------------------------- the streamed call
+// one piece of a batch's raw image: `bytes` bytes at `file_at` of file `file` to `image_at` of the image
+struct ReadPiece {
+  uint64_t file, file_at, bytes, image_at;
+};
+
+struct InputBatch {
+  uint64_t first_point = 0, points = 0;
+  uint64_t raw_bytes = 0, table_at = 0, image_bytes = 0;  // the image: the records back to back, then the segment table
+  std::vector<swz_las_segment> segs;
+  std::vector<ReadPiece> pieces;
+};
+
+// what a call holds besides the context's workspace; released however the call ends
+struct InputBuffers {
+  swz_ctx* c = nullptr;
+  void* host[2] = {nullptr, nullptr};
+  hipEvent_t begin[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr}, decoded[2] = {nullptr, nullptr};
+  ~InputBuffers() {
+    for (int b = 0; b < 2; ++b) {
+      if (host[b]) (void)hipHostFree(host[b]);
+      for (hipEvent_t e : {begin[b], copied[b], decoded[b]})
+        if (e) (void)hipEventDestroy(e);
+    }
+    // two raw batch images are the call's, not the data set's
+    for (const char* name : {"in_image0", "in_image1"}) {
+      const auto it = c->bufs.find(name);
+      if (it == c->bufs.end()) continue;
+      c->free_buf(it->second);
+      c->bufs.erase(it);
+    }
+  }
+};
+
+}  // namespace swz
+
+using namespace swz;
+
+extern "C" {
+
+uint32_t swz_las_input_tile(void) { return LASIN_TILE; }
+
+int swz_las_scan_files(swz_ctx* c, const char* const* paths, uint64_t num_files, uint32_t flags, swz_las_file_info* files_out,
+                       swz_las_dataset* dataset_out) {
+  if (!dataset_out || (num_files && !paths)) return fail(c, SWZ_ERR_BAD_ARG, "swz_las_scan_files: NULL argument");
+  if (flags & ~SWZ_LAS_SCAN_SKIP_UNREADABLE) return fail(c, SWZ_ERR_BAD_ARG, "swz_las_scan_files: unknown flag");
+  swz_las_dataset ds{};
+  ds.attribute_mask = LAS_MASK_ALWAYS | (1u << SWZ_ATTR_RGB) | (1u << SWZ_ATTR_GPS_TIME);
+  // AABB(): min = the largest double, max = its negative; update() takes std::min / std::max per axis (AABB.h:15-48)
+  for (int k = 0; k < 3; ++k) {
+    ds.tight_min[k] = std::numeric_limits<double>::max();
+    ds.tight_max[k] = -std::numeric_limits<double>::max();
+  }
+  for (uint64_t i = 0; i < num_files; ++i) {
+    if (!paths[i]) return fail(c, SWZ_ERR_BAD_ARG, "swz_las_scan_files: NULL path");
+    swz_las_file_info info;
+    std::string why;
+    const int status = scan_one(paths[i], &info, &why);
+    if (status != SWZ_LAS_FILE_OK) {
+      if (!(flags & SWZ_LAS_SCAN_SKIP_UNREADABLE)) return fail(c, SWZ_ERR_BAD_ARG, "swz_las_scan_files: " + why + ": " + paths[i]);
+      info = swz_las_file_info{};
+      info.status = status;
+      if (files_out) files_out[i] = info;
+      continue;
+    }
+    if (files_out) files_out[i] = info;
+    ds.total_points += info.point_count;
+    ++ds.readable_files;
+    ds.attribute_mask &= info.attribute_mask;
+    for (int k = 0; k < 3; ++k) {  // update(bounds.min), then update(bounds.max)
+      for (const double v : {info.layout.min[k], info.layout.max[k]}) {
+        ds.tight_min[k] = std::min(ds.tight_min[k], v);
+        ds.tight_max[k] = std::max(ds.tight_max[k], v);
+      }
+    }
+  }
+  if (ds.total_points == 0) return fail(c, SWZ_ERR_BAD_ARG, "swz_las_scan_files: Found no points to process");
+  // AABB::makeCubic (AABB.h:50-61) with getCenter = min + extent / 2 (:70)
+  double extent[3];
+  for (int k = 0; k < 3; ++k) extent[k] = ds.tight_max[k] - ds.tight_min[k];
+  const double max_extent = std::max(extent[0], std::max(extent[1], extent[2]));
+  const double half_length = max_extent / 2;
+  for (int k = 0; k < 3; ++k) {
+    const double center = ds.tight_min[k] + extent[k] / 2;
+    ds.cubic_min[k] = center - half_length;
+    ds.cubic_max[k] = center + half_length;
+  }
+  // total_bounds_cubic_at_origin (FileStats.cpp:30-37): minus the CUBIC box's centre
+  for (int k = 0; k < 3; ++k) {
+    ds.center[k] = ds.cubic_min[k] + (ds.cubic_max[k] - ds.cubic_min[k]) / 2;
+    ds.origin_min[k] = ds.cubic_min[k] - ds.center[k];
+    ds.origin_max[k] = ds.cubic_max[k] - ds.center[k];
+  }
+  *dataset_out = ds;
+  return SWZ_OK;
+}
+
+int swz_input_batches(uint64_t num_files, const uint64_t* file_count, uint64_t batch_points, uint64_t min_last, uint64_t max_batches,
+                      uint64_t* first_point_out, uint64_t* num_batches_out) {
+  if (!num_batches_out || (num_files && !file_count) || batch_points == 0) return SWZ_ERR_BAD_ARG;
+  uint64_t total = 0;
+  for (uint64_t i = 0; i < num_files; ++i) {
+    if (file_count[i] > ~0ull - total) return SWZ_ERR_BAD_ARG;
+    total += file_count[i];
+  }
+  if (total < min_last) return SWZ_ERR_BAD_ARG;
+  uint64_t batches = total / batch_points + (total % batch_points ? 1 : 0);
+  // OURS: a tail shorter than min_last joins the batch before it
+  if (batches > 1 && total - (batches - 1) * batch_points < min_last) --batches;
+  if (first_point_out) {
+    if (batches > max_batches) return SWZ_ERR_BAD_ARG;
+    for (uint64_t j = 0; j < batches; ++j) first_point_out[j] = j * batch_points;
+    first_point_out[batches] = total;
+  }
+  *num_batches_out = batches;
+  return SWZ_OK;
+}
+
+int swz_las_decode_segments_device(swz_ctx* c, const uint8_t* d_raw, uint64_t raw_bytes, uint64_t num_segments,
+                                   const swz_las_segment* segments, const double shift_center[3], double* d_xyz_out,
+                                   const swz_attribute_columns* d_out) {
+  if (!c) return SWZ_ERR_BAD_ARG;
+  SWZ_HIP(c, hipSetDevice(c->device));
+  // everything is checked on the host before anything is launched
+  std::vector<swz_las_segment> segs;
+  uint64_t rows = 0;
+  SWZ_TRY(check_segments(c, "swz_las_decode_segments_device", raw_bytes, num_segments, segments, &segs, &rows));
+  if (shift_center && !finite3(shift_center)) return c->fail(SWZ_ERR_BAD_ARG, "swz_las_decode_segments_device: the centre is not finite");
+  if (rows == 0) return SWZ_OK;
+  if (!d_raw) return c->fail(SWZ_ERR_BAD_ARG, "swz_las_decode_segments_device: NULL records");
+  swz_las_segment* d_table = nullptr;
+  SWZ_TRY(c->get("las_segments", segs.size(), &d_table));
+  SWZ_HIP(c, hipMemcpyAsync(d_table, segs.data(), segs.size() * sizeof(swz_las_segment), hipMemcpyHostToDevice, c->stream));
+  {
+    ProfScope ps(c, "las_decode_segments", decode_bytes(segs, d_xyz_out, d_out, ~0u), 1);
+    SWZ_TRY(launch_segments(c, c->stream, d_raw, raw_bytes, d_table, (uint32_t)segs.size(), (uint32_t)rows, shift_center, d_xyz_out, d_out,
+                            ~0u));
+  }
+  SWZ_HIP(c, hipStreamSynchronize(c->stream));  // (the table's host copy lives until here)
+  return SWZ_OK;
+}
+
+int swz_tiler_add_las_files(swz_tiler* t, const char* const* paths, uint64_t num_files, const swz_input_params* params,
+                            swz_input_stats* stats) {
+  if (!t) return SWZ_ERR_BAD_ARG;
+  swz_ctx* c = t->c;
+  const auto t_wall = std::chrono::steady_clock::now();
+  if (stats) *stats = swz_input_stats{};
+  SWZ_HIP(c, hipSetDevice(c->device));
+  SWZ_TRY(tiler_guard(t));
+  if (!params || (num_files && !paths)) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_add_las_files: NULL argument");
+  if (t->finalized) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler: batches cannot be added after finalize");
+  if (!t->staged_sizes.empty() || t->batch_open) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_add_las_files: a batch is staged or open");
+
+  // ---- the headers, and everything that is refused before a point is read
+  std::vector<swz_las_file_info> files(std::max<uint64_t>(num_files, 1));
+  swz_las_dataset ds{};
+  SWZ_TRY(swz_las_scan_files(c, paths, num_files, params->flags, files.data(), &ds));
+  const uint32_t mask = params->attribute_mask == ~0u ? ds.attribute_mask : params->attribute_mask;
+  if (mask & (1u << SWZ_ATTR_NORMAL)) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_add_las_files: LAS points carry no normals");
+  if (mask & ~ds.attribute_mask)
+    return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_add_las_files: the mask names an attribute that not every file has");
+  const bool first = t->staged_total == 0 && t->batches == 0;
+  if (!first && mask != t->attr_mask)
+    return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_add_las_files: every batch must carry the same attribute columns");
+  // The (shifted) tight box inside the root box.  AABB::makeCubic's own box can miss the tight box it was made from by an ulp
+  // of the coordinates (centre - half the extent need not round back to the minimum), so the comparison leaves that much
+  // room; the shift is taken in double.  A position that lies outside by such a rounding, or that the narrowing to float
+  // moves past the box, is clamped by the indexing, as in the reference.
+  const bool shift = params->shift_to_center != 0;
+  for (int k = 0; k < 3; ++k) {
+    const double lo = shift ? ds.tight_min[k] - ds.center[k] : ds.tight_min[k];
+    const double hi = shift ? ds.tight_max[k] - ds.center[k] : ds.tight_max[k];
+    const double size = std::max(std::max(std::fabs(ds.tight_min[k]), std::fabs(ds.tight_max[k])), std::fabs(ds.center[k]));
+    const double room = 4 * std::numeric_limits<double>::epsilon() * size;
+    if (!(t->bmin[k] - room <= lo && hi <= t->bmax[k] + room))
+      return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_add_las_files: the tiler's root box does not contain the data set's box");
+  }
+  if ((uint64_t)t->staged_total + ds.total_points > 0xFFFF0000ull)
+    return c->fail(SWZ_ERR_TOO_MANY_POINTS, "more than 2^32-65536 points per tiler");
+
+  // ---- the batches: their segments, the pieces the readers take, the size of their images
+  const uint64_t batch_points = params->batch_points ? params->batch_points : INPUT_BATCH_POINTS;
+  const uint64_t min_last = t->p.strategy == SWZ_FAST ? t->p.fast_concurrency : 0;
+  if (batch_points < min_last) return c->fail(SWZ_ERR_BAD_ARG, "FAST: a batch needs at least fast_concurrency points");
+  std::vector<uint64_t> counts(files.size());
+  for (uint64_t i = 0; i < num_files; ++i) counts[i] = files[i].point_count;
+  uint64_t num_batches = 0;
+  if (swz_input_batches(num_files, counts.data(), batch_points, min_last, 0, nullptr, &num_batches) != SWZ_OK)
+    return c->fail(SWZ_ERR_BAD_ARG, "FAST: a batch needs at least fast_concurrency points");
+  std::vector<uint64_t> cuts(num_batches + 1);
+  (void)swz_input_batches(num_files, counts.data(), batch_points, min_last, num_batches, cuts.data(), &num_batches);
+  std::vector<InputBatch> batches(num_batches);
+  uint64_t image_max = 0;
+  {
+    uint64_t file = 0, file_first = 0;  // the file the next point lies in, and the data set's point its first record is
+    for (uint64_t j = 0; j < num_batches; ++j) {
+      InputBatch& b = batches[j];
+      b.first_point = cuts[j];
+      b.points = cuts[j + 1] - cuts[j];
+      for (uint64_t p = cuts[j]; p < cuts[j + 1];) {
+        while (p >= file_first + counts[file]) file_first += counts[file++];
+        const swz_las_file_info& fi = files[file];
+        const uint64_t rec0 = p - file_first, cnt = std::min(cuts[j + 1], file_first + counts[file]) - p;
+        const uint64_t rb = fi.layout.record_bytes;
+        swz_las_segment sg{};
+        sg.first_row = p - cuts[j];
+        sg.count = cnt;
+        sg.byte_offset = b.raw_bytes;
+        sg.layout = fi.layout;
+        b.segs.push_back(sg);
+        for (uint64_t done = 0; done < cnt * rb; done += READ_PIECE)
+          b.pieces.push_back({file, fi.offset_to_point_data + rec0 * rb + done, std::min(READ_PIECE, cnt * rb - done), b.raw_bytes + done});
+        b.raw_bytes += cnt * rb;
+        p += cnt;
+      }
+      b.table_at = (b.raw_bytes + 15) & ~15ull;
+      b.image_bytes = b.table_at + b.segs.size() * sizeof(swz_las_segment);
+      image_max = std::max(image_max, b.image_bytes);
+    }
+  }
+
+  // ---- the pools, once for the total: nothing grows while a batch is in flight
+  const uint32_t mask_before = t->attr_mask;
+  auto reserve = [&]() -> int {
+    if (first) {
+      t->attr_mask = mask;
+      if (mask && t->pool_cap) {  // the pools were presized before the columns were known
+        const size_t cap = t->pool_cap;
+        t->pool_cap = 0;
+        t->pool_xyz = nullptr;
+        SWZ_TRY(pool_reserve(t, cap));
+      }
+    }
+    return pool_reserve(t, (size_t)t->staged_total + ds.total_points);
+  };
+  InputBuffers ib;
+  ib.c = c;
+  uint8_t* d_image[2] = {nullptr, nullptr};
+  auto prepare = [&]() -> int {
+    SWZ_TRY(reserve());
+    SWZ_TRY(c->get("in_image0", (size_t)image_max, &d_image[0]));
+    if (num_batches > 1) SWZ_TRY(c->get("in_image1", (size_t)image_max, &d_image[1]));
+    for (int b = 0; b < (num_batches > 1 ? 2 : 1); ++b) {
+      SWZ_HIP(c, hipHostMalloc(&ib.host[b], image_max, hipHostMallocDefault));
+      SWZ_HIP(c, hipEventCreate(&ib.begin[b]));
+      SWZ_HIP(c, hipEventCreate(&ib.copied[b]));
+      SWZ_HIP(c, hipEventCreate(&ib.decoded[b]));
+    }
+    return SWZ_OK;
+  };
+  {
+    const int st = prepare();
+    if (st != SWZ_OK) {
+      t->attr_mask = mask_before;
+      return st;
+    }
+  }
+
+  // ---- the stream.  Reads run two batches ahead of the tiling, copy + decode one: while batch k is tiled, batch k + 1 is
+  // copied and decoded on the copy stream and the readers fill the other host buffer with batch k + 2.
+  const long reader_threads =
+    std::max(1L, c->opt_int("SWZ_INPUT_READER_THREADS", (long)std::min(32u, std::max(1u, std::thread::hardware_concurrency()))));
+  double read_ms = 0, copy_ms = 0, decode_ms = 0, tile_ms = 0, wait_ms = 0;
+  uint64_t bytes_read = 0, batches_done = 0, points_done = 0;
+  int status = SWZ_OK;
+  std::string why;
+  TicketRun readers;
+  auto start_read = [&](uint64_t j) {
+    const InputBatch* b = &batches[j];
+    unsigned char* image = static_cast<unsigned char*>(ib.host[j & 1]);
+    memcpy(image + b->table_at, b->segs.data(), b->segs.size() * sizeof(swz_las_segment));
+    readers.start(c, b->pieces.size(), [b, image, paths](uint64_t i, std::string* err) {
+      const ReadPiece& p = b->pieces[i];
+      Fd f;
+      f.fd = open(paths[p.file], O_RDONLY | O_CLOEXEC);
+      if (f.fd < 0 || !pread_all(f.fd, image + p.image_at, p.bytes, p.file_at)) {
+        *err = std::string("swz_tiler_add_las_files: cannot read the point records of ") + paths[p.file];
+        return (int)SWZ_ERR_BAD_ARG;
+      }
+      return (int)SWZ_OK;
+    }, reader_threads);
+  };
+  // joins the readers of batch j; the time the call stood waiting for them counts as waiting for input
+  auto wait_read = [&](uint64_t j) -> bool {
+    const auto t0 = std::chrono::steady_clock::now();
+    double ms = 0;
+    std::string err;
+    const int st = readers.wait(&err, &ms);
+    wait_ms += ms_since(t0);
+    read_ms += ms;
+    if (st != SWZ_OK) {
+      status = st;
+      why = err;
+      return false;
+    }
+    bytes_read += batches[j].raw_bytes;
+    return true;
+  };
+  // batch j from its host buffer into the pool rows behind what is staged, on the copy stream; staged like a host batch
+  auto enqueue = [&](uint64_t j) -> int {
+    const InputBatch& b = batches[j];
+    const int s = (int)(j & 1);
+    const size_t at = t->staged_total;
+    SWZ_HIP(c, hipEventRecord(ib.begin[s], t->copy_stream));
+    SWZ_HIP(c, hipMemcpyAsync(d_image[s], ib.host[s], b.image_bytes, hipMemcpyHostToDevice, t->copy_stream));
+    SWZ_HIP(c, hipEventRecord(ib.copied[s], t->copy_stream));
+    swz_attribute_columns rows{};
+    for (int a = 0; a < SWZ_ATTR_COUNT; ++a)
+      rows.column[a] = (t->attr_mask & (1u << a)) ? (void*)((char*)t->pool_attr[a] + at * TILER_ATTR_BYTES[a]) : nullptr;
+    SWZ_TRY(launch_segments(c, t->copy_stream, d_image[s], b.raw_bytes, reinterpret_cast<const swz_las_segment*>(d_image[s] + b.table_at),
+                            (uint32_t)b.segs.size(), (uint32_t)b.points, shift ? ds.center : nullptr, t->pool_xyz + at * 3, &rows,
+                            t->attr_mask));
+    SWZ_HIP(c, hipEventRecord(ib.decoded[s], t->copy_stream));
+    hipEvent_t ev = nullptr;
+    SWZ_HIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    const hipError_t e = hipEventRecord(ev, t->copy_stream);
+    if (e != hipSuccess) {
+      (void)hipEventDestroy(ev);
+      return c->hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
+    }
+    t->staged_events.push_back(ev);
+    t->staged_sizes.push_back((uint32_t)b.points);
+    t->staged_total += (uint32_t)b.points;
+    t->staged_bytes += b.image_bytes;
+    return SWZ_OK;
+  };
+  // a failure once a batch has been staged: the pools are ahead of the ids, the store may be half merged
+  bool touched = false;
+  auto fail_stream = [&](int st, const std::string& text) {
+    if (status == SWZ_OK) {
+      status = st;
+      why = text;
+    }
+  };
+
+  start_read(0);
+  if (wait_read(0)) {
+    touched = true;
+    const int st = enqueue(0);
+    if (st != SWZ_OK) fail_stream(st, c->err);
+    if (status == SWZ_OK && num_batches > 1) start_read(1);
+  }
+  for (uint64_t j = 0; j < num_batches && status == SWZ_OK; ++j) {
+    bool next_staged = false;
+    if (j + 1 < num_batches) {
+      if (wait_read(j + 1)) {
+        const int st = enqueue(j + 1);
+        if (st != SWZ_OK) fail_stream(st, c->err);
+        next_staged = st == SWZ_OK;
+      }
+      // (a read that failed: batch j, which is staged, is still tiled -- the stream stops after the running batch)
+      if (next_staged && j + 2 < num_batches) {
+        // the host buffer of batch j + 2 is batch j's: its copy has left it
+        const hipError_t e = hipEventSynchronize(ib.copied[j & 1]);
+        if (e != hipSuccess) fail_stream(c->hip_fail(e, "the copy of a batch image", __FILE__, __LINE__), c->err);
+        else start_read(j + 2);
+      }
+    }
+    const double waited_before = t->staged_wait_ms;
+    const auto t_tile = std::chrono::steady_clock::now();
+    const int st = swz_tiler_tile_staged(t, nullptr);
+    const double waited = t->staged_wait_ms - waited_before;
+    tile_ms += ms_since(t_tile) - waited;
+    wait_ms += waited;
+    if (st != SWZ_OK) {
+      status = st;  // (the tiler's own failure comes first: it is poisoned with that text)
+      why = c->err;
+      break;
+    }
+    float ms = 0.f;  // batch j has been decoded: tile_staged waited for the event behind it
+    if (hipEventElapsedTime(&ms, ib.begin[j & 1], ib.copied[j & 1]) == hipSuccess) copy_ms += ms;
+    if (hipEventElapsedTime(&ms, ib.copied[j & 1], ib.decoded[j & 1]) == hipSuccess) decode_ms += ms;
+    ++batches_done;
+    points_done += batches[j].points;
+  }
+  if (readers.running()) (void)readers.wait(nullptr, nullptr);
+  (void)hipStreamSynchronize(t->copy_stream);
+  if (status != SWZ_OK) {
+    if (touched) {
+      (void)swz_tiler_poison(t, why.c_str());
+    } else {
+      t->attr_mask = mask_before;
+    }
+  }
+  if (stats) {
+    stats->files = ds.readable_files;
+    stats->points = points_done;
+    stats->batches = batches_done;
+    stats->bytes_read = bytes_read;
+    stats->read_ms = read_ms;
+    stats->copy_ms = copy_ms;
+    stats->decode_ms = decode_ms;
+    stats->tile_ms = tile_ms;
+    stats->wait_ms = wait_ms;
+    stats->wall_ms = ms_since(t_wall);
+  }
+  return status == SWZ_OK ? SWZ_OK : c->fail(status, why);
+}
+
+}  // extern "C"

@@ -16,7 +16,7 @@
 //   sample_points                    Sampling.h:799-821       sample_points (returns the partition point)
 //   TilerMetaParameters              process/Tiler.h:64-75    TilerMetaParameters
 //   PointsPersistence::persist_points io/PointsPersistence.h  PointsSink::persist_points
-//   TilingAlgorithmBase              TilingAlgorithms.h:70    TilingAlgorithmGPU::tile_batch / finalize / write_output
+//   TilingAlgorithmBase              TilingAlgorithms.h:70    TilingAlgorithmGPU::tile_batch / add_las_files / finalize / write_output
 //   get_octant_bounds                OctreeAlgorithms.cpp:3   get_octant_bounds
 //
 // Errors: every failing ABI call becomes std::runtime_error carrying swz_last_error(), the way the
@@ -408,7 +408,35 @@ public:
     return stats;
   }
 
+  // A data set of uncompressed LAS files, read by the library in one call (swz_tiler_add_las_files): headers scanned, files
+  // cut into batches of params.batch_points points, raw records read by reader threads, copied and decoded on the device
+  // straight into the tiler's pools, every batch tiled while the next is read -- what replaces MultiReaderPointSource and
+  // the tile_batch loop for files that need neither a PROJ transformation nor LASzip.  bounds: the octree's root bounds,
+  // the data set's cubic box (swz_las_scan_files), or that box at the origin with params.shift_to_center.
+  swz_input_stats add_las_files(const std::vector<std::string>& paths, const AABB& bounds, const swz_input_params& params) {
+    if (_finalized || _tiler_finalized) throw std::runtime_error{"TilingAlgorithmGPU: add_las_files after finalize"};
+    open_tiler(bounds);
+    std::vector<const char*> names;
+    for (const std::string& p : paths) names.push_back(p.c_str());
+    swz_input_stats stats{};
+    _ctx.check(swz_tiler_add_las_files(_tiler, names.data(), names.size(), &params, &stats));
+    return stats;
+  }
+
 private:
+  void open_tiler(const AABB& bounds) {
+    if (_tiler) return;
+    swz_tile_params p{};
+    p.sampler = _sampling_strategy.kind;
+    p.max_points_per_node = _sampling_strategy.max_points_per_node;
+    p.spacing_at_root = _meta.spacing_at_root;
+    p.max_depth = _meta.max_depth;
+    p.strategy = _meta.tiling_strategy == TilingStrategy::Fast ? SWZ_FAST : SWZ_ACCURATE;
+    p.fast_concurrency = _meta.num_indexing_threads;
+    const double mn[3] = {bounds.min.x, bounds.min.y, bounds.min.z}, mx[3] = {bounds.max.x, bounds.max.y, bounds.max.z};
+    _ctx.check(swz_tiler_create(_ctx.get(), mn, mx, &p, 0, &_tiler));
+    _bounds = bounds;
+  }
   void finalize_tiler() {
     if (_tiler_finalized) return;
     swz_tile_stats stats{};
@@ -417,18 +445,7 @@ private:
   }
   swz_tile_stats tile_batch(const double* positions, const swz_attribute_columns* attributes, size_t n, const AABB& bounds) {
     if (_finalized || _tiler_finalized) throw std::runtime_error{"TilingAlgorithmGPU: tile_batch after finalize"};
-    if (!_tiler) {
-      swz_tile_params p{};
-      p.sampler = _sampling_strategy.kind;
-      p.max_points_per_node = _sampling_strategy.max_points_per_node;
-      p.spacing_at_root = _meta.spacing_at_root;
-      p.max_depth = _meta.max_depth;
-      p.strategy = _meta.tiling_strategy == TilingStrategy::Fast ? SWZ_FAST : SWZ_ACCURATE;
-      p.fast_concurrency = _meta.num_indexing_threads;
-      const double mn[3] = {bounds.min.x, bounds.min.y, bounds.min.z}, mx[3] = {bounds.max.x, bounds.max.y, bounds.max.z};
-      _ctx.check(swz_tiler_create(_ctx.get(), mn, mx, &p, 0, &_tiler));
-      _bounds = bounds;
-    }
+    open_tiler(bounds);
     swz_tile_stats stats{};
     _ctx.check(swz_tiler_add_batch(_tiler, positions, n, attributes, &stats));
     return stats;
