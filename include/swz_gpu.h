@@ -89,7 +89,9 @@ int swz_set_stream(swz_ctx* ctx, void* hip_stream);
  *   exact), SWZ_GROUP_JOINT_ROOT=0; how the key sweep numbers its cells: SWZ_MD_DIRECT (1: by their place in the grid
  *   whatever the occupancy, 0: always the occupied cells compacted), SWZ_MD_DIRECT_MIN_OCCUPANCY (0.5: the estimated share of
  *   occupied grid cells from which a level is numbered directly), SWZ_MD_DIRECT_MAX_CELLS (the largest grid that is numbered
- *   directly; default: what fits the free device memory);
+ *   directly; default: what fits the free device memory); chains of dense levels that share one active set:
+ *   SWZ_MD_DEFER=0 (every level compacts its survivors, as the other paths do), SWZ_MD_DEFER_MAX_GONE (1/8: the share of
+ *   taken points in the shared arrays from which a chain ends);
  *   the frontier sweeps: SWZ_MD_PATIENT, SWZ_MD_LAZY, SWZ_MD_LAZY_FRAC, SWZ_MD_BIG, SWZ_MD_GROUPS, SWZ_MD_GRID,
  *   SWZ_MD_NBR_GRID, SWZ_MD_BATCH, SWZ_MD_COARSEN, SWZ_MD_COARSEN_MIN, SWZ_MD_FF_MIN, SWZ_MD_NO_DEAD_TEST=1 (blocker scans
  *   without the dead-point test), SWZ_MD_CHAIN, SWZ_MD_KEYS_RG, SWZ_MD_DENSE_MIN;

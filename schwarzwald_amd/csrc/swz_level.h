@@ -21,6 +21,7 @@ enum {
   CTR_REMAINING = 4,     // points handed to the next level
   CTR_NUM_CELLS = 5,     // MIN_DISTANCE: cells
   CTR_DONE_CELLS = 6,    // MIN_DISTANCE: cells finished
+  CTR_LIVE_NODES = 7,    // a level that shares its arrays with the level above (ActiveSet::gone): nodes that hold an open point
   CTR_Q0 = 8,            // MIN_DISTANCE: three rotating queue counters
   // MIN_DISTANCE sweep, builds with -DSWZ_MD_STATS only (printed with SWZ_DEBUG=1): timings of a sample of the
   // activations in 10 ns ticks
@@ -57,6 +58,18 @@ struct ActiveSet {
   // instead of by a scan over all points (level_step; null: scan)
   const uint64_t* parent_prefix = nullptr;
   uint32_t parents = 0;
+  // A chain of dense exact-MIN_DISTANCE levels shares one active set (level_step, LevelChain): the level above did not
+  // compact its survivors, akey / aidx / m are still its arrays.  gone[i] == 0: point i is open; gone[i] == k: it was taken
+  // at level k - 2 (the root is level -1: code 1).  live: the open points; gone_tiles[t]: the open points before tile t of
+  // FS_TILE points (live_before).  Null and m: every point is open, as everywhere outside a chain.
+  const uint8_t* gone = nullptr;
+  const uint32_t* gone_tiles = nullptr;
+  uint32_t live = 0;
+};
+// what the host decided about the chain a level belongs to (swz_session.hip decides, once, for every level)
+struct LevelChain {
+  bool may_defer = false;   // this level may leave its survivors where they are (the static conditions and the next level's plan hold)
+  double max_gone = 0.125;  // ... while the share of taken points in the shared arrays stays below this
 };
 
 struct SortedPoints {
@@ -111,6 +124,9 @@ struct LevelPlan {
   uint32_t jitter_start = 0; // (3 * (level + 1)) % 16
   // MIN_DISTANCE
   double sq_spacing = 0.0;   // (double)((float)spacing_node * (float)spacing_node)
+  // what a taken point's byte in LevelBuffers::taken receives from the key sweep and from take-all nodes: 1, or -- a level
+  // that may start or continue a chain of levels on one active set -- level + 2 (ActiveSet::gone)
+  uint8_t take_code = 1;
   int cell_levels_geo = 0;   // finest cell subdivision (levels below the node) whose cells are >= spacing
 };
 
@@ -127,6 +143,11 @@ struct LevelResult {
   uint32_t remaining = 0;
   uint32_t num_nodes = 0;
   uint32_t md_rounds = 0;
+  uint32_t table_nodes = 0;   // entries of the node table (num_nodes, plus -- inside a chain -- the nodes without an open point)
+  bool md_keys_direct = false; // the key sweep with direct numbering sampled the level
+  bool deferred = false;      // the survivors stayed where they are: lb.taken is the next level's ActiveSet::gone
+  const uint32_t* gone_tiles = nullptr;  // ... and its gone_tiles
+  bool needs_flush = false;   // a level inside a chain that the key sweep cannot take: nothing was decided, compact and call again
   // the key prefixes of the level's nodes, ascending (device; only when the step compacted survivors: for the next
   // level's ActiveSet::parent_prefix).  Valid until the step after the next one on this context.
   const uint64_t* node_prefix = nullptr;
@@ -141,8 +162,13 @@ int alloc_level_buffers(swz_ctx* c, uint32_t m, LevelBuffers* lb);
 int required_depth_host(int sampler, int node_level, double root_extent_x, float root_max_spacing);
 // Samples every node of the level.  When okey/oidx are given the survivors are compacted into them and level_out
 // receives plan.level for the taken points; otherwise only lb.taken is produced.
+// chain: the level may leave the survivors in place (res->deferred) when the key sweep sampled it; a level that receives
+// such arrays (as.gone) either samples them as they are or asks for the compaction (res->needs_flush).
 int level_step(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp, const LevelBuffers& lb,
-               int8_t* level_out, uint64_t* okey, uint32_t* oidx, LevelResult* res);
+               int8_t* level_out, uint64_t* okey, uint32_t* oidx, LevelResult* res, const LevelChain* chain = nullptr);
+// the compaction that ends a chain: the open points of as into okey / oidx, level_out = code - 2 for the others
+int level_flush_chain(swz_ctx* c, const ActiveSet& as, const LevelBuffers& lb, int8_t* level_out, uint64_t* okey, uint32_t* oidx,
+                      uint32_t* remaining);
 // what a kernel of the level raised in CTR_ERROR, in words
 const char* level_error_message(int code);
 // estimate_start_node_level_in_octree (TilingAlgorithms.cpp:1473-1535) of a sorted batch
@@ -163,9 +189,11 @@ bool grid_level_uses_keys(const swz_ctx* c, const LevelPlan& plan, const SortedP
 // MIN_DISTANCE for one level, exact or (plan.md_property) in property mode; fills lb.taken for the points of
 // MODE_SAMPLE nodes (take-all points are flagged by the caller).  rounds_out accumulates the dependency rounds or
 // phases executed.  swz_md.hip decides which algorithm samples the level.
+// keys_direct (may be null): the key sweep with direct numbering took the level.  Inside a chain (as.gone) no other
+// algorithm may: *needs_flush then says that the level was left untouched.
 int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp,
                        const LevelBuffers& lb, uint32_t num_nodes, uint32_t sample_nodes,
-                       uint32_t sample_points, uint32_t* rounds_out);
+                       uint32_t sample_points, uint32_t* rounds_out, bool* keys_direct = nullptr, bool* needs_flush = nullptr);
 // MIN_DISTANCE_FAST on a level whose stride is above one (swz_mdfast.hip): the candidates -- every stride-th point of every
 // MODE_SAMPLE node, counted from the node's first -- as an active set of their own through min_distance_level, the decisions
 // scattered back into lb.taken (zero for the points of sampled nodes on entry).

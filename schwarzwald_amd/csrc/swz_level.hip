@@ -185,17 +185,73 @@ __global__ __launch_bounds__(256) void node_finish_kernel(const uint32_t* __rest
   if (i == m - 1) nstart[id + 1] = m;
 }
 
+// ---- a level that shares its arrays with the level above (ActiveSet::gone): the open points before point i, from the
+// open points before i's tile of FS_TILE (level_live_counts) and the bytes of that tile in front of i
+__device__ __forceinline__ uint32_t live_before(const uint8_t* __restrict__ gone, const uint32_t* __restrict__ tiles, uint32_t i) {
+  uint32_t off = i & ~(uint32_t)(FS_TILE - 1);
+  uint32_t cnt = tiles[i / (uint32_t)FS_TILE];  // (i == m on a tile boundary reads the total behind the last tile)
+  for (; off + 16u <= i; off += 16u) {
+    const uint4 v = *reinterpret_cast<const uint4*>(gone + off);
+    cnt += fs_zero_bytes(v.x) + fs_zero_bytes(v.y) + fs_zero_bytes(v.z) + fs_zero_bytes(v.w);
+  }
+  for (; off < i; ++off) cnt += gone[off] == 0 ? 1u : 0u;
+  return cnt;
+}
+// tiles[t] = open points before tile t, tiles[tiles of m] = *live = all of them: one pass over the bytes
+static int level_live_counts(swz_ctx* c, const uint8_t* gone, uint32_t m, const uint32_t** tiles_out, uint32_t* live) {
+  ProfScope ps(c, "level_live_count", (uint64_t)m, 1);
+  const uint32_t nb = div_up(m, FS_TILE);
+  uint32_t* tiles = nullptr;
+  SWZ_TRY(c->get("lvl_gone_tiles", (size_t)nb + 1, &tiles));
+  hipLaunchKernelGGL(fscan_partial_zero_bytes_kernel, dim3(div_up(nb, (uint32_t)(FS_THREADS / 32))), dim3(FS_THREADS), 0, c->stream, gone,
+                     m, nb, tiles);
+  SWZ_LAUNCH_CHECK(c);
+  SWZ_TRY(scan_exclusive_u32(c, tiles, tiles, nb, tiles + nb, "gone"));
+  SWZ_TRY(read_u32(c, tiles + nb, live));
+  *tiles_out = tiles;
+  return SWZ_OK;
+}
+// the compaction that ends a chain: every taken point gets the level its code stands for
+struct CompactCodedG {
+  const uint64_t* akey;
+  const uint32_t* aidx;
+  const uint8_t* gone;
+  int8_t* level_out;
+  uint64_t* okey;
+  uint32_t* oidx;
+  __device__ void operator()(uint32_t i, uint32_t excl, uint32_t keep) const {
+    const uint32_t p = aidx ? aidx[i] : i;
+    if (keep) {
+      okey[excl] = akey[i];
+      oidx[excl] = p;
+    } else {
+      level_out[p] = (int8_t)((int)gone[i] - 2);
+    }
+  }
+};
+
 // tile_node / tile_internal_node decisions per node: terminal nodes and nodes with <= max_points
 // points (SamplingBehaviour::TakeAllWhenCountBelowMaxPoints, Sampling.h:201-208) keep everything.
 __global__ __launch_bounds__(256) void node_mode_kernel(const uint32_t* __restrict__ nstart,
                                                         uint8_t* __restrict__ nmode, uint32_t* __restrict__ counters,
                                                         uint64_t max_points, int force_sample, int terminal,
                                                         int reroot, const uint64_t* __restrict__ akey, uint32_t nsh,
-                                                        const uint64_t* __restrict__ ckey, uint32_t nc) {
+                                                        const uint64_t* __restrict__ ckey, uint32_t nc,
+                                                        const uint8_t* __restrict__ gone, const uint32_t* __restrict__ gone_tiles) {
   // grid-stride over the nodes: their number is only known on the device, and it is small next to the points
   const uint32_t nnodes = counters[CTR_NUM_NODES];
   for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < nnodes; j += gridDim.x * 256u) {
-    const uint32_t cnt = nstart[j + 1] - nstart[j];
+    uint32_t cnt = nstart[j + 1] - nstart[j];
+    if (gone) {
+      // the arrays still hold the points taken further up: a node is what it holds of OPEN points, and one that holds none
+      // does not exist -- its entry stays in the table as a take-all node with nothing to take and is counted nowhere
+      cnt = live_before(gone, gone_tiles, nstart[j + 1]) - live_before(gone, gone_tiles, nstart[j]);
+      if (cnt == 0u) {
+        nmode[j] = MODE_TAKE_ALL;
+        continue;
+      }
+      atomicAdd(&counters[CTR_LIVE_NODES], 1u);
+    }
     bool cached = false;  // previously_taken_points_count > 0 (TilingAlgorithms.cpp:272-275)
     if (nc) {
       const uint64_t prefix = akey[nstart[j]] >> nsh;
@@ -219,10 +275,11 @@ __global__ __launch_bounds__(256) void node_mode_kernel(const uint32_t* __restri
 // MIN_DISTANCE: the points of take-all nodes (the grid samplers flag them in their own pass)
 __global__ __launch_bounds__(256) void take_all_kernel(uint32_t m, const uint32_t* __restrict__ nid,
                                                        const uint8_t* __restrict__ nmode,
-                                                       uint8_t* __restrict__ taken) {
+                                                       uint8_t* __restrict__ taken, uint8_t code, int open_only) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= m) return;
-  if (nmode[nid[i]] == MODE_TAKE_ALL) taken[i] = 1;
+  // (open_only: the bytes of points taken further up hold those levels' codes, ActiveSet::gone)
+  if (nmode[nid[i]] == MODE_TAKE_ALL && !(open_only && taken[i])) taken[i] = code;
 }
 
 // ----------------------------------------------------------------------------- host: level plans
@@ -337,9 +394,16 @@ const char* level_error_message(int code) {
 // and level_out receives plan.level for the taken points; otherwise only lb.taken is produced.
 int level_step(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp,
                       const LevelBuffers& lb, int8_t* level_out, uint64_t* okey, uint32_t* oidx,
-                      LevelResult* res) {
+                      LevelResult* res, const LevelChain* chain) {
   const uint32_t m = as.m;
   const uint32_t nb = div_up(m, 256);
+  // inside a chain: lb.taken IS as.gone and holds the codes of the levels above
+  const bool shared = as.gone != nullptr;
+  if (shared && !(as.gone == lb.taken && as.gone_tiles && as.parent_prefix && as.parents && m > 0 && plan.node_shift < 63u &&
+                  plan.sampler == SWZ_MIN_DISTANCE && !plan.md_property && !as.ckey && okey && !c->opt("SWZ_LEVEL_NODES_SCAN"))) {
+    res->needs_flush = true;
+    return SWZ_OK;
+  }
   SWZ_HIP(c, hipMemsetAsync(lb.counters, 0, CTR_COUNT * sizeof(uint32_t), c->stream));
   {  // ---- segment the nodes
     ProfScope ps(c, "level_nodes", (uint64_t)m * 8ull, 3);
@@ -368,7 +432,7 @@ int level_step(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const Sor
     }
     hipLaunchKernelGGL(node_mode_kernel, dim3(std::min(nb, 2048u)), dim3(256), 0, c->stream, lb.nstart, lb.nmode, lb.counters,
                        plan.max_points, plan.force_sample ? 1 : 0, plan.terminal ? 1 : 0, plan.reroot ? 1 : 0, as.akey,
-                       plan.node_shift, as.ckey, as.nc);
+                       plan.node_shift, as.ckey, as.nc, as.gone, as.gone_tiles);
     SWZ_LAUNCH_CHECK(c);
     if (fill_after_modes) {  // the node id per point, from the node starts (MIN_DISTANCE reads it on every level)
       hipLaunchKernelGGL(node_fill_kernel, dim3(div_up(m, NF_TILE)), dim3(256), 0, c->stream, lb.nstart, lb.counters, m, lb.nid,
@@ -386,13 +450,16 @@ int level_step(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const Sor
     // AdaptivePoissonDiskSampling, Sampling.h:510-512: "just take the first point" of every sampled node, no sweep
     SWZ_TRY(random_grid_level(c, plan, as, lb));
   } else {  // MIN_DISTANCE; MIN_DISTANCE_FAST: the same on every n-th point of a node
-    SWZ_HIP(c, hipMemsetAsync(lb.taken, 0, m, c->stream));
+    if (!shared) SWZ_HIP(c, hipMemsetAsync(lb.taken, 0, m, c->stream));
     uint32_t h[CTR_COUNT];
     SWZ_HIP(c, hipMemcpyAsync(h, lb.counters, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     SWZ_HIP(c, hipStreamSynchronize(c->stream));
     if (h[CTR_ERROR]) return c->fail((int)h[CTR_ERROR], level_error_message((int)h[CTR_ERROR]));
-    if (h[CTR_SAMPLE_NODES] < h[CTR_NUM_NODES]) {  // only levels that have take-all nodes pay for the pass
-      hipLaunchKernelGGL(take_all_kernel, dim3(nb), dim3(256), 0, c->stream, m, lb.nid, lb.nmode, lb.taken);
+    // only levels that have take-all nodes pay for the pass
+    const bool take_all = h[CTR_SAMPLE_NODES] < (shared ? h[CTR_LIVE_NODES] : h[CTR_NUM_NODES]);
+    // (inside a chain after the sampler: it may still hand the level back untouched, and the two write disjoint nodes)
+    if (take_all && !shared) {
+      hipLaunchKernelGGL(take_all_kernel, dim3(nb), dim3(256), 0, c->stream, m, lb.nid, lb.nmode, lb.taken, plan.take_code, 0);
       SWZ_LAUNCH_CHECK(c);
     }
     const uint32_t stride = plan.sampler == SWZ_MIN_DISTANCE_FAST ? (uint32_t)swz_min_distance_fast_stride(plan.level) : 1u;
@@ -400,14 +467,32 @@ int level_step(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const Sor
       SWZ_TRY(min_distance_fast_level(c, plan, as, sp, lb, stride, h[CTR_NUM_NODES], h[CTR_SAMPLE_NODES], &res->md_rounds));
     } else if (h[CTR_SAMPLE_NODES] > 0) {
       SWZ_TRY(min_distance_level(c, plan, as, sp, lb, h[CTR_NUM_NODES], h[CTR_SAMPLE_NODES], h[CTR_SAMPLE_POINTS],
-                                 &res->md_rounds));
+                                 &res->md_rounds, &res->md_keys_direct, &res->needs_flush));
+      if (res->needs_flush) {
+        c->prof_collect();
+        return SWZ_OK;
+      }
+    }
+    if (take_all && shared) {
+      hipLaunchKernelGGL(take_all_kernel, dim3(nb), dim3(256), 0, c->stream, m, lb.nid, lb.nmode, lb.taken, plan.take_code, 1);
+      SWZ_LAUNCH_CHECK(c);
     }
   }
 
-  if (okey) {  // ---- compact
+  // ---- the survivors: left where they are for the next level of the chain (lb.taken becomes its ActiveSet::gone), or compacted
+  uint32_t live = 0;
+  if (okey && chain && chain->may_defer && res->md_keys_direct) {
+    SWZ_TRY(level_live_counts(c, lb.taken, m, &res->gone_tiles, &live));
+    res->deferred = live > 0u && (double)(m - live) < chain->max_gone * (double)m;
+  }
+  if (okey && !res->deferred) {
     ProfScope ps(c, "level_compact", (uint64_t)m * 14ull, 2);
-    SWZ_TRY(fused_scan(c, KeepF{lb.taken}, CompactG{as.akey, as.aidx, (int8_t)plan.level, level_out, okey, oidx}, m,
-                       lb.counters + CTR_REMAINING, "lvl"));
+    if (shared)  // every level of the chain at once
+      SWZ_TRY(fused_scan(c, KeepF{lb.taken}, CompactCodedG{as.akey, as.aidx, lb.taken, level_out, okey, oidx}, m,
+                         lb.counters + CTR_REMAINING, "lvl"));
+    else
+      SWZ_TRY(fused_scan(c, KeepF{lb.taken}, CompactG{as.akey, as.aidx, (int8_t)plan.level, level_out, okey, oidx}, m,
+                         lb.counters + CTR_REMAINING, "lvl"));
   }
   // ---- read the counters
   uint32_t h[CTR_COUNT];
@@ -418,19 +503,29 @@ int level_step(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const Sor
     const int code = (int)h[CTR_ERROR];
     return c->fail(code, level_error_message(code));
   }
-  res->remaining = h[CTR_REMAINING];
-  res->num_nodes = h[CTR_NUM_NODES];
+  res->remaining = res->deferred ? live : h[CTR_REMAINING];
+  res->num_nodes = shared ? h[CTR_LIVE_NODES] : h[CTR_NUM_NODES];
+  res->table_nodes = h[CTR_NUM_NODES];
   res->node_prefix = nullptr;
   // ---- publish the node prefixes
-  if (okey && res->remaining && res->num_nodes) {  // for the next level's segmentation (two buffers: the one of the level above is still read)
+  // (all entries of the table: the children of a node without an open point hold none either and drop out the same way)
+  if (okey && res->remaining && res->table_nodes) {  // for the next level's segmentation (two buffers: the one of the level above is still read)
     uint64_t* np = nullptr;
-    SWZ_TRY(c->get((plan.level & 1) ? "lvl_node_prefix_1" : "lvl_node_prefix_0", (size_t)res->num_nodes, &np));
-    hipLaunchKernelGGL(node_prefix_kernel, dim3(div_up(res->num_nodes, 256)), dim3(256), 0, c->stream, lb.nstart, as.akey,
-                       plan.node_shift, res->num_nodes, np);
+    SWZ_TRY(c->get((plan.level & 1) ? "lvl_node_prefix_1" : "lvl_node_prefix_0", (size_t)res->table_nodes, &np));
+    hipLaunchKernelGGL(node_prefix_kernel, dim3(div_up(res->table_nodes, 256)), dim3(256), 0, c->stream, lb.nstart, as.akey,
+                       plan.node_shift, res->table_nodes, np);
     SWZ_LAUNCH_CHECK(c);
     res->node_prefix = np;
   }
   return SWZ_OK;
+}
+
+int level_flush_chain(swz_ctx* c, const ActiveSet& as, const LevelBuffers& lb, int8_t* level_out, uint64_t* okey, uint32_t* oidx,
+                      uint32_t* remaining) {
+  ProfScope ps(c, "level_compact", (uint64_t)as.m * 14ull, 2);
+  SWZ_TRY(fused_scan(c, KeepF{as.gone}, CompactCodedG{as.akey, as.aidx, as.gone, level_out, okey, oidx}, as.m, lb.counters + CTR_REMAINING,
+                     "lvl"));
+  return read_u32(c, lb.counters + CTR_REMAINING, remaining);
 }
 
 int alloc_level_buffers(swz_ctx* c, uint32_t m, LevelBuffers* lb) {

@@ -89,8 +89,10 @@ int md_active_positions(swz_ctx* c, const MdLevel& L, size_t per_point, const do
 // Frontier sweep on key coordinates for a dense level (swz_mdkeys.hip); *used = false when the level does not qualify.
 // cl: cell levels below the node.  The points-weighted mean cell population at cl and the estimate of the occupied cells
 // at cl (it decides how the cells are numbered) come from the survey.
+// *direct (may be null): the cells were numbered by their place in the grid.  A level inside a chain (L.as.gone) is taken
+// with direct numbering or not at all.
 int min_distance_keys_level(swz_ctx* c, const MdLevel& L, int cl, uint32_t* rounds_out, bool* used,
-                            const MdShardRoot* shard_root = nullptr);
+                            const MdShardRoot* shard_root = nullptr, bool* direct = nullptr);
 // Sparse levels by blocks of 8^3 cells staged in LDS, blocks in Morton order, decisions in the same launch
 // (swz_mdblock.hip); *done = false: the level does not qualify or a block did not fit, nothing is lost.
 int min_distance_block_level(swz_ctx* c, const MdLevel& L, bool* done);

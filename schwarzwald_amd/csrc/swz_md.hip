@@ -243,7 +243,17 @@ static int phases_cell_levels(swz_ctx* c, MdLevel& L, int* cl_out) {
 
 // ----------------------------------------------------------------------------- the ladder
 int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, const SortedPoints& sp, const LevelBuffers& lb,
-                       uint32_t num_nodes, uint32_t sample_nodes, uint32_t sample_points, uint32_t* rounds_out) {
+                       uint32_t num_nodes, uint32_t sample_nodes, uint32_t sample_points, uint32_t* rounds_out, bool* keys_direct,
+                       bool* needs_flush) {
+  bool direct = false;
+  if (keys_direct) *keys_direct = false;
+  if (needs_flush) *needs_flush = false;
+  // A level inside a chain (as.gone: the arrays still hold the points taken further up, swz_level.h) is the key sweep's
+  // with direct numbering or nobody's: every other rung hands it back before anything is decided, and the caller compacts.
+  // (The survey counts the cells of those points as occupied -- a per cent or two of a dense level, in numbers that only
+  // steer the choice of cell size.)
+  const bool shared = as.gone != nullptr;
+  if (shared && !needs_flush) return c->fail(SWZ_ERR_INTERNAL, "MIN_DISTANCE: a level on shared arrays needs a caller that can compact them");
   c->next_scratch_epoch();  // what the level before asked for ("md_*", "sp_*", "pm_*") may go if memory runs out
   MdLevel L{plan, as, sp, lb, num_nodes, sample_nodes, sample_points, sample_nodes == num_nodes};
   SWZ_TRY(survey(c, L));
@@ -264,6 +274,10 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
   // (per occupied cell; a uniform level with 1.5 points per cell of volume has 1.93)
   const bool sparse = (double)sample_points / (double)std::max(1u, L.occupied[cl_sparse]) < c->opt_num("SWZ_MD_SPARSE_LIMIT", 2.0);
   // (not the root of a sharded batch with ghosts in front, decided on keys: the sweep looks up two position arrays, these paths one)
+  if (sparse && shared) {
+    *needs_flush = true;
+    return SWZ_OK;
+  }
   if (sparse && !(sp.ghosts && plan.level == -1 && !sp.X)) {
     // blocks of cells out of LDS, decisions in the same launch; levels it cannot take -- no key metric, a block that does
     // not fit its LDS capacity -- go on to one thread per point
@@ -296,8 +310,15 @@ int min_distance_level(swz_ctx* c, const LevelPlan& plan, const ActiveSet& as, c
   if (!plan.md_property || !sp.X) {
     SWZ_TRY(md_populations(c, L));
     cl = sweep_cell_levels(c, L);
-    SWZ_TRY(min_distance_keys_level(c, L, cl, rounds_out, &used));
-    if (used) return SWZ_OK;
+    SWZ_TRY(min_distance_keys_level(c, L, cl, rounds_out, &used, nullptr, &direct));
+    if (used) {
+      if (keys_direct) *keys_direct = direct;
+      return SWZ_OK;
+    }
+  }
+  if (shared) {
+    *needs_flush = true;
+    return SWZ_OK;
   }
 
   if (!sp.X) return c->fail(SWZ_ERR_INTERNAL, "MIN_DISTANCE: this level needs the positions in Morton order and they were not gathered");

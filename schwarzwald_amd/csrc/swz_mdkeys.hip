@@ -190,6 +190,11 @@ struct MqArgs {
   const uint32_t* dlist;  // the dense cells
   uint32_t* round_word;   // sharded root: the round this shard's sweep is in, for the shards that read its records
   MqPeers peers;
+  // build time, a level inside a chain of levels on one active set (ActiveSet::gone): a non-zero byte is a point taken
+  // further up -- it starts QS_DEAD: never accepted, rejects nobody, keeps nobody waiting --, and qpos already holds the
+  // key coordinates of these very keys
+  const uint8_t* gone;
+  uint32_t keep_qpos;
 };
 
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
@@ -352,18 +357,29 @@ __global__ __launch_bounds__(256) void mq_direct_build_kernel(MqArgs a, uint32_t
   }
   key[0] = i0 ? a.akey[i0 - 1u] : 0ull;
   key[5] = i0 + 4u < a.m ? a.akey[i0 + 4u] : 0ull;
+  if (!a.keep_qpos) {
 #pragma unroll
-  for (int j = 0; j < 4; ++j) q[j] = mq_pack(key[1 + j]);
+    for (int j = 0; j < 4; ++j) q[j] = mq_pack(key[1 + j]);
+  }
   if (n == 4u) {
-    ulonglong2 w0, w1;
-    w0.x = q[0], w0.y = q[1], w1.x = q[2], w1.y = q[3];
-    *reinterpret_cast<ulonglong2*>(a.qpos + i0) = w0;
-    *reinterpret_cast<ulonglong2*>(a.qpos + i0 + 2) = w1;
-    *reinterpret_cast<uint32_t*>(a.state + i0) = 0x01010101u * (uint32_t)QS_OPEN;
+    if (!a.keep_qpos) {
+      ulonglong2 w0, w1;
+      w0.x = q[0], w0.y = q[1], w1.x = q[2], w1.y = q[3];
+      *reinterpret_cast<ulonglong2*>(a.qpos + i0) = w0;
+      *reinterpret_cast<ulonglong2*>(a.qpos + i0 + 2) = w1;
+    }
+    uint32_t sw = 0x01010101u * (uint32_t)QS_OPEN;
+    if (a.gone) {
+      const uint32_t g = *reinterpret_cast<const uint32_t*>(a.gone + i0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if ((g >> (8 * j)) & 0xFFu) sw = (sw & ~(0xFFu << (8 * j))) | ((uint32_t)QS_DEAD << (8 * j));
+    }
+    *reinterpret_cast<uint32_t*>(a.state + i0) = sw;
   } else {
     for (uint32_t j = 0; j < n; ++j) {
-      a.qpos[i0 + j] = q[j];
-      a.state[i0 + j] = QS_OPEN;
+      if (!a.keep_qpos) a.qpos[i0 + j] = q[j];
+      a.state[i0 + j] = (a.gone && a.gone[i0 + j]) ? (uint8_t)QS_DEAD : (uint8_t)QS_OPEN;
     }
   }
 #pragma unroll
@@ -1323,6 +1339,27 @@ __global__ void mq_round_word_kernel(uint32_t* word, uint32_t value) {
   __hip_atomic_store(word, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// A level whose taken bytes carry a code (LevelPlan::take_code): the sweep's own stores went to the state bytes (MqArgs::taken
+// is the state array then, and 1 is QS_TAKEN), and this pass writes the level's code for every accepted point -- the bytes
+// of points taken further up stay what they are.  Four points per thread.
+__global__ __launch_bounds__(256) void mq_commit_kernel(const uint8_t* __restrict__ state, uint32_t m, uint8_t code, uint8_t* __restrict__ taken) {
+  const uint64_t i0 = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 4u;
+  if (i0 >= m) return;
+  if (m - i0 >= 4u) {
+    const uint32_t sw = *reinterpret_cast<const uint32_t*>(state + i0);
+    uint32_t hit = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (((sw >> (8 * j)) & 0xFFu) == (uint32_t)QS_TAKEN) hit |= 0xFFu << (8 * j);
+    if (!hit) return;
+    uint32_t* w = reinterpret_cast<uint32_t*>(taken + i0);
+    *w = (*w & ~hit) | ((0x01010101u * (uint32_t)code) & hit);
+  } else {
+    for (uint32_t j = 0; i0 + j < m; ++j)
+      if (state[i0 + j] == QS_TAKEN) taken[i0 + j] = code;
+  }
+}
+
 // after the last round: every cell must have reached its end (a protocol error would otherwise go unnoticed)
 __global__ __launch_bounds__(256) void mq_verify_kernel(MqArgs a, uint32_t ncells, uint32_t* __restrict__ open_cells) {
   const uint32_t c = blockIdx.x * 256 + threadIdx.x;
@@ -1342,8 +1379,10 @@ bool min_distance_level_uses_keys(const swz_ctx* c, const LevelPlan& plan, const
   return key_metric(c, plan, sp).ok;  // (property mode decides on keys as well: swz_mdrounds.hip, or the exact set)
 }
 
-int min_distance_keys_level(swz_ctx* c, const MdLevel& L, int cl, uint32_t* rounds_out, bool* used, const MdShardRoot* shard_root) {
+int min_distance_keys_level(swz_ctx* c, const MdLevel& L, int cl, uint32_t* rounds_out, bool* used, const MdShardRoot* shard_root,
+                            bool* direct_out) {
   *used = false;
+  if (direct_out) *direct_out = false;
   const LevelPlan& plan = L.plan;
   const ActiveSet& as = L.as;
   const SortedPoints& sp = L.sp;
@@ -1419,6 +1458,8 @@ int min_distance_keys_level(swz_ctx* c, const MdLevel& L, int cl, uint32_t* roun
     if (const char* f = c->opt("SWZ_MD_DIRECT")) direct = atoi(f) != 0;  // tests: 1 whatever the occupancy, 0 never
     a.direct = (direct && !sharded && grid_entries <= max_cells) ? 1u : 0u;
   }
+  if (as.gone && !a.direct) return SWZ_OK;  // (a level inside a chain: with direct numbering or not at all)
+  if (direct_out) *direct_out = a.direct != 0u;
   *used = true;
   uint32_t ncells = 0;  // entries of the per-cell arrays
   uint32_t* d_cell_sums = nullptr;
@@ -1441,6 +1482,14 @@ int min_distance_keys_level(swz_ctx* c, const MdLevel& L, int cl, uint32_t* roun
 
   SWZ_TRY(c->get(("md_qpos" + sfx).c_str(), (size_t)m, &a.qpos));
   SWZ_TRY(c->get(("md_qstate" + sfx).c_str(), (size_t)m, &a.state));
+  // the level's code for its taken points, where that is not the 1 the sweep stores: see mq_commit_kernel
+  const bool coded = as.gone != nullptr || plan.take_code != 1;
+  if (coded) a.taken = a.state;
+  a.gone = as.gone;
+  a.keep_qpos = (as.gone && c->mq_qpos_buf == a.qpos && c->mq_qpos_keys == as.akey && c->mq_qpos_m == m) ? 1u : 0u;
+  c->mq_qpos_buf = sharded ? nullptr : a.qpos;
+  c->mq_qpos_keys = as.akey;
+  c->mq_qpos_m = m;
   SWZ_TRY(c->get(("md_qovf" + sfx).c_str(), (size_t)m, &a.ovf));
   SWZ_TRY(c->get(("md_qcinfo" + sfx).c_str(), (size_t)ncells, &a.cinfo));
   if (!a.direct) {
@@ -1737,6 +1786,10 @@ int min_distance_keys_level(swz_ctx* c, const MdLevel& L, int cl, uint32_t* roun
                open_cells, ncells, plan.level, round - MQ_FIRST_ROUND, err ? "yes" : "no");
       return c->fail(SWZ_ERR_INTERNAL, msg);
     }
+  }
+  if (coded) {
+    hipLaunchKernelGGL(mq_commit_kernel, dim3(div_up(m, 1024)), dim3(256), 0, c->stream, a.state, m, plan.take_code, lb.taken);
+    SWZ_LAUNCH_CHECK(c);
   }
   if (rounds_out) *rounds_out += round - MQ_FIRST_ROUND;
   if (dbg) {

@@ -38,7 +38,9 @@ int session_prepare(swz_ctx* c, TileSession& t, double* d_xyz, uint32_t n, const
 // Runs the level loop from t.next_level while points remain and level <= last_level.
 // first_mode: -1 = decide per node from its count; 0/1 force take-all/sample for the FIRST level run
 // (sharded batches decide the root from the global point count).
-int session_run_levels(swz_ctx* c, TileSession& t, int last_level, int first_mode);
+// chains: dense exact-MIN_DISTANCE levels may share one active set instead of compacting after each (the single batch of
+// swz_tile* only: see session_run_levels for who defers).
+int session_run_levels(swz_ctx* c, TileSession& t, int last_level, int first_mode, bool chains = false);
 void session_stats(const TileSession& t, swz_tile_stats* stats);
 
 // FAST: is sorted point i a candidate of a reconstruct level?  Persisted at level S - 1 by a start node (child_bit == 0),

@@ -85,10 +85,26 @@ int session_prepare(swz_ctx* c, TileSession& t, double* d_xyz, uint32_t n, const
   return SWZ_OK;
 }
 
-int session_run_levels(swz_ctx* c, TileSession& t, int last_level, int first_mode) {
+// Who defers its compaction is decided here and nowhere else.  A level leaves its survivors where they are -- the next
+// level then runs on the same key / index arrays and gets the taken bytes as ActiveSet::gone -- when
+//   * the caller allows chains at all (the single batch of swz_tile*, ACCURATE), the sampler is MIN_DISTANCE in exact
+//     mode, nothing is sharded or forced, and SWZ_MD_DEFER is not 0;
+//   * the key sweep with direct numbering sampled this level (level_step reports it);
+//   * the next level is neither terminal nor re-rooted;
+//   * the taken points stay below SWZ_MD_DEFER_MAX_GONE of the shared arrays (1/8: beyond that the dead bytes every sweep
+//     steps over cost more than a quarter of the copy saved; reasoned, not measured).
+// Whether the key sweep takes the NEXT level as well is known only once that level has been surveyed: if it does not, the
+// level hands the arrays back untouched (LevelResult::needs_flush), the chain's one compaction runs and the level starts
+// again on the compacted arrays.
+int session_run_levels(swz_ctx* c, TileSession& t, int last_level, int first_mode, bool chains) {
   const uint64_t* pprefix = nullptr;
   uint32_t parents = 0;
-  for (int level = t.next_level; t.as.m > 0 && level <= last_level; ++level) {
+  const bool chain_static = chains && first_mode < 0 && t.params.sampler == SWZ_MIN_DISTANCE &&
+                            !(t.params.flags & SWZ_FLAG_MIN_DISTANCE_PROPERTY) && !t.sp.ghosts && !t.front && !c->shard &&
+                            !c->md_shard_root && c->opt_on("SWZ_MD_DEFER", true);
+  LevelChain chain;
+  chain.max_gone = c->opt_num("SWZ_MD_DEFER_MAX_GONE", 0.125);
+  for (int level = t.next_level; (t.as.gone ? t.as.live : t.as.m) > 0 && level <= last_level; ++level) {
     if (level > 20) return c->fail(SWZ_ERR_INTERNAL, "level loop ran past level 20");
     if (!t.key_buf[t.which]) {
       SWZ_TRY(c->get("active_keys_2", (size_t)t.as.m, &t.key_buf[t.which]));
@@ -97,6 +113,13 @@ int session_run_levels(swz_ctx* c, TileSession& t, int last_level, int first_mod
     LevelPlan plan = make_plan(level, t.params.sampler, t.params.max_points_per_node, t.params.spacing_at_root,
                                t.params.max_depth, t.bmin, t.bmax, false, true);
     plan.md_property = (t.params.flags & SWZ_FLAG_MIN_DISTANCE_PROPERTY) != 0;
+    chain.may_defer = false;
+    if (chain_static && level < 20) {
+      const LevelPlan next = make_plan(level + 1, t.params.sampler, t.params.max_points_per_node, t.params.spacing_at_root,
+                                       t.params.max_depth, t.bmin, t.bmax, false, true);
+      chain.may_defer = !plan.terminal && !plan.reroot && !next.terminal && !next.reroot;
+    }
+    if (chain.may_defer || t.as.gone) plan.take_code = (uint8_t)(level + 2);
     // (the root of a sharded batch spans the shards: it is sampled exactly -- the lower shards' samples as ghosts, or all
     // shards sweeping together -- which has the property a fortiori; the flag decides the levels below)
     if (first_mode >= 0 && level == t.next_level) plan.md_property = false;
@@ -111,18 +134,34 @@ int session_run_levels(swz_ctx* c, TileSession& t, int last_level, int first_mod
     LevelResult r;
     t.as.parent_prefix = pprefix;
     t.as.parents = pprefix ? parents : 0u;
-    SWZ_TRY(level_step(c, plan, t.as, t.sp, t.lb, t.level, t.key_buf[t.which], t.idx_buf[t.which], &r));
-    t.visited += t.as.m;
+    SWZ_TRY(level_step(c, plan, t.as, t.sp, t.lb, t.level, t.key_buf[t.which], t.idx_buf[t.which], &r, &chain));
+    if (r.needs_flush) {
+      // the chain ends in front of this level: its one compaction, then the level again on the survivors
+      if (!t.as.gone) return c->fail(SWZ_ERR_INTERNAL, "a level outside a chain asked for the chain's compaction");
+      uint32_t remaining = 0;
+      SWZ_TRY(level_flush_chain(c, t.as, t.lb, t.level, t.key_buf[t.which], t.idx_buf[t.which], &remaining));
+      t.as = ActiveSet{t.key_buf[t.which], t.idx_buf[t.which], remaining};
+      t.which ^= 1;
+      --level;
+      continue;
+    }
+    t.visited += t.as.gone ? t.as.live : t.as.m;
     t.nodes += r.num_nodes;
     t.rounds += r.md_rounds;
     t.max_level = level;
     ++t.nlevels;
-    t.as = ActiveSet{t.key_buf[t.which], t.idx_buf[t.which], r.remaining};
+    if (r.deferred) {  // the same arrays once more, with the taken bytes
+      t.as.gone = t.lb.taken;
+      t.as.gone_tiles = r.gone_tiles;
+      t.as.live = r.remaining;
+    } else {
+      t.as = ActiveSet{t.key_buf[t.which], t.idx_buf[t.which], r.remaining};
+      t.which ^= 1;
+    }
     // (the nodes of this level for the next one's segmentation -- inside this call only: between two calls of a sharded
     // batch other work of the context may reuse the buffer)
     pprefix = r.node_prefix;
-    parents = r.num_nodes;
-    t.which ^= 1;
+    parents = r.table_nodes;
     t.next_level = level + 1;
   }
   return SWZ_OK;
@@ -299,7 +338,7 @@ int tile_device(swz_ctx* c, double* d_xyz, uint32_t n, const double bmin[3], con
   TileSession t;
   SWZ_TRY(session_prepare(c, t, d_xyz, n, bmin, bmax, p, out));
   if (p.strategy == SWZ_ACCURATE) {
-    SWZ_TRY(session_run_levels(c, t, 20, -1));
+    SWZ_TRY(session_run_levels(c, t, 20, -1, true));
     session_stats(t, stats);
     return SWZ_OK;
   }
