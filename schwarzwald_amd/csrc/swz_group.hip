@@ -9,6 +9,13 @@
 // on demand so that nothing else depends on it) or peer copies (hipMemcpyPeerAsync), which also work with several
 // shards on one GPU -- that is how the shard logic is tested on a one-GPU box.  The Python driver (sharded.py) is the
 // multi-process counterpart used by bench.py.
+//
+// How the file reads: shard_thread is the collective skeleton -- the barriers of every path are listed above it -- and
+// every step is a function of its own on a Step (the shard's "do it only while ok, record the first failure" context):
+// encode_and_group, exchange (exchange_rccl / exchange_peer_copies), root_step (plain, root_joint, root_in_turns; what
+// differs between one batch and a tiler's batch is a RootOps), fast_start_vote, rows_to_shard0 / flags_to_shard (the
+// FAST root rebuilt on shard 0, by the threads of one batch and by swz_group_finalize), levels_and_result, batch_levels.
+// swz_group_tile and swz_group_add_batch run their threads through group_run_call.
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -16,6 +23,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -185,454 +193,538 @@ bool all_ok(const swz_group* g) {
   return true;
 }
 
-bool fail(swz_group* g, int r, int code, const std::string& msg) {
-  g->status[r] = code;
-  g->status_msg[r] = msg;
-  return false;
-}
-#define GRP_TRY(expr)                                                                  \
-  do {                                                                                 \
-    if (ok) {                                                                          \
-      const int _s = (expr);                                                           \
-      if (_s != SWZ_OK) ok = fail(g, r, _s, swz_last_error(c));                        \
-    }                                                                                  \
-  } while (0)
-#define GRP_HIP(expr)                                                                  \
-  do {                                                                                 \
-    if (ok) {                                                                          \
-      const hipError_t _e = (expr);                                                    \
-      if (_e != hipSuccess) ok = fail(g, r, SWZ_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    }                                                                                  \
-  } while (0)
-
-// One shard's part of a batch.  A failing shard keeps walking through the barriers (with nothing to contribute) so
-// that the others are not stranded; swz_group_tile reports the first failure.
-void shard_thread(ShardCall a) {
-  swz_group* g = a.g;
-  const int r = a.r, N = g->n;
-  swz_ctx* c = g->ctx[r];
+// What a shard thread carries from step to step.  The rule of every step: do it only while ok, record the first failure.
+// A shard that has failed keeps walking through the barriers (with nothing to contribute) so that the others are not
+// stranded; the call reports the first failure.  (The methods take a status that has been computed already: a call that
+// must not run on a failed shard stands behind `if (s.ok)` or `&&`.)
+struct Step {
+  swz_group* g;
+  int r, N;
+  swz_ctx* c;
   bool ok = true;
-  (void)hipSetDevice(g->devices[r]);
-  const uint64_t n = a.n;
-
-  // 1. encode locally, group the rows by destination shard
-  uint64_t* d_keys = nullptr;
-  uint32_t* d_perm = nullptr;
-  if (ok && c->get("grp_keys", (size_t)n, &d_keys) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-  if (ok && c->get("grp_perm", (size_t)n, &d_perm) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-  uint64_t oct[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (n) {
-    GRP_TRY(swz_morton_encode_device(c, a.d_xyz, n, a.bmin, a.bmax, d_keys));
-    GRP_TRY(swz_partition_by_octant_device(c, d_keys, n, d_perm, oct));
+  Step(swz_group* group, int shard) : g(group), r(shard), N(group->n), c(group->ctx[shard]) { (void)hipSetDevice(g->devices[r]); }
+  bool fail(int code, const std::string& msg) {
+    g->status[r] = code;
+    g->status_msg[r] = msg;
+    return ok = false;
   }
-  std::fill(g->send_counts[r].begin(), g->send_counts[r].end(), 0);
-  for (int o = 0; o < 8; ++o) g->send_counts[r][owner_of_octant(o, N)] += ok ? oct[o] : 0;
-  double* send = nullptr;
-  if (ok && c->get("grp_send", (size_t)n * 3, &send) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-  swz_attribute_columns send_attr{};
-  uint32_t row_bytes[SWZ_ATTR_COUNT];
-  for (int t = 0; t < SWZ_ATTR_COUNT; ++t) {
-    row_bytes[t] = (a.attrs && a.attrs->column[t]) ? swz_attribute_row_bytes(t) : 0;
-    if (!row_bytes[t]) continue;
-    const std::string name = "grp_send_attr" + std::to_string(t);
-    if (ok && c->get(name.c_str(), (size_t)n * row_bytes[t], &send_attr.column[t]) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
+  template <typename T>
+  T* buf(const std::string& name, size_t count) {  // a named buffer of the shard's workspace (T = void: count bytes)
+    T* p = nullptr;
+    if (ok && c->get(name.c_str(), count, &p) != SWZ_OK) fail(SWZ_ERR_HIP, c->err);
+    return p;
   }
-  if (n) GRP_TRY(swz_gather_payload_device(c, d_perm, nullptr, n, a.d_xyz, a.attrs, send, a.attrs ? &send_attr : nullptr));
-  g->barrier.wait();  // ---- every shard knows every count
-
-  // 2. the one exchange step
-  uint64_t m = 0;
-  std::vector<uint64_t> recv_off(N, 0), send_off(N, 0);
-  for (int s = 0; s < N; ++s) {
-    recv_off[s] = m;
-    m += g->send_counts[s][r];
+  bool swz(int st) {
+    if (ok && st != SWZ_OK) fail(st, swz_last_error(c));
+    return ok;
   }
-  for (int d = 1; d < N; ++d) send_off[d] = send_off[d - 1] + g->send_counts[r][d - 1];
-  uint64_t global_points = 0;
-  for (int s = 0; s < N; ++s)
-    for (int d = 0; d < N; ++d) global_points += g->send_counts[s][d];
-  double* buf = nullptr;
-  if (ok && c->get("grp_recv", (size_t)(m + kGhostHeadroom) * 3, &buf) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-  double* recv = buf ? buf + kGhostHeadroom * 3 : nullptr;
-  g->recv_rows[r] = recv;
-  g->recv_total[r] = m;
-  swz_attribute_columns recv_attr{};
-  for (int t = 0; t < SWZ_ATTR_COUNT; ++t) {
-    g->recv_attr[r][t] = nullptr;
-    if (!row_bytes[t]) continue;
-    const std::string name = "grp_recv_attr" + std::to_string(t);
-    if (ok && c->get(name.c_str(), (size_t)std::max<uint64_t>(m, 1) * row_bytes[t], &recv_attr.column[t]) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-    g->recv_attr[r][t] = ok ? (char*)recv_attr.column[t] : nullptr;
+  bool hip(hipError_t e, const char* what) {
+    if (ok && e != hipSuccess) fail(SWZ_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    return ok;
   }
-  // the columns of one row travel as separate blocks: [0] positions, [1 + t] attribute t
-  struct Column {
-    const char* src;
-    char* dst_here;
-    uint32_t bytes;
-    int attr;
-  };
-  std::vector<Column> columns{{(const char*)send, (char*)recv, 24u, -1}};
-  for (int t = 0; t < SWZ_ATTR_COUNT; ++t)
-    if (row_bytes[t]) columns.push_back({(const char*)send_attr.column[t], (char*)recv_attr.column[t], row_bytes[t], t});
-  g->barrier.wait();  // ---- every receive buffer exists
-  // A shard that has failed so far posts no sends or receives, and its peers would wait for them for ever (RCCL) or
-  // copy into buffers that do not exist: every shard looks at every status HERE -- nobody changes one between the
-  // barrier above and the one after the exchange -- and they skip the collective steps together.
-  const bool go = all_ok(g);
-  if (!go) {
-    ok = false;  // (this shard's own status stays as it is: the group reports the shard that failed first)
-  } else if (g->transport == 1 && N > 1) {
-    // grouped RCCL point-to-point = the all-to-all(v): bounded messages, both sides cut their block the same way
-    bool started = false;
-    if (ok) {
-      started = g->rccl.GroupStart() == 0;
-      if (!started) ok = fail(g, r, SWZ_ERR_HIP, "ncclGroupStart failed");
-    }
-    for (const Column& col : columns)
-      for (int p = 0; p < N && ok; ++p) {
-        if (p == r) continue;
-        const size_t sb = (size_t)g->send_counts[r][p] * col.bytes, rb = (size_t)g->send_counts[p][r] * col.bytes;
-        for (size_t at = 0; at < sb && ok; at += kChunkBytes)
-          if (g->rccl.Send(col.src + send_off[p] * col.bytes + at, std::min(kChunkBytes, sb - at), Rccl::kUint8, p, g->comms[r], c->stream) != 0)
-            ok = fail(g, r, SWZ_ERR_HIP, "ncclSend failed");
-        for (size_t at = 0; at < rb && ok; at += kChunkBytes)
-          if (g->rccl.Recv(col.dst_here + recv_off[p] * col.bytes + at, std::min(kChunkBytes, rb - at), Rccl::kUint8, p, g->comms[r], c->stream) != 0)
-            ok = fail(g, r, SWZ_ERR_HIP, "ncclRecv failed");
-      }
-    if (started && g->rccl.GroupEnd() != 0 && ok) ok = fail(g, r, SWZ_ERR_HIP, "ncclGroupEnd failed");
-    for (const Column& col : columns)
-      if (ok && g->send_counts[r][r])
-        GRP_HIP(hipMemcpyAsync(col.dst_here + recv_off[r] * col.bytes, col.src + send_off[r] * col.bytes,
-                               (size_t)g->send_counts[r][r] * col.bytes, hipMemcpyDeviceToDevice, c->stream));
-  } else {
-    // peer copies: every source pushes its blocks
-    for (int d = 0; d < N && ok; ++d) {
-      const uint64_t cnt = g->send_counts[r][d];
-      if (!cnt || !g->recv_rows[d]) continue;
-      uint64_t off = 0;  // where this source's block starts on the destination
-      for (int s = 0; s < r; ++s) off += g->send_counts[s][d];
-      for (const Column& col : columns) {
-        char* dst = col.attr < 0 ? (char*)g->recv_rows[d] : g->recv_attr[d][col.attr];
-        if (!dst) continue;
-        GRP_HIP(hipMemcpyPeerAsync(dst + off * col.bytes, g->devices[d], col.src + send_off[d] * col.bytes, g->devices[r],
-                                   (size_t)cnt * col.bytes, c->stream));
-      }
-    }
+  bool agree() {  // right after a barrier: has any shard failed?
+    if (!all_ok(g)) ok = false;  // (this shard's own status stays as it is: the group reports the shard that failed first)
+    return ok;
   }
-  GRP_HIP(hipStreamSynchronize(c->stream));
-  g->barrier.wait();  // ---- all rows have arrived everywhere
-
-  auto stamp = [&](int k) { g->timing[r][k] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g->t_call).count(); };
-  stamp(0);
-  // (the same vote again: a shard whose exchange failed must not keep the others waiting at the root)
-  if (!all_ok(g)) ok = false;
-  const bool proceed = ok || a.batch;  // a batch keeps every shard's tiler in step with the collective decisions below
-
-  if (!a.batch && a.params->strategy == SWZ_FAST) {
-    // 3F. TilingAlgorithmV3: no root step.  The start level from the distribution of the whole batch, the levels from
-    // there down and the skipped levels down to 0 on every shard by itself, the root from the level-0 nodes of all shards
-    // on shard 0 (swz_shard_fast_*).
-    stamp(1);
-    g->hist[r].assign(1u << 18, 0u);
-    if (ok && global_points < a.params->fast_concurrency) ok = fail(g, r, SWZ_ERR_BAD_ARG, "FAST: a batch needs at least fast_concurrency points");
-    GRP_TRY(swz_shard_fast_begin_device(c, recv, m, a.bmin, a.bmax, a.params, g->hist[r].data()));
+  bool vote() {
     g->barrier.wait();
-    if (r == 0) {
-      std::vector<uint64_t> sum(1u << 18, 0);
-      for (int s = 0; s < N; ++s)
-        for (uint32_t b = 0; b < (1u << 18); ++b) sum[b] += g->hist[s][b];
-      int32_t S = -1;
-      const int rc = swz_fast_start_level_from_counts(sum.data(), a.params->fast_concurrency, &S);
-      g->fast_tile_start = S;
-      if (ok && (rc != SWZ_OK || S < 0))  // (raised before the barrier: all_ok() then stops every shard with the real cause)
-        ok = fail(g, 0, rc != SWZ_OK ? rc : SWZ_ERR_INTERNAL, "FAST: no start level from the summed prefix histograms of the batch");
-    }
-    g->barrier.wait();
-    if (!all_ok(g)) ok = false;
-    uint64_t ncand = 0;
-    GRP_TRY(swz_shard_fast_run(c, g->fast_tile_start, &ncand));
-    uint64_t* ck = nullptr;
-    double* cx = nullptr;
-    if (ok && c->get("grp_cand_keys", (size_t)std::max<uint64_t>(ncand, 1), &ck) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-    if (ok && c->get("grp_cand_xyz", (size_t)std::max<uint64_t>(ncand, 1) * 3, &cx) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-    if (ncand) GRP_TRY(swz_shard_fast_root_candidates_device(c, ck, cx));
-    GRP_HIP(hipStreamSynchronize(c->stream));
-    g->cand_keys[r] = ck;
-    g->cand_xyz[r] = cx;
-    g->cand_count[r] = ok ? ncand : 0;
-    stamp(2);
-    g->barrier.wait();  // ---- every shard's candidates are in place
-    const bool go_root = all_ok(g);
-    if (!go_root) ok = false;
-    std::vector<uint64_t> off(N + 1, 0);
-    for (int s = 0; s < N; ++s) off[s + 1] = off[s] + g->cand_count[s];
-    if (r == 0 && go_root) {
-      const uint64_t total = off[N];
-      g->cand_flags = nullptr;
-      if (total > 0xFFFF0000ull) ok = fail(g, r, SWZ_ERR_TOO_MANY_POINTS, "more than 2^32-65536 points in the level-0 nodes");
-      if (ok && total) {
-        uint64_t* keys = nullptr;
-        double* all = nullptr;
-        uint32_t* iota = nullptr;
-        uint8_t* taken = nullptr;
-        if (c->get("grp_root_skeys", (size_t)total, &keys) != SWZ_OK || c->get("grp_root_xyz", (size_t)total * 3, &all) != SWZ_OK ||
-            c->get("grp_root_perm", (size_t)total, &iota) != SWZ_OK || c->get("grp_root_taken", (size_t)total, &taken) != SWZ_OK)
-          ok = fail(g, r, SWZ_ERR_HIP, c->err);
-        GRP_HIP(hipStreamSynchronize(c->stream));  // (the peer copies are not ordered with this shard's stream)
-        for (int s = 0; s < N && ok; ++s) {
-          if (!g->cand_count[s]) continue;
-          GRP_HIP(hipMemcpyPeer(keys + off[s], g->devices[0], g->cand_keys[s], g->devices[s], (size_t)g->cand_count[s] * 8));
-          GRP_HIP(hipMemcpyPeer(all + off[s] * 3, g->devices[0], g->cand_xyz[s], g->devices[s], (size_t)g->cand_count[s] * 24));
-        }
-        GRP_HIP(hipDeviceSynchronize());  // (a device-to-device hipMemcpyPeer may return before it is done; this shard's stream does not wait for it)
-        if (ok) {
-          hipLaunchKernelGGL(grp_iota_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, c->stream, iota, (uint32_t)total);
-          // the candidates of the shards one behind the other are in key order: the shards own ascending octants
-          GRP_TRY(swz::sample_points_device(c, a.params->sampler, a.params->max_points_per_node, keys, iota, (uint32_t)total, all, 0, -1, a.bmin,
-                                            a.bmax, a.params->spacing_at_root, SWZ_ALWAYS_ADHERE_TO_MIN_SPACING, taken, nullptr));
-          GRP_HIP(hipStreamSynchronize(c->stream));
-        }
-        g->cand_flags = taken;
-      }
-    }
-    g->barrier.wait();  // ---- the root is sampled (or shard 0 has failed)
-    if (!all_ok(g)) ok = false;
-    if (ok && ncand) {
-      uint8_t* mine = nullptr;
-      if (r == 0) {
-        mine = g->cand_flags;
-      } else {
-        if (c->get("grp_cand_flags", (size_t)ncand, &mine) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-        GRP_HIP(hipStreamSynchronize(c->stream));
-        GRP_HIP(hipMemcpyPeer(mine, g->devices[r], g->cand_flags + off[r], g->devices[0], (size_t)ncand));
-        GRP_HIP(hipDeviceSynchronize());
-      }
-      GRP_TRY(swz_shard_fast_set_root_device(c, mine));
-    }
-    uint64_t* okeys = nullptr;
-    uint32_t *operm = nullptr, *odup = nullptr;
-    int8_t* olevel = nullptr;
-    if (ok && c->get("grp_out_keys", (size_t)m, &okeys) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-    if (ok && c->get("grp_out_perm", (size_t)m, &operm) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-    if (ok && c->get("grp_out_level", (size_t)m, &olevel) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-    if (ok && c->get("grp_out_dup", (size_t)m, &odup) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-    swz_tile_stats stats{};
-    GRP_TRY(swz_shard_fast_finish_device(c, okeys, operm, olevel, odup, &stats));
-    GRP_HIP(hipStreamSynchronize(c->stream));
-    stamp(3);
-    if (a.result) {
-      a.result->d_xyz = recv;
-      a.result->d_keys = okeys;
-      a.result->d_perm = operm;
-      a.result->d_level = olevel;
-      a.result->attrs = recv_attr;
-      a.result->num_points = ok ? m : 0;
-      a.result->stats = stats;
-      a.result->d_dup = odup;
-    }
-  } else if (!a.batch) {
-  // 3. the root node
-  stamp(1);
-  const bool sequential_root = a.params->sampler == SWZ_MIN_DISTANCE && global_points > a.params->max_points_per_node;
-  uint64_t taken = 0;
-  g->root_taken_count[r] = 0;
-  bool in_turns = false;
-  if (!sequential_root) {
-    swz_shard_info info{global_points, nullptr, 0};
-    GRP_TRY(swz_shard_begin_device(c, recv, m, a.bmin, a.bmax, a.params, &info, &taken));
-  } else if (N > 1 && g->peer_access && joint_root_possible(c, *a.params, a.bmin, a.bmax)) {
-    // All shards sweep the root cells of their own octants at the same time; a cell at the face of a lower octant reads
-    // that shard's records through peer access (swz_mdkeys.hip).  No ghosts, no turns.
-    swz::MdShardRoot sr;
-    sr.shard = r;
-    sr.shards = N;
-    sr.views = g->views.data();
-    sr.barrier = group_barrier;
-    sr.barrier_arg = g;
-    g->views[r] = swz::MdPeerView{};
-    c->md_shard_root = &sr;
-    c->md_shard_root_published = true;  // the higher shards read this root's "md_*_sr" arrays until the barrier at the end of the batch
-    swz_shard_info info{global_points, nullptr, 0};
-    // (a shard whose octants are empty -- flat terrain in a cubic box -- opens its batch all the same: swz_shard_finish_device
-    // below pairs up with it; it never reaches the sweep, so the group meets the others for it)
-    GRP_TRY(swz_shard_begin_device(c, recv, m, a.bmin, a.bmax, a.params, &info, &taken));
-    c->md_shard_root = nullptr;
-    if (!g->views[r].entered) {  // no points here, or the call failed before its sweep met the others: meet them for it
-      g->views[r].ncells = 0;
-      g->views[r].status = ok ? SWZ_OK : SWZ_ERR_INTERNAL;
-      g->views[r].entered = 1;
-      g->barrier.wait();
-    }
-  } else {
-    if (m) GRP_TRY(swz_shard_presort_device(c, recv, m, a.bmin, a.bmax, a.params, kGhostHeadroom));
-    {
-      std::unique_lock<std::mutex> lk(g->turn_m);
-      g->turn_cv.wait(lk, [&] { return g->turn == r; });
-    }
-    // (the stamps of a root taken in turns say so: "root begun" when the turn has come, "root done" before it is passed on,
-    // so that no shard's root begins before the lower shard's is done -- tests/test_shard_seams.py tells the paths apart by it)
-    in_turns = true;
-    stamp(1);
-    // ghosts: what the root took on all lower shards, right in front of the received points
-    uint64_t gh = 0;
-    for (int s = 0; s < r; ++s) gh += g->root_taken_count[s];
-    if (gh > kGhostHeadroom && ok) ok = fail(g, r, SWZ_ERR_TOO_MANY_POINTS, "more root samples on lower shards than the ghost headroom holds");
-    double* gp = recv ? recv - gh * 3 : nullptr;
-    uint64_t at = 0;
-    for (int s = 0; s < r && ok && m; ++s) {
-      if (!g->root_taken_count[s]) continue;
-      GRP_HIP(hipMemcpyPeerAsync(gp + at * 3, g->devices[r], g->root_taken[s], g->devices[s], (size_t)g->root_taken_count[s] * 24, c->stream));
-      at += g->root_taken_count[s];
-    }
-    GRP_HIP(hipStreamSynchronize(c->stream));
-    swz_shard_info info{global_points, m ? gp : nullptr, m ? gh : 0};
-    GRP_TRY(swz_shard_begin_device(c, recv, m, a.bmin, a.bmax, a.params, &info, &taken));
-    double* mine = nullptr;
-    if (ok && c->get("grp_root_taken", (size_t)std::max<uint64_t>(taken, 1) * 3, &mine) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-    if (taken) GRP_TRY(swz_shard_root_taken_device(c, mine));
-    g->root_taken[r] = mine;
-    g->root_taken_count[r] = ok ? taken : 0;
-    stamp(2);  // (both calls above return with the stream idle)
+    return agree();
+  }
+  void stamp(int k) { g->timing[r][k] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g->t_call).count(); }
+  void wait_turn() {
+    std::unique_lock<std::mutex> lk(g->turn_m);
+    g->turn_cv.wait(lk, [&] { return g->turn == r; });
+  }
+  void pass_turn() {
     {
       std::lock_guard<std::mutex> lk(g->turn_m);
       g->turn = r + 1;
     }
     g->turn_cv.notify_all();
   }
+};
 
-  // 4. everything below the root is local
-  GRP_HIP(hipStreamSynchronize(c->stream));
-  if (!in_turns) stamp(2);
-  uint64_t* okeys = nullptr;
-  uint32_t* operm = nullptr;
-  int8_t* olevel = nullptr;
-  if (ok && c->get("grp_out_keys", (size_t)m, &okeys) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-  if (ok && c->get("grp_out_perm", (size_t)m, &operm) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-  if (ok && c->get("grp_out_level", (size_t)m, &olevel) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
+// ---------------------------------------------------------------------------------- step 1: encode, group by destination
+struct Grouped {  // this shard's rows in the order of their destination shards, column by column
+  double* send = nullptr;
+  swz_attribute_columns send_attr{};
+  uint32_t row_bytes[SWZ_ATTR_COUNT];  // 0: the batch has no such column
+};
+
+// Encodes locally, groups the rows by destination shard and publishes how many go where (send_counts[r]; a failed
+// shard sends nothing).
+Grouped encode_and_group(Step& s, const ShardCall& a) {
+  swz_ctx* c = s.c;
+  const uint64_t n = a.n;
+  Grouped out;
+  uint64_t* d_keys = s.buf<uint64_t>("grp_keys", (size_t)n);
+  uint32_t* d_perm = s.buf<uint32_t>("grp_perm", (size_t)n);
+  uint64_t oct[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (n && s.ok) s.swz(swz_morton_encode_device(c, a.d_xyz, n, a.bmin, a.bmax, d_keys)) && s.swz(swz_partition_by_octant_device(c, d_keys, n, d_perm, oct));
+  std::fill(s.g->send_counts[s.r].begin(), s.g->send_counts[s.r].end(), 0);
+  for (int o = 0; o < 8; ++o) s.g->send_counts[s.r][owner_of_octant(o, s.N)] += s.ok ? oct[o] : 0;
+  out.send = s.buf<double>("grp_send", (size_t)n * 3);
+  for (int t = 0; t < SWZ_ATTR_COUNT; ++t) {
+    out.row_bytes[t] = (a.attrs && a.attrs->column[t]) ? swz_attribute_row_bytes(t) : 0;
+    if (out.row_bytes[t]) out.send_attr.column[t] = s.buf<void>("grp_send_attr" + std::to_string(t), (size_t)n * out.row_bytes[t]);
+  }
+  if (n && s.ok) s.swz(swz_gather_payload_device(c, d_perm, nullptr, n, a.d_xyz, a.attrs, out.send, a.attrs ? &out.send_attr : nullptr));
+  return out;
+}
+
+// ---------------------------------------------------------------------------------------------- step 2: the one exchange
+struct Exchanged {  // what a shard owns after the exchange
+  double* recv = nullptr;  // m rows, kGhostHeadroom rows free in front of them
+  uint64_t m = 0;
+  swz_attribute_columns recv_attr{};
+  uint64_t global_points = 0;  // of the whole batch
+};
+// the columns of one row travel as separate blocks: [0] positions, [1 + t] attribute t
+struct Column {
+  const char* src;
+  char* dst_here;
+  uint32_t bytes;
+  int attr;
+};
+struct Blocks {
+  std::vector<Column> columns;
+  std::vector<uint64_t> recv_off, send_off;  // rows: where shard p's block starts in this shard's receive / send buffers
+};
+
+// grouped RCCL point-to-point = the all-to-all(v): bounded messages, both sides cut their block the same way
+void exchange_rccl(Step& s, const Blocks& b) {
+  swz_group* g = s.g;
+  const int r = s.r;
+  if (g->rccl.GroupStart() != 0) {
+    s.fail(SWZ_ERR_HIP, "ncclGroupStart failed");
+    return;
+  }
+  for (const Column& col : b.columns)
+    for (int p = 0; p < s.N && s.ok; ++p) {
+      if (p == r) continue;
+      const size_t sb = (size_t)g->send_counts[r][p] * col.bytes, rb = (size_t)g->send_counts[p][r] * col.bytes;
+      for (size_t at = 0; at < sb && s.ok; at += kChunkBytes)
+        if (g->rccl.Send(col.src + b.send_off[p] * col.bytes + at, std::min(kChunkBytes, sb - at), Rccl::kUint8, p, g->comms[r], s.c->stream) != 0)
+          s.fail(SWZ_ERR_HIP, "ncclSend failed");
+      for (size_t at = 0; at < rb && s.ok; at += kChunkBytes)
+        if (g->rccl.Recv(col.dst_here + b.recv_off[p] * col.bytes + at, std::min(kChunkBytes, rb - at), Rccl::kUint8, p, g->comms[r], s.c->stream) != 0)
+          s.fail(SWZ_ERR_HIP, "ncclRecv failed");
+    }
+  if (g->rccl.GroupEnd() != 0 && s.ok) s.fail(SWZ_ERR_HIP, "ncclGroupEnd failed");
+  for (const Column& col : b.columns)
+    if (s.ok && g->send_counts[r][r])
+      s.hip(hipMemcpyAsync(col.dst_here + b.recv_off[r] * col.bytes, col.src + b.send_off[r] * col.bytes, (size_t)g->send_counts[r][r] * col.bytes,
+                           hipMemcpyDeviceToDevice, s.c->stream),
+            "hipMemcpyAsync(own block)");
+}
+
+// peer copies: every source pushes its blocks
+void exchange_peer_copies(Step& s, const Blocks& b) {
+  swz_group* g = s.g;
+  const int r = s.r;
+  for (int d = 0; d < s.N && s.ok; ++d) {
+    const uint64_t cnt = g->send_counts[r][d];
+    if (!cnt || !g->recv_rows[d]) continue;
+    uint64_t off = 0;  // where this source's block starts on the destination
+    for (int p = 0; p < r; ++p) off += g->send_counts[p][d];
+    for (const Column& col : b.columns) {
+      char* dst = col.attr < 0 ? (char*)g->recv_rows[d] : g->recv_attr[d][col.attr];
+      if (!dst || !s.ok) continue;
+      s.hip(hipMemcpyPeerAsync(dst + off * col.bytes, g->devices[d], col.src + b.send_off[d] * col.bytes, g->devices[r], (size_t)cnt * col.bytes, s.c->stream),
+            "hipMemcpyPeerAsync(exchange)");
+    }
+  }
+}
+
+// Allocates and publishes the receive buffers, meets the others (barrier: every receive buffer exists), sends and
+// receives, and meets them again (barrier: all rows have arrived everywhere).
+Exchanged exchange(Step& s, const Grouped& rows) {
+  swz_group* g = s.g;
+  const int r = s.r, N = s.N;
+  Exchanged ex;
+  Blocks b;
+  b.recv_off.assign(N, 0);
+  b.send_off.assign(N, 0);
+  for (int p = 0; p < N; ++p) {
+    b.recv_off[p] = ex.m;
+    ex.m += g->send_counts[p][r];
+  }
+  for (int d = 1; d < N; ++d) b.send_off[d] = b.send_off[d - 1] + g->send_counts[r][d - 1];
+  for (int p = 0; p < N; ++p)
+    for (int d = 0; d < N; ++d) ex.global_points += g->send_counts[p][d];
+  double* front = s.buf<double>("grp_recv", (size_t)(ex.m + kGhostHeadroom) * 3);
+  ex.recv = front ? front + kGhostHeadroom * 3 : nullptr;
+  g->recv_rows[r] = ex.recv;
+  g->recv_total[r] = ex.m;
+  b.columns.push_back({(const char*)rows.send, (char*)ex.recv, 24u, -1});
+  for (int t = 0; t < SWZ_ATTR_COUNT; ++t) {
+    g->recv_attr[r][t] = nullptr;
+    if (!rows.row_bytes[t]) continue;
+    ex.recv_attr.column[t] = s.buf<void>("grp_recv_attr" + std::to_string(t), (size_t)std::max<uint64_t>(ex.m, 1) * rows.row_bytes[t]);
+    g->recv_attr[r][t] = s.ok ? (char*)ex.recv_attr.column[t] : nullptr;
+    b.columns.push_back({(const char*)rows.send_attr.column[t], (char*)ex.recv_attr.column[t], rows.row_bytes[t], t});
+  }
+  // A shard that has failed so far posts no sends or receives, and its peers would wait for them for ever (RCCL) or
+  // copy into buffers that do not exist: every shard looks at every status right after this barrier -- nobody changes
+  // one between it and the one after the exchange -- and they skip the collective step together.
+  if (s.vote()) {  // ---- every receive buffer exists
+    if (g->transport == 1 && N > 1) exchange_rccl(s, b);
+    else exchange_peer_copies(s, b);
+    if (s.ok) s.hip(hipStreamSynchronize(s.c->stream), "hipStreamSynchronize(exchange)");
+  }
+  g->barrier.wait();  // ---- all rows have arrived everywhere
+  return ex;
+}
+
+// ------------------------------------------------------------------------------------ step 3: the root node, ACCURATE
+// What differs between one batch (swz_shard_*) and one batch of the shard's tiler (swz_tiler_shard_*).
+struct RootOps {
+  // the root samples with MIN_DISTANCE: its greedy order spans the shards (else every shard decides its part by itself,
+  // the take-all / sample decision on the counts of the whole root)
+  bool sequential = false;
+  // one batch: a root taken in turns stamps "root begun" when its turn has come and "root done" before it passes the turn
+  // on, so that no shard's root begins before the lower shard's is done (tests/test_shard_seams.py tells the paths apart
+  // by it), and "root done" waits for the stream; a tiler's begin returns with the stream idle and stamps after the step
+  bool single_batch = false;
+  std::function<void(Step&)> before_turn;                                                // work that does not need the lower shards
+  std::function<double*(Step&, uint64_t ghosts)> ghost_room;                             // where the ghosts go (NULL: none are copied)
+  std::function<int(double* d_ghosts, uint64_t ghosts, uint64_t* taken)> begin;          // the root step; taken: points in the root's file here
+  std::function<int(double* d_out)> taken_positions;                                     // the positions the root took here
+};
+
+// All shards sweep the root cells of their own octants at the same time; a cell at the face of a lower octant reads that
+// shard's records through peer access (swz_mdkeys.hip), exact positions of a tiler through its working index
+// (MdPeerView::aidx).  No ghosts, no turns.  One barrier: inside the sweep, or here for a shard that never entered it.
+void root_joint(Step& s, const RootOps& ops, uint64_t* taken) {
+  swz_group* g = s.g;
+  swz::MdShardRoot sr;
+  sr.shard = s.r;
+  sr.shards = s.N;
+  sr.views = g->views.data();
+  sr.barrier = group_barrier;
+  sr.barrier_arg = g;
+  g->views[s.r] = swz::MdPeerView{};
+  s.c->md_shard_root = &sr;
+  s.c->md_shard_root_published = true;  // the higher shards read this root's "md_*_sr" arrays until the barrier at the end of the call
+  // (a shard whose octants are empty -- flat terrain in a cubic box -- opens its batch all the same: the finish call pairs
+  // up with it; it never reaches the sweep, so the group meets the others for it)
+  if (s.ok) s.swz(ops.begin(nullptr, 0, taken));
+  s.c->md_shard_root = nullptr;
+  if (!g->views[s.r].entered) {  // nothing to sample here, or the shard failed before its sweep met the others: meet them for it
+    g->views[s.r].ncells = 0;
+    g->views[s.r].status = s.ok ? SWZ_OK : SWZ_ERR_INTERNAL;
+    g->views[s.r].entered = 1;
+    g->barrier.wait();
+  }
+}
+
+// The greedy order visits the shards in turn, each with what the root took on the lower shards as ghosts.  A failed shard
+// still waits for its turn and passes it on.
+void root_in_turns(Step& s, const RootOps& ops, uint64_t* taken) {
+  swz_group* g = s.g;
+  const int r = s.r;
+  if (ops.before_turn) ops.before_turn(s);
+  s.wait_turn();
+  if (ops.single_batch) s.stamp(1);
+  uint64_t gh = 0;
+  for (int p = 0; p < r; ++p) gh += g->root_taken_count[p];
+  double* gp = ops.ghost_room(s, gh);
+  uint64_t at = 0;
+  for (int p = 0; p < r && s.ok && gp; ++p) {
+    if (!g->root_taken_count[p]) continue;
+    s.hip(hipMemcpyPeerAsync(gp + at * 3, g->devices[r], g->root_taken[p], g->devices[p], (size_t)g->root_taken_count[p] * 24, s.c->stream),
+          "hipMemcpyPeerAsync(ghosts)");
+    at += g->root_taken_count[p];
+  }
+  if (s.ok) s.hip(hipStreamSynchronize(s.c->stream), "hipStreamSynchronize(ghosts)");
+  if (s.ok) s.swz(ops.begin(gp, gh, taken));
+  double* mine = s.buf<double>("grp_root_taken", (size_t)std::max<uint64_t>(*taken, 1) * 3);
+  if (s.ok && *taken) s.swz(ops.taken_positions(mine));
+  g->root_taken[r] = mine;
+  g->root_taken_count[r] = s.ok ? *taken : 0;
+  if (ops.single_batch) s.stamp(2);  // (both calls above return with the stream idle)
+  s.pass_turn();
+}
+
+// The root step: plain, swept by all shards at once, or in turns.  Ends with the "root done" stamp.
+void root_step(Step& s, const ShardCall& a, const RootOps& ops) {
+  uint64_t taken = 0;
+  bool in_turns = false;
+  if (!ops.sequential) {
+    if (s.ok) s.swz(ops.begin(nullptr, 0, &taken));
+  } else if (s.N > 1 && s.g->peer_access && joint_root_possible(s.c, *a.params, a.bmin, a.bmax)) {
+    root_joint(s, ops, &taken);
+  } else {
+    root_in_turns(s, ops, &taken);
+    in_turns = true;
+  }
+  if (ops.single_batch && s.ok) s.hip(hipStreamSynchronize(s.c->stream), "hipStreamSynchronize(root)");
+  if (!(in_turns && ops.single_batch)) s.stamp(2);
+}
+
+// one batch: ghosts right in front of the received points (the presort leaves the headroom free)
+RootOps tile_root_ops(const ShardCall& a, const Exchanged& ex) {
+  swz_ctx* c = a.g->ctx[a.r];
+  RootOps ops;
+  ops.single_batch = true;
+  ops.sequential = a.params->sampler == SWZ_MIN_DISTANCE && ex.global_points > a.params->max_points_per_node;
+  ops.before_turn = [=](Step& s) {
+    if (ex.m && s.ok) s.swz(swz_shard_presort_device(c, ex.recv, ex.m, a.bmin, a.bmax, a.params, kGhostHeadroom));
+  };
+  ops.ghost_room = [=](Step& s, uint64_t gh) -> double* {
+    if (gh > kGhostHeadroom && s.ok) s.fail(SWZ_ERR_TOO_MANY_POINTS, "more root samples on lower shards than the ghost headroom holds");
+    return (ex.recv && ex.m) ? ex.recv - gh * 3 : nullptr;
+  };
+  ops.begin = [=](double* gp, uint64_t gh, uint64_t* taken) {
+    swz_shard_info info{ex.global_points, ex.m ? gp : nullptr, ex.m ? gh : 0};
+    return swz_shard_begin_device(c, ex.recv, ex.m, a.bmin, a.bmax, a.params, &info, taken);
+  };
+  ops.taken_positions = [=](double* out) { return swz_shard_root_taken_device(c, out); };
+  return ops;
+}
+
+// one batch of the shard's tiler: the root's take-all / sample decision uses the counts of the WHOLE root (cached points
+// anywhere force sampling, TilingAlgorithms.cpp:272-275); in turns, the ghosts are the root files of the lower shards as
+// they are after this batch, in a buffer of their own
+RootOps batch_root_ops(const ShardCall& a, const Exchanged& ex) {
+  swz_group* g = a.g;
+  swz_tiler* t = g->tiler[a.r];
+  uint64_t root_before = 0;
+  for (int p = 0; p < g->n; ++p) root_before += g->root_stored[p];
+  const bool sample = root_before > 0 || ex.global_points + root_before > a.params->max_points_per_node;
+  RootOps ops;
+  ops.sequential = a.params->sampler == SWZ_MIN_DISTANCE && sample && ex.global_points > 0;
+  ops.ghost_room = [](Step& s, uint64_t gh) { return s.buf<double>("grp_ghosts", (size_t)std::max<uint64_t>(gh, 1) * 3); };
+  ops.begin = [=](double* gp, uint64_t gh, uint64_t* have) {
+    swz_tiler_shard_info info{ex.global_points, root_before, gh ? gp : nullptr, gh};
+    return swz_tiler_shard_begin_device(t, ex.recv, ex.m, &ex.recv_attr, &info, have);
+  };
+  ops.taken_positions = [=](double* out) { return swz_tiler_level_positions_device(t, -1, out); };
+  return ops;
+}
+
+// ------------------------------------------------------------------------------------------ FAST (TilingAlgorithmV3)
+// The start level from the distribution of the whole batch: every shard has filled hist[r]; shard 0 sums them and writes
+// the level to *level between two barriers (every histogram is in place / the level is known).  What a level that cannot
+// be had means is the caller's business: on_shard0(status, level) runs on shard 0 before the second barrier.
+template <typename F>
+void fast_start_vote(Step& s, uint32_t fast_concurrency, int* level, F on_shard0) {
+  swz_group* g = s.g;
+  g->barrier.wait();
+  if (s.r == 0) {
+    std::vector<uint64_t> sum(1u << 18, 0);
+    for (int p = 0; p < s.N; ++p)
+      for (uint32_t b = 0; b < (1u << 18); ++b) sum[b] += g->hist[p][b];
+    int32_t S = -1;
+    const int rc = swz_fast_start_level_from_counts(sum.data(), fast_concurrency, &S);
+    *level = S;
+    on_shard0(rc, S);
+  }
+  g->barrier.wait();
+}
+
+// "Rows of all shards onto shard 0": cnt[p] rows of every column from shard p to row off[p] on shard 0, by peer copies on
+// the default stream.  Called with shard 0's device current; the sources' streams are idle.  Returns the first error.
+struct PeerColumn {
+  void* dst;                     // on shard 0
+  std::vector<const void*> src;  // per shard
+  size_t row_bytes;
+};
+hipError_t rows_to_shard0(swz_group* g, const std::vector<uint64_t>& cnt, const std::vector<uint64_t>& off, const std::vector<PeerColumn>& columns) {
+  // (the peer copies are not ordered with shard 0's stream: nothing queued on it -- the SWZ_POISON fill of a buffer that
+  // has just been allocated -- may still be writing the destination)
+  hipError_t e = hipStreamSynchronize(g->ctx[0]->stream);
+  for (int p = 0; p < g->n; ++p)
+    for (const PeerColumn& col : columns)
+      if (e == hipSuccess && cnt[p])
+        e = hipMemcpyPeer((char*)col.dst + off[p] * col.row_bytes, g->devices[0], col.src[p], g->devices[p], (size_t)cnt[p] * col.row_bytes);
+  // (a device-to-device hipMemcpyPeer may return before it is done; shard 0's stream does not wait for it)
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return e;
+}
+
+// "Flags back to their shards": count flags from shard 0 to shard r > 0, whose device is current.
+hipError_t flags_to_shard(swz_group* g, int r, uint8_t* mine, const uint8_t* d_flags0, uint64_t count) {
+  hipError_t e = hipStreamSynchronize(g->ctx[r]->stream);  // (the copy is not ordered with this shard's stream)
+  if (e == hipSuccess) e = hipMemcpyPeer(mine, g->devices[r], d_flags0, g->devices[0], (size_t)count);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return e;
+}
+
+// One batch, FAST: no root step.  The start level from the distribution of the whole batch, the levels from there down and
+// the skipped levels down to 0 on every shard by itself, the root from the level-0 nodes of all shards on shard 0
+// (swz_shard_fast_*).  This step: index the batch, count it per 6-octant prefix.
+void tile_fast_index(Step& s, const ShardCall& a, const Exchanged& ex) {
+  s.g->hist[s.r].assign(1u << 18, 0u);
+  if (s.ok && ex.global_points < a.params->fast_concurrency) s.fail(SWZ_ERR_BAD_ARG, "FAST: a batch needs at least fast_concurrency points");
+  if (s.ok) s.swz(swz_shard_fast_begin_device(s.c, ex.recv, ex.m, a.bmin, a.bmax, a.params, s.g->hist[s.r].data()));
+}
+
+// the levels from the start level down to 0; publishes what the shard's level-0 nodes hold
+uint64_t tile_fast_candidates(Step& s) {
+  swz_group* g = s.g;
+  uint64_t ncand = 0;
+  if (s.ok) s.swz(swz_shard_fast_run(s.c, g->fast_tile_start, &ncand));
+  uint64_t* ck = s.buf<uint64_t>("grp_cand_keys", (size_t)std::max<uint64_t>(ncand, 1));
+  double* cx = s.buf<double>("grp_cand_xyz", (size_t)std::max<uint64_t>(ncand, 1) * 3);
+  if (ncand && s.ok) s.swz(swz_shard_fast_root_candidates_device(s.c, ck, cx));
+  if (s.ok) s.hip(hipStreamSynchronize(s.c->stream), "hipStreamSynchronize(candidates)");
+  g->cand_keys[s.r] = ck;
+  g->cand_xyz[s.r] = cx;
+  g->cand_count[s.r] = s.ok ? ncand : 0;
+  s.stamp(2);
+  return ncand;
+}
+
+std::vector<uint64_t> cand_offsets(const swz_group* g) {
+  std::vector<uint64_t> off(g->n + 1, 0);
+  for (int p = 0; p < g->n; ++p) off[p + 1] = off[p] + g->cand_count[p];
+  return off;
+}
+
+// shard 0: the root from the candidates of all shards
+void tile_fast_root_on_shard0(Step& s, const ShardCall& a) {
+  swz_group* g = s.g;
+  const std::vector<uint64_t> off = cand_offsets(g);
+  const uint64_t total = off[s.N];
+  g->cand_flags = nullptr;
+  if (total > 0xFFFF0000ull) s.fail(SWZ_ERR_TOO_MANY_POINTS, "more than 2^32-65536 points in the level-0 nodes");
+  if (!s.ok || !total) return;
+  uint64_t* keys = s.buf<uint64_t>("grp_root_skeys", (size_t)total);
+  double* all = s.buf<double>("grp_root_xyz", (size_t)total * 3);
+  uint32_t* iota = s.buf<uint32_t>("grp_root_perm", (size_t)total);
+  uint8_t* taken = s.buf<uint8_t>("grp_root_taken", (size_t)total);
+  if (s.ok)
+    s.hip(rows_to_shard0(g, g->cand_count, off,
+                         {{keys, {g->cand_keys.begin(), g->cand_keys.end()}, 8}, {all, {g->cand_xyz.begin(), g->cand_xyz.end()}, 24}}),
+          "copy of the level-0 nodes to shard 0");
+  if (s.ok) {
+    hipLaunchKernelGGL(grp_iota_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s.c->stream, iota, (uint32_t)total);
+    // the candidates of the shards one behind the other are in key order: the shards own ascending octants
+    s.swz(swz::sample_points_device(s.c, a.params->sampler, a.params->max_points_per_node, keys, iota, (uint32_t)total, all, 0, -1, a.bmin, a.bmax,
+                                    a.params->spacing_at_root, SWZ_ALWAYS_ADHERE_TO_MIN_SPACING, taken, nullptr)) &&
+        s.hip(hipStreamSynchronize(s.c->stream), "hipStreamSynchronize(root)");
+  }
+  g->cand_flags = taken;
+}
+
+// every shard: which of its candidates the root took
+void tile_fast_take_root(Step& s, uint64_t ncand) {
+  swz_group* g = s.g;
+  if (!s.ok || !ncand) return;
+  uint8_t* mine = g->cand_flags;
+  if (s.r != 0) {
+    mine = s.buf<uint8_t>("grp_cand_flags", (size_t)ncand);
+    if (s.ok) s.hip(flags_to_shard(g, s.r, mine, g->cand_flags + cand_offsets(g)[s.r], ncand), "copy of the root flags");
+  }
+  if (s.ok) s.swz(swz_shard_fast_set_root_device(s.c, mine));
+}
+
+// Step 4 of one batch: everything below the root is local; the result record.  FAST adds the dup mask.
+void levels_and_result(Step& s, const ShardCall& a, const Exchanged& ex, bool fast) {
+  uint64_t* okeys = s.buf<uint64_t>("grp_out_keys", (size_t)ex.m);
+  uint32_t* operm = s.buf<uint32_t>("grp_out_perm", (size_t)ex.m);
+  int8_t* olevel = s.buf<int8_t>("grp_out_level", (size_t)ex.m);
+  uint32_t* odup = fast ? s.buf<uint32_t>("grp_out_dup", (size_t)ex.m) : nullptr;
   swz_tile_stats stats{};
-  GRP_TRY(swz_shard_finish_device(c, okeys, operm, olevel, &stats));
-  GRP_HIP(hipStreamSynchronize(c->stream));
-  stamp(3);
-  if (a.result) {
-    a.result->d_xyz = recv;
-    a.result->d_keys = okeys;
-    a.result->d_perm = operm;
-    a.result->d_level = olevel;
-    a.result->attrs = recv_attr;
-    a.result->num_points = ok ? m : 0;
-    a.result->stats = stats;
-    a.result->d_dup = nullptr;
+  if (s.ok) s.swz(fast ? swz_shard_fast_finish_device(s.c, okeys, operm, olevel, odup, &stats) : swz_shard_finish_device(s.c, okeys, operm, olevel, &stats));
+  if (s.ok) s.hip(hipStreamSynchronize(s.c->stream), "hipStreamSynchronize(levels)");
+  s.stamp(3);
+  if (!a.result) return;
+  a.result->d_xyz = ex.recv;
+  a.result->d_keys = okeys;
+  a.result->d_perm = operm;
+  a.result->d_level = olevel;
+  a.result->attrs = ex.recv_attr;
+  a.result->num_points = s.ok ? ex.m : 0;
+  a.result->stats = stats;
+  a.result->d_dup = odup;
+}
+
+// One batch of the shard's tiler, FAST: no root step per batch.  The start level comes from the FIRST batch's distribution
+// over all shards (TilingAlgorithms.cpp:1473-1535) and is kept (:1230-1236).  This step: index the batch, and count the
+// first one per 6-octant prefix.
+void batch_fast_index(Step& s, const ShardCall& a, const Exchanged& ex, bool first) {
+  swz_tiler* t = s.g->tiler[s.r];
+  uint64_t have = 0;
+  if (s.ok && ex.global_points < a.params->fast_concurrency) s.fail(SWZ_ERR_BAD_ARG, "FAST: a batch needs at least fast_concurrency points");
+  if (s.ok) s.swz(batch_root_ops(a, ex).begin(nullptr, 0, &have));  // (FAST: begin indexes the batch and leaves the root alone)
+  if (!first) return;
+  s.g->hist[s.r].assign(1u << 18, 0u);
+  if (s.ok) s.swz(swz_tiler_shard_fast_histogram(t, s.g->hist[s.r].data()));
+}
+
+// the levels of a tiler's batch below the root (FAST: from the start level down) and its statistics
+void batch_levels(Step& s, const ShardCall& a) {
+  swz_tile_stats stats{};
+  if (s.ok) s.swz(swz_tiler_shard_finish(s.g->tiler[s.r], &stats));
+  if (a.stats) *a.stats = stats;
+  (void)hipStreamSynchronize(s.c->stream);
+  s.stamp(3);
+}
+
+// One shard's part of a call: the collective skeleton.  EVERY shard thread, failed or not, passes the same barriers in the
+// same order on a given path -- which path is decided by the call's parameters and by counts every shard knows, never by a
+// shard's own state.  Barriers by path (B1..B3 and the last one are common to all):
+//
+//   every path            B1 every shard knows every count (after encode_and_group)
+//                         B2 every receive buffer exists, B3 all rows have arrived (both inside exchange)
+//   tile  ACCURATE plain  --
+//   tile  ACCURATE joint  J  the views of the root level are published (inside the sweep; root_joint meets the others for
+//                            a shard that never entered it)
+//   tile  ACCURATE turns  no barrier: wait for turn == r, pass on turn = r + 1 (a failed shard too)
+//   tile  FAST            F1 every histogram is in place, F2 the start level is known (fast_start_vote),
+//                         F3 every shard's candidates are in place, F4 the root is sampled on shard 0
+//   batch ACCURATE plain / joint / turns: as for tile
+//   batch FAST, first     F1, F2 (fast_start_vote)
+//   batch FAST, later     --
+//   every path            L  nobody reads a neighbour's buffers any more; then md_shard_root_published is reset
+//
+// The stamps of swz_group_shard_timing: 0 after B3, 1 here, 2 and 3 in the steps (root_step / tile_fast_candidates /
+// batch FAST below: 2; levels_and_result / batch_levels: 3).
+void shard_thread(ShardCall a) {
+  Step s(a.g, a.r);
+  swz_group* g = a.g;
+  const Grouped rows = encode_and_group(s, a);
+  g->barrier.wait();  // B1
+  const Exchanged ex = exchange(s, rows);  // B2, B3
+  s.stamp(0);
+  s.agree();  // (the same vote again: a shard whose exchange failed must not keep the others waiting at the root)
+  s.stamp(1);  // (a tiler's batch stamps like one batch: root step begun / done, levels done -- for FAST, which has no root step
+               // per batch, "root" is the indexing of the batch and the vote on the start level)
+  const bool fast = a.params->strategy == SWZ_FAST;
+  if (!a.batch && fast) {
+    tile_fast_index(s, a, ex);
+    fast_start_vote(s, a.params->fast_concurrency, &g->fast_tile_start, [&](int rc, int32_t S) {  // F1, F2
+      if (s.ok && (rc != SWZ_OK || S < 0))  // (raised before the barrier: agree() then stops every shard with the real cause)
+        s.fail(rc != SWZ_OK ? rc : SWZ_ERR_INTERNAL, "FAST: no start level from the summed prefix histograms of the batch");
+    });
+    s.agree();
+    const uint64_t ncand = tile_fast_candidates(s);
+    const bool go_root = s.vote();  // F3
+    if (s.r == 0 && go_root) tile_fast_root_on_shard0(s, a);
+    s.vote();  // F4 (or shard 0 has failed)
+    tile_fast_take_root(s, ncand);
+    levels_and_result(s, a, ex, true);
+  } else if (!a.batch) {
+    g->root_taken_count[s.r] = 0;
+    root_step(s, a, tile_root_ops(a, ex));  // J, or the turn
+    levels_and_result(s, a, ex, false);
+  } else if (fast) {
+    // (a failed shard goes on: a batch keeps every shard's tiler in step with the collective decisions)
+    const bool first = g->fast_start < 0;  // (read before F1; shard 0 writes it after that barrier)
+    batch_fast_index(s, a, ex, first);
+    // (a level that cannot be had stays as computed: swz_tiler_shard_set_start_level refuses it on every shard)
+    if (first) fast_start_vote(s, a.params->fast_concurrency, &g->fast_start, [](int, int32_t) {});  // F1, F2
+    if (s.ok) s.swz(swz_tiler_shard_set_start_level(g->tiler[s.r], g->fast_start));
+    s.stamp(2);
+    batch_levels(s, a);
+  } else {
+    root_step(s, a, batch_root_ops(a, ex));  // J, or the turn
+    batch_levels(s, a);
   }
-  } else if (proceed) {
-    // 3'. one batch of the shard's tiler (swz_tiler_shard_*): the root's take-all / sample decision uses the counts of
-    // the WHOLE root (cached points anywhere force sampling, TilingAlgorithms.cpp:272-275); for MIN_DISTANCE the greedy
-    // order visits the shards in turn, each with the root files of the lower ones -- as they are after this batch --
-    // as ghosts.  4'. the levels below are local.
-    swz_tiler* t = g->tiler[r];
-    auto tiler_try = [&](int st) {
-      if (ok && st != SWZ_OK) ok = fail(g, r, st, swz_last_error(c));
-    };
-    stamp(1);  // (the batch path stamps like the single-batch one: root step begun / done, levels done -- for FAST, which has
-               // no root step per batch, "root" is the indexing of the batch and the vote on the start level)
-    if (g->tparams.strategy == SWZ_FAST) {
-      // TilingAlgorithmV3: no root step per batch.  The start level comes from the FIRST batch's distribution over all
-      // shards (TilingAlgorithms.cpp:1473-1535) and is kept (:1230-1236).
-      const bool first = g->fast_start < 0;  // (read before the first barrier below; shard 0 writes it after that barrier)
-      swz_tiler_shard_info info{global_points, 0, nullptr, 0};
-      uint64_t have = 0;
-      if (ok && global_points < g->tparams.fast_concurrency) ok = fail(g, r, SWZ_ERR_BAD_ARG, "FAST: a batch needs at least fast_concurrency points");
-      if (ok) tiler_try(swz_tiler_shard_begin_device(t, recv, m, &recv_attr, &info, &have));
-      if (first) {
-        g->hist[r].assign(1u << 18, 0u);
-        if (ok) tiler_try(swz_tiler_shard_fast_histogram(t, g->hist[r].data()));
-        g->barrier.wait();
-        if (r == 0) {
-          std::vector<uint64_t> sum(1u << 18, 0);
-          for (int s = 0; s < N; ++s)
-            for (uint32_t b = 0; b < (1u << 18); ++b) sum[b] += g->hist[s][b];
-          int32_t S = -1;
-          (void)swz_fast_start_level_from_counts(sum.data(), g->tparams.fast_concurrency, &S);
-          g->fast_start = S;
-        }
-        g->barrier.wait();
-      }
-      if (ok) tiler_try(swz_tiler_shard_set_start_level(t, g->fast_start));
-      stamp(2);
-      swz_tile_stats stats{};
-      if (ok) tiler_try(swz_tiler_shard_finish(t, &stats));
-      if (a.stats) *a.stats = stats;
-      (void)hipStreamSynchronize(c->stream);
-      stamp(3);
-    } else {
-    uint64_t root_before = 0;
-    for (int s = 0; s < N; ++s) root_before += g->root_stored[s];
-    const bool sample = root_before > 0 || global_points + root_before > g->tparams.max_points_per_node;
-    const bool sequential_root = g->tparams.sampler == SWZ_MIN_DISTANCE && sample && global_points > 0;
-    swz_tiler_shard_info info{global_points, root_before, nullptr, 0};
-    uint64_t have = 0;
-    if (!sequential_root) {
-      if (ok) tiler_try(swz_tiler_shard_begin_device(t, recv, m, &recv_attr, &info, &have));
-    } else if (N > 1 && g->peer_access && joint_root_possible(c, g->tparams, g->tbmin, g->tbmax)) {
-      // All shards sweep the root level of their tilers -- the batch's points merged with the shard's part of the root's
-      // file -- at the same time; a cell at the face of a lower octant reads that shard's records through peer access, exact
-      // positions through its working index (MdPeerView::aidx).  No ghosts, no turns: like swz_group_tile.
-      swz::MdShardRoot sr;
-      sr.shard = r;
-      sr.shards = N;
-      sr.views = g->views.data();
-      sr.barrier = group_barrier;
-      sr.barrier_arg = g;
-      g->views[r] = swz::MdPeerView{};
-      c->md_shard_root = &sr;
-      c->md_shard_root_published = true;
-      if (ok) tiler_try(swz_tiler_shard_begin_device(t, recv, m, &recv_attr, &info, &have));
-      c->md_shard_root = nullptr;
-      if (!g->views[r].entered) {  // nothing to sample here, or the call failed before its sweep met the others: meet them for it
-        g->views[r].ncells = 0;
-        g->views[r].status = ok ? SWZ_OK : SWZ_ERR_INTERNAL;
-        g->views[r].entered = 1;
-        g->barrier.wait();
-      }
-    } else {
-      {
-        std::unique_lock<std::mutex> lk(g->turn_m);
-        g->turn_cv.wait(lk, [&] { return g->turn == r; });
-      }
-      uint64_t gh = 0;
-      for (int s = 0; s < r; ++s) gh += g->root_taken_count[s];
-      double* gp = nullptr;
-      if (ok && c->get("grp_ghosts", (size_t)std::max<uint64_t>(gh, 1) * 3, &gp) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-      uint64_t at = 0;
-      for (int s = 0; s < r && ok; ++s) {
-        if (!g->root_taken_count[s]) continue;
-        GRP_HIP(hipMemcpyPeerAsync(gp + at * 3, g->devices[r], g->root_taken[s], g->devices[s], (size_t)g->root_taken_count[s] * 24, c->stream));
-        at += g->root_taken_count[s];
-      }
-      GRP_HIP(hipStreamSynchronize(c->stream));
-      info.d_ghost_xyz = gh ? gp : nullptr;
-      info.num_ghosts = gh;
-      if (ok) tiler_try(swz_tiler_shard_begin_device(t, recv, m, &recv_attr, &info, &have));
-      double* mine = nullptr;
-      if (ok && c->get("grp_root_taken", (size_t)std::max<uint64_t>(have, 1) * 3, &mine) != SWZ_OK) ok = fail(g, r, SWZ_ERR_HIP, c->err);
-      if (ok && have) tiler_try(swz_tiler_level_positions_device(t, -1, mine));
-      g->root_taken[r] = mine;
-      g->root_taken_count[r] = ok ? have : 0;
-      {
-        std::lock_guard<std::mutex> lk(g->turn_m);
-        g->turn = r + 1;
-      }
-      g->turn_cv.notify_all();
-    }
-    stamp(2);
-    swz_tile_stats stats{};
-    if (ok) tiler_try(swz_tiler_shard_finish(t, &stats));
-    if (a.stats) *a.stats = stats;
-    (void)hipStreamSynchronize(c->stream);
-    stamp(3);
-    }
-  }
-  g->barrier.wait();  // ---- nobody reads a neighbour's buffers any more
-  c->md_shard_root_published = false;
+  g->barrier.wait();  // L
+  s.c->md_shard_root_published = false;
 }
 
 // flag of the i-th sorted element back to the position its element had before the sort
@@ -763,6 +855,43 @@ int swz_group_shard_timing(const swz_group* g, int shard, double ms_out[4]) {
 }
 swz_ctx* swz_group_ctx(swz_group* g, int shard) { return (g && shard >= 0 && shard < g->n) ? g->ctx[shard] : nullptr; }
 
+// One call over all shards: refuses shards that hand over different attribute columns, resets what a call shares (after
+// the caller's own `reset`, which may refuse the call), runs a thread per shard and reports the first failure.
+static int group_run_call(swz_group* g, double* const* d_xyz, const swz_attribute_columns* d_attrs, const uint64_t* n, ShardCall call,
+                          swz_group_result* results, swz_tile_stats* stats, const std::function<int()>& reset) {
+  std::fill(g->status.begin(), g->status.end(), SWZ_OK);  // (first: a call refused below leaves no shard marked as failed)
+  if (d_attrs)
+    for (int r = 1; r < g->n; ++r)
+      for (int t = 0; t < SWZ_ATTR_COUNT; ++t)
+        if ((d_attrs[r].column[t] != nullptr) != (d_attrs[0].column[t] != nullptr)) {
+          g->err = "every shard must hand over the same attribute columns";
+          return SWZ_ERR_BAD_ARG;
+        }
+  const int st = reset();
+  if (st != SWZ_OK) return st;
+  g->turn = 0;
+  g->t_call = std::chrono::steady_clock::now();  // (swz_group_shard_timing: milliseconds since this call began)
+  for (auto& t4 : g->timing) std::fill(std::begin(t4), std::end(t4), 0.0);  // a stamp a path does not reach reads 0, never an older call's
+  std::vector<std::thread> threads;
+  for (int r = 0; r < g->n; ++r) {
+    call.g = g;
+    call.r = r;
+    call.d_xyz = d_xyz[r];
+    call.n = n[r];
+    call.attrs = d_attrs ? &d_attrs[r] : nullptr;
+    call.result = results ? &results[r] : nullptr;
+    call.stats = stats ? &stats[r] : nullptr;
+    threads.emplace_back(shard_thread, call);
+  }
+  for (auto& t : threads) t.join();
+  for (int r = 0; r < g->n; ++r)
+    if (g->status[r] != SWZ_OK) {
+      g->err = "shard " + std::to_string(r) + ": " + g->status_msg[r];
+      return g->status[r];
+    }
+  return SWZ_OK;
+}
+
 int swz_group_tile(swz_group* g, double* const* d_xyz, const swz_attribute_columns* d_attrs, const uint64_t* n, const double bmin[3],
                    const double bmax[3], const swz_tile_params* params, swz_group_result* results) {
   if (!g || !d_xyz || !n || !bmin || !bmax || !params) return SWZ_ERR_BAD_ARG;
@@ -774,41 +903,18 @@ int swz_group_tile(swz_group* g, double* const* d_xyz, const swz_attribute_colum
     g->err = why;
     return SWZ_ERR_BAD_ARG;
   }
-  if (d_attrs)
-    for (int r = 1; r < g->n; ++r)
-      for (int t = 0; t < SWZ_ATTR_COUNT; ++t)
-        if ((d_attrs[r].column[t] != nullptr) != (d_attrs[0].column[t] != nullptr)) {
-          g->err = "every shard must hand over the same attribute columns";
-          return SWZ_ERR_BAD_ARG;
-        }
-  g->turn = 0;
-  g->fast_tile_start = -1;  // (group state shard 0 writes: nothing of an earlier call, failed or not, may be seen by this one)
-  g->cand_flags = nullptr;
-  g->t_call = std::chrono::steady_clock::now();
-  for (auto& t4 : g->timing) std::fill(std::begin(t4), std::end(t4), 0.0);
-  std::fill(g->status.begin(), g->status.end(), SWZ_OK);
-  std::vector<std::thread> threads;
-  for (int r = 0; r < g->n; ++r)
-    threads.emplace_back(shard_thread, ShardCall{g, r, d_xyz[r], n[r], bmin, bmax, params, d_attrs ? &d_attrs[r] : nullptr, results ? &results[r] : nullptr});
-  for (auto& t : threads) t.join();
-  for (int r = 0; r < g->n; ++r)
-    if (g->status[r] != SWZ_OK) {
-      g->err = "shard " + std::to_string(r) + ": " + g->status_msg[r];
-      return g->status[r];
-    }
-  return SWZ_OK;
+  ShardCall call{};
+  call.bmin = bmin;
+  call.bmax = bmax;
+  call.params = params;
+  return group_run_call(g, d_xyz, d_attrs, n, call, results, nullptr, [&] {
+    g->fast_tile_start = -1;  // (group state shard 0 writes: nothing of an earlier call, failed or not, may be seen by this one)
+    g->cand_flags = nullptr;
+    return SWZ_OK;
+  });
 }
 
 // ---- a data set in several batches (BASELINE config 5 from the C++ host): one swz_tiler per shard -------------------
-static int group_first_failure(swz_group* g) {
-  for (int r = 0; r < g->n; ++r)
-    if (g->status[r] != SWZ_OK) {
-      g->err = "shard " + std::to_string(r) + ": " + g->status_msg[r];
-      return g->status[r];
-    }
-  return SWZ_OK;
-}
-
 int swz_group_tiler_open(swz_group* g, const double bmin[3], const double bmax[3], const swz_tile_params* params,
                          uint64_t capacity_hint_per_shard) {
   if (!g || !bmin || !bmax || !params) return SWZ_ERR_BAD_ARG;
@@ -865,36 +971,26 @@ int swz_group_add_batch(swz_group* g, double* const* d_xyz, const swz_attribute_
     g->err = "swz_group_add_batch: no data set is open (swz_group_tiler_open)";
     return SWZ_ERR_BAD_ARG;
   }
-  if (d_attrs)
-    for (int r = 1; r < g->n; ++r)
-      for (int t = 0; t < SWZ_ATTR_COUNT; ++t)
-        if ((d_attrs[r].column[t] != nullptr) != (d_attrs[0].column[t] != nullptr)) {
-          g->err = "every shard must hand over the same attribute columns";
-          return SWZ_ERR_BAD_ARG;
-        }
-  for (int r = 0; r < g->n; ++r) {
-    (void)hipSetDevice(g->devices[r]);
-    const int st = swz_tiler_level_count(g->tiler[r], -1, &g->root_stored[r]);
-    if (st != SWZ_OK) {
-      g->err = "shard " + std::to_string(r) + ": " + swz_last_error(g->ctx[r]);
-      return st;
+  ShardCall call{};
+  call.bmin = g->tbmin;
+  call.bmax = g->tbmax;
+  call.params = &g->tparams;
+  call.batch = true;
+  const int st = group_run_call(g, d_xyz, d_attrs, n, call, nullptr, stats, [&] {
+    for (int r = 0; r < g->n; ++r) {
+      (void)hipSetDevice(g->devices[r]);
+      const int rc = swz_tiler_level_count(g->tiler[r], -1, &g->root_stored[r]);
+      if (rc != SWZ_OK) {
+        g->err = "shard " + std::to_string(r) + ": " + swz_last_error(g->ctx[r]);
+        return rc;
+      }
     }
-  }
-  g->turn = 0;
-  g->t_call = std::chrono::steady_clock::now();  // (swz_group_shard_timing: milliseconds since this batch's call began)
-  for (auto& t4 : g->timing) std::fill(std::begin(t4), std::end(t4), 0.0);  // a stamp a path does not reach reads 0, never an older call's
-  std::fill(g->status.begin(), g->status.end(), SWZ_OK);
-  std::fill(g->root_taken_count.begin(), g->root_taken_count.end(), 0);
-  std::vector<std::thread> threads;
-  for (int r = 0; r < g->n; ++r) {
-    ShardCall call{g, r, d_xyz[r], n[r], g->tbmin, g->tbmax, &g->tparams, d_attrs ? &d_attrs[r] : nullptr, nullptr};
-    call.batch = true;
-    call.stats = stats ? &stats[r] : nullptr;
-    threads.emplace_back(shard_thread, call);
-  }
-  for (auto& t : threads) t.join();
-  const int st = group_first_failure(g);
-  if (st != SWZ_OK)  // the shards that did not fail have committed the batch and the failing one has not: nobody goes on
+    std::fill(g->root_taken_count.begin(), g->root_taken_count.end(), 0);
+    return (int)SWZ_OK;
+  });
+  // the shards that did not fail have committed the batch and the failing one has not: nobody goes on (a call refused
+  // before its threads started has marked no shard and changed nothing)
+  if (st != SWZ_OK && !all_ok(g))
     for (int r = 0; r < g->n; ++r) (void)swz_tiler_poison(g->tiler[r], ("a shard of the group failed to tile a batch: " + g->err).c_str());
   return st;
 }
@@ -983,6 +1079,63 @@ int swz_group_tile_staged(swz_group* g, swz_tile_stats* stats) {
   return swz_group_add_batch(g, xyz.data(), g->stage_mask ? attrs.data() : nullptr, sb.n.data(), stats);
 }
 
+// a failure of shard r while the data set is finalized: nobody goes on
+static int finalize_fail(swz_group* g, int r, int rc) {
+  g->err = "shard " + std::to_string(r) + ": " + swz_last_error(g->ctx[r]);
+  for (int s = 0; s < g->n; ++s) (void)swz_tiler_poison(g->tiler[s], ("the group failed to finalize: " + g->err).c_str());
+  return rc;
+}
+
+// The root of TilingAlgorithmV3::finalize (reconstruct_single_node, :1661-1715) samples what its eight children hold,
+// and they lie on different shards: their files come together on shard 0 in shard order (= octant order: the order
+// the reference appends them in), are indexed against the root bounds and sampled with AlwaysAdhereToMinSpacing there.
+// *d_flags0: one flag per row, in the order the rows came in.
+static int finalize_fast_root_on_shard0(swz_group* g, const std::vector<uint64_t>& cnt, const std::vector<uint64_t>& off, uint8_t** d_flags0) {
+  const uint64_t total = off[g->n];
+  swz_ctx* c0 = g->ctx[0];
+  (void)hipSetDevice(g->devices[0]);
+  double* all = nullptr;
+  uint64_t *keys = nullptr, *skeys = nullptr;
+  uint32_t* perm = nullptr;
+  uint8_t* taken = nullptr;
+  if (c0->get("grp_root_xyz", (size_t)total * 3, &all) != SWZ_OK || c0->get("grp_root_keys", (size_t)total, &keys) != SWZ_OK ||
+      c0->get("grp_root_skeys", (size_t)total, &skeys) != SWZ_OK || c0->get("grp_root_perm", (size_t)total, &perm) != SWZ_OK ||
+      c0->get("grp_root_taken", (size_t)total, &taken) != SWZ_OK || c0->get("grp_root_flags", (size_t)total, d_flags0) != SWZ_OK)
+    return finalize_fail(g, 0, SWZ_ERR_HIP);
+  std::vector<const void*> files(g->n, nullptr);
+  for (int r = 0; r < g->n; ++r) {
+    if (!cnt[r]) continue;
+    (void)hipSetDevice(g->devices[r]);
+    swz_ctx* c = g->ctx[r];
+    double* mine = nullptr;
+    if (c->get("grp_l0_xyz", (size_t)cnt[r] * 3, &mine) != SWZ_OK) return finalize_fail(g, r, SWZ_ERR_HIP);
+    const int rc = swz_tiler_level_positions_device(g->tiler[r], 0, mine);
+    if (rc != SWZ_OK) return finalize_fail(g, r, rc);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) {
+      c->err = "copy of the level-0 file to shard 0 failed";
+      return finalize_fail(g, r, SWZ_ERR_HIP);
+    }
+    files[r] = mine;
+  }
+  (void)hipSetDevice(g->devices[0]);
+  if (rows_to_shard0(g, cnt, off, {{all, files, 24}}) != hipSuccess) {
+    c0->err = "copy of the level-0 files to shard 0 failed";
+    return finalize_fail(g, 0, SWZ_ERR_HIP);
+  }
+  int rc = swz_morton_encode_device(c0, all, total, g->tbmin, g->tbmax, keys);
+  if (rc == SWZ_OK) rc = swz_sort_by_key_device(c0, keys, total, perm, skeys);
+  if (rc == SWZ_OK)
+    rc = swz::sample_points_device(c0, g->tparams.sampler, g->tparams.max_points_per_node, skeys, perm, (uint32_t)total, all, 0, -1, g->tbmin,
+                                   g->tbmax, g->tparams.spacing_at_root, SWZ_ALWAYS_ADHERE_TO_MIN_SPACING, taken, nullptr);
+  if (rc != SWZ_OK) return finalize_fail(g, 0, rc);
+  hipLaunchKernelGGL(grp_unsort_flags_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, c0->stream, perm, taken, (uint32_t)total, *d_flags0);
+  if (hipStreamSynchronize(c0->stream) != hipSuccess) {
+    c0->err = "root reconstruction failed on the device";
+    return finalize_fail(g, 0, SWZ_ERR_HIP);
+  }
+  return SWZ_OK;
+}
+
 int swz_group_finalize(swz_group* g, swz_tile_stats* stats) {
   if (!g) return SWZ_ERR_BAD_ARG;
   if (g->tiler.empty() || !g->staged.empty()) {
@@ -990,105 +1143,52 @@ int swz_group_finalize(swz_group* g, swz_tile_stats* stats) {
     return SWZ_ERR_BAD_ARG;
   }
   const bool fast = g->tparams.strategy == SWZ_FAST && g->fast_start > 0;
-  auto shard_fail = [&](int r, int rc) {
-    g->err = "shard " + std::to_string(r) + ": " + swz_last_error(g->ctx[r]);
-    for (int s = 0; s < g->n; ++s) (void)swz_tiler_poison(g->tiler[s], ("the group failed to finalize: " + g->err).c_str());
-    return rc;
-  };
   for (int r = 0; r < g->n; ++r) {
     (void)hipSetDevice(g->devices[r]);
     swz_tile_stats st{};
     const int rc = fast ? swz_tiler_shard_fast_finalize_local(g->tiler[r], &st) : swz_tiler_finalize(g->tiler[r], &st);
-    if (rc != SWZ_OK) return shard_fail(r, rc);
+    if (rc != SWZ_OK) return finalize_fail(g, r, rc);
     if (stats) stats[r] = st;
   }
   if (!fast) return SWZ_OK;
-  // The root of TilingAlgorithmV3::finalize (reconstruct_single_node, :1661-1715) samples what its eight children hold,
-  // and they lie on different shards: their files come together on shard 0 in shard order (= octant order: the order
-  // the reference appends them in), are indexed against the root bounds and sampled with AlwaysAdhereToMinSpacing there;
-  // every shard keeps the part of the root's file that comes from its own points.
+  // FAST: the root is rebuilt from the level-0 files of all shards on shard 0; every shard keeps the part of the root's
+  // file that comes from its own points
   std::vector<uint64_t> cnt(g->n, 0), off(g->n + 1, 0);
   for (int r = 0; r < g->n; ++r) {
     (void)hipSetDevice(g->devices[r]);
     const int rc = swz_tiler_level_count(g->tiler[r], 0, &cnt[r]);
-    if (rc != SWZ_OK) return shard_fail(r, rc);
+    if (rc != SWZ_OK) return finalize_fail(g, r, rc);
     off[r + 1] = off[r] + cnt[r];
   }
-  const uint64_t total = off[g->n];
-  swz_ctx* c0 = g->ctx[0];
   uint8_t* d_flags0 = nullptr;
-  if (total) {
-    if (total > 0xFFFF0000ull) {
-      g->err = "more than 2^32-65536 points in the level-0 files";
-      return SWZ_ERR_TOO_MANY_POINTS;
-    }
-    (void)hipSetDevice(g->devices[0]);
-    double* all = nullptr;
-    uint64_t *keys = nullptr, *skeys = nullptr;
-    uint32_t* perm = nullptr;
-    uint8_t* taken = nullptr;
-    if (c0->get("grp_root_xyz", (size_t)total * 3, &all) != SWZ_OK || c0->get("grp_root_keys", (size_t)total, &keys) != SWZ_OK ||
-        c0->get("grp_root_skeys", (size_t)total, &skeys) != SWZ_OK || c0->get("grp_root_perm", (size_t)total, &perm) != SWZ_OK ||
-        c0->get("grp_root_taken", (size_t)total, &taken) != SWZ_OK || c0->get("grp_root_flags", (size_t)total, &d_flags0) != SWZ_OK)
-      return shard_fail(0, SWZ_ERR_HIP);
-    // (the peer copies below run on the default stream: nothing queued on shard 0's own stream -- the SWZ_POISON fill of a
-    // buffer that has just been allocated -- may still be writing the destination)
-    (void)hipStreamSynchronize(c0->stream);
-    for (int r = 0; r < g->n; ++r) {
-      if (!cnt[r]) continue;
-      (void)hipSetDevice(g->devices[r]);
-      swz_ctx* c = g->ctx[r];
-      double* mine = nullptr;
-      if (c->get("grp_l0_xyz", (size_t)cnt[r] * 3, &mine) != SWZ_OK) return shard_fail(r, SWZ_ERR_HIP);
-      const int rc = swz_tiler_level_positions_device(g->tiler[r], 0, mine);
-      if (rc != SWZ_OK) return shard_fail(r, rc);
-      if (hipStreamSynchronize(c->stream) != hipSuccess ||
-          hipMemcpyPeer(all + off[r] * 3, g->devices[0], mine, g->devices[r], (size_t)cnt[r] * 24) != hipSuccess) {
-        c->err = "copy of the level-0 file to shard 0 failed";
-        return shard_fail(r, SWZ_ERR_HIP);
-      }
-    }
-    (void)hipSetDevice(g->devices[0]);
-    (void)hipDeviceSynchronize();  // (a device-to-device hipMemcpyPeer may return before it is done; shard 0's stream does not wait for it)
-    int rc = swz_morton_encode_device(c0, all, total, g->tbmin, g->tbmax, keys);
-    if (rc == SWZ_OK) rc = swz_sort_by_key_device(c0, keys, total, perm, skeys);
-    if (rc == SWZ_OK)
-      rc = swz::sample_points_device(c0, g->tparams.sampler, g->tparams.max_points_per_node, skeys, perm, (uint32_t)total, all, 0, -1, g->tbmin,
-                                     g->tbmax, g->tparams.spacing_at_root, SWZ_ALWAYS_ADHERE_TO_MIN_SPACING, taken, nullptr);
-    if (rc != SWZ_OK) return shard_fail(0, rc);
-    hipLaunchKernelGGL(grp_unsort_flags_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, c0->stream, perm, taken, (uint32_t)total, d_flags0);
-    if (hipStreamSynchronize(c0->stream) != hipSuccess) {
-      c0->err = "root reconstruction failed on the device";
-      return shard_fail(0, SWZ_ERR_HIP);
-    }
+  if (off[g->n] > 0xFFFF0000ull) {
+    g->err = "more than 2^32-65536 points in the level-0 files";
+    return SWZ_ERR_TOO_MANY_POINTS;
+  }
+  if (off[g->n]) {
+    const int rc = finalize_fast_root_on_shard0(g, cnt, off, &d_flags0);
+    if (rc != SWZ_OK) return rc;
   }
   for (int r = 0; r < g->n; ++r) {
     (void)hipSetDevice(g->devices[r]);
     swz_ctx* c = g->ctx[r];
-    uint8_t* mine = nullptr;
-    if (cnt[r]) {
-      if (r == 0) {
-        mine = d_flags0;
-      } else {
-        if (c->get("grp_l0_flags", (size_t)cnt[r], &mine) != SWZ_OK) return shard_fail(r, SWZ_ERR_HIP);
-        (void)hipStreamSynchronize(c->stream);  // (as above: the copy is not ordered with this shard's stream)
-        if (hipMemcpyPeer(mine, g->devices[r], d_flags0 + off[r], g->devices[0], (size_t)cnt[r]) != hipSuccess) {
-          c->err = "copy of the root flags failed";
-          return shard_fail(r, SWZ_ERR_HIP);
-        }
-        (void)hipDeviceSynchronize();
+    uint8_t* mine = (r == 0 && cnt[0]) ? d_flags0 : nullptr;
+    if (cnt[r] && r != 0) {
+      if (c->get("grp_l0_flags", (size_t)cnt[r], &mine) != SWZ_OK) return finalize_fail(g, r, SWZ_ERR_HIP);
+      if (flags_to_shard(g, r, mine, d_flags0 + off[r], cnt[r]) != hipSuccess) {
+        c->err = "copy of the root flags failed";
+        return finalize_fail(g, r, SWZ_ERR_HIP);
       }
     }
     const int rc = swz_tiler_shard_fast_set_root(g->tiler[r], mine);
-    if (rc != SWZ_OK) return shard_fail(r, rc);
+    if (rc != SWZ_OK) return finalize_fail(g, r, rc);
   }
   return SWZ_OK;
 }
 
-
 // ------------------------------------------------------------------------- the joint root for one PROCESS per GPU
 // swz_group sweeps the MIN_DISTANCE root with all shards at once because its shards share an address space.  A driver
-// with one process per GPU (torch.distributed) gets the same through IPC: inside swz_shard_begin_device every rank
+// with one process per GPU (torch.distributed) gets the same through IPC: inside the begin call of its batch every rank
 // exports the arrays of its root level (hipIpcGetMemHandle on the allocations they live in + offsets), the driver's
 // all-gather callback passes the blobs round, and every rank maps the arrays of the LOWER ranks (hipIpcOpenMemHandle).
 // From there on the sweep is the one of swz_mdkeys.hip: remote records bracketed by the owner's round word, system-scope
@@ -1313,7 +1413,7 @@ int swz_shard_joint_root_begin(swz_ctx* c, int shard, int shards, swz_exchange_f
   return SWZ_OK;
 }
 
-// A rank whose swz_shard_begin_device did not reach the sweep (no points, or an error before it) meets the others here.
+// A rank whose begin call did not reach the sweep (no points, or an error before it) meets the others here.
 int swz_shard_joint_root_meet(swz_ctx* c, int ok) {
   if (!c) return SWZ_ERR_BAD_ARG;
   JointState* js = nullptr;
