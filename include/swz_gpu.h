@@ -961,6 +961,68 @@ int swz_group_add_batch(swz_group* group, double* const* d_xyz, const swz_attrib
 int swz_group_stage_batch(swz_group* group, const double* const* xyz_host, const swz_attribute_columns* attrs_host, const uint64_t* n);
 int swz_group_tile_staged(swz_group* group, swz_tile_stats* stats_per_shard);
 int swz_group_finalize(swz_group* group, swz_tile_stats* stats_per_shard);
+/* ---- the node table and the output of a data set tiled on a group.
+ *   swz_merge_shard_node_tables (host, no GPU): the tables swz_tiler_node_table gives for the shards' tilers, merged into the
+ *     table a single tiler fed the same batches gives.  Order: swz_tiler_node_table lists level after level, and inside a
+ *     level the runs of equal node prefix of a store that ascends by it -- ascending node key, the key being the Morton key
+ *     with the bits below the node's level cleared.  A re-rooted subtree keeps that rule: its nodes carry the key of the node
+ *     that was re-rooted with the child octants appended at their ABSOLUTE levels (swz_treroot.hip), and every entry of such a
+ *     node carries the node's key, so the store of a level still ascends by node key.  The merged table is therefore ordered
+ *     by (level, node key), whatever the shards' tables contain.  The root (level -1) appears once, its count the sum of
+ *     the shards' parts, with shard_out -1; for every other node shard_out is the shard whose table lists it.  A node below
+ *     the root on two shards, or listed twice by one, is SWZ_ERR_INTERNAL.  *num_nodes_out is always set; max_nodes too small
+ *     is SWZ_ERR_BAD_ARG; with every output array NULL only the count is given (max_nodes is ignored).  shard_out alone may
+ *     be NULL.
+ *   swz_group_node_table: the same from the tilers of an open data set (swz_group_tiler_open).
+ *   swz_group_write_output: the directory swz_tiler_write_output writes for a single tiler fed the same batches -- the same
+ *     file names and the same bytes, metadata included.  Preconditions: a data set is open, no batch is staged on the group,
+ *     and on every shard's tiler what swz_tiler_write_output asks (not poisoned, nothing staged or open).  What that call
+ *     refuses with SWZ_ERR_BAD_ARG (an unknown format, a mask naming a column the batches did not carry, an rgb_mapping
+ *     without intensities, a global_offset that is not finite, a dir that cannot be created) is refused ONCE, before any
+ *     directory or file is created.  A failed write names the file through swz_group_last_error, poisons nothing and leaves
+ *     the group usable.
+ *     Below the root every node lives on one shard: each shard streams its own nodes on its own host thread, device and copy
+ *     stream with its own two chunk images, all into the same dir (dir/ept-data for ENTWINE_LAS); boxes, LAS scales and
+ *     offsets are swz_node_bounds of the group's root box.  The root's file is the concatenation of the shards' parts in
+ *     shard order (after a FAST swz_group_finalize too): every shard gathers the rows of its part (positions and the masked
+ *     columns, swz_gather_payload_device), after a status vote the parts are copied to shard 0, which packs them as a
+ *     one-node table with the format's pack call and writes the file through its own chunk images (the root's size enters
+ *     their maximum).  A root without points writes no file.  The metadata is written once, from the merged table, after
+ *     every shard's files are done and a second vote is clean.
+ *     Threads: SWZ_BIN_WRITER_THREADS (read from shard 0's context) is the budget of the whole call, divided among the
+ *     shards with at least one each.  chunk_points 0 reads SWZ_OUTPUT_CHUNK_POINTS from every shard's own context.
+ *     stats_per_shard (num_shards entries or NULL): as swz_tiler_write_output fills them for the shard's own nodes (shard
+ *     0: the root's file included; nodes and stored_points of the shard's own table).  total (or NULL): nodes and stored
+ *     points of the merged table, bytes and chunks summed, wall_ms of the call, the other *_ms the maximum over the shards.
+ *   swz_group_add_las_files: swz_tiler_add_las_files for the group.  The scan (swz_las_scan_files), the refusals before
+ *     anything is read (the mask rules, SWZ_ATTR_NORMAL, the box check with its 4 ulp against the group's root box,
+ *     SWZ_ERR_TOO_MANY_POINTS against the per-shard limit in the worst case that one shard receives everything), the cuts
+ *     (swz_input_batches, under FAST min_last = fast_concurrency, checked for the whole batch) and shift_to_center are that
+ *     call's.  Refused too: no data set open, a batch staged on the group or on a shard's tiler, a tiler that is poisoned or
+ *     finalized.  Per batch the point range is cut into num_shards consecutive slices in shard order (slice s: the points
+ *     [P * s / N, P * (s + 1) / N) of the batch's P); a slice is a list of swz_las_segment.  Shard s's share of the reader
+ *     threads preads its slice into one of its two page-locked images, its copy stream moves the image to its device and the
+ *     segment kernel decodes it there into one of the shard's two stage buffers (positions and the masked columns: the
+ *     buffers of swz_group_stage_batch), and the batch goes the way of swz_group_tile_staged -- encode, group, one exchange,
+ *     root, levels.  Read, copy and decode of batch k + 1 run beside the tiling of batch k.  Host and device hold two raw
+ *     slice images and two decoded batch buffers per shard at most, whatever the size of the data set.
+ *     Threads: SWZ_INPUT_READER_THREADS (read from shard 0's context) is the budget of the whole call, divided among the
+ *     shards with at least one each.
+ *     A read that fails ends the stream after the batch in flight and names the file (swz_group_last_error).  A failure
+ *     before the first batch is tiled leaves every tiler as it was, a later one poisons all of them as a failed group batch
+ *     does.  The call does not finalize.  stats (may be NULL): the fields of the single call -- files, points, batches and
+ *     bytes_read of the whole call, read_ms / copy_ms / decode_ms the maximum over the shards of their sums over the
+ *     batches, tile_ms the tiling calls', wait_ms the time the call waited for its readers. */
+int swz_group_add_las_files(swz_group* group, const char* const* paths, uint64_t num_files, const swz_input_params* params,
+                            swz_input_stats* stats);
+int swz_merge_shard_node_tables(int num_shards, const uint64_t* num_nodes, const int8_t* const* node_level,
+                                const uint64_t* const* node_key, const uint64_t* const* node_count, uint64_t max_nodes,
+                                int8_t* level_out, uint64_t* key_out, uint64_t* count_out, int32_t* shard_out,
+                                uint64_t* num_nodes_out);
+int swz_group_node_table(swz_group* group, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out, uint64_t* count_out,
+                         int32_t* shard_out, uint64_t* num_nodes_out);
+int swz_group_write_output(swz_group* group, const char* dir, const swz_output_params* params,
+                           swz_output_stats* stats_per_shard, swz_output_stats* total);
 
 /* ---- the MIN_DISTANCE root of a sharded batch swept by all ranks at once, ONE PROCESS PER GPU (the torch driver;
  * swz_group_tile does this by itself for the shards of one process).  Instead of the chain of ghosts from rank to rank

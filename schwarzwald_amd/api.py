@@ -535,6 +535,44 @@ def output_chunks(counts, chunk_points):
     return first
 
 
+def merge_shard_node_tables(tables, max_nodes=None, count_only=False):
+    """swz_merge_shard_node_tables (host, no GPU): `tables` holds one (level, key, count) triple of arrays per shard, as
+    swz_tiler_node_table gives them for the shard's tiler.  Returns (level, key, count, shard) of the merged table, ordered by
+    (level, node key): one root entry whose count is the sum of the parts with shard -1, the owner for every other node.
+    count_only: every output is NULL and only the number of nodes comes back.  max_nodes: the capacity of the outputs
+    (default: exactly what is needed).  ValueError for a capacity that is too small, RuntimeError for a node below the root
+    that lies on two shards."""
+    L = load_library()
+    n = len(tables)
+    lv = [np.ascontiguousarray(t[0], dtype=np.int8).reshape(-1) for t in tables]
+    ky = [np.ascontiguousarray(t[1], dtype=np.uint64).reshape(-1) for t in tables]
+    ct = [np.ascontiguousarray(t[2], dtype=np.uint64).reshape(-1) for t in tables]
+    nn = (C.c_uint64 * max(n, 1))(*[a.shape[0] for a in lv])
+    pl = (_i8p * max(n, 1))(*[a.ctypes.data_as(_i8p) for a in lv])
+    pk = (_u64p * max(n, 1))(*[a.ctypes.data_as(_u64p) for a in ky])
+    pc = (_u64p * max(n, 1))(*[a.ctypes.data_as(_u64p) for a in ct])
+    num = C.c_uint64()
+
+    def check(st):
+        if st == 7:
+            raise RuntimeError("a node below the root lies on two shards")
+        if st != 0:
+            raise ValueError("swz_merge_shard_node_tables: bad argument (max_nodes too small?)")
+
+    check(L.swz_merge_shard_node_tables(n, nn, pl, pk, pc, 0, None, None, None, None, C.byref(num)))
+    if count_only:
+        return int(num.value)
+    cap = int(num.value) if max_nodes is None else int(max_nodes)
+    level = np.zeros(max(cap, 1), dtype=np.int8)
+    key = np.zeros(max(cap, 1), dtype=np.uint64)
+    count = np.zeros(max(cap, 1), dtype=np.uint64)
+    shard = np.zeros(max(cap, 1), dtype=np.int32)
+    check(L.swz_merge_shard_node_tables(n, nn, pl, pk, pc, cap, level.ctypes.data_as(_i8p), key.ctypes.data_as(_u64p),
+                                        count.ctypes.data_as(_u64p), shard.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(num)))
+    m = int(num.value)
+    return level[:m], key[:m], count[:m], shard[:m]
+
+
 def las_persist_nodes(directory, nodes, image, attrs, box_min, box_max, scale, naming=LAS_NAMING_POTREE, ctx=None):
     """One LAS file per node of a node table out of a host copy of the image las_pack_device wrote.  box_min / box_max
     (num_nodes x 3) and scale (num_nodes) are the nodes' boxes and scales; naming: LAS_NAMING_POTREE or LAS_NAMING_ENTWINE."""
@@ -760,8 +798,10 @@ def load_library():
     L.swz_bin_persist_nodes_image.argtypes = [vp, C.c_char_p, C.c_uint64, _i8p, _u64p, _u64p, vp, C.c_uint64, C.c_uint32, C.c_int]
     L.swz_tiler_write_output.argtypes = [vp, C.c_char_p, C.POINTER(_OutputParams), C.POINTER(_OutputStats)]
     L.swz_output_chunks.argtypes = [C.c_uint64, _u64p, C.c_uint64, C.c_uint64, _u64p, _u64p]
+    L.swz_merge_shard_node_tables.argtypes = [C.c_int, _u64p, C.POINTER(_i8p), C.POINTER(_u64p), C.POINTER(_u64p), C.c_uint64, _i8p,
+                                              _u64p, _u64p, C.POINTER(C.c_int32), _u64p]
     for name in ("swz_bin_layout", "swz_bin_pack_device", "swz_bin_persist_nodes_image", "swz_tiler_write_output",
-                 "swz_output_chunks"):
+                 "swz_output_chunks", "swz_merge_shard_node_tables"):
         getattr(L, name).restype = C.c_int
     L.swz_node_name.argtypes = [C.c_int8, C.c_uint64, C.c_char_p]
     L.swz_node_name_entwine.argtypes = [C.c_int8, C.c_uint64, C.c_char_p]

@@ -15,7 +15,10 @@
 // encode_and_group, exchange (exchange_rccl / exchange_peer_copies), root_step (plain, root_joint, root_in_turns; what
 // differs between one batch and a tiler's batch is a RootOps), fast_start_vote, rows_to_shard0 / flags_to_shard (the
 // FAST root rebuilt on shard 0, by the threads of one batch and by swz_group_finalize), levels_and_result, batch_levels.
-// swz_group_tile and swz_group_add_batch run their threads through group_run_call.
+// swz_group_tile and swz_group_add_batch run their threads through group_run_call.  swz_group_write_output (a data set of
+// the group's tilers written in one call) has a thread per shard of its own, output_thread, over the parts of swz_toutput.h.
+// swz_group_add_las_files (a data set of LAS files read in one call) has no thread of its own: over the parts of swz_tinput.h
+// it fills the stage buffers from the shards' copy streams and hands every batch to swz_group_tile_staged.
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -32,6 +35,8 @@
 
 #include "swz_internal.h"
 #include "swz_md.h"
+#include "swz_tinput.h"
+#include "swz_toutput.h"
 
 namespace {
 
@@ -679,6 +684,8 @@ void batch_levels(Step& s, const ShardCall& a) {
 //   batch FAST, first     F1, F2 (fast_start_vote)
 //   batch FAST, later     --
 //   every path            L  nobody reads a neighbour's buffers any more; then md_shard_root_published is reset
+//   (swz_group_write_output has threads of its own, output_thread below: O1 every part of the root's file is gathered,
+//    O2 every shard's files are written)
 //
 // The stamps of swz_group_shard_timing: 0 after B3, 1 here, 2 and 3 in the steps (root_step / tile_fast_candidates /
 // batch FAST below: 2; levels_and_result / batch_levels: 3).
@@ -995,6 +1002,35 @@ int swz_group_add_batch(swz_group* g, double* const* d_xyz, const swz_attribute_
   return st;
 }
 
+static bool stage_hip(swz_group* g, int r, hipError_t e, const char* what) {
+  if (e == hipSuccess) return true;
+  g->err = "shard " + std::to_string(r) + ": " + what + ": " + hipGetErrorString(e);
+  return false;
+}
+
+// shard r's copy stream, the event of the slot and its device buffers for `rows` rows of the columns in `mask` (the device
+// of shard r is current); false: g->err.  A buffer that grows is free: the batch it held has been tiled --
+// swz_group_tile_staged returns after the shard's stream is idle.
+static bool stage_reserve(swz_group* g, int slot, int r, uint64_t rows, uint32_t mask) {
+  auto hip = [&](hipError_t e, const char* what) { return stage_hip(g, r, e, what); };
+  if (!g->copy_stream[r] && !hip(hipStreamCreateWithFlags(&g->copy_stream[r], hipStreamNonBlocking), "hipStreamCreate")) return false;
+  if (!g->copy_done[slot][r] && !hip(hipEventCreateWithFlags(&g->copy_done[slot][r], hipEventDisableTiming), "hipEventCreate")) return false;
+  if (g->stage_cap[slot][r] >= std::max<uint64_t>(rows, 1) && !(mask & ~g->stage_mask)) return true;
+  const uint64_t cap = std::max<uint64_t>(rows + rows / 8, 1);
+  if (g->stage_xyz[slot][r]) (void)hipFree(g->stage_xyz[slot][r]);
+  g->stage_xyz[slot][r] = nullptr;
+  g->stage_cap[slot][r] = 0;
+  if (!hip(hipMalloc(&g->stage_xyz[slot][r], cap * 24), "hipMalloc(stage)")) return false;
+  for (int t = 0; t < SWZ_ATTR_COUNT; ++t) {
+    if (g->stage_attr[slot][r].column[t]) (void)hipFree(g->stage_attr[slot][r].column[t]);
+    g->stage_attr[slot][r].column[t] = nullptr;
+    if ((mask >> t) & 1u)
+      if (!hip(hipMalloc(&g->stage_attr[slot][r].column[t], cap * swz_attribute_row_bytes(t)), "hipMalloc(stage column)")) return false;
+  }
+  g->stage_cap[slot][r] = cap;
+  return true;
+}
+
 // Staging: the batch is copied from pinned host memory into one of two device buffers per shard on the shard's copy
 // stream, beside whatever its tiling stream is doing (the batch before).  At most two batches are staged.
 int swz_group_stage_batch(swz_group* g, const double* const* xyz_host, const swz_attribute_columns* attrs_host, const uint64_t* n) {
@@ -1012,13 +1048,7 @@ int swz_group_stage_batch(swz_group* g, const double* const* xyz_host, const swz
   sb.n.assign(n, n + g->n);
   for (int r = 0; r < g->n; ++r) {
     (void)hipSetDevice(g->devices[r]);
-    auto hip = [&](hipError_t e, const char* what) {
-      if (e == hipSuccess) return true;
-      g->err = "shard " + std::to_string(r) + ": " + what + ": " + hipGetErrorString(e);
-      return false;
-    };
-    if (!g->copy_stream[r] && !hip(hipStreamCreateWithFlags(&g->copy_stream[r], hipStreamNonBlocking), "hipStreamCreate")) return SWZ_ERR_HIP;
-    if (!g->copy_done[slot][r] && !hip(hipEventCreateWithFlags(&g->copy_done[slot][r], hipEventDisableTiming), "hipEventCreate")) return SWZ_ERR_HIP;
+    auto hip = [&](hipError_t e, const char* what) { return stage_hip(g, r, e, what); };
     uint32_t mine = 0;
     for (int t = 0; t < SWZ_ATTR_COUNT; ++t)
       if (attrs_host && attrs_host[r].column[t]) mine |= 1u << t;
@@ -1026,20 +1056,7 @@ int swz_group_stage_batch(swz_group* g, const double* const* xyz_host, const swz
       g->err = "every shard must hand over the same attribute columns";
       return SWZ_ERR_BAD_ARG;
     }
-    if (g->stage_cap[slot][r] < std::max<uint64_t>(n[r], 1) || (mask & ~g->stage_mask)) {
-      // (the buffer is free: the batch it held has been tiled -- swz_group_tile_staged returns after the shard's stream is idle)
-      const uint64_t cap = std::max<uint64_t>(n[r] + n[r] / 8, 1);
-      if (g->stage_xyz[slot][r]) (void)hipFree(g->stage_xyz[slot][r]);
-      g->stage_xyz[slot][r] = nullptr;
-      if (!hip(hipMalloc(&g->stage_xyz[slot][r], cap * 24), "hipMalloc(stage)")) return SWZ_ERR_HIP;
-      for (int t = 0; t < SWZ_ATTR_COUNT; ++t) {
-        if (g->stage_attr[slot][r].column[t]) (void)hipFree(g->stage_attr[slot][r].column[t]);
-        g->stage_attr[slot][r].column[t] = nullptr;
-        if ((mask >> t) & 1u)
-          if (!hip(hipMalloc(&g->stage_attr[slot][r].column[t], cap * swz_attribute_row_bytes(t)), "hipMalloc(stage column)")) return SWZ_ERR_HIP;
-      }
-      g->stage_cap[slot][r] = cap;
-    }
+    if (!stage_reserve(g, slot, r, n[r], mask)) return SWZ_ERR_HIP;
     if (n[r]) {
       if (!hip(hipMemcpyAsync(g->stage_xyz[slot][r], xyz_host[r], n[r] * 24, hipMemcpyHostToDevice, g->copy_stream[r]), "hipMemcpyAsync")) return SWZ_ERR_HIP;
       for (int t = 0; t < SWZ_ATTR_COUNT; ++t)
@@ -1077,6 +1094,211 @@ int swz_group_tile_staged(swz_group* g, swz_tile_stats* stats) {
     attrs[r] = g->stage_attr[sb.slot][r];
   }
   return swz_group_add_batch(g, xyz.data(), g->stage_mask ? attrs.data() : nullptr, sb.n.data(), stats);
+}
+
+// A data set of LAS files through the group in one call: swz_tiler_add_las_files's scan, refusals and cuts ONCE
+// (swz_tinput.h), then per batch every shard reads, copies and decodes its slice of the batch's points -- consecutive
+// slices in shard order -- into one of its two stage buffers, and the batch goes the way of swz_group_tile_staged.
+int swz_group_add_las_files(swz_group* g, const char* const* paths, uint64_t num_files, const swz_input_params* params,
+                            swz_input_stats* stats) {
+  if (!g) return SWZ_ERR_BAD_ARG;
+  const char* who = "swz_group_add_las_files";
+  const auto t_wall = std::chrono::steady_clock::now();
+  auto ms_since = [](std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  };
+  if (stats) *stats = swz_input_stats{};
+  auto refuse = [&](int st, const std::string& why) {
+    g->err = why;
+    return st;
+  };
+  if (!params || (num_files && !paths)) return refuse(SWZ_ERR_BAD_ARG, "swz_group_add_las_files: NULL argument");
+  if (g->tiler.empty()) return refuse(SWZ_ERR_BAD_ARG, "swz_group_add_las_files: no data set is open (swz_group_tiler_open)");
+  if (!g->staged.empty()) return refuse(SWZ_ERR_BAD_ARG, "swz_group_add_las_files: a batch is staged or open");
+  const int N = g->n;
+  bool mask_fixed = false;
+  uint32_t mask_now = 0;
+  uint64_t points_now = 0;  // the worst case: one shard receives everything
+  for (int r = 0; r < N; ++r) {
+    const swz_tiler* t = g->tiler[r];
+    const std::string shard = "shard " + std::to_string(r) + ": ";
+    if (t->failed) return refuse(SWZ_ERR_TILER_FAILED, shard + "the tiler has failed: " + t->failed_why);
+    if (t->finalized) return refuse(SWZ_ERR_BAD_ARG, shard + "swz_tiler: batches cannot be added after finalize");
+    if (!t->staged_sizes.empty() || t->batch_open) return refuse(SWZ_ERR_BAD_ARG, shard + "swz_group_add_las_files: a batch is staged or open");
+    if (t->staged_total && !mask_fixed) {
+      mask_fixed = true;
+      mask_now = t->attr_mask;
+    }
+    points_now = std::max<uint64_t>(points_now, t->staged_total);
+  }
+  swz_ctx* c0 = g->ctx[0];
+  (void)hipSetDevice(g->devices[0]);
+  swz::LasInputPlan plan;
+  int st = swz::las_input_plan(c0, who, paths, num_files, params, g->tbmin, g->tbmax, g->tparams, mask_fixed, mask_now, points_now, &plan);
+  if (st != SWZ_OK) return refuse(st, swz_last_error(c0));
+  const uint64_t num_batches = plan.num_batches();
+  const uint32_t mask = plan.mask;
+
+  // ---- every batch's slices, the largest image and the most rows of a shard
+  std::vector<std::vector<swz::InputBatch>> slice(num_batches, std::vector<swz::InputBatch>(N));
+  std::vector<uint64_t> image_max(N, 0), rows_max(N, 0);
+  for (uint64_t j = 0; j < num_batches; ++j) {
+    const uint64_t b0 = plan.cuts[j], pts = plan.cuts[j + 1] - b0;
+    for (int r = 0; r < N; ++r) {
+      swz::las_input_image(plan, b0 + pts * (uint64_t)r / N, b0 + pts * (uint64_t)(r + 1) / N, &slice[j][r]);
+      image_max[r] = std::max(image_max[r], slice[j][r].image_bytes);
+      rows_max[r] = std::max(rows_max[r], slice[j][r].points);
+    }
+  }
+  // ---- per shard: two raw images, host and device, and the two stage buffers the slices are decoded into
+  std::vector<swz::InputBuffers> ib(N);
+  for (int r = 0; r < N; ++r) {
+    (void)hipSetDevice(g->devices[r]);
+    if ((st = ib[r].reserve(g->ctx[r], std::max<uint64_t>(image_max[r], 16), num_batches > 1)) != SWZ_OK)
+      return refuse(st, "shard " + std::to_string(r) + ": " + swz_last_error(g->ctx[r]));
+    for (int k = 0; k < (num_batches > 1 ? 2 : 1); ++k)
+      if (!stage_reserve(g, g->next_slot ^ k, r, rows_max[r], mask)) return SWZ_ERR_HIP;
+  }
+  g->stage_mask |= mask;
+
+  // ---- SWZ_INPUT_READER_THREADS is the budget of the whole call: every shard at least one
+  const long budget = std::max(1L, c0->opt_int("SWZ_INPUT_READER_THREADS", (long)std::min(32u, std::max(1u, std::thread::hardware_concurrency()))));
+  std::vector<long> reader_threads(N, 1);
+  for (int r = 0; r < N; ++r) reader_threads[r] = std::max(1L, budget / N + (r < budget % N ? 1 : 0));
+
+  // ---- the stream, as in swz_tiler_add_las_files: reads run two batches ahead of the tiling, copy + decode one
+  std::vector<double> read_ms(N, 0.0), copy_ms(N, 0.0), decode_ms(N, 0.0);
+  double tile_ms = 0, wait_ms = 0;
+  uint64_t bytes_read = 0, batches_done = 0, points_done = 0;
+  int status = SWZ_OK;
+  std::string why;
+  bool touched = false;
+  std::vector<swz::TicketRun> readers(N);
+  auto fail_stream = [&](int code, const std::string& text) {
+    if (status == SWZ_OK) {
+      status = code;
+      why = text;
+    }
+  };
+  auto start_read = [&](uint64_t j) {
+    for (int r = 0; r < N; ++r)
+      swz::las_start_read(readers[r], g->ctx[r], who, &slice[j][r], static_cast<unsigned char*>(ib[r].host[j & 1]), paths, reader_threads[r]);
+  };
+  auto wait_read = [&](uint64_t j) -> bool {
+    const auto t0 = std::chrono::steady_clock::now();
+    bool ok = true;
+    for (int r = 0; r < N; ++r) {
+      double ms = 0;
+      std::string err;
+      const int rc = readers[r].wait(&err, &ms);
+      read_ms[r] += ms;
+      if (rc != SWZ_OK) {
+        fail_stream(rc, err);
+        ok = false;
+      } else {
+        bytes_read += slice[j][r].raw_bytes;
+      }
+    }
+    wait_ms += ms_since(t0);
+    return ok;
+  };
+  // batch j: every shard's image to its device and decoded into the stage buffers of the next slot; staged like a pinned batch
+  auto enqueue = [&](uint64_t j) -> int {
+    const int slot = g->next_slot, s = (int)(j & 1);
+    swz_group::Staged sb;
+    sb.slot = slot;
+    sb.n.assign(N, 0);
+    for (int r = 0; r < N; ++r) {
+      (void)hipSetDevice(g->devices[r]);
+      const swz::InputBatch& b = slice[j][r];
+      hipStream_t cs = g->copy_stream[r];
+      auto hip = [&](hipError_t e, const char* what) { return stage_hip(g, r, e, what); };
+      if (!hip(hipEventRecord(ib[r].begin[s], cs), "hipEventRecord")) return SWZ_ERR_HIP;
+      if (b.image_bytes && !hip(hipMemcpyAsync(ib[r].device[s], ib[r].host[s], b.image_bytes, hipMemcpyHostToDevice, cs), "hipMemcpyAsync(image)")) return SWZ_ERR_HIP;
+      if (!hip(hipEventRecord(ib[r].copied[s], cs), "hipEventRecord")) return SWZ_ERR_HIP;
+      const int rc = swz::las_launch_image(g->ctx[r], cs, ib[r].device[s], b, plan.shift ? plan.ds.center : nullptr, g->stage_xyz[slot][r],
+                                           &g->stage_attr[slot][r], mask);
+      if (rc != SWZ_OK) {
+        g->err = "shard " + std::to_string(r) + ": " + swz_last_error(g->ctx[r]);
+        return rc;
+      }
+      if (!hip(hipEventRecord(ib[r].decoded[s], cs), "hipEventRecord")) return SWZ_ERR_HIP;
+      if (!hip(hipEventRecord(g->copy_done[slot][r], cs), "hipEventRecord")) return SWZ_ERR_HIP;
+      sb.n[r] = b.points;
+    }
+    g->staged.push_back(sb);
+    g->next_slot ^= 1;
+    return SWZ_OK;
+  };
+
+  start_read(0);
+  if (wait_read(0)) {
+    const int rc = enqueue(0);
+    if (rc != SWZ_OK) fail_stream(rc, g->err);
+    if (status == SWZ_OK && num_batches > 1) start_read(1);
+  }
+  for (uint64_t j = 0; j < num_batches && status == SWZ_OK; ++j) {
+    if (j + 1 < num_batches) {
+      bool next_staged = false;
+      if (wait_read(j + 1)) {
+        const int rc = enqueue(j + 1);
+        if (rc != SWZ_OK) fail_stream(rc, g->err);
+        next_staged = rc == SWZ_OK;
+      }
+      // (a read that failed: batch j, which is staged, is still tiled -- the stream stops after the running batch)
+      if (next_staged && j + 2 < num_batches) {
+        // the host images of batch j + 2 are batch j's: their copies have left them
+        bool left = true;
+        for (int r = 0; r < N && left; ++r) {
+          (void)hipSetDevice(g->devices[r]);
+          left = stage_hip(g, r, hipEventSynchronize(ib[r].copied[j & 1]), "the copy of a slice image");
+        }
+        if (!left) fail_stream(SWZ_ERR_HIP, g->err);
+        else start_read(j + 2);
+      }
+    }
+    if (g->staged.empty()) break;  // (batch j was never staged)
+    const auto t_tile = std::chrono::steady_clock::now();
+    touched = true;  // (until here the slices lie in the group's stage buffers: no tiler has seen them)
+    const int rc = swz_group_tile_staged(g, nullptr);  // (a failure here has poisoned every tiler with its own text)
+    tile_ms += ms_since(t_tile);
+    if (rc != SWZ_OK) {
+      status = rc;
+      why = g->err;
+      break;
+    }
+    for (int r = 0; r < N; ++r) {  // batch j has been decoded: its tiling waited for the event behind it
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, ib[r].begin[j & 1], ib[r].copied[j & 1]) == hipSuccess) copy_ms[r] += ms;
+      if (hipEventElapsedTime(&ms, ib[r].copied[j & 1], ib[r].decoded[j & 1]) == hipSuccess) decode_ms[r] += ms;
+    }
+    ++batches_done;
+    points_done += plan.cuts[j + 1] - plan.cuts[j];
+  }
+  for (int r = 0; r < N; ++r) {
+    if (readers[r].running()) (void)readers[r].wait(nullptr, nullptr);
+    (void)hipSetDevice(g->devices[r]);
+    if (g->copy_stream[r]) (void)hipStreamSynchronize(g->copy_stream[r]);
+  }
+  g->staged.clear();  // (a batch staged behind the one that failed is dropped)
+  if (status != SWZ_OK && touched)
+    for (int r = 0; r < N; ++r) (void)swz_tiler_poison(g->tiler[r], why.c_str());
+  if (stats) {
+    stats->files = plan.ds.readable_files;
+    stats->points = points_done;
+    stats->batches = batches_done;
+    stats->bytes_read = bytes_read;
+    for (int r = 0; r < N; ++r) {
+      stats->read_ms = std::max(stats->read_ms, read_ms[r]);
+      stats->copy_ms = std::max(stats->copy_ms, copy_ms[r]);
+      stats->decode_ms = std::max(stats->decode_ms, decode_ms[r]);
+    }
+    stats->tile_ms = tile_ms;
+    stats->wait_ms = wait_ms;
+    stats->wall_ms = ms_since(t_wall);
+  }
+  if (status != SWZ_OK) g->err = why;
+  return status;
 }
 
 // a failure of shard r while the data set is finalized: nobody goes on
@@ -1184,6 +1406,284 @@ int swz_group_finalize(swz_group* g, swz_tile_stats* stats) {
     if (rc != SWZ_OK) return finalize_fail(g, r, rc);
   }
   return SWZ_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------- the data set of a group written in one call
+// swz_group_write_output: swz_tiler_write_output's three parts (swz_toutput.h) -- validate and plan ONCE on the merged node
+// table, stream the node files per shard, write the metadata ONCE.  Barriers of a shard thread (every thread, failed or not,
+// passes both):
+//   O1  every shard's part of the root's file is gathered (then shard 0 copies the parts, packs and writes the root)
+//   O2  every shard's files are written; nobody reads a neighbour's part any more (then the call's workspace goes back)
+namespace {
+
+struct GroupOutput {  // what the threads of one call share
+  const swz_output_params* params = nullptr;
+  std::vector<swz::OutputPlan> plan;  // per shard: its own node table, the root's part first when it has one
+  std::vector<swz_tiler_info> info;
+  swz::OutputPlan root;  // the root as a one-node table (no node: the root has no points)
+  std::vector<uint64_t> part_cnt, part_off;  // rows of every shard's part of the root's file
+  std::vector<const void*> part_xyz;
+  std::vector<std::vector<const void*>> part_attr;  // [attribute][shard]
+  std::vector<long> writer_threads;
+  std::vector<swz_output_stats> stats;
+};
+
+void output_thread(swz_group* g, int r, GroupOutput* o) {
+  Step s(g, r);
+  swz_ctx* c = s.c;
+  swz_tiler* t = g->tiler[r];
+  const auto t_begin = std::chrono::steady_clock::now();
+  swz::OutputWorkspace ow{c};
+  const swz::OutputPlan& p = o->plan[r];
+  const uint64_t nn = p.count.size(), k0 = (nn && p.level[0] < 0) ? 1 : 0, ns = o->info[r].num_stored;
+  const uint64_t root_rows = o->part_off[s.N];
+  std::vector<uint64_t> first, root_first;
+  uint64_t image_max = 0, root_image = 0;
+  swz::output_cuts(c, p, k0, nn, o->params->chunk_points, &first, &image_max);
+  if (r == 0 && root_rows) swz::output_cuts(c, o->root, 0, 1, o->params->chunk_points, &root_first, &root_image);
+
+  // ---- the ids of all files, and this shard's part of the root's file as rows
+  swz::OutputSource src;
+  src.xyz = t->pool_xyz;
+  for (int a = 0; a < SWZ_ATTR_COUNT; ++a) src.in.column[a] = (t->attr_mask & (1u << a)) ? t->pool_attr[a] : nullptr;
+  uint32_t* d_ids = s.buf<uint32_t>("out_ids", (size_t)std::max<uint64_t>(ns, 1));
+  src.ids = d_ids;
+  if (s.ok && ns) s.swz(swz_tiler_export_device(t, nullptr, d_ids, nullptr));
+  const uint64_t m = o->part_cnt[r];
+  if (m) {
+    swz_attribute_columns masked{}, part{};
+    double* part_xyz = s.buf<double>("out_part_xyz", (size_t)m * 3);
+    for (int a = 0; a < SWZ_ATTR_COUNT; ++a) {
+      if (!((o->params->attribute_mask >> a) & 1u)) continue;
+      masked.column[a] = src.in.column[a];
+      part.column[a] = s.buf<void>("out_part_attr" + std::to_string(a), (size_t)m * swz_attribute_row_bytes(a));
+      o->part_attr[a][r] = part.column[a];
+    }
+    if (s.ok) s.swz(swz_gather_payload_device(c, d_ids, nullptr, m, t->pool_xyz, &masked, part_xyz, &part));  // (the root's part is the first file)
+    if (s.ok) s.hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize(root part)");
+    o->part_xyz[r] = part_xyz;
+  }
+  const bool go_root = s.vote();  // O1
+
+  swz::OutputStreamStats ss;
+  swz::OutputImages images;
+  const uint64_t image_bytes = std::max(image_max, root_image);
+  if (s.ok && image_bytes) s.swz(images.reserve(c, image_bytes, first.size() > 2));
+  if (r == 0 && go_root && s.ok && root_rows) {
+    swz::OutputSource all;
+    double* all_xyz = s.buf<double>("out_root_xyz", (size_t)root_rows * 3);
+    uint32_t* iota = s.buf<uint32_t>("out_root_ids", (size_t)root_rows);
+    std::vector<PeerColumn> columns;
+    columns.push_back({all_xyz, o->part_xyz, 24});
+    for (int a = 0; a < SWZ_ATTR_COUNT; ++a) {
+      if (!((o->params->attribute_mask >> a) & 1u)) continue;
+      all.in.column[a] = s.buf<void>("out_root_attr" + std::to_string(a), (size_t)root_rows * swz_attribute_row_bytes(a));
+      columns.push_back({all.in.column[a], o->part_attr[a], swz_attribute_row_bytes(a)});
+    }
+    all.xyz = all_xyz;
+    all.ids = iota;
+    if (s.ok) s.hip(rows_to_shard0(g, o->part_cnt, o->part_off, columns), "copy of the root's parts to shard 0");
+    if (s.ok) {
+      hipLaunchKernelGGL(grp_iota_kernel, dim3((uint32_t)((root_rows + 255) / 256)), dim3(256), 0, c->stream, iota, (uint32_t)root_rows);
+      s.hip(hipGetLastError(), "the ids of the root's rows");
+    }
+    if (s.ok) s.swz(swz::output_stream(c, o->root, root_first, all, images, o->writer_threads[r], &ss));
+  }
+  if (s.ok && image_max) s.swz(swz::output_stream(c, p, first, src, images, o->writer_threads[r], &ss));
+  (void)hipStreamSynchronize(c->stream);
+  g->barrier.wait();  // O2
+  swz_output_stats& st = o->stats[r];
+  st.nodes = nn;
+  st.stored_points = ns;
+  st.bytes_written = ss.bytes_written;
+  st.chunks = ss.chunks;
+  st.pack_ms = ss.pack_ms;
+  st.copy_ms = ss.copy_ms;
+  st.write_ms = ss.write_ms;
+  st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+}
+
+// the node tables of the shards' tilers; *st_shard: the shard whose tiler refused
+int shard_node_tables(swz_group* g, std::vector<std::vector<int8_t>>& level, std::vector<std::vector<uint64_t>>& key,
+                      std::vector<std::vector<uint64_t>>& count) {
+  level.assign(g->n, {});
+  key.assign(g->n, {});
+  count.assign(g->n, {});
+  for (int r = 0; r < g->n; ++r) {
+    (void)hipSetDevice(g->devices[r]);
+    swz_tiler_info info{};
+    int st = swz_tiler_get_info(g->tiler[r], &info);
+    const uint64_t cap = std::max<uint64_t>(info.num_nodes, 1);
+    std::vector<uint64_t> offset(cap);
+    level[r].resize(cap);
+    key[r].resize(cap);
+    count[r].resize(cap);
+    uint64_t nn = 0;
+    if (st == SWZ_OK) st = swz_tiler_node_table(g->tiler[r], cap, level[r].data(), key[r].data(), offset.data(), count[r].data(), &nn);
+    if (st != SWZ_OK) {
+      g->err = "shard " + std::to_string(r) + ": " + swz_last_error(g->ctx[r]);
+      return st;
+    }
+    level[r].resize(nn);
+    key[r].resize(nn);
+    count[r].resize(nn);
+  }
+  return SWZ_OK;
+}
+
+int merge_tables(swz_group* g, const std::vector<std::vector<int8_t>>& level, const std::vector<std::vector<uint64_t>>& key,
+                 const std::vector<std::vector<uint64_t>>& count, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out,
+                 uint64_t* count_out, int32_t* shard_out, uint64_t* num_nodes_out) {
+  std::vector<uint64_t> nn(g->n);
+  std::vector<const int8_t*> pl(g->n);
+  std::vector<const uint64_t*> pk(g->n), pc(g->n);
+  for (int r = 0; r < g->n; ++r) {
+    nn[r] = level[r].size();
+    pl[r] = level[r].data();
+    pk[r] = key[r].data();
+    pc[r] = count[r].data();
+  }
+  const int st = swz_merge_shard_node_tables(g->n, nn.data(), pl.data(), pk.data(), pc.data(), max_nodes, level_out, key_out, count_out, shard_out, num_nodes_out);
+  if (st == SWZ_ERR_INTERNAL) g->err = "a node below the root lies on two shards";
+  else if (st != SWZ_OK) g->err = "swz_group_node_table: max_nodes too small, or a NULL buffer";
+  return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+int swz_group_node_table(swz_group* g, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out, uint64_t* count_out,
+                         int32_t* shard_out, uint64_t* num_nodes_out) {
+  if (!g || !num_nodes_out) return SWZ_ERR_BAD_ARG;
+  if (g->tiler.empty()) {
+    g->err = "swz_group_node_table: no data set is open (swz_group_tiler_open)";
+    return SWZ_ERR_BAD_ARG;
+  }
+  std::vector<std::vector<int8_t>> level;
+  std::vector<std::vector<uint64_t>> key, count;
+  const int st = shard_node_tables(g, level, key, count);
+  if (st != SWZ_OK) return st;
+  return merge_tables(g, level, key, count, max_nodes, level_out, key_out, count_out, shard_out, num_nodes_out);
+}
+
+int swz_group_write_output(swz_group* g, const char* dir, const swz_output_params* params, swz_output_stats* stats_per_shard,
+                           swz_output_stats* total) {
+  if (!g) return SWZ_ERR_BAD_ARG;
+  const char* who = "swz_group_write_output";
+  if (!dir || !params) {
+    g->err = "swz_group_write_output: NULL argument";
+    return SWZ_ERR_BAD_ARG;
+  }
+  if (g->tiler.empty() || !g->staged.empty()) {
+    g->err = g->tiler.empty() ? "swz_group_write_output: no data set is open (swz_group_tiler_open)" : "swz_group_write_output: a batch is staged or open";
+    return SWZ_ERR_BAD_ARG;
+  }
+  const auto t_wall = std::chrono::steady_clock::now();
+  const int N = g->n;
+  std::fill(g->status.begin(), g->status.end(), SWZ_OK);
+  if (total) *total = swz_output_stats{};
+  for (int r = 0; stats_per_shard && r < N; ++r) stats_per_shard[r] = swz_output_stats{};
+  auto refuse = [&](int r, int st) {  // r < 0: refused once, for the whole group
+    g->err = r < 0 ? std::string(swz_last_error(g->ctx[0])) : "shard " + std::to_string(r) + ": " + swz_last_error(g->ctx[r]);
+    return st;
+  };
+
+  // ---- every shard's table (a poisoned tiler answers here), the merged one, and everything that is refused before
+  // anything is written -- once, on the merged table
+  GroupOutput o;
+  o.params = params;
+  o.plan.resize(N);
+  o.info.resize(N);
+  uint32_t attr_mask = 0;
+  std::vector<std::vector<int8_t>> level(N);
+  std::vector<std::vector<uint64_t>> key(N), count(N);
+  for (int r = 0; r < N; ++r) {
+    (void)hipSetDevice(g->devices[r]);
+    const int st = swz::output_tiler_table(g->tiler[r], who, &o.plan[r], &o.info[r]);
+    if (st != SWZ_OK) return refuse(r, st);
+    attr_mask |= g->tiler[r]->attr_mask;
+    level[r] = o.plan[r].level;
+    key[r] = o.plan[r].key;
+    count[r] = o.plan[r].count;
+  }
+  // (one merge: the merged table has at most as many nodes as the shards' tables together)
+  swz::OutputPlan merged;
+  uint64_t nn = 0, cap = 1;
+  for (int r = 0; r < N; ++r) cap += level[r].size();
+  merged.level.resize(cap);
+  merged.key.resize(cap);
+  merged.count.resize(cap);
+  int st = merge_tables(g, level, key, count, cap, merged.level.data(), merged.key.data(), merged.count.data(), nullptr, &nn);
+  if (st != SWZ_OK) return st;
+  merged.level.resize(nn);
+  merged.key.resize(nn);
+  merged.count.resize(nn);
+  merged.offset.assign(nn, 0);
+  uint64_t stored = 0;
+  for (uint64_t k = 0; k < nn; ++k) {
+    merged.offset[k] = stored;
+    stored += merged.count[k];
+  }
+  swz_ctx* c0 = g->ctx[0];
+  if ((st = swz::output_plan(c0, who, params, attr_mask, g->tbmin, g->tbmax, g->tparams.spacing_at_root, dir, &merged)) != SWZ_OK) return refuse(-1, st);
+  o.part_cnt.assign(N, 0);
+  o.part_off.assign(N + 1, 0);
+  o.part_xyz.assign(N, nullptr);
+  o.part_attr.assign(SWZ_ATTR_COUNT, std::vector<const void*>(N, nullptr));
+  for (int r = 0; r < N; ++r) {
+    if (!o.plan[r].count.empty() && o.plan[r].level[0] < 0) o.part_cnt[r] = o.plan[r].count[0];
+    o.part_off[r + 1] = o.part_off[r] + o.part_cnt[r];
+    if ((st = swz::output_plan(g->ctx[r], who, params, attr_mask, g->tbmin, g->tbmax, g->tparams.spacing_at_root, dir, &o.plan[r])) != SWZ_OK) return refuse(r, st);
+  }
+  if (o.part_off[N]) {
+    o.root.level.assign(1, (int8_t)-1);
+    o.root.key.assign(1, 0);
+    o.root.offset.assign(1, 0);
+    o.root.count.assign(1, o.part_off[N]);
+    if ((st = swz::output_plan(c0, who, params, attr_mask, g->tbmin, g->tbmax, g->tparams.spacing_at_root, dir, &o.root)) != SWZ_OK) return refuse(-1, st);
+  }
+  if ((st = swz::output_create_dirs(c0, who, &merged, dir)) != SWZ_OK) return refuse(-1, st);
+  o.root.data_dir = merged.data_dir;
+  for (int r = 0; r < N; ++r) o.plan[r].data_dir = merged.data_dir;
+
+  // ---- SWZ_BIN_WRITER_THREADS is the budget of the whole call: every shard at least one
+  const long budget = std::max(1L, c0->opt_int("SWZ_BIN_WRITER_THREADS", (long)std::min(32u, std::max(1u, std::thread::hardware_concurrency()))));
+  o.writer_threads.assign(N, 1);
+  for (int r = 0; r < N; ++r) o.writer_threads[r] = std::max(1L, budget / N + (r < budget % N ? 1 : 0));
+  o.stats.assign(N, swz_output_stats{});
+
+  std::vector<std::thread> threads;
+  for (int r = 0; r < N; ++r) threads.emplace_back(output_thread, g, r, &o);
+  for (auto& th : threads) th.join();
+  for (int r = 0; stats_per_shard && r < N; ++r) stats_per_shard[r] = o.stats[r];
+  st = SWZ_OK;
+  for (int r = 0; r < N && st == SWZ_OK; ++r)
+    if (g->status[r] != SWZ_OK) {
+      g->err = "shard " + std::to_string(r) + ": " + g->status_msg[r];
+      st = g->status[r];
+    }
+  std::fill(g->status.begin(), g->status.end(), SWZ_OK);  // (a failed write marks no shard: the group stays usable)
+  // ---- the metadata, once, from the merged table
+  if (st == SWZ_OK) {
+    (void)hipSetDevice(g->devices[0]);
+    if ((st = swz::output_metadata(c0, who, merged, dir, params)) != SWZ_OK) g->err = swz_last_error(c0);
+  }
+  if (total) {
+    total->nodes = nn;
+    total->stored_points = stored;
+    for (int r = 0; r < N; ++r) {
+      total->bytes_written += o.stats[r].bytes_written;
+      total->chunks += o.stats[r].chunks;
+      total->pack_ms = std::max(total->pack_ms, o.stats[r].pack_ms);
+      total->copy_ms = std::max(total->copy_ms, o.stats[r].copy_ms);
+      total->write_ms = std::max(total->write_ms, o.stats[r].write_ms);
+    }
+    total->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wall).count();
+  }
+  return st;
 }
 
 // ------------------------------------------------------------------------- the joint root for one PROCESS per GPU

@@ -136,7 +136,8 @@ public:
   TicketRun& operator=(const TicketRun&) = delete;
   ~TicketRun() { (void)wait(nullptr, nullptr); }
 
-  // want_threads > 0: that many threads (a caller with an option of its own: the readers of swz_tinput.hip)
+  // want_threads > 0: that many threads (a caller with an option of its own: the readers of swz_tinput.hip; or with a share
+  // of the option's budget: the shards of swz_group_write_output)
   template <typename F>
   void start(swz_ctx* c, uint64_t num, F item, long want_threads = 0) {
     unsigned threads = std::min(32u, std::max(1u, std::thread::hardware_concurrency()));

@@ -29,8 +29,7 @@
 #include <string>
 #include <vector>
 
-#include "swz_tiler.h"
-#include "swz_hostio.h"
+#include "swz_tinput.h"
 #include "swz_lasrec.h"
 
 namespace swz {
@@ -303,39 +302,130 @@ static int scan_one(const char* path, swz_las_file_info* info, std::string* why)
   return SWZ_LAS_FILE_OK;
 }
 
-// ---------------------------------------------------------------------------------- the streamed call
-// one piece of a batch's raw image: `bytes` bytes at `file_at` of file `file` to `image_at` of the image
-struct ReadPiece {
-  uint64_t file, file_at, bytes, image_at;
-};
-
-struct InputBatch {
-  uint64_t first_point = 0, points = 0;
-  uint64_t raw_bytes = 0, table_at = 0, image_bytes = 0;  // the image: the records back to back, then the segment table
-  std::vector<swz_las_segment> segs;
-  std::vector<ReadPiece> pieces;
-};
-
-// what a call holds besides the context's workspace; released however the call ends
-struct InputBuffers {
-  swz_ctx* c = nullptr;
-  void* host[2] = {nullptr, nullptr};
-  hipEvent_t begin[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr}, decoded[2] = {nullptr, nullptr};
-  ~InputBuffers() {
-    for (int b = 0; b < 2; ++b) {
-      if (host[b]) (void)hipHostFree(host[b]);
-      for (hipEvent_t e : {begin[b], copied[b], decoded[b]})
-        if (e) (void)hipEventDestroy(e);
-    }
-    // two raw batch images are the call's, not the data set's
-    for (const char* name : {"in_image0", "in_image1"}) {
-      const auto it = c->bufs.find(name);
-      if (it == c->bufs.end()) continue;
-      c->free_buf(it->second);
-      c->bufs.erase(it);
-    }
+// ---------------------------------------------------------------------------------- the parts of the streamed call
+int InputBuffers::reserve(swz_ctx* ctx, uint64_t image_bytes, bool two) {
+  c = ctx;
+  SWZ_TRY(c->get("in_image0", (size_t)image_bytes, &device[0]));
+  if (two) SWZ_TRY(c->get("in_image1", (size_t)image_bytes, &device[1]));
+  for (int b = 0; b < (two ? 2 : 1); ++b) {
+    SWZ_HIP(c, hipHostMalloc(&host[b], image_bytes, hipHostMallocDefault));
+    SWZ_HIP(c, hipEventCreate(&begin[b]));
+    SWZ_HIP(c, hipEventCreate(&copied[b]));
+    SWZ_HIP(c, hipEventCreate(&decoded[b]));
   }
-};
+  return SWZ_OK;
+}
+
+InputBuffers::~InputBuffers() {
+  for (int b = 0; b < 2; ++b) {
+    if (host[b]) (void)hipHostFree(host[b]);
+    for (hipEvent_t e : {begin[b], copied[b], decoded[b]})
+      if (e) (void)hipEventDestroy(e);
+  }
+  if (!c) return;
+  // two raw images are the call's, not the data set's
+  for (const char* name : {"in_image0", "in_image1"}) {
+    const auto it = c->bufs.find(name);
+    if (it == c->bufs.end()) continue;
+    c->free_buf(it->second);
+    c->bufs.erase(it);
+  }
+}
+
+int las_input_plan(swz_ctx* c, const char* who_c, const char* const* paths, uint64_t num_files, const swz_input_params* params,
+                   const double bmin[3], const double bmax[3], const swz_tile_params& tp, bool mask_fixed, uint32_t mask_now,
+                   uint64_t points_now, LasInputPlan* plan) {
+  const std::string who = std::string(who_c) + ": ";
+  // ---- the headers, and everything that is refused before a point is read
+  plan->files.assign(std::max<uint64_t>(num_files, 1), swz_las_file_info{});
+  swz_las_dataset& ds = plan->ds;
+  SWZ_TRY(swz_las_scan_files(c, paths, num_files, params->flags, plan->files.data(), &ds));
+  const uint32_t mask = params->attribute_mask == ~0u ? ds.attribute_mask : params->attribute_mask;
+  if (mask & (1u << SWZ_ATTR_NORMAL)) return c->fail(SWZ_ERR_BAD_ARG, who + "LAS points carry no normals");
+  if (mask & ~ds.attribute_mask) return c->fail(SWZ_ERR_BAD_ARG, who + "the mask names an attribute that not every file has");
+  if (mask_fixed && mask != mask_now) return c->fail(SWZ_ERR_BAD_ARG, who + "every batch must carry the same attribute columns");
+  // The (shifted) tight box inside the root box.  AABB::makeCubic's own box can miss the tight box it was made from by an ulp
+  // of the coordinates (centre - half the extent need not round back to the minimum), so the comparison leaves that much
+  // room; the shift is taken in double.  A position that lies outside by such a rounding, or that the narrowing to float
+  // moves past the box, is clamped by the indexing, as in the reference.
+  const bool shift = params->shift_to_center != 0;
+  for (int k = 0; k < 3; ++k) {
+    const double lo = shift ? ds.tight_min[k] - ds.center[k] : ds.tight_min[k];
+    const double hi = shift ? ds.tight_max[k] - ds.center[k] : ds.tight_max[k];
+    const double size = std::max(std::max(std::fabs(ds.tight_min[k]), std::fabs(ds.tight_max[k])), std::fabs(ds.center[k]));
+    const double room = 4 * std::numeric_limits<double>::epsilon() * size;
+    if (!(bmin[k] - room <= lo && hi <= bmax[k] + room))
+      return c->fail(SWZ_ERR_BAD_ARG, who + "the tiler's root box does not contain the data set's box");
+  }
+  if (points_now + ds.total_points > 0xFFFF0000ull) return c->fail(SWZ_ERR_TOO_MANY_POINTS, "more than 2^32-65536 points per tiler");
+
+  // ---- the batches
+  const uint64_t batch_points = params->batch_points ? params->batch_points : INPUT_BATCH_POINTS;
+  const uint64_t min_last = tp.strategy == SWZ_FAST ? tp.fast_concurrency : 0;
+  if (batch_points < min_last) return c->fail(SWZ_ERR_BAD_ARG, "FAST: a batch needs at least fast_concurrency points");
+  plan->counts.assign(plan->files.size(), 0);
+  for (uint64_t i = 0; i < num_files; ++i) plan->counts[i] = plan->files[i].point_count;
+  plan->file_first.assign(num_files + 1, 0);
+  for (uint64_t i = 0; i < num_files; ++i) plan->file_first[i + 1] = plan->file_first[i] + plan->counts[i];
+  uint64_t num_batches = 0;
+  if (swz_input_batches(num_files, plan->counts.data(), batch_points, min_last, 0, nullptr, &num_batches) != SWZ_OK)
+    return c->fail(SWZ_ERR_BAD_ARG, "FAST: a batch needs at least fast_concurrency points");
+  plan->cuts.assign(num_batches + 1, 0);
+  (void)swz_input_batches(num_files, plan->counts.data(), batch_points, min_last, num_batches, plan->cuts.data(), &num_batches);
+  plan->mask = mask;
+  plan->shift = shift;
+  return SWZ_OK;
+}
+
+void las_input_image(const LasInputPlan& plan, uint64_t p0, uint64_t p1, InputBatch* out) {
+  InputBatch& b = *out;
+  b = InputBatch{};
+  b.first_point = p0;
+  b.points = p1 - p0;
+  // the file the first point lies in: the last one that begins at or before it and holds a point
+  uint64_t file = (uint64_t)(std::upper_bound(plan.file_first.begin(), plan.file_first.end(), p0) - plan.file_first.begin());
+  file = file ? file - 1 : 0;
+  for (uint64_t p = p0; p < p1;) {
+    while (p >= plan.file_first[file + 1]) ++file;
+    const swz_las_file_info& fi = plan.files[file];
+    const uint64_t rec0 = p - plan.file_first[file], cnt = std::min(p1, plan.file_first[file + 1]) - p;
+    const uint64_t rb = fi.layout.record_bytes;
+    swz_las_segment sg{};
+    sg.first_row = p - p0;
+    sg.count = cnt;
+    sg.byte_offset = b.raw_bytes;
+    sg.layout = fi.layout;
+    b.segs.push_back(sg);
+    for (uint64_t done = 0; done < cnt * rb; done += READ_PIECE)
+      b.pieces.push_back({file, fi.offset_to_point_data + rec0 * rb + done, std::min(READ_PIECE, cnt * rb - done), b.raw_bytes + done});
+    b.raw_bytes += cnt * rb;
+    p += cnt;
+  }
+  b.table_at = (b.raw_bytes + 15) & ~15ull;
+  b.image_bytes = b.table_at + b.segs.size() * sizeof(swz_las_segment);
+}
+
+void las_start_read(TicketRun& run, swz_ctx* c, const char* who, const InputBatch* b, unsigned char* image, const char* const* paths,
+                    long threads) {
+  memcpy(image + b->table_at, b->segs.data(), b->segs.size() * sizeof(swz_las_segment));
+  run.start(c, b->pieces.size(), [who, b, image, paths](uint64_t i, std::string* err) {
+    const ReadPiece& p = b->pieces[i];
+    Fd f;
+    f.fd = open(paths[p.file], O_RDONLY | O_CLOEXEC);
+    if (f.fd < 0 || !pread_all(f.fd, image + p.image_at, p.bytes, p.file_at)) {
+      *err = std::string(who) + ": cannot read the point records of " + paths[p.file];
+      return (int)SWZ_ERR_BAD_ARG;
+    }
+    return (int)SWZ_OK;
+  }, threads);
+}
+
+int las_launch_image(swz_ctx* c, hipStream_t stream, const uint8_t* d_image, const InputBatch& b, const double* shift_center,
+                     double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t mask) {
+  if (!b.points) return SWZ_OK;
+  return launch_segments(c, stream, d_image, b.raw_bytes, reinterpret_cast<const swz_las_segment*>(d_image + b.table_at),
+                         (uint32_t)b.segs.size(), (uint32_t)b.points, shift_center, d_xyz_out, d_out, mask);
+}
 
 }  // namespace swz
 
@@ -457,72 +547,20 @@ int swz_tiler_add_las_files(swz_tiler* t, const char* const* paths, uint64_t num
   if (t->finalized) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler: batches cannot be added after finalize");
   if (!t->staged_sizes.empty() || t->batch_open) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_add_las_files: a batch is staged or open");
 
-  // ---- the headers, and everything that is refused before a point is read
-  std::vector<swz_las_file_info> files(std::max<uint64_t>(num_files, 1));
-  swz_las_dataset ds{};
-  SWZ_TRY(swz_las_scan_files(c, paths, num_files, params->flags, files.data(), &ds));
-  const uint32_t mask = params->attribute_mask == ~0u ? ds.attribute_mask : params->attribute_mask;
-  if (mask & (1u << SWZ_ATTR_NORMAL)) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_add_las_files: LAS points carry no normals");
-  if (mask & ~ds.attribute_mask)
-    return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_add_las_files: the mask names an attribute that not every file has");
+  // ---- the headers, everything that is refused before a point is read, and the cuts
+  const char* who = "swz_tiler_add_las_files";
   const bool first = t->staged_total == 0 && t->batches == 0;
-  if (!first && mask != t->attr_mask)
-    return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_add_las_files: every batch must carry the same attribute columns");
-  // The (shifted) tight box inside the root box.  AABB::makeCubic's own box can miss the tight box it was made from by an ulp
-  // of the coordinates (centre - half the extent need not round back to the minimum), so the comparison leaves that much
-  // room; the shift is taken in double.  A position that lies outside by such a rounding, or that the narrowing to float
-  // moves past the box, is clamped by the indexing, as in the reference.
-  const bool shift = params->shift_to_center != 0;
-  for (int k = 0; k < 3; ++k) {
-    const double lo = shift ? ds.tight_min[k] - ds.center[k] : ds.tight_min[k];
-    const double hi = shift ? ds.tight_max[k] - ds.center[k] : ds.tight_max[k];
-    const double size = std::max(std::max(std::fabs(ds.tight_min[k]), std::fabs(ds.tight_max[k])), std::fabs(ds.center[k]));
-    const double room = 4 * std::numeric_limits<double>::epsilon() * size;
-    if (!(t->bmin[k] - room <= lo && hi <= t->bmax[k] + room))
-      return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_add_las_files: the tiler's root box does not contain the data set's box");
-  }
-  if ((uint64_t)t->staged_total + ds.total_points > 0xFFFF0000ull)
-    return c->fail(SWZ_ERR_TOO_MANY_POINTS, "more than 2^32-65536 points per tiler");
-
-  // ---- the batches: their segments, the pieces the readers take, the size of their images
-  const uint64_t batch_points = params->batch_points ? params->batch_points : INPUT_BATCH_POINTS;
-  const uint64_t min_last = t->p.strategy == SWZ_FAST ? t->p.fast_concurrency : 0;
-  if (batch_points < min_last) return c->fail(SWZ_ERR_BAD_ARG, "FAST: a batch needs at least fast_concurrency points");
-  std::vector<uint64_t> counts(files.size());
-  for (uint64_t i = 0; i < num_files; ++i) counts[i] = files[i].point_count;
-  uint64_t num_batches = 0;
-  if (swz_input_batches(num_files, counts.data(), batch_points, min_last, 0, nullptr, &num_batches) != SWZ_OK)
-    return c->fail(SWZ_ERR_BAD_ARG, "FAST: a batch needs at least fast_concurrency points");
-  std::vector<uint64_t> cuts(num_batches + 1);
-  (void)swz_input_batches(num_files, counts.data(), batch_points, min_last, num_batches, cuts.data(), &num_batches);
+  LasInputPlan plan;
+  SWZ_TRY(las_input_plan(c, who, paths, num_files, params, t->bmin, t->bmax, t->p, !first, t->attr_mask, t->staged_total, &plan));
+  const swz_las_dataset& ds = plan.ds;
+  const uint32_t mask = plan.mask;
+  const bool shift = plan.shift;
+  const uint64_t num_batches = plan.num_batches();
   std::vector<InputBatch> batches(num_batches);
   uint64_t image_max = 0;
-  {
-    uint64_t file = 0, file_first = 0;  // the file the next point lies in, and the data set's point its first record is
-    for (uint64_t j = 0; j < num_batches; ++j) {
-      InputBatch& b = batches[j];
-      b.first_point = cuts[j];
-      b.points = cuts[j + 1] - cuts[j];
-      for (uint64_t p = cuts[j]; p < cuts[j + 1];) {
-        while (p >= file_first + counts[file]) file_first += counts[file++];
-        const swz_las_file_info& fi = files[file];
-        const uint64_t rec0 = p - file_first, cnt = std::min(cuts[j + 1], file_first + counts[file]) - p;
-        const uint64_t rb = fi.layout.record_bytes;
-        swz_las_segment sg{};
-        sg.first_row = p - cuts[j];
-        sg.count = cnt;
-        sg.byte_offset = b.raw_bytes;
-        sg.layout = fi.layout;
-        b.segs.push_back(sg);
-        for (uint64_t done = 0; done < cnt * rb; done += READ_PIECE)
-          b.pieces.push_back({file, fi.offset_to_point_data + rec0 * rb + done, std::min(READ_PIECE, cnt * rb - done), b.raw_bytes + done});
-        b.raw_bytes += cnt * rb;
-        p += cnt;
-      }
-      b.table_at = (b.raw_bytes + 15) & ~15ull;
-      b.image_bytes = b.table_at + b.segs.size() * sizeof(swz_las_segment);
-      image_max = std::max(image_max, b.image_bytes);
-    }
+  for (uint64_t j = 0; j < num_batches; ++j) {
+    las_input_image(plan, plan.cuts[j], plan.cuts[j + 1], &batches[j]);
+    image_max = std::max(image_max, batches[j].image_bytes);
   }
 
   // ---- the pools, once for the total: nothing grows while a batch is in flight
@@ -540,19 +578,9 @@ int swz_tiler_add_las_files(swz_tiler* t, const char* const* paths, uint64_t num
     return pool_reserve(t, (size_t)t->staged_total + ds.total_points);
   };
   InputBuffers ib;
-  ib.c = c;
-  uint8_t* d_image[2] = {nullptr, nullptr};
   auto prepare = [&]() -> int {
     SWZ_TRY(reserve());
-    SWZ_TRY(c->get("in_image0", (size_t)image_max, &d_image[0]));
-    if (num_batches > 1) SWZ_TRY(c->get("in_image1", (size_t)image_max, &d_image[1]));
-    for (int b = 0; b < (num_batches > 1 ? 2 : 1); ++b) {
-      SWZ_HIP(c, hipHostMalloc(&ib.host[b], image_max, hipHostMallocDefault));
-      SWZ_HIP(c, hipEventCreate(&ib.begin[b]));
-      SWZ_HIP(c, hipEventCreate(&ib.copied[b]));
-      SWZ_HIP(c, hipEventCreate(&ib.decoded[b]));
-    }
-    return SWZ_OK;
+    return ib.reserve(c, image_max, num_batches > 1);
   };
   {
     const int st = prepare();
@@ -572,19 +600,7 @@ int swz_tiler_add_las_files(swz_tiler* t, const char* const* paths, uint64_t num
   std::string why;
   TicketRun readers;
   auto start_read = [&](uint64_t j) {
-    const InputBatch* b = &batches[j];
-    unsigned char* image = static_cast<unsigned char*>(ib.host[j & 1]);
-    memcpy(image + b->table_at, b->segs.data(), b->segs.size() * sizeof(swz_las_segment));
-    readers.start(c, b->pieces.size(), [b, image, paths](uint64_t i, std::string* err) {
-      const ReadPiece& p = b->pieces[i];
-      Fd f;
-      f.fd = open(paths[p.file], O_RDONLY | O_CLOEXEC);
-      if (f.fd < 0 || !pread_all(f.fd, image + p.image_at, p.bytes, p.file_at)) {
-        *err = std::string("swz_tiler_add_las_files: cannot read the point records of ") + paths[p.file];
-        return (int)SWZ_ERR_BAD_ARG;
-      }
-      return (int)SWZ_OK;
-    }, reader_threads);
+    las_start_read(readers, c, who, &batches[j], static_cast<unsigned char*>(ib.host[j & 1]), paths, reader_threads);
   };
   // joins the readers of batch j; the time the call stood waiting for them counts as waiting for input
   auto wait_read = [&](uint64_t j) -> bool {
@@ -608,14 +624,12 @@ int swz_tiler_add_las_files(swz_tiler* t, const char* const* paths, uint64_t num
     const int s = (int)(j & 1);
     const size_t at = t->staged_total;
     SWZ_HIP(c, hipEventRecord(ib.begin[s], t->copy_stream));
-    SWZ_HIP(c, hipMemcpyAsync(d_image[s], ib.host[s], b.image_bytes, hipMemcpyHostToDevice, t->copy_stream));
+    SWZ_HIP(c, hipMemcpyAsync(ib.device[s], ib.host[s], b.image_bytes, hipMemcpyHostToDevice, t->copy_stream));
     SWZ_HIP(c, hipEventRecord(ib.copied[s], t->copy_stream));
     swz_attribute_columns rows{};
     for (int a = 0; a < SWZ_ATTR_COUNT; ++a)
       rows.column[a] = (t->attr_mask & (1u << a)) ? (void*)((char*)t->pool_attr[a] + at * TILER_ATTR_BYTES[a]) : nullptr;
-    SWZ_TRY(launch_segments(c, t->copy_stream, d_image[s], b.raw_bytes, reinterpret_cast<const swz_las_segment*>(d_image[s] + b.table_at),
-                            (uint32_t)b.segs.size(), (uint32_t)b.points, shift ? ds.center : nullptr, t->pool_xyz + at * 3, &rows,
-                            t->attr_mask));
+    SWZ_TRY(las_launch_image(c, t->copy_stream, ib.device[s], b, shift ? ds.center : nullptr, t->pool_xyz + at * 3, &rows, t->attr_mask));
     SWZ_HIP(c, hipEventRecord(ib.decoded[s], t->copy_stream));
     hipEvent_t ev = nullptr;
     SWZ_HIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));

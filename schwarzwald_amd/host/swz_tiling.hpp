@@ -640,7 +640,70 @@ public:
     return files;
   }
 
+  // ---- a data set in several batches on the group's tilers (swz_group_tiler_open ... swz_group_write_output): what
+  // TilingAlgorithmGPU's tile_batch / write_output are on one GPU.  The persistence is not involved.
+  // bounds: the octree's (cubic) root bounds; strategy: SWZ_ACCURATE or SWZ_FAST (fast_concurrency = num_indexing_threads)
+  void open_tiler(const AABB& bounds, int strategy = SWZ_ACCURATE) {
+    swz_tile_params p{};
+    p.sampler = _sampling_strategy.kind;
+    p.max_points_per_node = _sampling_strategy.max_points_per_node;
+    p.spacing_at_root = _meta.spacing_at_root;
+    p.max_depth = _meta.max_depth;
+    p.strategy = strategy;
+    p.fast_concurrency = _meta.num_indexing_threads;
+    const double mn[3] = {bounds.min.x, bounds.min.y, bounds.min.z}, mx[3] = {bounds.max.x, bounds.max.y, bounds.max.z};
+    group_check(swz_group_tiler_open(_group, mn, mx, &p, 0), "swz_group_tiler_open");
+    _tiler_finalized = false;
+  }
+  // host rows cut into equal consecutive pieces, one per shard, as tile_batch does; attributes may be NULL
+  void add_batch(const double* positions, const swz_attribute_columns* attributes, size_t n) {
+    if (_tiler_finalized) throw std::runtime_error{"ShardedTilingAlgorithmGPU: add_batch after finalize_tiler"};
+    std::vector<std::vector<Scratch>> owned(_shards);
+    std::vector<double*> d_xyz(_shards, nullptr);
+    std::vector<swz_attribute_columns> d_attrs(_shards);
+    std::vector<uint64_t> cnt(_shards, 0);
+    for (int s = 0; s < _shards; ++s) {
+      const size_t lo = n * s / _shards, hi = n * (s + 1) / _shards;
+      cnt[s] = hi - lo;
+      swz_ctx* c = swz_group_ctx(_group, s);
+      d_attrs[s] = swz_attribute_columns{};
+      d_xyz[s] = static_cast<double*>(upload(owned[s], c, positions + 3 * lo, cnt[s] * 24));
+      for (int t = 0; t < SWZ_ATTR_COUNT; ++t)
+        if (attributes && attributes->column[t]) {
+          const uint32_t rb = swz_attribute_row_bytes(t);
+          d_attrs[s].column[t] = upload(owned[s], c, static_cast<const char*>(attributes->column[t]) + lo * rb, cnt[s] * rb);
+        }
+    }
+    group_check(swz_group_add_batch(_group, d_xyz.data(), attributes ? d_attrs.data() : nullptr, cnt.data(), nullptr), "swz_group_add_batch");
+  }
+  // A data set of uncompressed LAS files, read by the library in one call (swz_group_add_las_files) into the tilers that
+  // open_tiler() opened; as TilingAlgorithmGPU::add_las_files it does not finalize
+  swz_input_stats add_las_files(const std::vector<std::string>& paths, const swz_input_params& params) {
+    if (_tiler_finalized) throw std::runtime_error{"ShardedTilingAlgorithmGPU: add_las_files after finalize_tiler"};
+    std::vector<const char*> names;
+    for (const std::string& p : paths) names.push_back(p.c_str());
+    swz_input_stats stats{};
+    group_check(swz_group_add_las_files(_group, names.data(), names.size(), &params, &stats), "swz_group_add_las_files");
+    return stats;
+  }
+  void finalize_tiler() {
+    if (_tiler_finalized) return;
+    group_check(swz_group_finalize(_group, nullptr), "swz_group_finalize");
+    _tiler_finalized = true;
+  }
+  // the data set's directory, written by the library in one call (swz_group_write_output); finalizes if finalize_tiler() has not
+  swz_output_stats write_output(const std::string& dir, const swz_output_params& params) {
+    finalize_tiler();
+    swz_output_stats total{};
+    group_check(swz_group_write_output(_group, dir.c_str(), &params, nullptr, &total), "swz_group_write_output");
+    return total;
+  }
+
 private:
+  void group_check(int status, const char* call) const {
+    if (status != SWZ_OK) throw std::runtime_error{std::string(call) + ": " + swz_group_last_error(_group)};
+  }
+  bool _tiler_finalized = false;
   struct Scratch {
     void* ptr = nullptr;
     Scratch() = default;

@@ -8,6 +8,10 @@
 // (swz_group_stage_batch / swz_group_tile_staged); the wall time then includes the host link.
 // BATCHES > 1: the shard's points in that many batches through swz_group_add_batch (one swz_tiler per shard) and
 // swz_group_finalize.  `bench.py --driver group` runs this program and reports its timings.
+// --write DIR --format F (anywhere on the line; with BATCHES > 1; F = 0 BIN, 1 BINZ, 2 3DTILES, 3 LAS, 4 ENTWINE_LAS): after the
+// last rep's finalize the data set is written to DIR with swz_group_write_output and its statistics are printed, per shard and
+// in total.  With one shard the same tiler is written to DIR_single with swz_tiler_write_output before and after it, for
+// comparison (the second run shows the spread).
 //   g++ -std=c++17 -O2 tools/group_bench.cpp -o /tmp/group_bench -Lschwarzwald_amd/lib -lswz_gpu -Wl,-rpath,$PWD/schwarzwald_amd/lib
 #include <algorithm>
 #include <array>
@@ -15,11 +19,31 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <string>
 #include <vector>
 
 #include "../include/swz_gpu.h"
 
+static void print_output_stats(const char* what, const swz_output_stats& s) {
+  std::printf("%s: %llu nodes, %llu stored points, %.1f MB in %llu chunks: pack %.1f ms, copy %.1f ms, write %.1f ms, wall %.1f ms\n", what,
+              (unsigned long long)s.nodes, (unsigned long long)s.stored_points, s.bytes_written / 1e6, (unsigned long long)s.chunks, s.pack_ms,
+              s.copy_ms, s.write_ms, s.wall_ms);
+}
+
 int main(int argc, char** argv) {
+  // the two options are taken out of the line; the positional arguments stay as they were
+  std::string write_dir;
+  int write_format = SWZ_OUT_BIN;
+  {
+    int kept = 1;
+    for (int i = 1; i < argc; ++i) {
+      if (!std::strcmp(argv[i], "--write") && i + 1 < argc) write_dir = argv[++i];
+      else if (!std::strcmp(argv[i], "--format") && i + 1 < argc) write_format = std::atoi(argv[++i]);
+      else argv[kept++] = argv[i];
+    }
+    argc = kept;
+  }
   const int shards = argc > 1 ? std::atoi(argv[1]) : 8;
   const uint64_t per = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : 25000000ull;
   const int reps = argc > 3 ? std::atoi(argv[3]) : 3;
@@ -130,9 +154,39 @@ int main(int argc, char** argv) {
         }
         add_stamps();
       }
-      if (swz_group_finalize(g, nullptr) != SWZ_OK || swz_group_tiler_close(g) != SWZ_OK) {
+      if (swz_group_finalize(g, nullptr) != SWZ_OK) {
         std::fprintf(stderr, "swz_group_finalize: %s\n", swz_group_last_error(g));
         return 4;
+      }
+      if (!write_dir.empty() && rep + 1 == reps) {
+        swz_output_params o{};
+        o.format = write_format;
+        o.attribute_mask = staged ? (1u << SWZ_ATTR_RGB) | (1u << SWZ_ATTR_INTENSITY) : 0u;
+        std::vector<swz_output_stats> per_shard(shards);
+        swz_output_stats total{}, single{};
+        const std::string single_dir = write_dir + "_single";
+        // (one shard: the single tiler's call on the same tiler, before and after, for comparison)
+        auto single_call = [&](const char* label) {
+          if (shards != 1) return true;
+          if (swz_tiler_write_output(swz_group_tiler(g, 0), single_dir.c_str(), &o, &single) != SWZ_OK) {
+            std::fprintf(stderr, "swz_tiler_write_output: %s\n", swz_last_error(swz_group_ctx(g, 0)));
+            return false;
+          }
+          print_output_stats(label, single);
+          return true;
+        };
+        if (!single_call("single tiler")) return 5;
+        if (swz_group_write_output(g, write_dir.c_str(), &o, per_shard.data(), &total) != SWZ_OK) {
+          std::fprintf(stderr, "swz_group_write_output: %s\n", swz_group_last_error(g));
+          return 5;
+        }
+        for (int s = 0; s < shards; ++s) print_output_stats(("output shard " + std::to_string(s)).c_str(), per_shard[s]);
+        print_output_stats("output total", total);
+        if (!single_call("single tiler again")) return 5;
+      }
+      if (swz_group_tiler_close(g) != SWZ_OK) {
+        std::fprintf(stderr, "swz_group_tiler_close: %s\n", swz_group_last_error(g));
+        return 6;
       }
     } else if (swz_group_tile(g, d_xyz.data(), nullptr, n.data(), mn, mx, &p, res.data()) != SWZ_OK) {
       std::fprintf(stderr, "swz_group_tile: %s\n", swz_group_last_error(g));

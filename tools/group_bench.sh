@@ -1,5 +1,5 @@
 # joint root sweep vs turns, 8 / 4 / 2 shards on the one device of the box
-cd $GRAFT_REPO_ROOT
+cd "$(dirname "$0")/.." || exit 1
 g++ -std=c++17 -O2 tools/group_bench.cpp -o /tmp/group_bench -Lschwarzwald_amd/lib -lswz_gpu -Wl,-rpath,$PWD/schwarzwald_amd/lib -Wl,-rpath,/opt/rocm/lib || exit 1
 for sh in 8 2; do
   per=$((200000000 / sh))
