@@ -679,6 +679,31 @@ int swz_tiler_reserve(swz_tiler* tiler, uint64_t total_points);
  * memory, or would push the workspace over SWZ_TILER_DEVICE_BUDGET_MB, is placed in mapped pinned host memory like a pool
  * and the merges stream through it over the host link. */
 int swz_tiler_store_residency(swz_tiler* tiler, uint64_t* device_bytes_out, uint64_t* host_bytes_out);
+/* OBSERVABILITY FOR TESTS (read-only; no kernel knows of either).
+ *   swz_tiler_merge_tile / swz_tiler_merge_lds: the merge of a level's active set with the files it pulled ranks
+ *     swz_tiler_merge_tile() consecutive elements of one run per workgroup against the bracket of the other run that its
+ *     first and last element span, out of LDS when the bracket holds at most swz_tiler_merge_lds() keys, else out of global
+ *     memory.  swz_tiler_gather_lds: the copy of pulled (or compacted) files takes 256 consecutive output entries per
+ *     workgroup and searches the segments they span out of LDS when they are at most swz_tiler_gather_lds().  Tests place
+ *     their run lengths, brackets and empty segments by these, like swz_las_input_tile / swz_bin_pack_tile.
+ *   swz_tiler_path_counts: how often this tiler's batches went which way through the node store, counted on the host where
+ *     the decision is made; the first min(n, SWZ_TILER_PATH_COUNT) slots of out, in the order of the SWZ_TILER_PATH_*
+ *     indices, further slots 0.  A test asserts that the path it is named after was taken. */
+#define SWZ_TILER_PATH_PULL_IN_PLACE 0       /* a level's side read where it lies: the batch reaches all of a linear level */
+#define SWZ_TILER_PATH_PULL_GATHERED 1       /* the files of the reached nodes copied out */
+#define SWZ_TILER_PATH_PULL_WHOLE_FILE 2     /* a re-rooted node took its cached file out of a populated level */
+#define SWZ_TILER_PATH_REKEY 3               /* pulled files re-keyed against their node (files finalize / re-rooting wrote) */
+#define SWZ_TILER_PATH_RESORT 4              /* pulled files sorted again after an inversion (see rekey_inversions) */
+#define SWZ_TILER_PATH_COMPACT_FULL 5        /* a level's live files gathered into the other side because the side was full */
+#define SWZ_TILER_PATH_LINEARIZE_MOVED 6     /* log form -> linear form that moved data (node table, export, FAST finalize) */
+#define SWZ_TILER_PATH_APPEND_BEHIND 7       /* new files appended behind the entries a side already held */
+#define SWZ_TILER_PATH_TABLE_MERGE_NF0 8     /* node tables merged with no untouched entry */
+#define SWZ_TILER_PATH_TABLE_MERGE_HEADS0 9  /* node tables merged with no new file */
+#define SWZ_TILER_PATH_COUNT 10
+uint32_t swz_tiler_merge_tile(void);
+uint32_t swz_tiler_merge_lds(void);
+uint32_t swz_tiler_gather_lds(void);
+int swz_tiler_path_counts(swz_tiler* tiler, uint64_t* out, uint32_t n);
 int swz_tiler_export_device(swz_tiler* tiler, uint64_t* d_keys_out, uint32_t* d_ids_out, int8_t* d_level_out);
 int swz_tiler_node_table(swz_tiler* tiler, uint64_t max_nodes, int8_t* node_level_out, uint64_t* node_key_out,
                          uint64_t* node_offset_out, uint64_t* node_count_out, uint64_t* num_nodes_out);

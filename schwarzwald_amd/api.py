@@ -711,6 +711,26 @@ def las_input_tile():
     return int(load_library().swz_las_input_tile())
 
 
+def tiler_merge_tile():
+    """Elements of a run that one workgroup of the multi-batch tiler's merge ranks (tests place their edges by it)."""
+    return int(load_library().swz_tiler_merge_tile())
+
+
+def tiler_merge_lds():
+    """The longest bracket of the other run that the merge searches out of LDS."""
+    return int(load_library().swz_tiler_merge_lds())
+
+
+def tiler_gather_lds():
+    """The most segments a workgroup's 256 outputs may span for the file gather to search them out of LDS."""
+    return int(load_library().swz_tiler_gather_lds())
+
+
+# swz_tiler_path_counts: the SWZ_TILER_PATH_* indices of include/swz_gpu.h, in order
+TILER_PATHS = ("pull_in_place", "pull_gathered", "pull_whole_file", "rekey", "resort", "compact_full", "linearize_moved",
+               "append_behind", "table_merge_nf0", "table_merge_heads0")
+
+
 def library_path():
     return os.environ.get("SWZ_GPU_LIBRARY", os.path.join(_HERE, "lib", "libswz_gpu.so"))
 
@@ -885,6 +905,11 @@ def load_library():
     L.swz_tiler_poison.argtypes = [vp, C.c_char_p]
     L.swz_tiler_pool_residency.argtypes = [vp, _u64p, _u64p]
     L.swz_tiler_store_residency.argtypes = [vp, _u64p, _u64p]
+    L.swz_tiler_path_counts.argtypes = [vp, _u64p, C.c_uint32]
+    L.swz_tiler_path_counts.restype = C.c_int
+    for name in ("swz_tiler_merge_tile", "swz_tiler_merge_lds", "swz_tiler_gather_lds"):
+        getattr(L, name).argtypes = []
+        getattr(L, name).restype = C.c_uint32
     L.swz_shard_joint_root_possible.argtypes = [vp, C.POINTER(_TileParams), _dp, _dp]
     L.swz_shard_joint_root_begin.argtypes = [vp, C.c_int, C.c_int, EXCHANGE_FN, vp]
     L.swz_shard_joint_root_probe.argtypes = [vp, C.c_int, C.c_int, EXCHANGE_FN, vp, C.POINTER(C.c_int)]
@@ -1386,6 +1411,12 @@ class Tiler:
         dev, host = C.c_uint64(), C.c_uint64()
         self._ctx._check(self._lib.swz_tiler_store_residency(self._t, C.byref(dev), C.byref(host)))
         return int(dev.value), int(host.value)
+
+    def path_counts(self):
+        """swz_tiler_path_counts: {name of TILER_PATHS: how often the tiler's batches took that way through the node store}"""
+        out = (C.c_uint64 * len(TILER_PATHS))()
+        self._ctx._check(self._lib.swz_tiler_path_counts(self._t, out, len(TILER_PATHS)))
+        return {name: int(out[i]) for i, name in enumerate(TILER_PATHS)}
 
     def close(self):
         if getattr(self, "_t", None):

@@ -61,6 +61,22 @@ struct BatchWork {
   int which = 0;
 };
 
+// Which way a batch went through the node store: plain host counters, bumped where the host code decides (no kernel knows
+// of them), read by swz_tiler_path_counts in this order.  Tests assert that the path they are named after was taken.
+enum TilerPath : uint32_t {
+  TP_PULL_IN_PLACE = 0,    // level_pull: the batch reaches every node of a linear level, the side is read where it lies
+  TP_PULL_GATHERED,        // level_pull: the files were copied out (tl_gather_files_kernel)
+  TP_PULL_WHOLE_FILE,      // rr_node: a re-rooted node took its cached file out of a populated level (tl_touch_kernel, SplitG)
+  TP_REKEY,                // tl_rekey_kernel launches
+  TP_RESORT,               // resort_if_inverted found an inversion and sorted
+  TP_COMPACT_FULL,         // level_store: store_compact because the side in use was full
+  TP_LINEARIZE_MOVED,      // store_linearize calls that moved data (log form -> linear form)
+  TP_APPEND_BEHIND,        // level_store: new files appended behind existing entries (at != 0)
+  TP_TABLE_MERGE_NF0,      // tl_table_merge_kernel with no untouched table entry (nf == 0)
+  TP_TABLE_MERGE_HEADS0,   // tl_table_merge_kernel with no new file (heads == 0)
+  TP_COUNT
+};
+
 // what a shard of a multi-GPU batch knows about the other shards (root node only)
 struct ShardRoot {
   bool active = false;
@@ -90,6 +106,7 @@ struct swz_tiler {
   bool finalized = false;
   uint64_t batches = 0;
   uint64_t rekey_inversions = 0;
+  uint64_t paths[swz::TP_COUNT] = {0};
   uint64_t staged_bytes = 0;
   double staged_wait_ms = 0.0;  // time swz_tiler_tile_staged had to WAIT for its copy (0 when fully overlapped)
   // a batch between swz_tiler_shard_begin_device and swz_tiler_shard_finish
@@ -153,7 +170,7 @@ int table_reserve(swz_ctx* c, StoreLevel& s, int level_index, int which, size_t 
 int store_table(swz_ctx* c, StoreLevel& s, int level_index);
 int store_compact(swz_ctx* c, StoreLevel& s, int level_index, uint64_t* off, const uint32_t* cnt, uint32_t ntab,
                   uint32_t live, size_t room);
-int store_linearize(swz_ctx* c, StoreLevel& s, int level_index);
+int store_linearize(swz_tiler* t, StoreLevel& s, int level_index);  // (counts TP_LINEARIZE_MOVED when it moves data)
 int store_write_linear(swz_ctx* c, StoreLevel& dst, int level_index, const uint64_t* tkey, const uint32_t* tgid, uint32_t nt);
 int pool_reserve(swz_tiler* t, size_t points);
 // The nodes of n keys that ascend by node prefix (key >> shift): where each node starts and its key with the bits below
@@ -166,7 +183,11 @@ int node_heads(swz_ctx* c, const uint64_t* keys, uint32_t n, uint32_t shift, uin
 int gather_files(swz_ctx* c, const uint32_t* poff, const uint64_t* psrc, uint32_t segs, uint32_t total, const uint64_t* skey,
                  const uint32_t* sgid, uint64_t* okey, uint32_t* ogid);
 
+uint32_t gather_lds();  // TL_SEG_LDS: the longest bracket of segment starts tl_gather_files_kernel searches out of LDS
+
 // ---- swz_tlevel.hip: one level of a batch
+uint32_t merge_tile();  // TL_MERGE_TILE: elements of a run one workgroup of tl_merge_rank_kernel ranks
+uint32_t merge_lds();   // TL_MERGE_LDS: the longest bracket of the other run it searches out of LDS
 int tiler_level(swz_tiler* t, BatchWork& w, const LevelPlan& plan_in, ActiveSet& as, LevelResult* res, uint32_t* merged_out,
                 const ShardRoot* sr = nullptr);
 int work_need_positions(swz_tiler* t, BatchWork& w);

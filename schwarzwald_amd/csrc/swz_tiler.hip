@@ -303,7 +303,7 @@ static int tiler_finalize(swz_tiler* t, swz_tile_stats* stats, int lowest_childr
     StoreLevel& dst = t->lv[lv];
     const uint32_t m = src.cnt;
     if (m == 0) continue;
-    SWZ_TRY(store_linearize(c, src, lv + 1));
+    SWZ_TRY(store_linearize(t, src, lv + 1));
     uint64_t* keys = nullptr;
     uint32_t *gid = nullptr, *wgid = nullptr;
     double *wx = nullptr, *wy = nullptr, *wz = nullptr;
@@ -372,7 +372,7 @@ static int tiler_node_table(swz_tiler* t, std::vector<int8_t>* nl, std::vector<u
       offset += s.cnt;
       continue;
     }
-    SWZ_TRY(store_linearize(c, s, l));
+    SWZ_TRY(store_linearize(t, s, l));
     const int level = l - 1;
     uint32_t* hp = nullptr;
     uint64_t* hk = nullptr;
@@ -594,7 +594,7 @@ int swz_tiler_shard_fast_set_root(swz_tiler* t, const uint8_t* d_taken) {
   if (!d_taken) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_shard_fast_set_root: NULL flags");
   TilerScratchLive live(c);
   auto body = [&]() -> int {
-    SWZ_TRY(store_linearize(c, src, 1));
+    SWZ_TRY(store_linearize(t, src, 1));
     uint64_t *keys = nullptr, *tkey = nullptr;
     uint32_t *tgid = nullptr, *counters = nullptr;
     SWZ_TRY(c->get("tl_keys", (size_t)m, &keys));
@@ -638,7 +638,7 @@ int swz_tiler_level_positions_device(swz_tiler* t, int level, double* d_xyz_out)
   StoreLevel& s = t->lv[level + 1];
   if (!s.cnt) return SWZ_OK;
   if (!d_xyz_out) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_level_positions_device: NULL buffer");
-  SWZ_TRY(store_linearize(c, s, level + 1));
+  SWZ_TRY(store_linearize(t, s, level + 1));
   hipLaunchKernelGGL(tl_rows_kernel, dim3(div_up(s.cnt, 256)), dim3(256), 0, c->stream, s.gid[s.cur], s.cnt, t->pool_xyz, d_xyz_out);
   SWZ_LAUNCH_CHECK(c);
   SWZ_HIP(c, hipStreamSynchronize(c->stream));
@@ -744,6 +744,16 @@ int swz_tiler_get_info(swz_tiler* t, swz_tiler_info* info) {
   return SWZ_OK;
 }
 
+uint32_t swz_tiler_merge_tile(void) { return merge_tile(); }
+uint32_t swz_tiler_merge_lds(void) { return merge_lds(); }
+uint32_t swz_tiler_gather_lds(void) { return gather_lds(); }
+
+int swz_tiler_path_counts(swz_tiler* t, uint64_t* out, uint32_t n) {
+  if (!t || (n && !out)) return SWZ_ERR_BAD_ARG;
+  for (uint32_t i = 0; i < n; ++i) out[i] = i < TP_COUNT ? t->paths[i] : 0ull;
+  return SWZ_OK;
+}
+
 int swz_tiler_pool_residency(swz_tiler* t, uint64_t* device_bytes_out, uint64_t* host_bytes_out) {
   if (!t) return SWZ_ERR_BAD_ARG;
   uint64_t dev = 0, host = 0;
@@ -810,7 +820,7 @@ int swz_tiler_export_device(swz_tiler* t, uint64_t* d_keys_out, uint32_t* d_ids_
   for (int l = 0; l < 22; ++l) {
     StoreLevel& s = t->lv[l];
     if (!s.cnt) continue;
-    SWZ_TRY(store_linearize(c, s, l));
+    SWZ_TRY(store_linearize(t, s, l));
     if (d_keys_out) SWZ_HIP(c, hipMemcpyAsync(d_keys_out + off, s.key[s.cur], (size_t)s.cnt * 8, hipMemcpyDeviceToDevice, c->stream));
     if (d_ids_out) SWZ_HIP(c, hipMemcpyAsync(d_ids_out + off, s.gid[s.cur], (size_t)s.cnt * 4, hipMemcpyDeviceToDevice, c->stream));
     if (d_level_out) {

@@ -258,6 +258,8 @@ int merge_pairs(swz_ctx* c, const uint64_t* k1, const uint32_t* v1, uint32_t n1,
   }
   return SWZ_OK;
 }
+uint32_t merge_tile() { return TL_MERGE_TILE; }
+uint32_t merge_lds() { return TL_MERGE_LDS; }
 
 // (key, gid) ascending by key when the re-keyed order is not (the reference only sorts for a lossy persistence,
 // :103-106 / :1690-1692; counted in rekey_inversions)
@@ -284,6 +286,7 @@ int resort_if_inverted(swz_tiler* t, uint64_t* key, uint32_t* gid, uint32_t n, u
   SWZ_TRY(read_u32(c, counters + 1, &inv));
   if (inv) {
     t->rekey_inversions += inv;
+    ++t->paths[TP_RESORT];
     SWZ_TRY(sort_pairs_by_key(c, key, gid, n));
   }
   return SWZ_OK;
@@ -327,7 +330,7 @@ static int level_pull(swz_tiler* t, BatchWork& w, const LevelPlan& plan, const A
   SWZ_TRY(c->get("tl_counters", (size_t)4, &counters));
   const int lvi = plan.level + 1;
   if (st.cnt && sr) {  // the root is reached by the batch as a whole: all of its local file
-    SWZ_TRY(store_linearize(c, st, lvi));
+    SWZ_TRY(store_linearize(t, st, lvi));
     SWZ_TRY(store_table(c, st, lvi));
     SWZ_TRY(c->get("tl_ckey", (size_t)st.cnt, &p->ckey));
     SWZ_TRY(c->get("tl_cgid", (size_t)st.cnt, &p->cgid));
@@ -362,7 +365,9 @@ static int level_pull(swz_tiler* t, BatchWork& w, const LevelPlan& plan, const A
       // or on the other side --, so the merge may read it in place (and a re-sort after an inversion may reorder it).
       p->ckey = st.key[st.cur];
       p->cgid = st.gid[st.cur];
+      ++t->paths[TP_PULL_IN_PLACE];
     } else if (p->nc) {
+      ++t->paths[TP_PULL_GATHERED];
       ProfScope ps(c, "tiler_pull", (uint64_t)p->nc * 24ull, 1);
       SWZ_TRY(c->get("tl_ckey", (size_t)p->nc, &p->ckey));
       SWZ_TRY(c->get("tl_cgid", (size_t)p->nc, &p->cgid));
@@ -395,6 +400,7 @@ static int level_merge(swz_tiler* t, BatchWork& w, const LevelPlan& plan, const 
     hipLaunchKernelGGL(tl_rekey_kernel, dim3(div_up(nc, 256)), dim3(256), 0, c->stream, ckey, cgid, nc, t->pool_xyz,
                        root_box(t), plan.level);
     SWZ_LAUNCH_CHECK(c);
+    ++t->paths[TP_REKEY];
   }
   // (needed for files the level loop wrote as well: TakeStoreG stores the key against the NODE's bounds, which may order two
   // points the other way round than the key they were sorted by -- tests/test_multibatch.py constructs such a pair)
@@ -485,11 +491,13 @@ static int level_store(swz_tiler* t, BatchWork& w, const LevelPlan& plan, const 
       SWZ_TRY(read_u32(c, counters + 1, &nf));
       nf_known = true;
     }
+    if (st.key[st.cur]) ++t->paths[TP_COMPACT_FULL];  // (else the level's first file: there is no side yet)
     ProfScope ps(c, "tiler_store", (uint64_t)rest * 24ull, 2);
     const size_t room = (size_t)rest + nt;
     SWZ_TRY(store_compact(c, st, lvi, foff, fcnt, nf, rest, room + room / 4));
   }
   const uint32_t at = st.end;
+  if (at) ++t->paths[TP_APPEND_BEHIND];
   uint32_t* texcl = nullptr;
   SWZ_TRY(c->get("tl_texcl", (size_t)ms.m, &texcl));
   {
@@ -528,6 +536,8 @@ static int level_store(swz_tiler* t, BatchWork& w, const LevelPlan& plan, const 
       hipLaunchKernelGGL(tl_table_merge_kernel, dim3(div_up(nf + heads, 256)), dim3(256), 0, c->stream, fkey, foff, fcnt, nf, hk, hp,
                          heads, nt, (uint64_t)at, st.nkey[nd], st.noff[nd], st.ncnt[nd]);
       SWZ_LAUNCH_CHECK(c);
+      if (!nf) ++t->paths[TP_TABLE_MERGE_NF0];
+      if (!heads) ++t->paths[TP_TABLE_MERGE_HEADS0];
     }
     st.ncur = nd;
     st.nn = nf + heads;

@@ -139,7 +139,7 @@ static int rr_node(swz_tiler* t, BatchWork& w, const RrNode& node, double root_e
   SWZ_TRY(c->get("tl_counters", (size_t)4, &counters));
   // ---- the node's file (read_pnts_from_disk; the re-keying is irrelevant: everything is re-indexed or appended)
   StoreLevel& st = t->lv[node.level + 1];
-  SWZ_TRY(store_linearize(c, st, node.level + 1));
+  SWZ_TRY(store_linearize(t, st, node.level + 1));
   uint64_t *ckey = nullptr, *rkey = nullptr;
   uint32_t *cgid = nullptr, *rgid = nullptr;
   uint32_t nc = 0, nr = 0;
@@ -159,6 +159,7 @@ static int rr_node(swz_tiler* t, BatchWork& w, const RrNode& node, double root_e
     SWZ_TRY(fused_scan(c, TouchF{touch}, SplitG{st.key[st.cur], st.gid[st.cur], ckey, cgid, rkey, rgid}, st.cnt, counters, "tl"));
     SWZ_TRY(read_u32(c, counters, &nc));
     nr = st.cnt - nc;
+    if (nc) ++t->paths[TP_PULL_WHOLE_FILE];
   }
   const uint32_t m = cnt + nc;
   tot.nodes += 1;

@@ -237,6 +237,8 @@ int gather_files(swz_ctx* c, const uint32_t* poff, const uint64_t* psrc, uint32_
   return SWZ_OK;
 }
 
+uint32_t gather_lds() { return TL_SEG_LDS; }
+
 // Gathers the files a table lists (ntab entries, `live` entries in all, in table order) into the other side, which gets
 // room for `room` entries, and makes it the current one; off[] (device) is rewritten to the new places.
 int store_compact(swz_ctx* c, StoreLevel& s, int level_index, uint64_t* off, const uint32_t* cnt, uint32_t ntab,
@@ -257,11 +259,13 @@ int store_compact(swz_ctx* c, StoreLevel& s, int level_index, uint64_t* off, con
   return SWZ_OK;
 }
 // log form -> linear form (the table stays valid)
-int store_linearize(swz_ctx* c, StoreLevel& s, int level_index) {
+int store_linearize(swz_tiler* t, StoreLevel& s, int level_index) {
+  swz_ctx* c = t->c;
   if (s.linear) return SWZ_OK;
   if (!s.table_valid) return c->fail(SWZ_ERR_INTERNAL, "node store: log without a table");
   SWZ_TRY(store_compact(c, s, level_index, s.noff[s.ncur], s.ncnt[s.ncur], s.nn, s.cnt, s.cnt));
   s.linear = true;
+  ++t->paths[TP_LINEARIZE_MOVED];
   return SWZ_OK;
 }
 

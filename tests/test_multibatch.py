@@ -543,15 +543,8 @@ def _constructed_inversion(bounds):
     raise AssertionError("no such point found")
 
 
-@pytest.mark.gpu
-def test_gpu_rekey_inversion_is_counted_and_confined(ctx):
-    """swz_tiler sorts the cached points of a node when their re-keyed order is no longer ascending; the reference
-    merges them as they are (a lossless store is read without a sort, TilingAlgorithms.cpp:103-106).  The library counts
-    such nodes' inversions (swz_tiler_info.rekey_inversions) and documents that results may differ from the reference
-    only then.  Here an inversion is constructed: the counter must see it (the oracle's own counter too), every point
-    must still be stored exactly once, and whatever differs from the oracle must be confined to the node in question."""
-    import schwarzwald_amd as swz
-    bounds = ODD
+def _inversion_batches(bounds):
+    """(batches, ia, ib): two batches around the pair of _constructed_inversion; ia, ib are the ids of a and b"""
     lo, side = np.array(bounds[0]), bounds[1][0] - bounds[0][0]
     i, xa = _constructed_inversion(bounds)
     cell = side / 2097152.0
@@ -565,7 +558,19 @@ def test_gpu_rekey_inversion_is_counted_and_confined(ctx):
     fill1 = lo + rng.random((4000, 3)) * side
     fill2 = lo + (0.5 + 0.5 * rng.random((3000, 3))) * side   # the second batch touches octant 7, whose file holds a and b
     batches = [np.vstack([fill1, decoy[None], b[None], a[None]]), fill2]
-    ia, ib = 4002, 4001
+    return batches, 4002, 4001
+
+
+@pytest.mark.gpu
+def test_gpu_rekey_inversion_is_counted_and_confined(ctx):
+    """swz_tiler sorts the cached points of a node when their re-keyed order is no longer ascending; the reference
+    merges them as they are (a lossless store is read without a sort, TilingAlgorithms.cpp:103-106).  The library counts
+    such nodes' inversions (swz_tiler_info.rekey_inversions) and documents that results may differ from the reference
+    only then.  Here an inversion is constructed: the counter must see it (the oracle's own counter too), every point
+    must still be stored exactly once, and whatever differs from the oracle must be confined to the node in question."""
+    import schwarzwald_amd as swz
+    bounds = ODD
+    batches, ia, ib = _inversion_batches(bounds)
     sp = O.spacing_from_diagonal(*bounds, 250)
     t = O.Tiler(bounds[0], bounds[1], O.RANDOM_GRID, 100, sp)
     for part in batches:
