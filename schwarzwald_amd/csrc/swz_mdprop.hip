@@ -505,7 +505,7 @@ int min_distance_phases_level(swz_ctx* c, const MdLevel& L, int cl, uint32_t* ph
   if (c->opt("SWZ_DEBUG")) {
     SWZ_HIP(c, hipStreamSynchronize(c->stream));
     fprintf(stderr, "[swz] MIN_DISTANCE property level %d: %u pts in %u nodes, cell levels %d of %d, %u cells (%.1f pts each), "
-            "%.1f ms\n", plan.level, sample_points, sample_nodes, cl, plan.cell_levels_geo, ncells, pts_per_cell,
+            "%u big-cell units, %.1f ms\n", plan.level, sample_points, sample_nodes, cl, plan.cell_levels_geo, ncells, pts_per_cell, uoff[8],
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count());
   }
   return SWZ_OK;

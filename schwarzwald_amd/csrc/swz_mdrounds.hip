@@ -747,12 +747,15 @@ int min_distance_rounds_level(swz_ctx* c, const MdLevel& L, uint32_t* rounds_out
   const bool cell_lists = c->opt_on("SWZ_MD_ROUNDS_CELL_LISTS", true);
   bool prev_list = false;   // the round before ran over a list (list[cur ^ 1], nprev entries: still intact)
   uint32_t nprev = 0;
+  uint32_t list_round = 0, cell_list_rounds = 0;  // (SWZ_DEBUG: the first round over the list of alive points, rounds with the per-cell steps over it)
   for (;;) {
     ++rounds;
+    if (use_list && !list_round) list_round = rounds;
     // (a list of more entries than a quarter of the cells: the kernels over the cell grid are the cheaper ones -- a list entry
     // costs its head test, two keys and two node ids, before its cell's work)
     const bool by_list = use_list && cell_lists && (uint64_t)nlist * 4u < a.ncells;
     if (by_list) {
+      ++cell_list_rounds;
       if (prev_list) {
         hipLaunchKernelGGL(pr_candidates_list_kernel, dim3(div_up(std::max(nprev, 1u), 256)), dim3(256), 0, c->stream, a, cur, a.list[cur ^ 1u], nprev);
       } else {
@@ -829,10 +832,15 @@ int min_distance_rounds_level(swz_ctx* c, const MdLevel& L, uint32_t* rounds_out
   if (dbg) {
     uint32_t hc[CTR_COUNT];
     SWZ_HIP(c, hipMemcpy(hc, lb.counters, sizeof(hc), hipMemcpyDeviceToHost));
+    // which kill pass the rounds before the list ran, and how far the list took over: what a test of a path reads
+    uint32_t extra_chunks = 0;
+    if (blk) SWZ_HIP(c, hipMemcpy(&extra_chunks, g.eoff + g.blocks, 4, hipMemcpyDeviceToHost));
+    const std::string kill = blk ? "block B=" + std::to_string(1u << g.bl) : (wl ? "records" : "mask loop");
     fprintf(stderr, "[swz] MIN_DISTANCE property level %d in rounds: %u pts in %u nodes, %llu cells (cell levels %d, %.1f pts each), spacing %.1f key cells, "
-                    "%u rounds, %u exact compares, %.1f ms; alive after each round:%s\n",
+                    "%u rounds, %u exact compares, %.1f ms; kill pass %s, %u extra chunks, list from round %u, %u rounds by cell lists; alive after each round:%s\n",
             plan.level, sample_points, sample_nodes, (unsigned long long)a.ncells, cl, (double)sample_points / (double)a.ncells, km.T, rounds, hc[PRC_BAND],
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count(), trace.c_str());
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count(), kill.c_str(), extra_chunks, list_round,
+            cell_list_rounds, trace.c_str());
   }
   SWZ_HIP(c, hipMemsetAsync(lb.counters + CTR_DBG_HIST, 0, 8 * sizeof(uint32_t), c->stream));
   return SWZ_OK;

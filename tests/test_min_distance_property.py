@@ -19,12 +19,14 @@ pytestmark = pytest.mark.gpu
 UNIT = ([0.0, 0.0, 0.0], [1.0, 1.0, 1.0])
 
 
-def _check_property(keys, level, pos, spacing_at_root, max_points, max_level, rng=None, box_points=None):
+def _check_property(keys, level, pos, spacing_at_root, max_points, max_level, rng=None, box_points=None, min_level=-1):
     """keys/level/pos in Morton order (numpy).  Verifies (a) and (b) on every sampled node (or, with box_points, on
-    the points of a random box).  Returns (pairs checked, points checked for maximality)."""
+    the points of a random box) of the levels min_level .. max_level (FAST starts below the root).  Returns (pairs
+    checked, points checked for maximality).  A failure names one offending pair (a) or point (b): sorted positions and
+    the squared distance against the float-squared spacing."""
     from scipy.spatial import cKDTree
     checked_a = checked_b = 0
-    for L in range(-1, max_level + 1):
+    for L in range(min_level, max_level + 1):
         s = np.float32(spacing_at_root) / np.float32(2.0 ** (L + 1))
         sq = float(np.float32(s) * np.float32(s))
         active = level >= L
@@ -50,6 +52,7 @@ def _check_property(keys, level, pos, spacing_at_root, max_points, max_level, rn
         P, nd = pos[idx], node[idx]
         taken = level[idx] == L
         T, Tn = P[taken], nd[taken]
+        Ti = idx[taken]
         assert T.shape[0] > 0
         tree = cKDTree(T)
         # (a) no two taken points of one node closer than the spacing
@@ -58,7 +61,10 @@ def _check_property(keys, level, pos, spacing_at_root, max_points, max_level, rn
             d = T[pairs[:, 0]] - T[pairs[:, 1]]
             d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
             bad = (d2 < sq) & (Tn[pairs[:, 0]] == Tn[pairs[:, 1]])
-            assert not bad.any(), "level %d: %d taken pairs closer than the spacing" % (L, int(bad.sum()))
+            if bad.any():
+                k = int(np.flatnonzero(bad)[0])
+                raise AssertionError("level %d: %d taken pairs closer than the spacing, e.g. sorted positions %d and %d: d^2 = %r < %r" % (
+                    L, int(bad.sum()), int(Ti[pairs[k, 0]]), int(Ti[pairs[k, 1]]), float(d2[k]), sq))
         checked_a += int(T.shape[0])
         # (b) every point handed down has a taken point of its node within the spacing
         rest = ~taken
@@ -72,8 +78,14 @@ def _check_property(keys, level, pos, spacing_at_root, max_points, max_level, rn
             ok = (d2 < sq) & (Qn[m["i"]] == Tn[m["j"]])
             covered = np.zeros(Q.shape[0], dtype=bool)
             covered[m["i"][ok]] = True
-            assert covered.all(), "level %d: %d points left out although no taken point is within the spacing" % (
-                L, int((~covered).sum()))
+            if not covered.all():
+                q = int(np.flatnonzero(~covered)[0])
+                mine = (m["i"] == q) & (Qn[m["i"]] == Tn[m["j"]])
+                nearest = ("its nearest taken point of the node, sorted position %d, has d^2 = %r >= %r" % (
+                    int(Ti[m["j"][mine][np.argmin(d2[mine])]]), float(d2[mine].min()), sq)) if mine.any() else (
+                    "no taken point of its node within reach (%r)" % sq)
+                raise AssertionError("level %d: %d points left out although no taken point is within the spacing, e.g. sorted position %d: %s" % (
+                    L, int((~covered).sum()), int(idx[rest][q]), nearest))
             checked_b += int(Q.shape[0])
     return checked_a, checked_b
 
