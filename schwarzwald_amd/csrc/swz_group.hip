@@ -398,7 +398,7 @@ struct RootOps {
 };
 
 // All shards sweep the root cells of their own octants at the same time; a cell at the face of a lower octant reads that
-// shard's records through peer access (swz_mdkeys.hip), exact positions of a tiler through its working index
+// shard's records through peer access (swz_mqsweep.hip), exact positions of a tiler through its working index
 // (MdPeerView::aidx).  No ghosts, no turns.  One barrier: inside the sweep, or here for a shard that never entered it.
 void root_joint(Step& s, const RootOps& ops, uint64_t* taken) {
   swz_group* g = s.g;
@@ -1691,7 +1691,7 @@ int swz_group_write_output(swz_group* g, const char* dir, const swz_output_param
 // with one process per GPU (torch.distributed) gets the same through IPC: inside the begin call of its batch every rank
 // exports the arrays of its root level (hipIpcGetMemHandle on the allocations they live in + offsets), the driver's
 // all-gather callback passes the blobs round, and every rank maps the arrays of the LOWER ranks (hipIpcOpenMemHandle).
-// From there on the sweep is the one of swz_mdkeys.hip: remote records bracketed by the owner's round word, system-scope
+// From there on the sweep is the one of swz_mdkeys.hip / swz_mqsweep.hip: remote records bracketed by the owner's round word, system-scope
 // loads, cells at the faces polling.  swz_shard_joint_root_end -- after the driver's barrier, when every rank has
 // finished its root -- unmaps.
 }  // extern "C"

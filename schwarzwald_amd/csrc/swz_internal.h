@@ -89,7 +89,7 @@ struct swz_ctx {
   // swz_mdblock.hip, sb_incremental: [sbi_clean_ptr, + sbi_clean_bytes) of the "sbi_bits" buffer is known to be zero
   const void* sbi_clean_ptr = nullptr;
   size_t sbi_clean_bytes = 0;
-  // swz_mdkeys.hip: "md_qpos" at mq_qpos_buf holds the packed key coordinates of the mq_qpos_m keys at mq_qpos_keys (the
+  // the key sweep (swz_mqbuild.hip, mq_alloc_arrays): "md_qpos" at mq_qpos_buf holds the packed key coordinates of the mq_qpos_m keys at mq_qpos_keys (the
   // next level of a chain on the same arrays does not write them again); free_buf forgets it with the buffer
   const void* mq_qpos_buf = nullptr;
   const void* mq_qpos_keys = nullptr;

@@ -77,7 +77,7 @@ struct SortedPoints {
   const double* Y = nullptr;
   const double* Z = nullptr;
   // The clamped input positions (AoS, caller's order) and the sort's permutation: sorted position s is point perm[s].
-  // MIN_DISTANCE decides almost every pair on the coordinates its keys already hold (swz_mdkeys.hip) and looks up the
+  // MIN_DISTANCE decides almost every pair on the coordinates its keys already hold (swz_mqsweep.hip) and looks up the
   // few pairs inside the quantisation band here, so the positions are never brought into Morton order.
   const double* xyz = nullptr;
   const uint32_t* perm = nullptr;

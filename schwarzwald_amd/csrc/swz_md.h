@@ -35,7 +35,7 @@ struct MdShardRoot {
   void* barrier_arg = nullptr;
 };
 
-// ---- MIN_DISTANCE on key coordinates (swz_mdkeys.hip) ----------------------------------------------------------
+// ---- MIN_DISTANCE on key coordinates (swz_mdkeys.hip; tables: swz_mqbuild.hip, rounds: swz_mqsweep.hip) --------
 // The key of a point is its position quantised to 2^-21 of the (cubic) bounds: the integer coordinates of two points
 // bound their distance to +-sqrt(3) key cells, so a compare against the spacing is decided on the keys alone unless the
 // integer distance lies within that band around it; those pairs -- a few in ten thousand at the root, a few per cent of
@@ -54,7 +54,7 @@ int key_point_ids(swz_ctx* c, const ActiveSet& as, const SortedPoints& sp, const
 // true when min_distance_level will not need sp.X / sp.Y / sp.Z for this level
 bool min_distance_level_uses_keys(const swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp);
 // no sampler of this level reads sp.X / Y / Z: RANDOM_GRID never does, the others decide on key coordinates and look up
-// sp.xyz through sp.perm (swz_mdkeys.hip, grid_argmin_keys_kernel)
+// sp.xyz through sp.perm (swz_mqsweep.hip, grid_argmin_keys_kernel)
 bool level_decides_on_keys(const swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp);
 // ---- one level as every algorithm sees it ------------------------------------------------------------------------
 // Filled by the dispatcher's survey of the level.  A parameter list with a name, not an interface.

@@ -66,7 +66,7 @@ int session_prepare(swz_ctx* c, TileSession& t, double* d_xyz, uint32_t n, const
   SWZ_STAGE(c, "encode");
   SWZ_TRY(radix_sort_pairs(c, keys_b, vals_b, out.keys, out.perm, n, true));
   // The positions in Morton order (SoA).  RANDOM_GRID decides on the keys alone.  MIN_DISTANCE decides on the key
-  // coordinates and looks up the pairs inside the quantisation band through the permutation (swz_mdkeys.hip): there
+  // coordinates and looks up the pairs inside the quantisation band through the permutation (swz_mqsweep.hip): there
   // the gather is put off until a level asks for it (session_need_positions) -- for cubic bounds and exact mode that is
   // a level so deep that its spacing spans fewer than 64 key cells, which few clouds reach.  Sharded batches that
   // prepend ghosts (front > 0) look up two position arrays: the sorted positions in front are the ghosts

@@ -581,7 +581,7 @@ int tiler_level(swz_tiler* t, BatchWork& w, const LevelPlan& plan_in, ActiveSet&
   SWZ_TRY(c->get(w.which ? "tl_surv_idx_1" : "tl_surv_idx_0", (size_t)ms.m, &w.surv_idx[w.which]));
   LevelBuffers lb;
   SWZ_TRY(alloc_level_buffers(c, ms.m, &lb));
-  // (exact positions for MIN_DISTANCE on key coordinates, swz_mdkeys.hip: working index -> point id -> position pool;
+  // (exact positions for MIN_DISTANCE on key coordinates, swz_mqsweep.hip: working index -> point id -> position pool;
   // ghosts of a sharded root lie outside the pool)
   SortedPoints sp{nullptr, nullptr, nullptr, ng ? nullptr : t->pool_xyz, w.wgid};
   if (!level_decides_on_keys(c, plan, sp)) SWZ_TRY(work_need_positions(t, w));

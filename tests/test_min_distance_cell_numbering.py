@@ -1,4 +1,4 @@
-"""The two ways the key sweep numbers its cells (schwarzwald_amd/csrc/swz_mdkeys.hip, MqArgs::direct) against the CPU oracle.
+"""The two ways the key sweep numbers its cells (schwarzwald_amd/csrc/swz_mqbuild.hip, MqArgs::direct) against the CPU oracle.
 
 Compacted: the occupied cells get consecutive ids from a count and a scan over the keys.  Direct: a cell's id is its place in
 the grid of its node, every per-cell array covers the whole grid and an empty cell is an entry that says so.  The accepted set

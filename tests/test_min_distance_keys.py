@@ -1,4 +1,4 @@
-"""MIN_DISTANCE decided on key coordinates (schwarzwald_amd/csrc/swz_mdkeys.hip) against the CPU oracle.
+"""MIN_DISTANCE decided on key coordinates (schwarzwald_amd/csrc/swz_mdkeys.hip, swz_mqbuild.hip, swz_mqsweep.hip) against the CPU oracle.
 
 The sweep compares integer key coordinates and evaluates only the pairs inside the quantisation band around the spacing
 on the exact positions; the accepted set must be the oracle's, point for point, whatever the scheduling, the record
