@@ -874,6 +874,77 @@ typedef struct {
 } swz_input_stats;
 int swz_tiler_add_las_files(swz_tiler* tiler, const char* const* paths, uint64_t num_files, const swz_input_params* params,
                             swz_input_stats* stats);
+/* ---- a source projection (the reference's --source-projection: Proj4Transform, core/util/Transformation.cpp:74-211, source
+ * -> "+proj=geocent +datum=WGS84").  PROJ is not linked: the library maps the projection families LAS data comes in itself,
+ * in double, and refuses every other definition by name.
+ *   swz_srs_parse (host; ctx only carries the error text and may be NULL).  Accepted, as whitespace-separated +key[=value]:
+ *     +proj=utm +zone=1..60 [+south] | +proj=tmerc [+lat_0 +lon_0 +k | +k_0 +x_0 +y_0] (degrees, metres; defaults 0, 0, 1, 0, 0)
+ *     | +proj=longlat / latlong (x = longitude, y = latitude in degrees, z = ellipsoidal height); the ellipsoid, which must be
+ *     given, by +ellps=WGS84|GRS80, +datum=WGS84 or +a with +rf or +b (+ellps beside +datum only when they agree); +units=m,
+ *     +no_defs, +type=crs; the shorthands EPSG:32601-32660, EPSG:32701-32760 (WGS 84 / UTM) and EPSG:25828-25838 (ETRS89 /
+ *     UTM on GRS80).  On an ellipsoid other than WGS84 the inverse projection runs on THAT ellipsoid; latitude, longitude and
+ *     height are then carried unchanged onto WGS84 (no datum shift), and the geocentric step is always WGS84's.
+ *     SWZ_ERR_BAD_ARG, naming the token, for everything else: another +proj, +towgs84, +nadgrids, +geoidgrids, +vunits,
+ *     +units other than m, +axis, +pm, +approx, any other key, a key a projection does not take (+zone with tmerc, ...),
+ *     a key given twice, other EPSG codes (EPSG:4326 too: its axis order differs between PROJ versions, write +proj=longlat
+ *     +datum=WGS84), WKT, a zone out of range, ellipsoid parameters that are not finite and positive, no ellipsoid, an
+ *     empty string.
+ *   The map, per point (swz_srs_transform on the host, swz_srs_transform_device in place on AoS rows of 24 bytes, staged
+ *     through LDS by tiles of swz_srs_tile() rows; n = 0 launches nothing, more than 2^32 - 65536 rows are refused): the
+ *     inverse transverse Mercator is the Krueger series in the third flattening n to order n^6 (Karney 2011, "Transverse
+ *     Mercator with an accuracy of a few nanometers"): false origin and scale removed, the six beta coefficients summed by a
+ *     complex Clenshaw recurrence on sin / cos / sinh / cosh of the doubled arguments, longitude = lon_0 + atan2(sinh eta',
+ *     cos xi'), conformal -> geodetic latitude by the six-term series in n as well (no iteration: a point far outside the
+ *     domain costs what every point costs and yields a meaningless or non-finite value).  The coefficients are computed once,
+ *     by swz_srs_parse (tools/srs_series.py derives them).  Geodetic -> ECEF is the closed form.  Targets: SWZ_SRS_ECEF (X,
+ *     Y, Z in metres) and SWZ_SRS_WGS84 (longitude and latitude in RADIANS, longitude in [-pi, pi], and the height: the
+ *     reference's TargetSRS::WGS84).  Non-finite input gives non-finite output; nothing traps.  Floating-point contraction
+ *     is off inside the map, so the device result for given input bits is the same in every kernel it is inlined into.
+ *   swz_srs_transform_box (host): the eight corners of the box, corner i = (i & 1 ? max : min).x, (i & 2 ? max : min).y,
+ *     (i & 4 ? max : min).z, mapped and then min / max per axis: transformAABBWithProj4 (Transformation.cpp:10-44).  The
+ *     image of a flat tile bulges, so a point INSIDE the source box can land a few centimetres OUTSIDE this box.  The
+ *     reference has the same property and clamps such a point in place when it indexes it (index_point); so does this
+ *     library.  The box is neither widened nor are such points refused.
+ *   swz_las_scan_files_srs: swz_las_scan_files with the header box of every readable file sent through
+ *     swz_srs_transform_box to ECEF BEFORE it joins the union (TilerProcess::calculate_dataset_metadata,
+ *     TilerProcess.cpp:352-387; not the transformed union); cubic, origin box and centre come from that union by the same
+ *     arithmetic.  files_out[i].layout keeps the file's own header values: the decode clamps against them in the source CRS,
+ *     as the reference's reader does.  srs == NULL is swz_las_scan_files.
+ *   swz_las_decode_segments_srs_device: swz_las_decode_segments_device with the map to ECEF after the clamp into the header
+ *     box and before the shift (make_tiler, TilerProcess.cpp:539-561), in a kernel instantiation of its own -- the one
+ *     without a projection is untouched.  srs == NULL is swz_las_decode_segments_device.
+ *   swz_tiler_set_source_srs (NULL clears): swz_tiler_add_las_files then scans with swz_las_scan_files_srs -- the
+ *     containment check against the root box and the centre of the shift use the ECEF boxes -- and decodes with the map.
+ *     SWZ_ERR_BAD_ARG unless the tiler holds no points and no batch is staged or open: set and clear alike, so a tiler
+ *     that has read points with a projection keeps it for its life and every later swz_tiler_add_las_files projects too.  swz_group_set_source_srs: the same
+ *     for swz_group_add_las_files, between swz_group_tiler_open and the first batch (the close forgets it). */
+enum { SWZ_SRS_LONGLAT = 0, SWZ_SRS_TMERC = 1 };
+enum { SWZ_SRS_ECEF = 0, SWZ_SRS_WGS84 = 1 };
+typedef struct {
+  int32_t kind; /* SWZ_SRS_LONGLAT / SWZ_SRS_TMERC (utm is a tmerc) */
+  int32_t reserved;
+  double a, f, e2, n;      /* the source ellipsoid: semi-major axis, flattening, e^2 = f (2 - f), n = f / (2 - f) */
+  double lat_0, lon_0;     /* radians */
+  double k_0, x_0, y_0;
+  double radius;           /* k_0 A, A = a / (1 + n) (1 + n^2/4 + n^4/64 + n^6/256) the rectifying radius */
+  double xi_0;             /* the rectifying latitude of lat_0 */
+  double beta[6];          /* rectifying -> conformal: chi = mu - sum beta_j sin 2 j mu */
+  double delta[6];         /* conformal -> geodetic: phi = chi + sum delta_j sin 2 j chi */
+} swz_srs;
+int swz_srs_parse(swz_ctx* ctx, const char* definition, swz_srs* out);
+/* swz_srs_parse for callers without a context: the refusal's text goes into why_out (why_bytes bytes, cut and terminated) */
+int swz_srs_parse_why(const char* definition, swz_srs* out, char* why_out, uint64_t why_bytes);
+int swz_srs_transform(const swz_srs* srs, int target, double* xyz, uint64_t n);
+uint32_t swz_srs_tile(void); /* rows one workgroup takes at a time; tests place their edges by it */
+int swz_srs_transform_device(swz_ctx* ctx, const swz_srs* srs, int target, double* d_xyz, uint64_t n);
+int swz_srs_transform_box(const swz_srs* srs, int target, const double min[3], const double max[3], double out_min[3],
+                          double out_max[3]);
+int swz_las_scan_files_srs(swz_ctx* ctx, const char* const* paths, uint64_t num_files, uint32_t flags, const swz_srs* srs,
+                           swz_las_file_info* files_out, swz_las_dataset* dataset_out);
+int swz_las_decode_segments_srs_device(swz_ctx* ctx, const uint8_t* d_raw, uint64_t raw_bytes, uint64_t num_segments,
+                                       const swz_las_segment* segments /* host */, const double shift_center[3] /* or NULL */,
+                                       double* d_xyz_out, const swz_attribute_columns* d_out, const swz_srs* srs /* or NULL */);
+int swz_tiler_set_source_srs(swz_tiler* tiler, const swz_srs* srs /* NULL clears */);
 /* ---- one tiler per GPU of a multi-GPU run (BASELINE config 5: sharded + multi-batch).  Points are owned by their
  * level-0 octant as in swz_shard_* above; every shard keeps the subtrees of its octants and ITS part of the root's
  * file.  Per batch, after the exchange of the batch's points (and attribute columns) by octant:
@@ -1040,6 +1111,9 @@ int swz_group_finalize(swz_group* group, swz_tile_stats* stats_per_shard);
  *     batches, tile_ms the tiling calls', wait_ms the time the call waited for its readers. */
 int swz_group_add_las_files(swz_group* group, const char* const* paths, uint64_t num_files, const swz_input_params* params,
                             swz_input_stats* stats);
+/* swz_tiler_set_source_srs for the group's data set: allowed between swz_group_tiler_open and the first batch (NULL clears;
+ * swz_group_tiler_close forgets it).  The data set's ECEF boxes are computed once on the host, not per shard. */
+int swz_group_set_source_srs(swz_group* group, const swz_srs* srs);
 int swz_merge_shard_node_tables(int num_shards, const uint64_t* num_nodes, const int8_t* const* node_level,
                                 const uint64_t* const* node_key, const uint64_t* const* node_count, uint64_t max_nodes,
                                 int8_t* level_out, uint64_t* key_out, uint64_t* count_out, int32_t* shard_out,

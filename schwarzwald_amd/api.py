@@ -663,16 +663,91 @@ def attribute_names(mask):
     return [name for name, (idx, _, _) in ATTRIBUTES.items() if int(mask) >> idx & 1]
 
 
-def las_scan_files(paths, skip_unreadable=False, ctx=None):
+SRS_LONGLAT, SRS_TMERC = 0, 1
+SRS_ECEF, SRS_WGS84 = 0, 1
+
+
+class _Srs(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("a", C.c_double), ("f", C.c_double), ("e2", C.c_double),
+                ("n", C.c_double), ("lat_0", C.c_double), ("lon_0", C.c_double), ("k_0", C.c_double), ("x_0", C.c_double),
+                ("y_0", C.c_double), ("radius", C.c_double), ("xi_0", C.c_double), ("beta", C.c_double * 6),
+                ("delta", C.c_double * 6)]
+
+
+class Srs:
+    """swz_srs_parse: a source projection, swz.Srs("+proj=utm +zone=32 +datum=WGS84").  Raises SwzError, naming the token,
+    for everything the library does not map itself.  fields(): the struct as a dict."""
+
+    def __init__(self, definition):
+        self.definition = str(definition)
+        self._s = _Srs()
+        why = C.create_string_buffer(512)
+        st = load_library().swz_srs_parse_why(self.definition.encode(), C.byref(self._s), why, len(why))
+        if st != 0:
+            raise SwzError(st, why.value.decode(errors="replace"))
+
+    def fields(self):
+        out = {}
+        for name, _ in _Srs._fields_:
+            v = getattr(self._s, name)
+            out[name] = list(v) if hasattr(v, "__len__") else v
+        return out
+
+    def _ref(self):
+        return C.byref(self._s)
+
+
+def _as_srs(srs):
+    return None if srs is None else (srs if isinstance(srs, Srs) else Srs(srs))
+
+
+def _check_target(target):
+    if target not in (SRS_ECEF, SRS_WGS84):
+        raise ValueError("target must be SRS_ECEF or SRS_WGS84")
+
+
+def srs_transform(srs, xyz, target=SRS_ECEF):
+    """swz_srs_transform: positions (n, 3) in the source projection -> a new float64 array in ECEF (metres) or WGS84 (longitude
+    and latitude in radians, height), on the host."""
+    _check_target(target)
+    out = np.array(xyz, dtype=np.float64, order="C").reshape(-1, 3)
+    st = load_library().swz_srs_transform(_as_srs(srs)._ref(), int(target), out.ctypes.data_as(_dp), out.shape[0])
+    if st != 0:
+        raise SwzError(st, "swz_srs_transform failed")
+    return out
+
+
+def srs_transform_box(srs, box_min, box_max, target=SRS_ECEF):
+    """swz_srs_transform_box: min / max per axis of the eight mapped corners.  Returns (min, max)."""
+    _check_target(target)
+    lo, hi = (C.c_double * 3)(), (C.c_double * 3)()
+    st = load_library().swz_srs_transform_box(_as_srs(srs)._ref(), int(target), _vec3(box_min), _vec3(box_max), lo, hi)
+    if st != 0:
+        raise SwzError(st, "swz_srs_transform_box failed")
+    return np.array(list(lo)), np.array(list(hi))
+
+
+def srs_tile():
+    """The rows one workgroup of srs_transform_device takes at a time."""
+    return int(load_library().swz_srs_tile())
+
+
+def las_scan_files(paths, skip_unreadable=False, ctx=None, srs=None):
     """swz_las_scan_files: the headers of a data set of uncompressed LAS files (host only).  Returns (files, dataset):
     files is a list of dicts (count, offset_to_point_data, point_format, record_bytes, scale, offset, min, max, attrs,
     status), dataset a dict (total_points, readable_files, tight / cubic / origin boxes as (min, max) of float64 arrays,
-    center, attrs: the names common to all readable files, attribute_mask)."""
+    center, attrs: the names common to all readable files, attribute_mask).  srs (a string or an Srs): the boxes of the data
+    set are those of the files' boxes in ECEF (swz_las_scan_files_srs); the files' entries keep their headers' values."""
     arr, n = _path_array(paths)
     infos = (_LasFileInfo * max(n, 1))()
     ds = _LasDataset()
     L = load_library()
-    st = L.swz_las_scan_files(ctx, arr, n, LAS_SCAN_SKIP_UNREADABLE if skip_unreadable else 0, infos, C.byref(ds))
+    flags = LAS_SCAN_SKIP_UNREADABLE if skip_unreadable else 0
+    srs = _as_srs(srs)
+    if srs is None:
+        st = L.swz_las_scan_files(ctx, arr, n, flags, infos, C.byref(ds))
+    else:
+        st = L.swz_las_scan_files_srs(ctx, arr, n, flags, srs._ref(), infos, C.byref(ds))
     if st != 0:
         raise SwzError(st, L.swz_last_error(ctx).decode() if ctx else "swz_las_scan_files failed")
     files = []
@@ -853,6 +928,20 @@ def load_library():
     L.swz_las_input_tile.restype = C.c_uint32
     L.swz_las_decode_segments_device.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(_LasSegment), _dp, vp, cols]
     L.swz_tiler_add_las_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(_InputParams), C.POINTER(_InputStats)]
+    srsp = C.POINTER(_Srs)
+    L.swz_srs_parse.argtypes = [vp, C.c_char_p, srsp]
+    L.swz_srs_parse_why.argtypes = [C.c_char_p, srsp, C.c_char_p, C.c_uint64]
+    L.swz_srs_transform.argtypes = [srsp, C.c_int, _dp, C.c_uint64]
+    L.swz_srs_transform_device.argtypes = [vp, srsp, C.c_int, vp, C.c_uint64]
+    L.swz_srs_transform_box.argtypes = [srsp, C.c_int, _dp, _dp, _dp, _dp]
+    L.swz_srs_tile.argtypes = []
+    L.swz_srs_tile.restype = C.c_uint32
+    L.swz_las_scan_files_srs.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.c_uint32, srsp, C.POINTER(_LasFileInfo), C.POINTER(_LasDataset)]
+    L.swz_las_decode_segments_srs_device.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(_LasSegment), _dp, vp, cols, srsp]
+    L.swz_tiler_set_source_srs.argtypes = [vp, srsp]
+    for name in ("swz_srs_parse", "swz_srs_parse_why", "swz_srs_transform", "swz_srs_transform_device", "swz_srs_transform_box",
+                 "swz_las_scan_files_srs", "swz_las_decode_segments_srs_device", "swz_tiler_set_source_srs"):
+        getattr(L, name).restype = C.c_int
     for name in ("swz_las_scan_files", "swz_input_batches", "swz_las_decode_segments_device", "swz_tiler_add_las_files"):
         getattr(L, name).restype = C.c_int
     L.swz_las_scale_from_bounds.argtypes = [_dp, _dp]
@@ -1171,10 +1260,22 @@ class Context:
         self._check(self._lib.swz_las_decode_device(self._ctx, C.c_void_p(d_records), int(n), C.byref(lay),
                                                     C.c_void_p(d_xyz), C.byref(cols)))
 
-    def las_decode_segments_device(self, d_raw, raw_bytes, segments, d_xyz, d_attrs=None, shift_center=None):
+    def srs_transform_device(self, srs, d_xyz, n=None, target=SRS_ECEF):
+        """swz_srs_transform_device: n rows of 24 bytes at d_xyz (a device pointer, or a contiguous float64 torch tensor of
+        shape (n, 3)) from the source projection to ECEF or WGS84, in place."""
+        _check_target(target)
+        if hasattr(d_xyz, "data_ptr"):
+            if not d_xyz.is_contiguous() or d_xyz.element_size() != 8 or d_xyz.numel() % 3:
+                raise ValueError("srs_transform_device: a contiguous float64 tensor of rows of three")
+            n = d_xyz.numel() // 3 if n is None else n
+            d_xyz = d_xyz.data_ptr()
+        self._check(self._lib.swz_srs_transform_device(self._ctx, _as_srs(srs)._ref(), int(target), C.c_void_p(d_xyz), int(n)))
+
+    def las_decode_segments_device(self, d_raw, raw_bytes, segments, d_xyz, d_attrs=None, shift_center=None, srs=None):
         """swz_las_decode_segments_device: raw point records of several files (device memory, any alignment) -> positions and
         attribute columns in one launch.  segments: dicts of first_row, count, byte_offset, scale, offset, min, max,
-        point_format, record_bytes (the keys of a las_scan_files entry)."""
+        point_format, record_bytes (the keys of a las_scan_files entry).  srs (a string or an Srs): positions go through the
+        source projection to ECEF after the clamp and before the shift (swz_las_decode_segments_srs_device)."""
         segs = (_LasSegment * max(len(segments), 1))()
         for i, g in enumerate(segments):
             segs[i] = _LasSegment(int(g["first_row"]), int(g["count"]), int(g["byte_offset"]),
@@ -1182,6 +1283,11 @@ class Context:
                                              int(g["point_format"]), int(g["record_bytes"])))
         cols = device_columns(d_attrs)
         center = None if shift_center is None else _vec3(shift_center)
+        srs = _as_srs(srs)
+        if srs is not None:
+            self._check(self._lib.swz_las_decode_segments_srs_device(self._ctx, C.c_void_p(d_raw), int(raw_bytes), len(segments), segs,
+                                                                     center, C.c_void_p(d_xyz), C.byref(cols), srs._ref()))
+            return
         self._check(self._lib.swz_las_decode_segments_device(self._ctx, C.c_void_p(d_raw), int(raw_bytes), len(segments), segs, center,
                                                              C.c_void_p(d_xyz), C.byref(cols)))
 
@@ -1548,16 +1654,34 @@ class Tiler:
         self._ctx._check(self._lib.swz_tiler_write_output(self._t, os.fsencode(directory), C.byref(p), C.byref(stats)))
         return {k: getattr(stats, k) for k, _ in _OutputStats._fields_}
 
-    def add_las_files(self, paths, batch_points=0, attrs=None, shift_to_center=False, skip_unreadable=False):
+    def set_source_srs(self, srs):
+        """swz_tiler_set_source_srs: add_las_files projects its input to ECEF (a string or an Srs; None clears).  Refused once
+        the tiler holds points."""
+        srs = _as_srs(srs)
+        self._ctx._check(self._lib.swz_tiler_set_source_srs(self._t, None if srs is None else srs._ref()))
+
+    def add_las_files(self, paths, batch_points=0, attrs=None, shift_to_center=False, skip_unreadable=False, source_projection=None):
         """swz_tiler_add_las_files: a data set of uncompressed LAS files read, decoded on the device straight into the pools
         and tiled, batch after batch.  attrs: the attribute columns to carry (names or a mask; None = all the files have in
         common); batch_points 0 = 10 M.  Does not finalize.  Returns the stats as a dict (files, points, batches, bytes_read,
-        read_ms, copy_ms, decode_ms, tile_ms, wait_ms, wall_ms)."""
+        read_ms, copy_ms, decode_ms, tile_ms, wait_ms, wall_ms).  source_projection (a string or an Srs): set_source_srs before
+        the call -- the root box and the shift are then ECEF's (las_scan_files(srs=...)) --, so it can only be given to the
+        call that brings the first points.  If the call is refused before a point is read the projection is cleared again and
+        the tiler is as it was; once the call has brought points THE TILER KEEPS THE PROJECTION for its life (the library
+        allows neither set nor clear on a tiler that holds points): a later add_las_files without source_projection projects
+        too, which is what one data set in one CRS needs."""
         arr, n = _path_array(paths)
         mask = 0xFFFFFFFF if attrs is None else _las_mask(attrs)
         p = _InputParams(int(batch_points), mask, 1 if shift_to_center else 0, LAS_SCAN_SKIP_UNREADABLE if skip_unreadable else 0, 0)
         stats = _InputStats()
-        self._ctx._check(self._lib.swz_tiler_add_las_files(self._t, arr, n, C.byref(p), C.byref(stats)))
+        if source_projection is not None:
+            self.set_source_srs(source_projection)
+        try:
+            self._ctx._check(self._lib.swz_tiler_add_las_files(self._t, arr, n, C.byref(p), C.byref(stats)))
+        except SwzError:
+            if source_projection is not None and stats.points == 0 and self.info()["num_points"] == 0:
+                self._lib.swz_tiler_set_source_srs(self._t, None)   # refused before a point was read: as it was
+            raise
         return {k: getattr(stats, k) for k, _ in _InputStats._fields_}
 
     def pools_device(self):

@@ -35,6 +35,7 @@
 
 #include "swz_internal.h"
 #include "swz_md.h"
+#include "swz_srs.h"
 #include "swz_tinput.h"
 #include "swz_toutput.h"
 
@@ -124,6 +125,8 @@ struct swz_group {
   std::vector<uint64_t> root_stored;  // points in the root's file on every shard (before / after the batch's root step)
   double tbmin[3] = {0, 0, 0}, tbmax[3] = {0, 0, 0};
   swz_tile_params tparams{};
+  bool has_srs = false;  // swz_group_set_source_srs: swz_group_add_las_files projects its input to ECEF
+  swz_srs srs{};
   std::vector<std::array<double, 4>> timing;  // per shard, ms since the call began: exchange done, root begun, root done, levels done
   std::chrono::steady_clock::time_point t_call;
   std::vector<swz::MdPeerView> views;        // MIN_DISTANCE root swept by all shards at once: what every shard publishes
@@ -934,6 +937,7 @@ int swz_group_tiler_open(swz_group* g, const double bmin[3], const double bmax[3
     return SWZ_ERR_BAD_ARG;
   }
   g->fast_start = -1;
+  g->has_srs = false;
   g->hist.assign(g->n, std::vector<uint32_t>());
   for (int a = 0; a < 3; ++a) {
     g->tbmin[a] = bmin[a];
@@ -964,6 +968,25 @@ int swz_group_tiler_open(swz_group* g, const double bmin[3], const double bmax[3
 int swz_group_tiler_close(swz_group* g) {
   if (!g) return SWZ_ERR_BAD_ARG;
   group_free_tilers(g);
+  g->has_srs = false;
+  return SWZ_OK;
+}
+
+int swz_group_set_source_srs(swz_group* g, const swz_srs* srs) {
+  if (!g) return SWZ_ERR_BAD_ARG;
+  auto refuse = [&](const std::string& why) {
+    g->err = why;
+    return (int)SWZ_ERR_BAD_ARG;
+  };
+  if (g->tiler.empty()) return refuse("swz_group_set_source_srs: no data set is open (swz_group_tiler_open)");
+  if (!g->staged.empty()) return refuse("swz_group_set_source_srs: a batch is staged or open");
+  for (const swz_tiler* t : g->tiler)
+    if (t->failed || t->finalized || t->total || t->staged_total || t->batches || !t->staged_sizes.empty() || t->batch_open)
+      return refuse("swz_group_set_source_srs: the data set holds points, or a batch is staged or open");
+  if (srs && !swz::srs_valid(srs))
+    return refuse("swz_group_set_source_srs: not a definition swz_srs_parse made");
+  g->has_srs = srs != nullptr;
+  if (srs) g->srs = *srs;
   return SWZ_OK;
 }
 
@@ -1134,7 +1157,8 @@ int swz_group_add_las_files(swz_group* g, const char* const* paths, uint64_t num
   swz_ctx* c0 = g->ctx[0];
   (void)hipSetDevice(g->devices[0]);
   swz::LasInputPlan plan;
-  int st = swz::las_input_plan(c0, who, paths, num_files, params, g->tbmin, g->tbmax, g->tparams, mask_fixed, mask_now, points_now, &plan);
+  int st = swz::las_input_plan(c0, who, paths, num_files, params, g->tbmin, g->tbmax, g->tparams, mask_fixed, mask_now, points_now,
+                               g->has_srs ? &g->srs : nullptr, &plan);
   if (st != SWZ_OK) return refuse(st, swz_last_error(c0));
   const uint64_t num_batches = plan.num_batches();
   const uint32_t mask = plan.mask;
@@ -1217,7 +1241,7 @@ int swz_group_add_las_files(swz_group* g, const char* const* paths, uint64_t num
       if (b.image_bytes && !hip(hipMemcpyAsync(ib[r].device[s], ib[r].host[s], b.image_bytes, hipMemcpyHostToDevice, cs), "hipMemcpyAsync(image)")) return SWZ_ERR_HIP;
       if (!hip(hipEventRecord(ib[r].copied[s], cs), "hipEventRecord")) return SWZ_ERR_HIP;
       const int rc = swz::las_launch_image(g->ctx[r], cs, ib[r].device[s], b, plan.shift ? plan.ds.center : nullptr, g->stage_xyz[slot][r],
-                                           &g->stage_attr[slot][r], mask);
+                                           &g->stage_attr[slot][r], mask, g->has_srs ? &g->srs : nullptr);
       if (rc != SWZ_OK) {
         g->err = "shard " + std::to_string(r) + ": " + swz_last_error(g->ctx[r]);
         return rc;

@@ -3,6 +3,7 @@
 // swz_las_decode_segments_device (swz_tinput.hip: a batch that spans files, any alignment).
 #pragma once
 #include "swz_internal.h"
+#include "swz_srs.h"
 
 namespace swz {
 
@@ -28,10 +29,31 @@ __device__ __forceinline__ int32_t las_i32(const uint8_t* p) {
   return (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
 }
 
-// r: the record, read byte by byte (any alignment, global memory or LDS); i: the output row
-__device__ __forceinline__ void las_unpack(const LasArgs& a, const uint8_t* r, uint32_t i) {
+// r: the record, read byte by byte (any alignment, global memory or LDS); i: the output row.  SRS: the position goes through
+// the source projection `srs` to ECEF after the clamp and before the shift (make_tiler, TilerProcess.cpp:539-561); the
+// instantiation without it does not know of one.
+template <bool SRS = false>
+__device__ __forceinline__ void las_unpack(const LasArgs& a, const uint8_t* r, uint32_t i, const swz_srs* srs = nullptr) {
   // position_from_las_point (LASFile.cpp:79-94): offset + X * scale, then min(max, max(min, p)) per axis
-  if (a.xyz) {
+  if constexpr (SRS) {
+    if (a.xyz) {
+      double p[3];
+#pragma unroll
+      for (int ax = 0; ax < 3; ++ax) {
+        p[ax] = a.offset[ax] + (double)las_i32(r + 4 * ax) * a.scale[ax];
+        p[ax] = fmin(a.mx[ax], fmax(a.mn[ax], p[ax]));
+      }
+      srs_to_target(*srs, SWZ_SRS_ECEF, p[0], p[1], p[2]);
+#pragma unroll
+      for (int ax = 0; ax < 3; ++ax) {
+        if (a.shift) {
+          const double moved = p[ax] - a.center[ax];
+          p[ax] = (double)(float)moved;
+        }
+        a.xyz[(size_t)i * 3 + ax] = p[ax];
+      }
+    }
+  } else if (a.xyz) {
 #pragma unroll
     for (int ax = 0; ax < 3; ++ax) {
       double p = a.offset[ax] + (double)las_i32(r + 4 * ax) * a.scale[ax];

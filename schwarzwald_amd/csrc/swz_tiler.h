@@ -95,6 +95,8 @@ struct swz_tiler {
   double* pool_xyz = nullptr;
   void* pool_attr[SWZ_ATTR_COUNT] = {nullptr};
   uint32_t attr_mask = 0;   // attribute columns the pools hold (fixed by the first staged batch)
+  bool has_srs = false;     // swz_tiler_set_source_srs: swz_tiler_add_las_files projects its input to ECEF
+  swz_srs srs{};
   size_t pool_cap = 0;      // points
   uint32_t total = 0;       // points tiled so far
   uint32_t staged_total = 0;  // points copied (or being copied) into the pools

@@ -48,17 +48,19 @@ struct LasInputPlan {
 
 // Scans the headers and refuses what is refused before a point is read: the mask rules (mask_fixed: a batch has fixed the
 // columns to mask_now), the 4-ulp box check against [bmin, bmax], more than 2^32 - 65536 points with the points_now a tiler
-// holds, FAST's fast_concurrency.  `who` starts the messages; a refusal is c's error.
+// holds, FAST's fast_concurrency.  `who` starts the messages; a refusal is c's error.  srs (may be NULL): the source projection;
+// the data set's boxes and the centre of the shift are then those of the files' boxes in ECEF (swz_las_scan_files_srs).
 int las_input_plan(swz_ctx* c, const char* who, const char* const* paths, uint64_t num_files, const swz_input_params* params,
                    const double bmin[3], const double bmax[3], const swz_tile_params& tp, bool mask_fixed, uint32_t mask_now,
-                   uint64_t points_now, LasInputPlan* plan);
+                   uint64_t points_now, const swz_srs* srs, LasInputPlan* plan);
 // the image of the points [p0, p1) of the data set: segments with rows from 0, and the pieces the readers take
 void las_input_image(const LasInputPlan& plan, uint64_t p0, uint64_t p1, InputBatch* b);
 // puts the segment table into the image and starts `threads` reader threads on its pieces (run.wait joins them)
 void las_start_read(TicketRun& run, swz_ctx* c, const char* who, const InputBatch* b, unsigned char* image, const char* const* paths,
                     long threads);
-// the segment kernel on `stream` for an image that lies on the device (c's device is current); no synchronisation
+// the segment kernel on `stream` for an image that lies on the device (c's device is current); no synchronisation.  srs (may
+// be NULL): the instantiation that projects every position to ECEF between clamp and shift
 int las_launch_image(swz_ctx* c, hipStream_t stream, const uint8_t* d_image, const InputBatch& b, const double* shift_center,
-                     double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t mask);
+                     double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t mask, const swz_srs* srs);
 
 }  // namespace swz

@@ -62,7 +62,17 @@ struct LasSegArgs {
   double center[3];
 };
 
-__global__ __launch_bounds__(LASIN_TILE) void las_segments_kernel(LasSegArgs a) {
+// the kernel's arguments without and with a source projection: the first is LasSegArgs and nothing else
+template <bool SRS>
+struct LasSegArgsOf : LasSegArgs {};
+template <>
+struct LasSegArgsOf<true> : LasSegArgs {
+  swz_srs srs;
+};
+
+// SRS: every position goes through the source projection to ECEF between clamp and shift (las_unpack<true>)
+template <bool SRS>
+__global__ __launch_bounds__(LASIN_TILE) void las_segments_kernel(LasSegArgsOf<SRS> a) {
   __shared__ uint32_t s_first[LASIN_TILE];  // first rows of the segments k0 .. k0 + LASIN_TILE - 1 (past the table: no row)
   __shared__ unsigned long long s_lo, s_hi;  // the byte range of the tile's records in raw
   __shared__ uint32_t s_stage[LASIN_STAGE / 4 + 2];
@@ -134,9 +144,14 @@ __global__ __launch_bounds__(LASIN_TILE) void las_segments_kernel(LasSegArgs a) 
       s_stage[w] = v;
     }
     __syncthreads();
-    if (live) las_unpack(la, reinterpret_cast<const uint8_t*>(s_stage) + (size_t)((raw_begin + start) - word0), r);
+    if (live) {
+      const uint8_t* rec = reinterpret_cast<const uint8_t*>(s_stage) + (size_t)((raw_begin + start) - word0);
+      if constexpr (SRS) las_unpack<true>(la, rec, r, &a.srs);
+      else las_unpack(la, rec, r);
+    }
   } else if (live) {
-    las_unpack(la, a.raw + start, r);
+    if constexpr (SRS) las_unpack<true>(la, a.raw + start, r, &a.srs);
+    else las_unpack(la, a.raw + start, r);
   }
 }
 
@@ -174,7 +189,7 @@ static uint64_t decode_bytes(const std::vector<swz_las_segment>& segs, const dou
 // launches the kernel on `stream`; d_table holds num_segs checked segments with points.  No synchronisation.
 static int launch_segments(swz_ctx* c, hipStream_t stream, const uint8_t* d_raw, uint64_t raw_bytes, const swz_las_segment* d_table,
                            uint32_t num_segs, uint32_t rows, const double* shift_center, double* d_xyz_out,
-                           const swz_attribute_columns* d_out, uint32_t mask) {
+                           const swz_attribute_columns* d_out, uint32_t mask, const swz_srs* srs) {
   LasSegArgs a{};
   a.raw = d_raw;
   a.raw_bytes = raw_bytes;
@@ -186,7 +201,16 @@ static int launch_segments(swz_ctx* c, hipStream_t stream, const uint8_t* d_raw,
     a.col[k] = (d_out && k != SWZ_ATTR_NORMAL && ((mask >> k) & 1u)) ? d_out->column[k] : nullptr;
   a.shift = shift_center != nullptr;
   for (int k = 0; k < 3; ++k) a.center[k] = shift_center ? shift_center[k] : 0.0;
-  hipLaunchKernelGGL(las_segments_kernel, dim3(div_up(rows, LASIN_TILE)), dim3(LASIN_TILE), 0, stream, a);
+  if (srs) {
+    LasSegArgsOf<true> as{};
+    static_cast<LasSegArgs&>(as) = a;
+    as.srs = *srs;
+    hipLaunchKernelGGL(las_segments_kernel<true>, dim3(div_up(rows, LASIN_TILE)), dim3(LASIN_TILE), 0, stream, as);
+  } else {
+    LasSegArgsOf<false> an{};
+    static_cast<LasSegArgs&>(an) = a;
+    hipLaunchKernelGGL(las_segments_kernel<false>, dim3(div_up(rows, LASIN_TILE)), dim3(LASIN_TILE), 0, stream, an);
+  }
   SWZ_LAUNCH_CHECK(c);
   return SWZ_OK;
 }
@@ -334,12 +358,12 @@ InputBuffers::~InputBuffers() {
 
 int las_input_plan(swz_ctx* c, const char* who_c, const char* const* paths, uint64_t num_files, const swz_input_params* params,
                    const double bmin[3], const double bmax[3], const swz_tile_params& tp, bool mask_fixed, uint32_t mask_now,
-                   uint64_t points_now, LasInputPlan* plan) {
+                   uint64_t points_now, const swz_srs* srs, LasInputPlan* plan) {
   const std::string who = std::string(who_c) + ": ";
   // ---- the headers, and everything that is refused before a point is read
   plan->files.assign(std::max<uint64_t>(num_files, 1), swz_las_file_info{});
   swz_las_dataset& ds = plan->ds;
-  SWZ_TRY(swz_las_scan_files(c, paths, num_files, params->flags, plan->files.data(), &ds));
+  SWZ_TRY(swz_las_scan_files_srs(c, paths, num_files, params->flags, srs, plan->files.data(), &ds));  // (ECEF boxes with srs)
   const uint32_t mask = params->attribute_mask == ~0u ? ds.attribute_mask : params->attribute_mask;
   if (mask & (1u << SWZ_ATTR_NORMAL)) return c->fail(SWZ_ERR_BAD_ARG, who + "LAS points carry no normals");
   if (mask & ~ds.attribute_mask) return c->fail(SWZ_ERR_BAD_ARG, who + "the mask names an attribute that not every file has");
@@ -421,10 +445,10 @@ void las_start_read(TicketRun& run, swz_ctx* c, const char* who, const InputBatc
 }
 
 int las_launch_image(swz_ctx* c, hipStream_t stream, const uint8_t* d_image, const InputBatch& b, const double* shift_center,
-                     double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t mask) {
+                     double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t mask, const swz_srs* srs) {
   if (!b.points) return SWZ_OK;
   return launch_segments(c, stream, d_image, b.raw_bytes, reinterpret_cast<const swz_las_segment*>(d_image + b.table_at),
-                         (uint32_t)b.segs.size(), (uint32_t)b.points, shift_center, d_xyz_out, d_out, mask);
+                         (uint32_t)b.segs.size(), (uint32_t)b.points, shift_center, d_xyz_out, d_out, mask, srs);
 }
 
 }  // namespace swz
@@ -437,7 +461,14 @@ uint32_t swz_las_input_tile(void) { return LASIN_TILE; }
 
 int swz_las_scan_files(swz_ctx* c, const char* const* paths, uint64_t num_files, uint32_t flags, swz_las_file_info* files_out,
                        swz_las_dataset* dataset_out) {
+  return swz_las_scan_files_srs(c, paths, num_files, flags, nullptr, files_out, dataset_out);
+}
+
+// (the messages name swz_las_scan_files with and without a projection: it is that call)
+int swz_las_scan_files_srs(swz_ctx* c, const char* const* paths, uint64_t num_files, uint32_t flags, const swz_srs* srs,
+                           swz_las_file_info* files_out, swz_las_dataset* dataset_out) {
   if (!dataset_out || (num_files && !paths)) return fail(c, SWZ_ERR_BAD_ARG, "swz_las_scan_files: NULL argument");
+  if (srs && !srs_valid(srs)) return fail(c, SWZ_ERR_BAD_ARG, "swz_las_scan_files_srs: not a definition swz_srs_parse made");
   if (flags & ~SWZ_LAS_SCAN_SKIP_UNREADABLE) return fail(c, SWZ_ERR_BAD_ARG, "swz_las_scan_files: unknown flag");
   swz_las_dataset ds{};
   ds.attribute_mask = LAS_MASK_ALWAYS | (1u << SWZ_ATTR_RGB) | (1u << SWZ_ATTR_GPS_TIME);
@@ -462,8 +493,17 @@ int swz_las_scan_files(swz_ctx* c, const char* const* paths, uint64_t num_files,
     ds.total_points += info.point_count;
     ++ds.readable_files;
     ds.attribute_mask &= info.attribute_mask;
+    // with a projection the file's box joins the union as the box of its eight corners in ECEF (calculate_dataset_metadata,
+    // TilerProcess.cpp:352-387); files_out keeps the header's own values
+    double box_min[3], box_max[3];
+    for (int k = 0; k < 3; ++k) {
+      box_min[k] = info.layout.min[k];
+      box_max[k] = info.layout.max[k];
+    }
+    if (srs && swz_srs_transform_box(srs, SWZ_SRS_ECEF, info.layout.min, info.layout.max, box_min, box_max) != SWZ_OK)
+      return fail(c, SWZ_ERR_BAD_ARG, "swz_las_scan_files: the source projection could not map a header box");
     for (int k = 0; k < 3; ++k) {  // update(bounds.min), then update(bounds.max)
-      for (const double v : {info.layout.min[k], info.layout.max[k]}) {
+      for (const double v : {box_min[k], box_max[k]}) {
         ds.tight_min[k] = std::min(ds.tight_min[k], v);
         ds.tight_max[k] = std::max(ds.tight_max[k], v);
       }
@@ -514,7 +554,14 @@ int swz_input_batches(uint64_t num_files, const uint64_t* file_count, uint64_t b
 int swz_las_decode_segments_device(swz_ctx* c, const uint8_t* d_raw, uint64_t raw_bytes, uint64_t num_segments,
                                    const swz_las_segment* segments, const double shift_center[3], double* d_xyz_out,
                                    const swz_attribute_columns* d_out) {
+  return swz_las_decode_segments_srs_device(c, d_raw, raw_bytes, num_segments, segments, shift_center, d_xyz_out, d_out, nullptr);
+}
+
+int swz_las_decode_segments_srs_device(swz_ctx* c, const uint8_t* d_raw, uint64_t raw_bytes, uint64_t num_segments,
+                                       const swz_las_segment* segments, const double shift_center[3], double* d_xyz_out,
+                                       const swz_attribute_columns* d_out, const swz_srs* srs) {
   if (!c) return SWZ_ERR_BAD_ARG;
+  if (srs && !srs_valid(srs)) return c->fail(SWZ_ERR_BAD_ARG, "swz_las_decode_segments_srs_device: not a definition swz_srs_parse made");
   SWZ_HIP(c, hipSetDevice(c->device));
   // everything is checked on the host before anything is launched
   std::vector<swz_las_segment> segs;
@@ -527,9 +574,9 @@ int swz_las_decode_segments_device(swz_ctx* c, const uint8_t* d_raw, uint64_t ra
   SWZ_TRY(c->get("las_segments", segs.size(), &d_table));
   SWZ_HIP(c, hipMemcpyAsync(d_table, segs.data(), segs.size() * sizeof(swz_las_segment), hipMemcpyHostToDevice, c->stream));
   {
-    ProfScope ps(c, "las_decode_segments", decode_bytes(segs, d_xyz_out, d_out, ~0u), 1);
+    ProfScope ps(c, srs ? "las_decode_segments_srs" : "las_decode_segments", decode_bytes(segs, d_xyz_out, d_out, ~0u), 1);
     SWZ_TRY(launch_segments(c, c->stream, d_raw, raw_bytes, d_table, (uint32_t)segs.size(), (uint32_t)rows, shift_center, d_xyz_out, d_out,
-                            ~0u));
+                            ~0u, srs));
   }
   SWZ_HIP(c, hipStreamSynchronize(c->stream));  // (the table's host copy lives until here)
   return SWZ_OK;
@@ -551,7 +598,8 @@ int swz_tiler_add_las_files(swz_tiler* t, const char* const* paths, uint64_t num
   const char* who = "swz_tiler_add_las_files";
   const bool first = t->staged_total == 0 && t->batches == 0;
   LasInputPlan plan;
-  SWZ_TRY(las_input_plan(c, who, paths, num_files, params, t->bmin, t->bmax, t->p, !first, t->attr_mask, t->staged_total, &plan));
+  const swz_srs* const srs = t->has_srs ? &t->srs : nullptr;
+  SWZ_TRY(las_input_plan(c, who, paths, num_files, params, t->bmin, t->bmax, t->p, !first, t->attr_mask, t->staged_total, srs, &plan));
   const swz_las_dataset& ds = plan.ds;
   const uint32_t mask = plan.mask;
   const bool shift = plan.shift;
@@ -629,7 +677,8 @@ int swz_tiler_add_las_files(swz_tiler* t, const char* const* paths, uint64_t num
     swz_attribute_columns rows{};
     for (int a = 0; a < SWZ_ATTR_COUNT; ++a)
       rows.column[a] = (t->attr_mask & (1u << a)) ? (void*)((char*)t->pool_attr[a] + at * TILER_ATTR_BYTES[a]) : nullptr;
-    SWZ_TRY(las_launch_image(c, t->copy_stream, ib.device[s], b, shift ? ds.center : nullptr, t->pool_xyz + at * 3, &rows, t->attr_mask));
+    SWZ_TRY(las_launch_image(c, t->copy_stream, ib.device[s], b, shift ? ds.center : nullptr, t->pool_xyz + at * 3, &rows, t->attr_mask,
+                             srs));
     SWZ_HIP(c, hipEventRecord(ib.decoded[s], t->copy_stream));
     hipEvent_t ev = nullptr;
     SWZ_HIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -715,6 +764,18 @@ int swz_tiler_add_las_files(swz_tiler* t, const char* const* paths, uint64_t num
     stats->wall_ms = ms_since(t_wall);
   }
   return status == SWZ_OK ? SWZ_OK : c->fail(status, why);
+}
+
+int swz_tiler_set_source_srs(swz_tiler* t, const swz_srs* srs) {
+  if (!t) return SWZ_ERR_BAD_ARG;
+  swz_ctx* c = t->c;
+  SWZ_TRY(tiler_guard(t));
+  if (t->finalized || t->total || t->staged_total || t->batches || !t->staged_sizes.empty() || t->batch_open)
+    return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_set_source_srs: the tiler holds points, or a batch is staged or open");
+  if (srs && !srs_valid(srs)) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_set_source_srs: not a definition swz_srs_parse made");
+  t->has_srs = srs != nullptr;
+  if (srs) t->srs = *srs;
+  return SWZ_OK;
 }
 
 }  // extern "C"

@@ -103,6 +103,37 @@ inline uint8_t get_octant_at_level(MortonIndex64 key, uint32_t level) {
 }
 
 // One swz_ctx, owned.  Not thread-safe (one call in flight per context).
+// SRSTransformHelper's two calls (core/util/Transformation.h) over the library's own map of a source projection
+// (swz_srs_parse: UTM zones, +proj=tmerc, longlat; no PROJ).  The constructor throws the reference's "Source projection ...
+// not recognized!" (Proj4Transform, Transformation.cpp:74-85) for a definition the library refuses; why() says which token.
+class SourceProjection {
+public:
+  explicit SourceProjection(const std::string& definition) {
+    char why[512] = {0};
+    if (swz_srs_parse_why(definition.c_str(), &_srs, why, sizeof(why)) != SWZ_OK)
+      throw std::runtime_error{"Source projection " + definition + " not recognized! (" + why + ")"};
+  }
+  const swz_srs* srs() const { return &_srs; }
+  // target: SWZ_SRS_ECEF (the reference's TargetSRS::CesiumWorld) or SWZ_SRS_WGS84; in place
+  void transformPositionsTo(int target, Vector3d* positions, size_t count) const {
+    static_assert(sizeof(Vector3d) == 24, "positions are rows of three doubles");
+    if (swz_srs_transform(&_srs, target, reinterpret_cast<double*>(positions), count) != SWZ_OK)
+      throw std::runtime_error{"SourceProjection: unknown target"};
+  }
+  void transformAABBsTo(int target, AABB* boxes, size_t count) const {
+    for (size_t i = 0; i < count; ++i) {
+      const double mn[3] = {boxes[i].min.x, boxes[i].min.y, boxes[i].min.z}, mx[3] = {boxes[i].max.x, boxes[i].max.y, boxes[i].max.z};
+      double lo[3], hi[3];
+      if (swz_srs_transform_box(&_srs, target, mn, mx, lo, hi) != SWZ_OK) throw std::runtime_error{"SourceProjection: unknown target"};
+      boxes[i].min = {lo[0], lo[1], lo[2]};
+      boxes[i].max = {hi[0], hi[1], hi[2]};
+    }
+  }
+
+private:
+  swz_srs _srs{};
+};
+
 class Context {
 public:
   explicit Context(int device = 0) {
@@ -413,9 +444,13 @@ public:
   // straight into the tiler's pools, every batch tiled while the next is read -- what replaces MultiReaderPointSource and
   // the tile_batch loop for files that need neither a PROJ transformation nor LASzip.  bounds: the octree's root bounds,
   // the data set's cubic box (swz_las_scan_files), or that box at the origin with params.shift_to_center.
-  swz_input_stats add_las_files(const std::vector<std::string>& paths, const AABB& bounds, const swz_input_params& params) {
+  // projection (may be null): the files are in that source projection and are tiled in ECEF; bounds is then a box of
+  // swz_las_scan_files_srs.  It can only come with the call that brings the first points.
+  swz_input_stats add_las_files(const std::vector<std::string>& paths, const AABB& bounds, const swz_input_params& params,
+                                const SourceProjection* projection = nullptr) {
     if (_finalized || _tiler_finalized) throw std::runtime_error{"TilingAlgorithmGPU: add_las_files after finalize"};
     open_tiler(bounds);
+    if (projection) _ctx.check(swz_tiler_set_source_srs(_tiler, projection->srs()));
     std::vector<const char*> names;
     for (const std::string& p : paths) names.push_back(p.c_str());
     swz_input_stats stats{};
@@ -678,8 +713,10 @@ public:
   }
   // A data set of uncompressed LAS files, read by the library in one call (swz_group_add_las_files) into the tilers that
   // open_tiler() opened; as TilingAlgorithmGPU::add_las_files it does not finalize
-  swz_input_stats add_las_files(const std::vector<std::string>& paths, const swz_input_params& params) {
+  swz_input_stats add_las_files(const std::vector<std::string>& paths, const swz_input_params& params,
+                                const SourceProjection* projection = nullptr) {
     if (_tiler_finalized) throw std::runtime_error{"ShardedTilingAlgorithmGPU: add_las_files after finalize_tiler"};
+    if (projection) group_check(swz_group_set_source_srs(_group, projection->srs()), "swz_group_set_source_srs");
     std::vector<const char*> names;
     for (const std::string& p : paths) names.push_back(p.c_str());
     swz_input_stats stats{};
