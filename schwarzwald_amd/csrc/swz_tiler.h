@@ -7,6 +7,8 @@
 //   swz_tiler.hip    the batch life cycle, FAST finalize, the node table and the C ABI
 //   swz_toutput.hip  the node files written in one call
 //   swz_tinput.hip   a data set of LAS files read in one call
+// and, for several GPUs in one process, over swz_group.h:
+//   swz_group.hip    the steps of a sharded call   swz_gtiler.hip  the group's tilers   swz_goutput.hip  their output
 #pragma once
 #include <string>
 #include <vector>
@@ -129,6 +131,19 @@ struct swz_tiler {
 // swz_tiler.hip: what every call of the tiler's API starts with -- SWZ_ERR_TILER_FAILED for a poisoned tiler, else a new
 // scratch epoch (swz_tinput.hip's call is one of them)
 int tiler_guard(swz_tiler* t);
+// the tiler holds no point, has counted no batch, and nothing is staged or open
+inline bool tiler_empty(const swz_tiler* t) {
+  return !t->total && !t->staged_total && !t->batches && t->staged_sizes.empty() && !t->batch_open;
+}
+// Why the call `who`, which adds batches, must refuse this tiler: failed (*why = failed_why alone: a tiler and a group word
+// that case differently), finalized, or a batch is staged or open.  SWZ_OK: none of them.
+inline int tiler_refuses_input(const swz_tiler* t, const char* who, std::string* why) {
+  if (t->failed) *why = t->failed_why;
+  else if (t->finalized) *why = "swz_tiler: batches cannot be added after finalize";
+  else if (!t->staged_sizes.empty() || t->batch_open) *why = std::string(who) + ": a batch is staged or open";
+  else return SWZ_OK;
+  return t->failed ? SWZ_ERR_TILER_FAILED : SWZ_ERR_BAD_ARG;
+}
 
 namespace swz {
 

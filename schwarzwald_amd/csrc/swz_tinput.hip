@@ -3,7 +3,7 @@
 // calculate_dataset_metadata do, core/process/TilerProcess.cpp:250-390), the concatenated files are cut into batches
 // (swz_input_batches), and while batch k is tiled the reader threads pread the raw records of batch k + 1 into a page-locked
 // buffer, the tiler's copy stream moves them to the device and ONE kernel decodes them straight into the pool rows of the
-// batch (swz_las_decode_segments_device's kernel).
+// batch (swz_las_decode_segments_device's kernel).  The loop is las_input_stream, which swz_group_add_las_files runs too.
 //
 // The kernel.  A batch is a run of points of the concatenated files, so its raw image holds SEGMENTS: records of several
 // files, each with its own scale, offset, box, point format and record length, one behind the other.  The point data of a
@@ -451,6 +451,126 @@ int las_launch_image(swz_ctx* c, hipStream_t stream, const uint8_t* d_image, con
                          (uint32_t)b.segs.size(), (uint32_t)b.points, shift_center, d_xyz_out, d_out, mask, srs);
 }
 
+void InputLane::cut(const LasInputPlan& plan, int r, int of) {
+  batches.assign(plan.num_batches(), InputBatch{});
+  for (uint64_t j = 0; j < plan.num_batches(); ++j) {
+    const uint64_t b0 = plan.cuts[j], pts = plan.cuts[j + 1] - b0;
+    las_input_image(plan, b0 + pts * (uint64_t)r / of, b0 + pts * (uint64_t)(r + 1) / of, &batches[j]);
+    image_max = std::max(image_max, batches[j].image_bytes);
+    rows_max = std::max(rows_max, batches[j].points);
+  }
+}
+
+void las_input_stream(const LasInputPlan& plan, const swz_srs* srs, const char* who, const char* const* paths, std::vector<InputLane>& lanes,
+                      const InputStreamOps& ops, InputStreamResult* result) {
+  InputStreamResult& o = *result;
+  const int N = (int)lanes.size();
+  const uint64_t num_batches = plan.num_batches();
+  const long budget =
+    std::max(1L, lanes[0].c->opt_int("SWZ_INPUT_READER_THREADS", (long)std::min(32u, std::max(1u, std::thread::hardware_concurrency()))));
+  auto label = [&](int r) { return ops.lane_name ? std::string(ops.lane_name) + " " + std::to_string(r) + ": " : std::string(); };
+  auto fail_stream = [&](int st, const std::string& text) {
+    if (o.status == SWZ_OK) {
+      o.status = st;
+      o.why = text;
+    }
+  };
+  auto start_read = [&](uint64_t j) {
+    for (int r = 0; r < N; ++r)
+      las_start_read(lanes[r].readers, lanes[r].c, who, &lanes[r].batches[j], static_cast<unsigned char*>(lanes[r].ib.host[j & 1]), paths,
+                     std::max(1L, budget / N + (r < budget % N ? 1 : 0)));
+  };
+  // joins the readers of batch j; the time the call stood waiting for them counts as waiting for input
+  auto wait_read = [&](uint64_t j) -> bool {
+    const auto t0 = std::chrono::steady_clock::now();
+    bool ok = true;
+    for (InputLane& L : lanes) {
+      double ms = 0;
+      std::string err;
+      const int st = L.readers.wait(&err, &ms);
+      L.read_ms += ms;
+      if (st != SWZ_OK) {
+        fail_stream(st, err);
+        ok = false;
+      } else {
+        o.bytes_read += L.batches[j].raw_bytes;
+      }
+    }
+    o.wait_ms += ms_since(t0);
+    return ok;
+  };
+  // batch j: every lane's image to its device and decoded to where the caller wants it (a lane with no point of the batch
+  // copies and launches nothing, and records its events all the same), then the caller's commit
+  auto enqueue = [&](uint64_t j) -> int {
+    const int s = (int)(j & 1);
+    std::string why;
+    for (int r = 0; r < N && o.status == SWZ_OK; ++r) {
+      InputLane& L = lanes[r];
+      const InputBatch& b = L.batches[j];
+      (void)hipSetDevice(L.c->device);
+      const InputTarget to = ops.target(r);
+      hipError_t e = hipEventRecord(L.ib.begin[s], L.copy);
+      if (e == hipSuccess && b.image_bytes) e = hipMemcpyAsync(L.ib.device[s], L.ib.host[s], b.image_bytes, hipMemcpyHostToDevice, L.copy);
+      if (e == hipSuccess) e = hipEventRecord(L.ib.copied[s], L.copy);
+      if (e == hipSuccess) {
+        const int st = las_launch_image(L.c, L.copy, L.ib.device[s], b, plan.shift ? plan.ds.center : nullptr, to.xyz, &to.cols, to.mask, srs);
+        if (st != SWZ_OK) fail_stream(st, label(r) + L.c->err);
+        else e = hipEventRecord(L.ib.decoded[s], L.copy);
+      }
+      if (e != hipSuccess) fail_stream(SWZ_ERR_HIP, label(r) + "the copy and decode of a batch image: " + hipGetErrorString(e));
+    }
+    if (o.status != SWZ_OK) return o.status;
+    const int st = ops.commit(j, &why);
+    if (st != SWZ_OK) fail_stream(st, why);
+    return st;
+  };
+
+  start_read(0);
+  if (wait_read(0)) {
+    o.enqueued = true;
+    if (enqueue(0) == SWZ_OK && num_batches > 1) start_read(1);
+  }
+  for (uint64_t j = 0; j < num_batches && o.status == SWZ_OK; ++j) {
+    // (a read that failed: batch j, which is staged, is still tiled -- the stream stops after the running batch)
+    if (j + 1 < num_batches && wait_read(j + 1) && enqueue(j + 1) == SWZ_OK && j + 2 < num_batches) {
+      // the host images of batch j + 2 are batch j's: their copies have left them
+      for (int r = 0; r < N && o.status == SWZ_OK; ++r) {
+        (void)hipSetDevice(lanes[r].c->device);
+        const hipError_t e = hipEventSynchronize(lanes[r].ib.copied[j & 1]);
+        if (e != hipSuccess) fail_stream(SWZ_ERR_HIP, label(r) + "the copy of a batch image: " + hipGetErrorString(e));
+      }
+      if (o.status == SWZ_OK) start_read(j + 2);
+    }
+    const auto t_tile = std::chrono::steady_clock::now();
+    double waited = 0;
+    std::string why;
+    o.tiled = true;
+    const int st = ops.tile(&waited, &why);
+    o.tile_ms += ms_since(t_tile) - waited;
+    o.wait_ms += waited;
+    if (st != SWZ_OK) {
+      o.status = st;  // (the failure of the tiling comes first: its tiler is poisoned with that text)
+      o.why = why;
+      break;
+    }
+    for (InputLane& L : lanes) {  // batch j has been decoded: its tiling waited for the event behind it
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, L.ib.begin[j & 1], L.ib.copied[j & 1]) == hipSuccess) L.copy_ms += ms;
+      if (hipEventElapsedTime(&ms, L.ib.copied[j & 1], L.ib.decoded[j & 1]) == hipSuccess) L.decode_ms += ms;
+    }
+    ++o.batches;
+    o.points += plan.cuts[j + 1] - plan.cuts[j];
+  }
+  for (InputLane& L : lanes) {
+    if (L.readers.running()) (void)L.readers.wait(nullptr, nullptr);
+    (void)hipSetDevice(L.c->device);
+    if (L.copy) (void)hipStreamSynchronize(L.copy);
+    o.read_ms = std::max(o.read_ms, L.read_ms);
+    o.copy_ms = std::max(o.copy_ms, L.copy_ms);
+    o.decode_ms = std::max(o.decode_ms, L.decode_ms);
+  }
+}
+
 }  // namespace swz
 
 using namespace swz;
@@ -586,191 +706,92 @@ int swz_tiler_add_las_files(swz_tiler* t, const char* const* paths, uint64_t num
                             swz_input_stats* stats) {
   if (!t) return SWZ_ERR_BAD_ARG;
   swz_ctx* c = t->c;
+  const char* who = "swz_tiler_add_las_files";
   const auto t_wall = std::chrono::steady_clock::now();
   if (stats) *stats = swz_input_stats{};
   SWZ_HIP(c, hipSetDevice(c->device));
   SWZ_TRY(tiler_guard(t));
   if (!params || (num_files && !paths)) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_add_las_files: NULL argument");
-  if (t->finalized) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler: batches cannot be added after finalize");
-  if (!t->staged_sizes.empty() || t->batch_open) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_add_las_files: a batch is staged or open");
+  std::string refusal;
+  if (const int st = tiler_refuses_input(t, who, &refusal)) return c->fail(st, refusal);
 
-  // ---- the headers, everything that is refused before a point is read, and the cuts
-  const char* who = "swz_tiler_add_las_files";
-  const bool first = t->staged_total == 0 && t->batches == 0;
+  // ---- the headers, everything that is refused before a point is read, the cuts and the images
+  const bool first = tiler_empty(t);
   LasInputPlan plan;
   const swz_srs* const srs = t->has_srs ? &t->srs : nullptr;
   SWZ_TRY(las_input_plan(c, who, paths, num_files, params, t->bmin, t->bmax, t->p, !first, t->attr_mask, t->staged_total, srs, &plan));
-  const swz_las_dataset& ds = plan.ds;
-  const uint32_t mask = plan.mask;
-  const bool shift = plan.shift;
-  const uint64_t num_batches = plan.num_batches();
-  std::vector<InputBatch> batches(num_batches);
-  uint64_t image_max = 0;
-  for (uint64_t j = 0; j < num_batches; ++j) {
-    las_input_image(plan, plan.cuts[j], plan.cuts[j + 1], &batches[j]);
-    image_max = std::max(image_max, batches[j].image_bytes);
-  }
+  std::vector<InputLane> lanes(1);
+  InputLane& lane = lanes[0];
+  lane.c = c;
+  lane.copy = t->copy_stream;
+  lane.cut(plan, 0, 1);
 
   // ---- the pools, once for the total: nothing grows while a batch is in flight
   const uint32_t mask_before = t->attr_mask;
-  auto reserve = [&]() -> int {
+  auto prepare = [&]() -> int {
     if (first) {
-      t->attr_mask = mask;
-      if (mask && t->pool_cap) {  // the pools were presized before the columns were known
+      t->attr_mask = plan.mask;
+      if (plan.mask && t->pool_cap) {  // the pools were presized before the columns were known
         const size_t cap = t->pool_cap;
         t->pool_cap = 0;
         t->pool_xyz = nullptr;
         SWZ_TRY(pool_reserve(t, cap));
       }
     }
-    return pool_reserve(t, (size_t)t->staged_total + ds.total_points);
+    SWZ_TRY(pool_reserve(t, (size_t)t->staged_total + plan.ds.total_points));
+    return lane.ib.reserve(c, lane.image_max, plan.num_batches() > 1);
   };
-  InputBuffers ib;
-  auto prepare = [&]() -> int {
-    SWZ_TRY(reserve());
-    return ib.reserve(c, image_max, num_batches > 1);
-  };
-  {
-    const int st = prepare();
-    if (st != SWZ_OK) {
-      t->attr_mask = mask_before;
-      return st;
-    }
+  if (const int st = prepare()) {
+    t->attr_mask = mask_before;
+    return st;
   }
 
-  // ---- the stream.  Reads run two batches ahead of the tiling, copy + decode one: while batch k is tiled, batch k + 1 is
-  // copied and decoded on the copy stream and the readers fill the other host buffer with batch k + 2.
-  const long reader_threads =
-    std::max(1L, c->opt_int("SWZ_INPUT_READER_THREADS", (long)std::min(32u, std::max(1u, std::thread::hardware_concurrency()))));
-  double read_ms = 0, copy_ms = 0, decode_ms = 0, tile_ms = 0, wait_ms = 0;
-  uint64_t bytes_read = 0, batches_done = 0, points_done = 0;
-  int status = SWZ_OK;
-  std::string why;
-  TicketRun readers;
-  auto start_read = [&](uint64_t j) {
-    las_start_read(readers, c, who, &batches[j], static_cast<unsigned char*>(ib.host[j & 1]), paths, reader_threads);
-  };
-  // joins the readers of batch j; the time the call stood waiting for them counts as waiting for input
-  auto wait_read = [&](uint64_t j) -> bool {
-    const auto t0 = std::chrono::steady_clock::now();
-    double ms = 0;
-    std::string err;
-    const int st = readers.wait(&err, &ms);
-    wait_ms += ms_since(t0);
-    read_ms += ms;
-    if (st != SWZ_OK) {
-      status = st;
-      why = err;
-      return false;
-    }
-    bytes_read += batches[j].raw_bytes;
-    return true;
-  };
-  // batch j from its host buffer into the pool rows behind what is staged, on the copy stream; staged like a host batch
-  auto enqueue = [&](uint64_t j) -> int {
-    const InputBatch& b = batches[j];
-    const int s = (int)(j & 1);
+  // ---- the stream: every batch into the pool rows behind what is staged, staged like a host batch
+  InputStreamOps ops;
+  ops.target = [&](int) {
     const size_t at = t->staged_total;
-    SWZ_HIP(c, hipEventRecord(ib.begin[s], t->copy_stream));
-    SWZ_HIP(c, hipMemcpyAsync(ib.device[s], ib.host[s], b.image_bytes, hipMemcpyHostToDevice, t->copy_stream));
-    SWZ_HIP(c, hipEventRecord(ib.copied[s], t->copy_stream));
-    swz_attribute_columns rows{};
+    InputTarget to{t->pool_xyz + at * 3, {}, t->attr_mask};
     for (int a = 0; a < SWZ_ATTR_COUNT; ++a)
-      rows.column[a] = (t->attr_mask & (1u << a)) ? (void*)((char*)t->pool_attr[a] + at * TILER_ATTR_BYTES[a]) : nullptr;
-    SWZ_TRY(las_launch_image(c, t->copy_stream, ib.device[s], b, shift ? ds.center : nullptr, t->pool_xyz + at * 3, &rows, t->attr_mask,
-                             srs));
-    SWZ_HIP(c, hipEventRecord(ib.decoded[s], t->copy_stream));
+      to.cols.column[a] = (t->attr_mask & (1u << a)) ? (void*)((char*)t->pool_attr[a] + at * TILER_ATTR_BYTES[a]) : nullptr;
+    return to;
+  };
+  ops.commit = [&](uint64_t j, std::string* why) -> int {
     hipEvent_t ev = nullptr;
-    SWZ_HIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    const hipError_t e = hipEventRecord(ev, t->copy_stream);
+    hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(ev, t->copy_stream);
     if (e != hipSuccess) {
-      (void)hipEventDestroy(ev);
-      return c->hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
+      if (ev) (void)hipEventDestroy(ev);
+      *why = std::string("the event behind a staged batch: ") + hipGetErrorString(e);
+      return SWZ_ERR_HIP;
     }
+    const InputBatch& b = lane.batches[j];
     t->staged_events.push_back(ev);
     t->staged_sizes.push_back((uint32_t)b.points);
     t->staged_total += (uint32_t)b.points;
     t->staged_bytes += b.image_bytes;
     return SWZ_OK;
   };
-  // a failure once a batch has been staged: the pools are ahead of the ids, the store may be half merged
-  bool touched = false;
-  auto fail_stream = [&](int st, const std::string& text) {
-    if (status == SWZ_OK) {
-      status = st;
-      why = text;
-    }
-  };
-
-  start_read(0);
-  if (wait_read(0)) {
-    touched = true;
-    const int st = enqueue(0);
-    if (st != SWZ_OK) fail_stream(st, c->err);
-    if (status == SWZ_OK && num_batches > 1) start_read(1);
-  }
-  for (uint64_t j = 0; j < num_batches && status == SWZ_OK; ++j) {
-    bool next_staged = false;
-    if (j + 1 < num_batches) {
-      if (wait_read(j + 1)) {
-        const int st = enqueue(j + 1);
-        if (st != SWZ_OK) fail_stream(st, c->err);
-        next_staged = st == SWZ_OK;
-      }
-      // (a read that failed: batch j, which is staged, is still tiled -- the stream stops after the running batch)
-      if (next_staged && j + 2 < num_batches) {
-        // the host buffer of batch j + 2 is batch j's: its copy has left it
-        const hipError_t e = hipEventSynchronize(ib.copied[j & 1]);
-        if (e != hipSuccess) fail_stream(c->hip_fail(e, "the copy of a batch image", __FILE__, __LINE__), c->err);
-        else start_read(j + 2);
-      }
-    }
+  ops.tile = [&](double* waited_ms, std::string* why) -> int {
     const double waited_before = t->staged_wait_ms;
-    const auto t_tile = std::chrono::steady_clock::now();
     const int st = swz_tiler_tile_staged(t, nullptr);
-    const double waited = t->staged_wait_ms - waited_before;
-    tile_ms += ms_since(t_tile) - waited;
-    wait_ms += waited;
-    if (st != SWZ_OK) {
-      status = st;  // (the tiler's own failure comes first: it is poisoned with that text)
-      why = c->err;
-      break;
-    }
-    float ms = 0.f;  // batch j has been decoded: tile_staged waited for the event behind it
-    if (hipEventElapsedTime(&ms, ib.begin[j & 1], ib.copied[j & 1]) == hipSuccess) copy_ms += ms;
-    if (hipEventElapsedTime(&ms, ib.copied[j & 1], ib.decoded[j & 1]) == hipSuccess) decode_ms += ms;
-    ++batches_done;
-    points_done += batches[j].points;
-  }
-  if (readers.running()) (void)readers.wait(nullptr, nullptr);
-  (void)hipStreamSynchronize(t->copy_stream);
-  if (status != SWZ_OK) {
-    if (touched) {
-      (void)swz_tiler_poison(t, why.c_str());
-    } else {
-      t->attr_mask = mask_before;
-    }
-  }
-  if (stats) {
-    stats->files = ds.readable_files;
-    stats->points = points_done;
-    stats->batches = batches_done;
-    stats->bytes_read = bytes_read;
-    stats->read_ms = read_ms;
-    stats->copy_ms = copy_ms;
-    stats->decode_ms = decode_ms;
-    stats->tile_ms = tile_ms;
-    stats->wait_ms = wait_ms;
-    stats->wall_ms = ms_since(t_wall);
-  }
-  return status == SWZ_OK ? SWZ_OK : c->fail(status, why);
+    *waited_ms = t->staged_wait_ms - waited_before;
+    if (st != SWZ_OK) *why = c->err;
+    return st;
+  };
+  InputStreamResult res;
+  las_input_stream(plan, srs, who, paths, lanes, ops, &res);
+  // a failure once a batch has been enqueued: the pools are ahead of the ids, the store may be half merged
+  if (res.status != SWZ_OK && res.enqueued) (void)swz_tiler_poison(t, res.why.c_str());
+  else if (res.status != SWZ_OK) t->attr_mask = mask_before;
+  if (stats) res.fill(stats, plan.ds.readable_files, ms_since(t_wall));
+  return res.status == SWZ_OK ? SWZ_OK : c->fail(res.status, res.why);
 }
 
 int swz_tiler_set_source_srs(swz_tiler* t, const swz_srs* srs) {
   if (!t) return SWZ_ERR_BAD_ARG;
   swz_ctx* c = t->c;
   SWZ_TRY(tiler_guard(t));
-  if (t->finalized || t->total || t->staged_total || t->batches || !t->staged_sizes.empty() || t->batch_open)
+  if (t->finalized || !tiler_empty(t))
     return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_set_source_srs: the tiler holds points, or a batch is staged or open");
   if (srs && !srs_valid(srs)) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_set_source_srs: not a definition swz_srs_parse made");
   t->has_srs = srs != nullptr;

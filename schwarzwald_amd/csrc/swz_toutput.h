@@ -1,7 +1,7 @@
 // swz_toutput.h -- the three parts of swz_tiler_write_output (swz_toutput.hip), for the callers that run them apart:
 // validate and plan (output_plan, output_create_dirs), stream the files of a node range of a plan (output_cuts,
 // OutputImages, output_stream), write the metadata from a table (output_metadata).  swz_group_write_output
-// (swz_group.hip) runs the middle part per shard and the other two once.
+// (swz_goutput.hip) runs the middle part per shard and the other two once.
 #pragma once
 #include <string>
 #include <vector>

@@ -3,7 +3,7 @@
 // k + 1 is packed on the device (swz_bin_pack_device, swz_pnts_pack_device, swz_las_pack_device, straight from the pools) and
 // copied into the other one.  File names, node boxes, LAS offsets and scales are what TilingAlgorithmGPU::finalize and the
 // sinks of host/swz_tiling.hpp compute from the node table.  The call's three parts -- plan, stream a node range, metadata --
-// are functions of their own (swz_toutput.h): swz_group_write_output (swz_group.hip) runs the middle one per shard and the
+// are functions of their own (swz_toutput.h): swz_group_write_output (swz_goutput.hip) runs the middle one per shard and the
 // other two once, on the table swz_merge_shard_node_tables (here) makes of the shards' tables.
 #include <sys/stat.h>
 

@@ -8,6 +8,9 @@
 // mode: acc   = ACCURATE MIN_DISTANCE, the refusals first
 //       fast  = FAST RANDOM_GRID, fast_concurrency 5000: the tail of 4002 points joins the batch before it
 //       shift = ACCURATE MIN_DISTANCE with shift_to_center, the group driven through ShardedTilingAlgorithmGPU
+//       tail  = acc without the refusals, batch_points 13 333: the last batch holds 3 of the 40 002 points, so with 8 shards
+//               most shards get an empty slice of a batch that is not empty
+//       one   = acc without the refusals, batch_points 50 000: the whole data set is one batch, every shard holds one image
 // Exit code 0 = pass.
 #include <cstdio>
 #include <cstdlib>
@@ -26,7 +29,7 @@
     }                                                                           \
   } while (0)
 
-static const uint64_t kBatchPoints = 9000;
+static uint64_t kBatchPoints = 9000;  // (modes tail and one set their own)
 
 static bool same_info(const swz_tiler_info& a, const swz_tiler_info& b) {
   return a.num_points == b.num_points && a.num_stored == b.num_stored && a.num_nodes == b.num_nodes && a.num_batches == b.num_batches &&
@@ -55,8 +58,10 @@ static bool refused(swz_group* g, const std::vector<const char*>& paths, const s
 }
 
 static bool run(const std::string& work, int shards, const std::string& mode, const char* laz, const std::vector<const char*>& paths) {
-  const bool fast = mode == "fast", shift = mode == "shift";
-  REQUIRE(fast || shift || mode == "acc", "mode: acc | fast | shift");
+  const bool fast = mode == "fast", shift = mode == "shift", tail = mode == "tail", one = mode == "one";
+  REQUIRE(fast || shift || tail || one || mode == "acc", "mode: acc | fast | shift | tail | one");
+  if (tail) kBatchPoints = 13333;
+  if (one) kBatchPoints = 50000;
   swz_ctx* c = nullptr;
   REQUIRE(swz_create(&c, 0) == SWZ_OK, "swz_create");
   swz_las_dataset ds{};
@@ -81,7 +86,9 @@ static bool run(const std::string& work, int shards, const std::string& mode, co
   REQUIRE(swz_tiler_create(c, mn, mx, &p, 0, &single) == SWZ_OK, swz_last_error(c));
   REQUIRE(swz_tiler_add_las_files(single, paths.data(), paths.size(), &ip, &want) == SWZ_OK, swz_last_error(c));
   REQUIRE(swz_tiler_finalize(single, nullptr) == SWZ_OK, swz_last_error(c));
-  REQUIRE(want.points == ds.total_points && want.points > 4 * kBatchPoints, "the data set spans several batches");
+  REQUIRE(want.points == ds.total_points && (one || want.points > (tail ? 3 : 4) * kBatchPoints), "the data set spans several batches");
+  if (tail) REQUIRE(want.points % kBatchPoints == 3 && shards == 8, "the last batch has fewer points than the group has shards");
+  if (one) REQUIRE(want.batches == 1 && kBatchPoints >= want.points, "the whole data set is one batch");
   const uint64_t cut_batches = (ds.total_points + kBatchPoints - 1) / kBatchPoints;
   REQUIRE(want.batches == (fast ? cut_batches - 1 : cut_batches), "FAST folds the short tail into the batch before it, ACCURATE keeps it");
 
@@ -128,7 +135,7 @@ static bool run(const std::string& work, int shards, const std::string& mode, co
     REQUIRE(swz_group_create(shards, devices.data(), 0, &g) == SWZ_OK, "swz_group_create");
     REQUIRE(swz_group_add_las_files(g, paths.data(), paths.size(), &ip, nullptr) == SWZ_ERR_BAD_ARG, "the call before swz_group_tiler_open is refused");
     REQUIRE(swz_group_tiler_open(g, mn, mx, &p, 0) == SWZ_OK, swz_group_last_error(g));
-    if (!fast) {
+    if (mode == "acc") {
       std::vector<const char*> with_laz(paths);
       with_laz.insert(with_laz.begin() + 2, laz);
       if (!refused(g, with_laz, ip, SWZ_ERR_BAD_ARG, laz, "a LAZ-flagged file, named")) return false;
@@ -169,6 +176,8 @@ static bool run(const std::string& work, int shards, const std::string& mode, co
   std::printf("single: %llu points in %llu batches, %llu bytes; group: %llu points in %llu batches, %llu bytes\n", (unsigned long long)want.points,
               (unsigned long long)want.batches, (unsigned long long)want.bytes_read, (unsigned long long)got.points, (unsigned long long)got.batches,
               (unsigned long long)got.bytes_read);
+  std::printf("group stats ms: wall %.3f read %.3f copy %.3f decode %.3f tile %.3f wait %.3f\n", got.wall_ms, got.read_ms, got.copy_ms,
+              got.decode_ms, got.tile_ms, got.wait_ms);
   REQUIRE(got.points == want.points && got.batches == want.batches, "stats.points and stats.batches equal the single call's");
   REQUIRE(got.bytes_read == want.bytes_read && got.files == want.files, "stats.bytes_read and stats.files equal the single call's");
   REQUIRE(swz_tiler_destroy(single) == SWZ_OK, "swz_tiler_destroy");

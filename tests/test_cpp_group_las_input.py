@@ -4,7 +4,9 @@ length from extra bytes, a file of one point, an empty file) are read by a group
 call and by a single tiler in one call (swz_tiler_add_las_files: the yardstick); after finalize both data sets are written
 as LAS and as BIN and must be the same directories, byte for byte.  batch_points 9 000: batches span files, slices start
 in the middle of a file.  The files hold no two points with equal Morton keys (asserted here from the records), so the
-order inside every node file is defined by the keys alone.  The refusals run in the program's mode "acc"."""
+order inside every node file is defined by the keys alone.  The refusals run in the program's mode "acc".  Mode "tail" cuts
+batches of 13 333 points, which leaves a last batch of 3 points for 8 shards (most shards read, copy and decode nothing of a
+batch that is not empty); mode "one" reads the whole data set as one batch (one raw image per shard)."""
 import os
 import subprocess
 
@@ -15,7 +17,7 @@ from las_input_util import LasTile, make_cubic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 UTM = (412345.678, 5401234.321, 287.125)
-CASES = [(2, "acc"), (8, "acc"), (2, "fast"), (8, "fast"), (8, "shift")]
+CASES = [(2, "acc"), (8, "acc"), (2, "fast"), (8, "fast"), (8, "shift"), (8, "tail"), (8, "one")]
 
 
 @pytest.fixture(scope="module")
