@@ -338,7 +338,7 @@ typedef struct {
   int8_t level;              /* -1 = root "r" */
   uint8_t has_content;
   uint8_t is_tileset_root;
-  uint8_t reserved;
+  uint8_t tight;             /* swz_tileset_build_boxes: bounds are the points' box; written with HALF-axes */
   uint32_t num_children;
   uint64_t key;
   int64_t parent;            /* index into the output, -1 for the root */
@@ -349,6 +349,37 @@ typedef struct {
 int swz_tileset_build(uint64_t num_nodes, const int8_t* node_level, const uint64_t* node_key, const double root_min[3],
                       const double root_max[3], float spacing_at_root, const double global_offset[3], uint64_t max_out,
                       swz_tileset_node* out, uint64_t* num_out);
+/* The same tree with the boxes of the POINTS instead of the octree cubes: node_box_min / node_box_max hold 3 doubles per
+ * node of the table (what swz_node_boxes_device / swz_tiler_node_boxes return; a node without points has min = +inf, max =
+ * -inf).  bounds of an entry = the union of its own box (if has_content) and the bounds of all its descendants -- 3D Tiles
+ * requires a tile's volume to enclose its children's --, so an ancestor without a file gets the union of its children; one
+ * bottom-up pass over the output, whose (level, Morton index) order puts children behind their parent.  The boxes are
+ * translated by global_offset first, like the cubes.  Such entries are marked `tight`, and swz_tileset_write writes them as
+ * the 3D Tiles specification defines boundingVolume.box (HALF-axes).  An entry with no point below it keeps its cube and
+ * stays unmarked.  geometric_error, is_tileset_root and the links are swz_tileset_build's.  OURS: the reference only knows
+ * the cubes. */
+int swz_tileset_build_boxes(uint64_t num_nodes, const int8_t* node_level, const uint64_t* node_key, const double* node_box_min,
+                            const double* node_box_max, const double root_min[3], const double root_max[3], float spacing_at_root,
+                            const double global_offset[3], uint64_t max_out, swz_tileset_node* out, uint64_t* num_out);
+
+/* ---- the tight box of every node of a table: a segmented min/max over the stored rows, on the device.  OURS -- the
+ * reference writes the octree cube of a node wherever a box is asked for (Cesium3DTilesPersistence.cpp:100-112,
+ * LASPersistence.cpp:113-136), which wraps a thin, tilted sheet of airborne LiDAR in mostly empty volume.
+ *   swz_node_boxes_device: row i of node k is d_xyz[d_perm[d_order[node_offset[k] + i]]], composed as in
+ *     swz_pnts_pack_device (d_order NULL = identity, what a tiler's export ids need); node_offset / node_count are host
+ *     arrays, box_min_out / box_max_out host arrays of num_nodes x 3 doubles.  The result is EXACT: the componentwise min and
+ *     max of the node's doubles, nothing is computed on them (they are compared as order-preserving integer codes; -0.0 and
+ *     +0.0 compare equal in IEEE, either may come back).  A node of count 0 gets min = +inf, max = -inf.  The pools hold
+ *     finite, clamped positions; what a NaN does is not specified.  One workgroup takes swz_node_boxes_tile() consecutive
+ *     stored rows (tests place their edges by it): a shuffle reduction per wave and window entry, one LDS combine per entry,
+ *     then six 64-bit atomic min/max per (tile, node) on a table a small kernel presets -- the result does not depend on what
+ *     the workspace held nor on the order of the atomics.  Pools spilled to page-locked host memory are read in place.
+ *     SWZ_ERR_BAD_ARG before anything is launched for: offsets that do not ascend, ranges that overlap or pass n, a NULL
+ *     buffer when a node holds points, n above 2^32 - 65536.  n == 0, no nodes or only empty nodes launches nothing. */
+uint32_t swz_node_boxes_tile(void);
+int swz_node_boxes_device(swz_ctx* ctx, const uint32_t* d_perm, const uint32_t* d_order, uint64_t n, const double* d_xyz,
+                          uint64_t num_nodes, const uint64_t* node_offset, const uint64_t* node_count, double* box_min_out,
+                          double* box_max_out);
 
 /* ---- 3D Tiles node files and tileset JSON: Cesium3DTilesPersistence, the reference's default persistence
  * (executable/main.cpp:241-242; core/io/Cesium3DTilesPersistence.cpp:53-210, core/io/PNTSWriter.cpp:109-264).
@@ -388,7 +419,10 @@ int swz_tileset_build(uint64_t num_nodes, const int8_t* node_level, const uint64
  *   swz_tileset_write: the JSON files of swz_tileset_build's output (write_tilesets, Cesium3DTilesPersistence.cpp:173-210;
  *     writeTilesetJSON, core/io/TileSetWriter.cpp:42-210): "<name>.json" per is_tileset_root entry with asset.version "0.0",
  *     the entry's geometricError and its tile as root.  A tile holds boundingVolume.box = [centre, then the FULL extent on the
- *     diagonal] (boundingBoxFromAABB, core/pointcloud/Tileset.cpp:94-118: not halved), geometricError, refine "ADD",
+ *     diagonal] (boundingBoxFromAABB, core/pointcloud/Tileset.cpp:94-118: not halved) -- an entry marked `tight`
+ *     (swz_tileset_build_boxes) instead [centre, then the HALF extent on the diagonal], as the 3D Tiles specification has
+ *     it, the half-axes widened by the few ulps it takes for centre -/+ half, evaluated in double, to enclose bounds_min and
+ *     bounds_max --, geometricError, refine "ADD",
  *     content.uri and children (by octant); three levels below the file's root the uri is "<name>.json" and there are no
  *     children, everywhere else "<name>.pnts" -- for ancestors without a file of their own too, as setup_tileset does.
  *     Compact, no whitespace.
@@ -516,6 +550,16 @@ typedef struct {
   const char* version;
 } swz_ept_json;
 double swz_las_scale_from_bounds(const double box_min[3], const double box_max[3]);
+/* The box of the STORED records of a node whose points have the box [box_min, box_max]: both corners sent through the
+ * quantisation of the row writers against las_offset and scale and back the way swz_las_read_node dequantises (offset + X *
+ * scale).  The map is monotonic, so this is the min / max of the positions swz_las_read_node returns -- what a LAS header's
+ * max / min x, y, z should hold (swz_tiler_write_output with SWZ_OUT_TIGHT_BOUNDS). */
+int swz_las_stored_box(const double box_min[3], const double box_max[3], const double las_offset[3], double scale,
+                       double min_out[3], double max_out[3]);
+/* swz_las_write_node with a header whose max / min x, y, z are [extent_min, extent_max]; the offsets stay box_min. */
+int swz_las_write_node_extent(swz_ctx* ctx, const char* path, uint64_t count, const void* body, uint32_t mask,
+                              const double box_min[3], const double box_max[3], double scale, const double extent_min[3],
+                              const double extent_max[3]);
 int swz_las_record_layout(uint32_t mask, uint32_t* point_format_out, uint32_t* record_bytes_out);
 int swz_las_image_layout(uint64_t num_nodes, const uint64_t* node_count, uint32_t mask, uint64_t* body_offset_out,
                          uint64_t* body_size_out, uint64_t* total_out);
@@ -751,12 +795,27 @@ int swz_tiler_pools_device(swz_tiler* tiler, const double** d_xyz_out, swz_attri
  *     rgb_mapping without intensities in the mask, a global_offset that is not finite, a dir that cannot be created.  A file
  *     that cannot be written stops the stream after the running chunk and is reported by name.
  *   stats (may be NULL): pack_ms is the time in the pack calls, copy_ms the copy stream's, write_ms the writer threads',
- *     each summed over the chunks; wall_ms the whole call; bytes_written the chunk images that went into files. */
+ *     each summed over the chunks; wall_ms the whole call; bytes_written the chunk images that went into files.
+ *   flags: 0 is everything above, byte for byte; an unknown bit is SWZ_ERR_BAD_ARG.  SWZ_OUT_TIGHT_BOUNDS (OURS): the boxes
+ *     in the metadata are the boxes of the POINTS, not the octree cubes.  swz_node_boxes_device runs on every chunk's ids
+ *     beside the pack call (its time counts into pack_ms); no point record and no .pnts file changes.
+ *       3DTILES: the tileset goes through swz_tileset_build_boxes (unions bottom-up, half-axes); the box of a node is the box
+ *         of what its file HOLDS, the double box narrowed to float and widened again (narrowing is monotonic).
+ *       LAS, ENTWINE_LAS: offset, scale and records are unchanged; the header's max / min x, y, z become swz_las_stored_box
+ *         of the node's box -- exactly the min / max of what swz_las_read_node returns.
+ *       ENTWINE_LAS with ept: boundsConforming is the union of those boxes, overriding ept->conforming_*; bounds stays.
+ *       BIN, BINZ hold no box: the flag is refused by name.
+ *   swz_tiler_node_boxes: the double boxes of the nodes, in the order of swz_tiler_node_table (max_nodes x 3 doubles each;
+ *     a node without points: +inf / -inf).  Precondition: that of swz_tiler_export_device.  The ids are exported once and
+ *     swz_node_boxes_device runs over the pools chunk by chunk (SWZ_OUTPUT_CHUNK_POINTS), so memory stays bounded by a
+ *     chunk.  The tiler stays usable, a failure does not poison it. */
 enum { SWZ_OUT_BIN = 0, SWZ_OUT_BINZ = 1, SWZ_OUT_3DTILES = 2, SWZ_OUT_LAS = 3, SWZ_OUT_ENTWINE_LAS = 4 };
+enum { SWZ_OUT_TIGHT_BOUNDS = 1u };
 typedef struct {
   int format;
   uint32_t attribute_mask;   /* bits SWZ_ATTR_*, a subset of what the batches carried */
   int rgb_mapping;           /* 3DTILES only: SWZ_PNTS_RGB_FROM_* */
+  uint32_t flags;            /* SWZ_OUT_TIGHT_BOUNDS; 0 = none (these four bytes were padding: size and offsets are unchanged) */
   double global_offset[3];   /* 3DTILES: RTC_CENTER / the tileset boxes */
   uint64_t chunk_points;     /* 0 = default */
   const swz_ept_json* ept;   /* ENTWINE_LAS: NULL = do not write ept.json */
@@ -766,6 +825,10 @@ typedef struct {
   double pack_ms, copy_ms, write_ms, wall_ms;
 } swz_output_stats;
 int swz_tiler_write_output(swz_tiler* tiler, const char* dir, const swz_output_params* params, swz_output_stats* stats);
+/* what swz_tiler_write_output / swz_group_write_output refuse of `flags` for a format (host, no GPU): SWZ_ERR_BAD_ARG and
+ * the text of the refusal in *what_out (static; NULL when the flags are fine). */
+int swz_output_flags_check(int format, uint32_t flags, const char** what_out);
+int swz_tiler_node_boxes(swz_tiler* tiler, uint64_t max_nodes, double* box_min_out, double* box_max_out, uint64_t* num_nodes_out);
 /* The chunks swz_tiler_write_output cuts a node table into (host): chunk j holds the nodes [first_node_out[j],
  * first_node_out[j + 1]); first_node_out takes up to max_chunks + 1 entries and may be NULL (then only *num_chunks_out). */
 int swz_output_chunks(uint64_t num_nodes, const uint64_t* node_count, uint64_t chunk_points, uint64_t max_chunks,
@@ -1070,6 +1133,11 @@ int swz_group_finalize(swz_group* group, swz_tile_stats* stats_per_shard);
  *     is SWZ_ERR_BAD_ARG; with every output array NULL only the count is given (max_nodes is ignored).  shard_out alone may
  *     be NULL.
  *   swz_group_node_table: the same from the tilers of an open data set (swz_group_tiler_open).
+ *   swz_group_node_boxes: swz_tiler_node_boxes of every shard's tiler, in the order of swz_group_node_table (max_nodes x 3
+ *     doubles each); the root's box is the min / max of the shards' parts.  swz_group_write_output honours
+ *     SWZ_OUT_TIGHT_BOUNDS the same way: every shard reduces its own nodes while it streams them, shard 0 the root's
+ *     gathered rows, and the metadata is written once from the merged table and the merged boxes.  Both have only ever run
+ *     with all shards on ONE device.
  *   swz_group_write_output: the directory swz_tiler_write_output writes for a single tiler fed the same batches -- the same
  *     file names and the same bytes, metadata included.  Preconditions: a data set is open, no batch is staged on the group,
  *     and on every shard's tiler what swz_tiler_write_output asks (not poisoned, nothing staged or open).  What that call
@@ -1120,6 +1188,7 @@ int swz_merge_shard_node_tables(int num_shards, const uint64_t* num_nodes, const
                                 uint64_t* num_nodes_out);
 int swz_group_node_table(swz_group* group, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out, uint64_t* count_out,
                          int32_t* shard_out, uint64_t* num_nodes_out);
+int swz_group_node_boxes(swz_group* group, uint64_t max_nodes, double* box_min_out, double* box_max_out, uint64_t* num_nodes_out);
 int swz_group_write_output(swz_group* group, const char* dir, const swz_output_params* params,
                            swz_output_stats* stats_per_shard, swz_output_stats* total);
 

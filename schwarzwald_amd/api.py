@@ -202,29 +202,44 @@ def min_distance_fast_stride(node_level):
 
 
 class _TilesetNode(C.Structure):
-    _fields_ = [("level", C.c_int8), ("has_content", C.c_uint8), ("is_tileset_root", C.c_uint8), ("reserved", C.c_uint8),
+    _fields_ = [("level", C.c_int8), ("has_content", C.c_uint8), ("is_tileset_root", C.c_uint8), ("tight", C.c_uint8),
                 ("num_children", C.c_uint32), ("key", C.c_uint64), ("parent", C.c_int64), ("first_child", C.c_int64),
                 ("geometric_error", C.c_double), ("bounds_min", C.c_double * 3), ("bounds_max", C.c_double * 3)]
 
 
-def tileset_build(node_level, node_key, root_min, root_max, spacing_at_root, global_offset=None):
-    """Tileset tree of a node table (Cesium3DTilesPersistence.cpp:80-156): list of dicts ordered by (level, key)."""
+def tileset_build(node_level, node_key, root_min, root_max, spacing_at_root, global_offset=None, node_boxes=None):
+    """Tileset tree of a node table (Cesium3DTilesPersistence.cpp:80-156): list of dicts ordered by (level, key).
+    node_boxes: (box_min, box_max), num_nodes x 3 each in table order (Tiler.node_boxes) -- swz_tileset_build_boxes: the
+    bounds become the boxes of the points, united bottom-up, and the dicts carry `tight` (tileset_write then writes
+    half-axes)."""
     L = load_library()
     lv = np.ascontiguousarray(node_level, dtype=np.int8)
     key = np.ascontiguousarray(node_key, dtype=np.uint64)
     off = _vec3(global_offset) if global_offset is not None else None
     num = C.c_uint64()
-    args = (lv.shape[0], lv.ctypes.data_as(_i8p), key.ctypes.data_as(_u64p), _vec3(root_min), _vec3(root_max),
-            C.c_float(spacing_at_root), off)
-    if L.swz_tileset_build(*args, 0, None, C.byref(num)) != 0:
+    head = (lv.shape[0], lv.ctypes.data_as(_i8p), key.ctypes.data_as(_u64p))
+    tail = (_vec3(root_min), _vec3(root_max), C.c_float(spacing_at_root), off)
+    if node_boxes is None:
+        build, args = L.swz_tileset_build, head + tail
+    else:
+        lo = np.ascontiguousarray(node_boxes[0], dtype=np.float64).reshape(-1)
+        hi = np.ascontiguousarray(node_boxes[1], dtype=np.float64).reshape(-1)
+        if lo.shape[0] != 3 * lv.shape[0] or hi.shape[0] != 3 * lv.shape[0]:
+            raise ValueError("node_boxes must hold 3 values per node")
+        build, args = L.swz_tileset_build_boxes, head + (lo.ctypes.data_as(_dp), hi.ctypes.data_as(_dp)) + tail
+    if build(*args, 0, None, C.byref(num)) != 0:
         raise ValueError("bad node table")
     buf = (_TilesetNode * max(int(num.value), 1))()
-    if L.swz_tileset_build(*args, int(num.value), buf, C.byref(num)) != 0:
+    if build(*args, int(num.value), buf, C.byref(num)) != 0:
         raise ValueError("bad node table")
-    return [dict(level=int(t.level), key=int(t.key), has_content=bool(t.has_content), is_tileset_root=bool(t.is_tileset_root),
-                 num_children=int(t.num_children), parent=int(t.parent), first_child=int(t.first_child),
-                 geometric_error=float(t.geometric_error), bounds_min=list(t.bounds_min), bounds_max=list(t.bounds_max))
-            for t in buf[:int(num.value)]]
+    tiles = [dict(level=int(t.level), key=int(t.key), has_content=bool(t.has_content), is_tileset_root=bool(t.is_tileset_root),
+                  num_children=int(t.num_children), parent=int(t.parent), first_child=int(t.first_child),
+                  geometric_error=float(t.geometric_error), bounds_min=list(t.bounds_min), bounds_max=list(t.bounds_max))
+             for t in buf[:int(num.value)]]
+    if node_boxes is not None:
+        for d, t in zip(tiles, buf):
+            d["tight"] = bool(t.tight)
+    return tiles
 
 
 def bin_write_node(path, xyz, attrs=None, compressed=False):
@@ -347,6 +362,7 @@ def tileset_write(tiles, directory):
         t.level, t.key, t.has_content, t.is_tileset_root = d["level"], d["key"], int(d["has_content"]), int(d["is_tileset_root"])
         t.num_children, t.parent, t.first_child, t.geometric_error = d["num_children"], d["parent"], d["first_child"], d["geometric_error"]
         t.bounds_min, t.bounds_max = _vec3(d["bounds_min"]), _vec3(d["bounds_max"])
+        t.tight = int(bool(d.get("tight", False)))
     st = load_library().swz_tileset_write(None, buf, len(tiles), os.fsencode(directory))
     if st != 0:
         raise SwzError(st, "swz_tileset_write(%s) failed" % directory)
@@ -376,6 +392,14 @@ def _las_mask(attrs):
 def las_scale_from_bounds(bmin, bmax):
     """compute_las_scale_from_bounds (LASPersistence.cpp:16-28): the scale of a node file from the node box."""
     return float(load_library().swz_las_scale_from_bounds(_vec3(bmin), _vec3(bmax)))
+
+
+def las_stored_box(box_min, box_max, las_offset, scale):
+    """swz_las_stored_box: the box of the stored records of a node whose points have the box [box_min, box_max]."""
+    lo, hi = (C.c_double * 3)(), (C.c_double * 3)()
+    if load_library().swz_las_stored_box(_vec3(box_min), _vec3(box_max), _vec3(las_offset), float(scale), lo, hi) != 0:
+        raise ValueError("bad scale")
+    return list(lo), list(hi)
 
 
 def las_record_layout(attrs=()):
@@ -473,6 +497,11 @@ def bin_persist_nodes(directory, nodes, xyz, attrs=None, compressed=False, ctx=N
         raise SwzError(st, (L.swz_last_error(ctx) or b"").decode() if ctx else "swz_bin_persist_nodes(%s) failed" % directory)
 
 
+def node_boxes_tile():
+    """Stored rows one workgroup of swz_node_boxes_device takes (tests place their edges by it)."""
+    return int(load_library().swz_node_boxes_tile())
+
+
 def bin_pack_tile():
     """The stored rows one workgroup of bin_pack_device takes."""
     return int(load_library().swz_bin_pack_tile())
@@ -509,16 +538,26 @@ def bin_persist_nodes_image(directory, nodes, image, attrs=(), compressed=False,
 
 # swz_tiler_write_output: the formats, its parameters and what it reports
 OUTPUT_FORMATS = {"BIN": 0, "BINZ": 1, "3DTILES": 2, "LAS": 3, "ENTWINE_LAS": 4}
+OUT_TIGHT_BOUNDS = 1
 
 
 class _OutputParams(C.Structure):
-    _fields_ = [("format", C.c_int), ("attribute_mask", C.c_uint32), ("rgb_mapping", C.c_int), ("global_offset", C.c_double * 3),
-                ("chunk_points", C.c_uint64), ("ept", C.POINTER(_EptJson))]
+    _fields_ = [("format", C.c_int), ("attribute_mask", C.c_uint32), ("rgb_mapping", C.c_int), ("flags", C.c_uint32),
+                ("global_offset", C.c_double * 3), ("chunk_points", C.c_uint64), ("ept", C.POINTER(_EptJson))]
 
 
 class _OutputStats(C.Structure):
     _fields_ = [("nodes", C.c_uint64), ("stored_points", C.c_uint64), ("bytes_written", C.c_uint64), ("chunks", C.c_uint64),
                 ("pack_ms", C.c_double), ("copy_ms", C.c_double), ("write_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+def output_flags_check(format, flags):
+    """swz_output_flags_check: raises SwzError with the text write_output refuses these flags with for the format."""
+    fmt = OUTPUT_FORMATS[format] if isinstance(format, str) else int(format)
+    what = C.c_char_p()
+    st = load_library().swz_output_flags_check(fmt, int(flags), C.byref(what))
+    if st != 0:
+        raise SwzError(st, (what.value or b"").decode())
 
 
 def output_chunks(counts, chunk_points):
@@ -907,6 +946,19 @@ def load_library():
     L.swz_tileset_build.argtypes = [C.c_uint64, _i8p, _u64p, _dp, _dp, C.c_float, _dp, C.c_uint64,
                                     C.POINTER(_TilesetNode), _u64p]
     L.swz_tileset_build.restype = C.c_int
+    L.swz_tileset_build_boxes.argtypes = [C.c_uint64, _i8p, _u64p, _dp, _dp, _dp, _dp, C.c_float, _dp, C.c_uint64,
+                                          C.POINTER(_TilesetNode), _u64p]
+    L.swz_tileset_build_boxes.restype = C.c_int
+    L.swz_node_boxes_tile.argtypes = []
+    L.swz_node_boxes_tile.restype = C.c_uint32
+    L.swz_node_boxes_device.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, _u64p, _u64p, _dp, _dp]
+    L.swz_node_boxes_device.restype = C.c_int
+    L.swz_tiler_node_boxes.argtypes = [vp, C.c_uint64, _dp, _dp, _u64p]
+    L.swz_tiler_node_boxes.restype = C.c_int
+    L.swz_las_stored_box.argtypes = [_dp, _dp, _dp, C.c_double, _dp, _dp]
+    L.swz_las_stored_box.restype = C.c_int
+    L.swz_output_flags_check.argtypes = [C.c_int, C.c_uint32, C.POINTER(C.c_char_p)]
+    L.swz_output_flags_check.restype = C.c_int
     L.swz_pnts_layout.argtypes = [C.c_uint64, _u64p, C.c_uint32, C.c_int, _u64p, _u64p, _u64p, _u64p, _u64p]
     L.swz_pnts_pack_device.argtypes = [vp, vp, vp, C.c_uint64, vp, cols, C.c_uint64, _u64p, _u64p, C.c_uint32, C.c_int, vp,
                                        C.c_uint64]
@@ -1317,6 +1369,18 @@ class Context:
                                                    C.byref(cin), nc.shape[0], no.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p),
                                                    _pnts_mask(attrs), int(rgb_from), C.c_void_p(d_image), int(image_bytes)))
 
+    def node_boxes_device(self, d_perm, d_order, n, d_xyz, nodes):
+        """swz_node_boxes_device: (box_min, box_max), num_nodes x 3 float64 each -- the exact componentwise min and max of
+        the rows d_xyz[d_perm[d_order[offset + i]]] of every node of the table; a node without points has +inf / -inf.
+        d_order None = identity (a tiler's export ids as d_perm)."""
+        no, nc = _node_columns(nodes, "offset", "count")
+        lo = np.empty((nc.shape[0], 3), dtype=np.float64)
+        hi = np.empty((nc.shape[0], 3), dtype=np.float64)
+        self._check(self._lib.swz_node_boxes_device(self._ctx, C.c_void_p(d_perm), C.c_void_p(d_order), int(n), C.c_void_p(d_xyz),
+                                                    nc.shape[0], no.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p),
+                                                    lo.ctypes.data_as(_dp), hi.ctypes.data_as(_dp)))
+        return lo, hi
+
     def pnts_persist_nodes(self, directory, nodes, image, attrs=(), rtc_center=None):
         """One .pnts file per node of a node table out of a host copy of the image pnts_pack_device wrote."""
         img = np.ascontiguousarray(image, dtype=np.uint8).reshape(-1)
@@ -1587,6 +1651,17 @@ class Tiler:
         m = int(num.value)
         return dict(level=nl[:m].copy(), key=nk[:m].copy(), offset=no[:m].copy(), count=nc[:m].copy())
 
+    def node_boxes(self):
+        """swz_tiler_node_boxes: (box_min, box_max), num_nodes x 3 float64 each, the boxes of the nodes' points in the order
+        of node_table, reduced on the device from the pools (a node without points: +inf / -inf)."""
+        cap = max(int(self.info()["num_nodes"]), 1)
+        lo = np.empty((cap, 3), dtype=np.float64)
+        hi = np.empty((cap, 3), dtype=np.float64)
+        num = C.c_uint64()
+        self._ctx._check(self._lib.swz_tiler_node_boxes(self._t, cap, lo.ctypes.data_as(_dp), hi.ctypes.data_as(_dp), C.byref(num)))
+        m = int(num.value)
+        return lo[:m].copy(), hi[:m].copy()
+
     def export_device(self, d_keys, d_ids, d_level):
         self._ctx._check(self._lib.swz_tiler_export_device(self._t, C.c_void_p(d_keys), C.c_void_p(d_ids),
                                                            C.c_void_p(d_level)))
@@ -1633,15 +1708,18 @@ class Tiler:
     def level_positions_device(self, level, d_xyz_out):
         self._ctx._check(self._lib.swz_tiler_level_positions_device(self._t, int(level), C.c_void_p(d_xyz_out)))
 
-    def write_output(self, directory, format, attrs=(), rgb_from=RGB_FROM_COLOR, global_offset=None, chunk_points=0, ept=None):
+    def write_output(self, directory, format, attrs=(), rgb_from=RGB_FROM_COLOR, global_offset=None, chunk_points=0, ept=None,
+                     tight_bounds=False, flags=0):
         """swz_tiler_write_output: every node file of the tiler, and the format's metadata, into directory.  format: a key of
         OUTPUT_FORMATS; attrs: the attribute columns to write (names or a mask), a subset of what the batches carried;
         rgb_from / global_offset: 3DTILES; chunk_points: stored points per chunk (0 = default); ept: ENTWINE_LAS, the keyword
         arguments of ept_json_write as a dict (bounds, conforming_bounds, points, ...) or None for no ept.json.  Returns the
-        stats as a dict (nodes, stored_points, bytes_written, chunks, pack_ms, copy_ms, write_ms, wall_ms)."""
+        stats as a dict (nodes, stored_points, bytes_written, chunks, pack_ms, copy_ms, write_ms, wall_ms).  tight_bounds:
+        SWZ_OUT_TIGHT_BOUNDS -- tileset boxes, LAS header extents and ept.json's boundsConforming are the boxes of the points,
+        reduced on the device, not the octree cubes; refused for BIN / BINZ.  flags: further bits of the params' flags."""
         fmt = OUTPUT_FORMATS[format] if isinstance(format, str) else int(format)
-        p = _OutputParams(fmt, _las_mask(attrs), int(rgb_from), _vec3(global_offset if global_offset is not None else (0, 0, 0)),
-                          int(chunk_points), None)
+        p = _OutputParams(fmt, _las_mask(attrs), int(rgb_from), int(flags) | (OUT_TIGHT_BOUNDS if tight_bounds else 0),
+                          _vec3(global_offset if global_offset is not None else (0, 0, 0)), int(chunk_points), None)
         keep = None
         if ept is not None:
             srs = ept.get("srs") or {}

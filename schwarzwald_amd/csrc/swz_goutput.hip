@@ -5,6 +5,8 @@
 //   O1  every shard's part of the root's file is gathered (then shard 0 copies the parts, packs and writes the root)
 //   O2  every shard's files are written; nobody reads a neighbour's part any more (then the call's workspace goes back)
 #include <algorithm>
+#include <limits>
+#include <map>
 #include <thread>
 
 #include "swz_group.h"
@@ -32,7 +34,7 @@ void output_thread(swz_group* g, int r, GroupOutput* o) {
   swz_tiler* t = g->ds.tiler[r];
   const auto t_begin = std::chrono::steady_clock::now();
   swz::OutputWorkspace ow{c};
-  const swz::OutputPlan& p = o->plan[r];
+  swz::OutputPlan& p = o->plan[r];  // (a tight plan gets its boxes from the stream)
   const uint64_t nn = p.count.size(), k0 = (nn && p.level[0] < 0) ? 1 : 0, ns = o->info[r].num_stored;
   const uint64_t root_rows = o->part_off[s.N];
   std::vector<uint64_t> first, root_first;
@@ -144,9 +146,86 @@ int merge_tables(swz_group* g, const std::vector<std::vector<int8_t>>& level, co
   return st;
 }
 
+// The boxes of the merged table out of the shards' (3 doubles per node of a shard's table): a node below the root is found
+// by (level, key) in the one table that lists it; the root's box is the min / max of every root part given -- the shards'
+// own entries and, when the root's rows were reduced as one file, that box (extra_lo / extra_hi, may be null).
+void merge_boxes(const std::vector<std::vector<int8_t>>& level, const std::vector<std::vector<uint64_t>>& key,
+                 const std::vector<const double*>& lo, const std::vector<const double*>& hi, const double* extra_lo,
+                 const double* extra_hi, uint64_t nn, const int8_t* merged_level, const uint64_t* merged_key, double* lo_out,
+                 double* hi_out) {
+  const double inf = std::numeric_limits<double>::infinity();
+  double root_lo[3] = {inf, inf, inf}, root_hi[3] = {-inf, -inf, -inf};
+  auto join_root = [&](const double* a, const double* b) {
+    for (int ax = 0; ax < 3; ++ax) {
+      root_lo[ax] = std::min(root_lo[ax], a[ax]);
+      root_hi[ax] = std::max(root_hi[ax], b[ax]);
+    }
+  };
+  if (extra_lo && extra_hi) join_root(extra_lo, extra_hi);
+  std::map<std::pair<int, uint64_t>, std::pair<const double*, const double*>> where;
+  for (size_t r = 0; r < level.size(); ++r) {
+    for (size_t k = 0; k < level[r].size(); ++k) {
+      if (level[r][k] < 0) join_root(lo[r] + 3 * k, hi[r] + 3 * k);
+      else where[{level[r][k], key[r][k]}] = {lo[r] + 3 * k, hi[r] + 3 * k};
+    }
+  }
+  for (uint64_t k = 0; k < nn; ++k) {
+    const double *a = root_lo, *b = root_hi;
+    if (merged_level[k] >= 0) {
+      const auto& found = where[{merged_level[k], merged_key[k]}];
+      a = found.first;
+      b = found.second;
+    }
+    for (int ax = 0; ax < 3; ++ax) {
+      lo_out[3 * k + ax] = a[ax];
+      hi_out[3 * k + ax] = b[ax];
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+int swz_group_node_boxes(swz_group* g, uint64_t max_nodes, double* box_min_out, double* box_max_out, uint64_t* num_nodes_out) {
+  if (!g || !num_nodes_out) return SWZ_ERR_BAD_ARG;
+  if (g->ds.tiler.empty()) {
+    g->err = "swz_group_node_boxes: no data set is open (swz_group_tiler_open)";
+    return SWZ_ERR_BAD_ARG;
+  }
+  std::vector<std::vector<int8_t>> level;
+  std::vector<std::vector<uint64_t>> key, count;
+  int st = shard_node_tables(g, level, key, count);
+  if (st != SWZ_OK) return st;
+  uint64_t nn = 0, cap = 1;
+  for (int r = 0; r < g->n; ++r) cap += level[r].size();
+  std::vector<int8_t> merged_level(cap);
+  std::vector<uint64_t> merged_key(cap), merged_count(cap);
+  if ((st = merge_tables(g, level, key, count, cap, merged_level.data(), merged_key.data(), merged_count.data(), nullptr, &nn)) != SWZ_OK) return st;
+  *num_nodes_out = nn;
+  if (nn > max_nodes || (nn && (!box_min_out || !box_max_out))) {
+    g->err = "swz_group_node_boxes: max_nodes too small, or a NULL buffer";
+    return SWZ_ERR_BAD_ARG;
+  }
+  // every shard's own boxes, one shard after the other (each call is bounded by a chunk of that shard)
+  std::vector<std::vector<double>> lo(g->n), hi(g->n);
+  std::vector<const double*> plo(g->n), phi(g->n);
+  for (int r = 0; r < g->n; ++r) {
+    (void)hipSetDevice(g->devices[r]);
+    const uint64_t m = level[r].size();
+    lo[r].resize(3 * std::max<uint64_t>(m, 1));
+    hi[r].resize(3 * std::max<uint64_t>(m, 1));
+    uint64_t got = 0;
+    if ((st = swz_tiler_node_boxes(g->ds.tiler[r], m, lo[r].data(), hi[r].data(), &got)) != SWZ_OK) {
+      g->err = "shard " + std::to_string(r) + ": " + swz_last_error(g->ctx[r]);
+      return st;
+    }
+    plo[r] = lo[r].data();
+    phi[r] = hi[r].data();
+  }
+  merge_boxes(level, key, plo, phi, nullptr, nullptr, nn, merged_level.data(), merged_key.data(), box_min_out, box_max_out);
+  return SWZ_OK;
+}
 
 int swz_group_node_table(swz_group* g, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out, uint64_t* count_out,
                          int32_t* shard_out, uint64_t* num_nodes_out) {
@@ -254,7 +333,17 @@ int swz_group_write_output(swz_group* g, const char* dir, const swz_output_param
   for (int r = 0; stats_per_shard && r < N; ++r) stats_per_shard[r] = o.stats[r];
   st = first_failure(g);
   std::fill(g->call.status.begin(), g->call.status.end(), SWZ_OK);  // (a failed write marks no shard: the group stays usable)
-  // ---- the metadata, once, from the merged table
+  // ---- the metadata, once, from the merged table (and, tight, the merged boxes: the shards' own and the root's)
+  if (st == SWZ_OK && merged.tight) {
+    std::vector<const double*> plo(N), phi(N);
+    for (int r = 0; r < N; ++r) {
+      plo[r] = o.plan[r].tight_min.data();
+      phi[r] = o.plan[r].tight_max.data();
+    }
+    const bool root = o.root.tight && !o.root.tight_min.empty();
+    merge_boxes(level, key, plo, phi, root ? o.root.tight_min.data() : nullptr, root ? o.root.tight_max.data() : nullptr, nn,
+                merged.level.data(), merged.key.data(), merged.tight_min.data(), merged.tight_max.data());
+  }
   if (st == SWZ_OK) {
     (void)hipSetDevice(g->devices[0]);
     if ((st = swz::output_metadata(c0, who, merged, dir, params)) != SWZ_OK) g->err = swz_last_error(c0);

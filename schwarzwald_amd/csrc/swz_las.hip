@@ -274,8 +274,9 @@ static double get_f64(const unsigned char* p) {
 }
 
 // the LAS 1.2 public header block as LASPersistence::persist_points fills it (LASPersistence.cpp:113-136)
+// (extent: what max / min x, y, z hold when it is not the node box -- the box of the stored records; null = the node box)
 static void las_header(unsigned char h[LAS_HEADER_BYTES], uint64_t count, uint32_t format, const double box_min[3], const double box_max[3],
-                       double scale) {
+                       double scale, const double* extent_min = nullptr, const double* extent_max = nullptr) {
   memset(h, 0, LAS_HEADER_BYTES);
   memcpy(h, "LASF", 4);
   h[24] = 1;  // version 1.2
@@ -290,16 +291,17 @@ static void las_header(unsigned char h[LAS_HEADER_BYTES], uint64_t count, uint32
   for (int k = 0; k < 3; ++k) {
     put_f64(h + 131 + 8 * k, scale);
     put_f64(h + 155 + 8 * k, box_min[k]);   // the offsets are the box minimum
-    put_f64(h + 179 + 16 * k, box_max[k]);  // max x, min x, max y, min y, max z, min z
-    put_f64(h + 187 + 16 * k, box_min[k]);
+    put_f64(h + 179 + 16 * k, extent_max ? extent_max[k] : box_max[k]);  // max x, min x, max y, min y, max z, min z
+    put_f64(h + 187 + 16 * k, extent_min ? extent_min[k] : box_min[k]);
   }
 }
 
 // no context: the files of a table are written by several threads
 static int las_write_file(const char* path, uint64_t count, const void* body, uint32_t format, const double box_min[3],
-                          const double box_max[3], double scale, std::string* err) {
+                          const double box_max[3], double scale, std::string* err, const double* extent_min = nullptr,
+                          const double* extent_max = nullptr) {
   unsigned char h[LAS_HEADER_BYTES];
-  las_header(h, count, format, box_min, box_max, scale);
+  las_header(h, count, format, box_min, box_max, scale, extent_min, extent_max);
   return write_file(path, {{h, sizeof(h)}, {body, (size_t)(count * las_record_bytes(format))}}, err);
 }
 
@@ -411,6 +413,16 @@ double swz_las_scale_from_bounds(const double box_min[3], const double box_max[3
   return 0.0001;
 }
 
+int swz_las_stored_box(const double box_min[3], const double box_max[3], const double las_offset[3], double scale,
+                       double min_out[3], double max_out[3]) {
+  if (!box_min || !box_max || !las_offset || !min_out || !max_out || !scale_ok(scale)) return SWZ_ERR_BAD_ARG;
+  for (int ax = 0; ax < 3; ++ax) {  // las_quantize, then swz_las_read_node's offset + X * scale
+    min_out[ax] = las_offset[ax] + (double)las_quantize(box_min[ax], las_offset[ax], scale) * scale;
+    max_out[ax] = las_offset[ax] + (double)las_quantize(box_max[ax], las_offset[ax], scale) * scale;
+  }
+  return SWZ_OK;
+}
+
 int swz_las_record_layout(uint32_t mask, uint32_t* point_format_out, uint32_t* record_bytes_out) {
   if (mask & ~LAS_MASK_ALL) return SWZ_ERR_BAD_ARG;
   const uint32_t format = las_format(mask);
@@ -504,6 +516,20 @@ int swz_las_write_node(swz_ctx* c, const char* path, uint64_t count, const void*
   if (!body) return fail(c, SWZ_ERR_BAD_ARG, "swz_las_write_node: NULL body");
   std::string err;
   const int st = las_write_file(path, count, body, las_format(mask), box_min, box_max, scale, &err);
+  return st == SWZ_OK ? SWZ_OK : fail(c, st, err);
+}
+
+int swz_las_write_node_extent(swz_ctx* c, const char* path, uint64_t count, const void* body, uint32_t mask, const double box_min[3],
+                              const double box_max[3], double scale, const double extent_min[3], const double extent_max[3]) {
+  if (!path) return fail(c, SWZ_ERR_BAD_ARG, "swz_las_write_node_extent: NULL path");
+  if (mask & ~LAS_MASK_ALL) return fail(c, SWZ_ERR_BAD_ARG, "swz_las_write_node_extent: the mask names an attribute that does not exist");
+  SWZ_TRY(check_file_args(c, "swz_las_write_node_extent", count, box_min, box_max, scale));
+  if (count == 0) return SWZ_OK;
+  if (!body) return fail(c, SWZ_ERR_BAD_ARG, "swz_las_write_node_extent: NULL body");
+  if (!extent_min || !extent_max || !finite3(extent_min) || !finite3(extent_max))
+    return fail(c, SWZ_ERR_BAD_ARG, "swz_las_write_node_extent: the extent is not finite");
+  std::string err;
+  const int st = las_write_file(path, count, body, las_format(mask), box_min, box_max, scale, &err, extent_min, extent_max);
   return st == SWZ_OK ? SWZ_OK : fail(c, st, err);
 }
 

@@ -17,6 +17,8 @@
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
+#include <limits>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -453,6 +455,17 @@ static void put_tile(std::string& s, const swz_tileset_node* nodes, uint64_t i, 
     put_number(s, t.bounds_min[k] + e[k] / 2);
     s += ",";
   }
+  if (t.tight) {
+    // OURS (swz_tileset_build_boxes): the HALF extent, as the 3D Tiles specification defines the box -- the largest of the
+    // centre's distances to the two faces (the centre is rounded), then ulp by ulp until centre -/+ half, evaluated in
+    // double like a reader does, encloses the bounds: rounding is monotonic, so a half that is large enough as a real is
+    for (int k = 0; k < 3; ++k) {
+      const double centre = t.bounds_min[k] + e[k] / 2;
+      e[k] = std::max(e[k] / 2, std::max(centre - t.bounds_min[k], t.bounds_max[k] - centre));
+      for (int step = 0; step < 8 && (centre - e[k] > t.bounds_min[k] || centre + e[k] < t.bounds_max[k]); ++step)
+        e[k] = std::nextafter(e[k], std::numeric_limits<double>::infinity());
+    }
+  }
   for (int k = 0; k < 9; ++k) {
     put_number(s, k % 4 == 0 ? e[k / 4] : 0.0);
     if (k < 8) s += ",";
@@ -647,6 +660,50 @@ int swz_pnts_read_node(swz_ctx* c, const char* path, double* xyz_out, const swz_
     memcpy(columns_out->column[SWZ_ATTR_RGB], bin + f.rgb, (size_t)(3 * f.count));
   if (columns_out && columns_out->column[SWZ_ATTR_INTENSITY] && (f.mask & SWZ_PNTS_INTENSITY))
     memcpy(columns_out->column[SWZ_ATTR_INTENSITY], bin + f.intensity, (size_t)(2 * f.count));
+  return SWZ_OK;
+}
+
+int swz_tileset_build_boxes(uint64_t num_nodes, const int8_t* node_level, const uint64_t* node_key, const double* node_box_min,
+                            const double* node_box_max, const double root_min[3], const double root_max[3], float spacing_at_root,
+                            const double global_offset[3], uint64_t max_out, swz_tileset_node* out, uint64_t* num_out) {
+  if (num_nodes && (!node_box_min || !node_box_max)) return SWZ_ERR_BAD_ARG;
+  SWZ_TRY(swz_tileset_build(num_nodes, node_level, node_key, root_min, root_max, spacing_at_root, global_offset, max_out, out, num_out));
+  if (!out) return SWZ_OK;
+  const uint64_t num = *num_out;
+  // the table's node of an entry: both are ordered by (level, key), the entries hold the table's nodes and their ancestors
+  std::map<std::pair<int, uint64_t>, uint64_t> row;
+  for (uint64_t j = 0; j < num_nodes; ++j) {
+    const int lv = node_level[j];
+    row[{lv, lv < 0 ? 0ull : ((node_key[j] >> level_shift(lv)) << level_shift(lv))}] = j;
+  }
+  const double inf = std::numeric_limits<double>::infinity();
+  std::vector<double> lo(3 * num, inf), hi(3 * num, -inf);
+  // one pass from the back: children lie behind their parent, so an entry is complete when it is reached
+  for (uint64_t i = num; i-- > 0;) {
+    swz_tileset_node& t = out[i];
+    if (t.has_content) {
+      const uint64_t j = row[{(int)t.level, t.key}];
+      for (int ax = 0; ax < 3; ++ax) {
+        if (!(node_box_min[3 * j + ax] <= node_box_max[3 * j + ax])) continue;  // a node without points
+        const double off = global_offset ? global_offset[ax] : 0.0;
+        lo[3 * i + ax] = std::min(lo[3 * i + ax], node_box_min[3 * j + ax] + off);
+        hi[3 * i + ax] = std::max(hi[3 * i + ax], node_box_max[3 * j + ax] + off);
+      }
+    }
+    if (lo[3 * i] <= hi[3 * i] && lo[3 * i + 1] <= hi[3 * i + 1] && lo[3 * i + 2] <= hi[3 * i + 2]) {
+      t.tight = 1;
+      for (int ax = 0; ax < 3; ++ax) {
+        t.bounds_min[ax] = lo[3 * i + ax];
+        t.bounds_max[ax] = hi[3 * i + ax];
+      }
+    }
+    if (t.parent >= 0) {
+      for (int ax = 0; ax < 3; ++ax) {
+        lo[3 * t.parent + ax] = std::min(lo[3 * t.parent + ax], lo[3 * i + ax]);
+        hi[3 * t.parent + ax] = std::max(hi[3 * t.parent + ax], hi[3 * i + ax]);
+      }
+    }
+  }
   return SWZ_OK;
 }
 

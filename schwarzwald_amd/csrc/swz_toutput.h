@@ -23,6 +23,10 @@ struct OutputPlan {
   std::vector<uint64_t> key, offset, count;              // offset: rows of the source's ids
   std::vector<uint64_t> body_at, body_size, file_size;  // per node, body_at relative to the image of the whole table
   std::vector<double> box_min, box_max, scale;           // LAS
+  // SWZ_OUT_TIGHT_BOUNDS: the boxes of the nodes' points (3 per node; +inf / -inf until the node's chunk is reduced, and for
+  // a node without points).  output_stream fills them chunk by chunk, before the chunk's files are written.
+  bool tight = false;
+  std::vector<double> tight_min, tight_max;
 };
 
 // where the rows of a plan's nodes come from: row i of a node = row ids[offset + i] of xyz and of the columns
@@ -64,7 +68,8 @@ int output_create_dirs(swz_ctx* c, const char* who, OutputPlan* p, const char* d
 void output_cuts(swz_ctx* c, const OutputPlan& p, uint64_t k0, uint64_t k1, uint64_t chunk_points, std::vector<uint64_t>* first,
                  uint64_t* image_max);
 // packs, copies and writes chunk after chunk; writer_threads 0: option SWZ_BIN_WRITER_THREADS.  A failure is c's error.
-int output_stream(swz_ctx* c, const OutputPlan& p, const std::vector<uint64_t>& first, const OutputSource& src, OutputImages& img,
+// A tight plan also gets its chunk's boxes (swz_node_boxes_device beside the pack call).
+int output_stream(swz_ctx* c, OutputPlan& p, const std::vector<uint64_t>& first, const OutputSource& src, OutputImages& img,
                   long writer_threads, OutputStreamStats* st);
 int output_metadata(swz_ctx* c, const char* who, const OutputPlan& p, const char* dir, const swz_output_params* params);
 

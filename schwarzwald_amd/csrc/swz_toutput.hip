@@ -10,11 +10,21 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
+#include <limits>
 #include <string>
 #include <vector>
 
 #include "swz_toutput.h"
 #include "swz_hostio.h"
+
+// `flags` took the four bytes of padding behind rgb_mapping: a caller built against the struct without it, which
+// value-initialises the struct, passes 0 there and gets what it got before
+static_assert(sizeof(swz_output_params) == 56 && offsetof(swz_output_params, format) == 0 &&
+                offsetof(swz_output_params, attribute_mask) == 4 && offsetof(swz_output_params, rgb_mapping) == 8 &&
+                offsetof(swz_output_params, flags) == 12 && offsetof(swz_output_params, global_offset) == 16 &&
+                offsetof(swz_output_params, chunk_points) == 40 && offsetof(swz_output_params, ept) == 48,
+              "swz_output_params: flags must sit in the former padding, every other member where it was");
 
 namespace swz {
 
@@ -61,6 +71,12 @@ static int write_node_file(const OutputPlan& p, uint64_t k, const unsigned char*
       break;
     default:
       path = stem + ".las";
+      if (p.tight) {  // the header's extent: the box of the stored records; offset, scale and records as without the flag
+        double lo[3], hi[3];
+        (void)swz_las_stored_box(&p.tight_min[3 * k], &p.tight_max[3 * k], &p.box_min[3 * k], p.scale[k], lo, hi);
+        st = swz_las_write_node_extent(nullptr, path.c_str(), p.count[k], body, p.mask, &p.box_min[3 * k], &p.box_max[3 * k], p.scale[k], lo, hi);
+        break;
+      }
       st = swz_las_write_node(nullptr, path.c_str(), p.count[k], body, p.mask, &p.box_min[3 * k], &p.box_max[3 * k], p.scale[k]);
       break;
   }
@@ -133,6 +149,13 @@ int output_plan(swz_ctx* c, const char* who, const swz_output_params* params, ui
   const uint64_t nn = p.count.size();
   if (params->format < SWZ_OUT_BIN || params->format > SWZ_OUT_ENTWINE_LAS) return c->fail(SWZ_ERR_BAD_ARG, w + "unknown format");
   if (params->attribute_mask & ~attr_mask) return c->fail(SWZ_ERR_BAD_ARG, w + "the mask names a column the batches did not carry");
+  const char* bad_flags = nullptr;
+  if (swz_output_flags_check(params->format, params->flags, &bad_flags) != SWZ_OK) return c->fail(SWZ_ERR_BAD_ARG, w + bad_flags);
+  p.tight = (params->flags & SWZ_OUT_TIGHT_BOUNDS) != 0;
+  if (p.tight) {
+    p.tight_min.assign(3 * nn, std::numeric_limits<double>::infinity());
+    p.tight_max.assign(3 * nn, -std::numeric_limits<double>::infinity());
+  }
   p.format = params->format;
   p.mask = params->attribute_mask;
   p.data_dir = dir;
@@ -198,7 +221,7 @@ void output_cuts(swz_ctx* c, const OutputPlan& p, uint64_t k0, uint64_t k1, uint
   for (uint64_t j = 0; j < num_chunks; ++j) *image_max = std::max(*image_max, image_at(p, (*first)[j + 1]) - image_at(p, (*first)[j]));
 }
 
-int output_stream(swz_ctx* c, const OutputPlan& p, const std::vector<uint64_t>& first, const OutputSource& src, OutputImages& ob,
+int output_stream(swz_ctx* c, OutputPlan& p, const std::vector<uint64_t>& first, const OutputSource& src, OutputImages& ob,
                   long writer_threads, OutputStreamStats* stats) {
   const uint64_t num_chunks = first.empty() ? 0 : first.size() - 1;
   int status = SWZ_OK;
@@ -244,6 +267,10 @@ int output_stream(swz_ctx* c, const OutputPlan& p, const std::vector<uint64_t>& 
                                    &p.box_min[3 * k0], &p.scale[k0], p.mask, ob.device[b], bytes);
           break;
       }
+      // (the boxes of chunk j's nodes: the writers of chunk j - 1 read other entries, and chunk j's start after this)
+      if (st == SWZ_OK && p.tight)
+        st = swz_node_boxes_device(c, src.ids + row0, nullptr, rows, src.xyz, k1 - k0, rel_offset.data(), &p.count[k0],
+                                   &p.tight_min[3 * k0], &p.tight_max[3 * k0]);
       stats->pack_ms += ms_since(t_pack);
       if (!ob.device[1]) join_writers();  // one image: its files are written before it is overwritten
       hipError_t e = hipSuccess;
@@ -291,14 +318,42 @@ int output_metadata(swz_ctx* c, const char* who, const OutputPlan& p, const char
     int st = swz_tileset_build(nn, p.level.data(), p.key.data(), p.bmin, p.bmax, p.spacing_at_root, p.rtc, 0, nullptr, &num);
     if (st == SWZ_OK) {
       tiles.resize(num);
-      st = swz_tileset_build(nn, p.level.data(), p.key.data(), p.bmin, p.bmax, p.spacing_at_root, p.rtc, num, tiles.data(), &num);
+      if (p.tight) {
+        // the box of what a .pnts file HOLDS: the floats the positions were narrowed to (narrowing is monotonic)
+        std::vector<double> lo(p.tight_min), hi(p.tight_max);
+        for (double& v : lo) v = (double)(float)v;
+        for (double& v : hi) v = (double)(float)v;
+        st = swz_tileset_build_boxes(nn, p.level.data(), p.key.data(), lo.data(), hi.data(), p.bmin, p.bmax, p.spacing_at_root, p.rtc,
+                                     num, tiles.data(), &num);
+      } else {
+        st = swz_tileset_build(nn, p.level.data(), p.key.data(), p.bmin, p.bmax, p.spacing_at_root, p.rtc, num, tiles.data(), &num);
+      }
     }
     if (st != SWZ_OK) return c->fail(st, std::string(who) + ": swz_tileset_build failed");
     SWZ_TRY(swz_tileset_write(c, tiles.data(), num, dir));
   }
   if (p.format == SWZ_OUT_ENTWINE_LAS) {
     SWZ_TRY(swz_ept_hierarchy_write(c, dir, nn, p.level.data(), p.key.data(), p.count.data()));
-    if (params->ept) SWZ_TRY(swz_ept_json_write(c, (std::string(dir) + "/ept.json").c_str(), params->ept));
+    if (params->ept) {
+      swz_ept_json ept = *params->ept;
+      if (p.tight) {  // boundsConforming: the union of the files' extents; without a point it stays the caller's
+        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (uint64_t k = 0; k < nn; ++k) {
+          if (p.count[k] == 0) continue;
+          double a[3], b[3];
+          (void)swz_las_stored_box(&p.tight_min[3 * k], &p.tight_max[3 * k], &p.box_min[3 * k], p.scale[k], a, b);
+          for (int ax = 0; ax < 3; ++ax) {
+            lo[ax] = std::min(lo[ax], a[ax]);
+            hi[ax] = std::max(hi[ax], b[ax]);
+          }
+        }
+        for (int ax = 0; ax < 3 && lo[0] <= hi[0]; ++ax) {
+          ept.conforming_min[ax] = lo[ax];
+          ept.conforming_max[ax] = hi[ax];
+        }
+      }
+      SWZ_TRY(swz_ept_json_write(c, (std::string(dir) + "/ept.json").c_str(), &ept));
+    }
   }
   return SWZ_OK;
 }
@@ -380,6 +435,56 @@ int swz_tiler_write_output(swz_tiler* t, const char* dir, const swz_output_param
     stats->wall_ms = ms_since(t_wall);
   }
   return status;
+}
+
+int swz_output_flags_check(int format, uint32_t flags, const char** what_out) {
+  const char* what = nullptr;
+  if (flags & ~(uint32_t)SWZ_OUT_TIGHT_BOUNDS) what = "unknown flag bit";
+  else if ((flags & SWZ_OUT_TIGHT_BOUNDS) && (format == SWZ_OUT_BIN || format == SWZ_OUT_BINZ))
+    what = "SWZ_OUT_TIGHT_BOUNDS: BIN and BINZ files hold no box";
+  if (what_out) *what_out = what;
+  return what ? SWZ_ERR_BAD_ARG : SWZ_OK;
+}
+
+int swz_tiler_node_boxes(swz_tiler* t, uint64_t max_nodes, double* box_min_out, double* box_max_out, uint64_t* num_nodes_out) {
+  if (!t) return SWZ_ERR_BAD_ARG;
+  swz_ctx* c = t->c;
+  const char* who = "swz_tiler_node_boxes";
+  if (!num_nodes_out) return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_node_boxes: NULL argument");
+  SWZ_HIP(c, hipSetDevice(c->device));
+  swz_tiler_info info{};
+  OutputPlan p;
+  SWZ_TRY(output_tiler_table(t, who, &p, &info));
+  const uint64_t nn = p.count.size(), ns = info.num_stored;
+  *num_nodes_out = nn;
+  if (nn > max_nodes || (nn && (!box_min_out || !box_max_out)))
+    return c->fail(SWZ_ERR_BAD_ARG, "swz_tiler_node_boxes: max_nodes too small, or a NULL buffer");
+  for (uint64_t i = 0; i < 3 * nn; ++i) {
+    box_min_out[i] = std::numeric_limits<double>::infinity();
+    box_max_out[i] = -std::numeric_limits<double>::infinity();
+  }
+  if (!ns) return SWZ_OK;
+  // the chunks of swz_tiler_write_output (no image: only the rows count), the ids exported once
+  p.body_at.assign(nn, 0);
+  p.body_size.assign(nn, 0);
+  std::vector<uint64_t> first;
+  uint64_t image_max = 0;
+  output_cuts(c, p, 0, nn, 0, &first, &image_max);
+  uint32_t* d_ids = nullptr;
+  OutputWorkspace ow{c};
+  SWZ_TRY(c->get("out_ids", (size_t)ns, &d_ids));
+  SWZ_TRY(swz_tiler_export_device(t, nullptr, d_ids, nullptr));
+  std::vector<uint64_t> rel_offset;
+  for (size_t j = 0; j + 1 < first.size(); ++j) {
+    const uint64_t k0 = first[j], k1 = first[j + 1];
+    if (k0 == k1) continue;
+    const uint64_t row0 = p.offset[k0], rows = p.offset[k1 - 1] + p.count[k1 - 1] - row0;
+    rel_offset.resize(k1 - k0);
+    for (uint64_t k = k0; k < k1; ++k) rel_offset[k - k0] = p.offset[k] - row0;
+    SWZ_TRY(swz_node_boxes_device(c, d_ids + row0, nullptr, rows, t->pool_xyz, k1 - k0, rel_offset.data(), &p.count[k0],
+                                  box_min_out + 3 * k0, box_max_out + 3 * k0));
+  }
+  return SWZ_OK;
 }
 
 int swz_merge_shard_node_tables(int num_shards, const uint64_t* num_nodes, const int8_t* const* node_level,

@@ -439,6 +439,26 @@ public:
     return stats;
   }
 
+  // The boxes of the nodes' POINTS (3 doubles per node, in the order of the node table; a node without points: +inf / -inf),
+  // reduced on the device from the pools (swz_tiler_node_boxes) -- what write_output() writes into the metadata when
+  // params.flags carries SWZ_OUT_TIGHT_BOUNDS, instead of the octree cubes.  Finalizes the tiler if finalize() has not.
+  struct NodeBoxes {
+    std::vector<double> min, max;
+  };
+  NodeBoxes node_boxes() {
+    if (!_tiler) throw std::runtime_error{"TilingAlgorithmGPU: node_boxes before the first batch"};
+    finalize_tiler();
+    swz_tiler_info info{};
+    _ctx.check(swz_tiler_get_info(_tiler, &info));
+    const uint64_t cap = info.num_nodes ? info.num_nodes : 1;
+    NodeBoxes boxes{std::vector<double>(3 * cap), std::vector<double>(3 * cap)};
+    uint64_t got = 0;
+    _ctx.check(swz_tiler_node_boxes(_tiler, cap, boxes.min.data(), boxes.max.data(), &got));
+    boxes.min.resize(3 * got);
+    boxes.max.resize(3 * got);
+    return boxes;
+  }
+
   // A data set of uncompressed LAS files, read by the library in one call (swz_tiler_add_las_files): headers scanned, files
   // cut into batches of params.batch_points points, raw records read by reader threads, copied and decoded on the device
   // straight into the tiler's pools, every batch tiled while the next is read -- what replaces MultiReaderPointSource and
@@ -734,6 +754,18 @@ public:
     swz_output_stats total{};
     group_check(swz_group_write_output(_group, dir.c_str(), &params, nullptr, &total), "swz_group_write_output");
     return total;
+  }
+  // the boxes of the nodes' points in the order of swz_group_node_table (swz_group_node_boxes); see TilingAlgorithmGPU::node_boxes
+  TilingAlgorithmGPU::NodeBoxes node_boxes() {
+    finalize_tiler();
+    uint64_t nn = 0;
+    group_check(swz_group_node_table(_group, 0, nullptr, nullptr, nullptr, nullptr, &nn), "swz_group_node_table");
+    const uint64_t cap = nn ? nn : 1;
+    TilingAlgorithmGPU::NodeBoxes boxes{std::vector<double>(3 * cap), std::vector<double>(3 * cap)};
+    group_check(swz_group_node_boxes(_group, cap, boxes.min.data(), boxes.max.data(), &nn), "swz_group_node_boxes");
+    boxes.min.resize(3 * nn);
+    boxes.max.resize(3 * nn);
+    return boxes;
   }
 
 private:

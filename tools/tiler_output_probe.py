@@ -6,7 +6,9 @@
 Both write into a fresh directory under --dir (default: the system's temporary directory), per format, `--reps` times after
 one warm-up; the medians and the spread (min .. max) are reported.  Each format runs in a child process of its own under
 `timeout`; the first one that fails ends the script.
-usage: tiler_output_probe.py [points] [--batches K] [--reps R] [--formats BIN,LAS,...] [--dir DIR] [--json FILE]"""
+--tight-bounds adds, for the formats that hold a box (3DTILES, LAS, ENTWINE_LAS), a third series: (s) with tight_bounds=True,
+and the node-box kernel alone over the whole data set (its time and the bytes per second it reaches).
+usage: tiler_output_probe.py [points] [--batches K] [--reps R] [--formats BIN,LAS,...] [--dir DIR] [--json FILE] [--tight-bounds]"""
 import json
 import os
 import shutil
@@ -22,7 +24,7 @@ NAMES = ("rgb", "intensity")
 FORMATS = ("BIN", "BINZ", "3DTILES", "LAS", "ENTWINE_LAS")
 
 
-def step(fmt, n, batches, reps, base):
+def step(fmt, n, batches, reps, base, tight=False):
     import numpy as np
     import torch
     import schwarzwald_amd as swz
@@ -52,6 +54,10 @@ def step(fmt, n, batches, reps, base):
 
     def streamed():
         s = t.write_output(fresh("streamed"), fmt, attrs=NAMES)
+        return s["wall_ms"], s
+
+    def streamed_tight():
+        s = t.write_output(fresh("streamed_tight"), fmt, attrs=NAMES, tight_bounds=True)
         return s["wall_ms"], s
 
     def whole():
@@ -123,6 +129,22 @@ def step(fmt, n, batches, reps, base):
 
     out["streamed"] = series(streamed)
     out["whole"] = series(whole)
+    if tight and fmt not in ("BIN", "BINZ"):
+        out["streamed_tight"] = series(streamed_tight)
+        # the kernel alone: the boxes of all nodes in one call, timed by the library's own events
+        d_ids = torch.empty(ns, dtype=torch.int32, device=dev)
+        t.export_device(None, d_ids.data_ptr(), None)
+        pool_xyz, _ = t.pools_device()
+        nodes = t.node_table()
+        ctx.node_boxes_device(d_ids.data_ptr(), None, ns, pool_xyz, nodes)  # warm-up
+        ctx.profile_enable(True)
+        ctx.profile_reset()
+        for _ in range(reps):
+            ctx.node_boxes_device(d_ids.data_ptr(), None, ns, pool_xyz, nodes)
+        k = ctx.profile_get()["node_boxes"]
+        ctx.profile_enable(False)
+        out["node_boxes_kernel_ms"] = k["total_ms"] / reps
+        out["node_boxes_GBps"] = k["algorithmic_bytes"] / reps / (k["total_ms"] / reps * 1e-3) / 1e9
     if fmt == "BIN":  # the kernels alone, on the same rows: bin_pack_kernel against the gather of the same columns
         d_ids = torch.empty(ns, dtype=torch.int32, device=dev)
         t.export_device(None, d_ids.data_ptr(), None)
@@ -156,7 +178,8 @@ def step(fmt, n, batches, reps, base):
 def main():
     args = sys.argv[1:]
     if args and args[0] == "--step":
-        return step(args[1], int(args[2]), int(args[3]), int(args[4]), args[5] if len(args) > 5 and args[5] else None)
+        return step(args[1], int(args[2]), int(args[3]), int(args[4]), args[5] if len(args) > 5 and args[5] else None,
+                    len(args) > 6 and args[6] == "tight")
 
     def option(name, default):
         return args[args.index(name) + 1] if name in args else default
@@ -168,7 +191,8 @@ def main():
     for fmt in formats:
         # one child per format, each under its own time limit; check=True: a failure ends the script here
         r = subprocess.run(["timeout", "-k", "10", limit, sys.executable, os.path.abspath(__file__), "--step", fmt, str(n), str(batches),
-                            str(reps), option("--dir", "")], check=True, stdout=subprocess.PIPE, text=True)
+                            str(reps), option("--dir", ""), "tight" if "--tight-bounds" in args else ""], check=True,
+                           stdout=subprocess.PIPE, text=True)
         line = [l for l in r.stdout.splitlines() if l.startswith("OUTPUT_PROBE ")][-1]
         print(line[len("OUTPUT_PROBE "):], flush=True)
         results.append(json.loads(line[len("OUTPUT_PROBE "):]))
