@@ -78,7 +78,7 @@ int swz_set_stream(swz_ctx* ctx, void* hip_stream);
  *   SWZ_SYNC_ENTRY (synchronise the device when swz_tile_device starts), SWZ_MD_STATS (count the key sweep's activations by
  *   kind), SWZ_POISON=<byte> and SWZ_POISON_ONLY=<part of a buffer name> (fill new workspace memory),
  *   SWZ_BIN_WRITER_THREADS (host threads that write node files), SWZ_INPUT_READER_THREADS (host threads that read the
- *   LAS files of swz_tiler_add_las_files).
+ *   LAS files of swz_tiler_add_las_files and the node files of swz_convert_dataset).
  * - Switches that only force a path, a schedule or a capacity -- the samplers' results stay what they are:
  *   sort: SWZ_SORT_ONESWEEP=0, SWZ_SORT_HYBRID_MIN_N, SWZ_SORT_HYBRID_TOP, SWZ_SORT_FIX_SHORT, SWZ_SORT_FIX_LONG,
  *   SWZ_SORT_WIDE_MIN_N (keys from which a scatter pass takes its 8192-key tile);
@@ -937,6 +937,108 @@ typedef struct {
 } swz_input_stats;
 int swz_tiler_add_las_files(swz_tiler* tiler, const char* const* paths, uint64_t num_files, const swz_input_params* params,
                             swz_input_stats* stats);
+/* ---- a written data set converted to another format in ONE call: the reference's --converter mode
+ * (core/process/ConverterProcess.cpp).  Tile once into the lossless format (BIN keeps the doubles and all twelve columns),
+ * derive the delivery formats from those files, optionally down to a maximum depth, never tile again.
+ *   properties.json (host; ctx only carries the error text and may be NULL): what write_properties_json writes
+ *     (TilerProcess.cpp:76-151) and parse_properties_json reads (ConverterProcess.cpp:55-99), same names and nesting:
+ *     {"source_properties":{"bounds":{"min":[x,y,z],"max":[x,y,z]},"root_spacing":s,"processed_points":n},
+ *      "performance_stats":{"prepare_duration":0,"indexing_duration":0}}.  Numbers are the shortest text that parses back to
+ *     the same double; root_spacing is the float widened to double, as rapidjson writes it.  swz_properties_json_read is the
+ *     inverse (any output may be NULL).  swz_tiler_write_properties fills the file from the tiler's root box, spacing and
+ *     point count.  swz_tiler_write_output writes no such file: the file comes from a call of its own.
+ *   swz_dataset_scan (host, no GPU): what find_all_octree_node_files (:296-323) and the two metadata parsers find in dir.
+ *     The format is that of the node files: dir/r*.bin | r*.binz | r*.las | r*.pnts, or dir/ept-data/D-X-Y-Z.las; two kinds
+ *     together or none is SWZ_ERR_BAD_ARG.  A name becomes (level, Morton index), level -1 for "r"; a file with a node
+ *     extension whose stem is no node name is refused by name (OURS: the reference prints a message and skips it).
+ *     max_depth < 0: every node; else the nodes of depth (level + 1) <= max_depth, 0 is the root alone.  The table is
+ *     ordered by (level, Morton index) like swz_tiler_node_table; the counts are the file headers' (swz_bin_read_header,
+ *     swz_las_read_header; of a BINZ file the first 12 inflated bytes; of a .pnts file swz_pnts_read_header).  The attribute
+ *     mask -- the BIN bit mask, or what the LAS point format carries (everything but normals; RGB with formats 2 and 3, GPS
+ *     time with 1 and 3) -- must be the same in every file, else the first file that differs is named.  root_source says
+ *     where root_min / root_max / spacing_at_root come from: properties.json, else ept.json (bounds, x extent / span), else
+ *     SWZ_DATASET_ROOT_ABSENT.  The table outputs may be NULL (then only *num_nodes_out and the info); max_nodes too small
+ *     is SWZ_ERR_BAD_ARG.  A .laz file and a cloud.js without node files are refused by name: neither is read.
+ *   swz_bin_unpack_segments_device: the inverse of swz_bin_pack_device, shaped like swz_las_decode_segments_device.  Segment
+ *     s is one uncompressed BIN file image -- 12 bytes of mask and count, count x 24 bytes of positions, the arrays of the
+ *     segment's mask in file order (scan angle rank before scan direction flag) -- that starts at byte_offset of d_raw AT
+ *     ANY ALIGNMENT and goes to the output rows [first_row, first_row + count).  Row first_row + i of d_xyz_out and of every
+ *     column of d_out whose bit is in the segment's mask gets the file's value, a column of d_out outside the segment's mask
+ *     zeros for the segment's rows; columns absent from d_out are skipped, d_xyz_out may be NULL.  One kernel: a workgroup
+ *     takes swz_bin_unpack_tile() consecutive rows whatever segments they belong to, reads the segment table once into LDS
+ *     and searches it there; array by array the aligned words that cover the tile's part of it are loaded into LDS -- whole
+ *     words only where they lie inside [d_raw, d_raw + raw_bytes), single bytes at the two ends -- and every lane takes its
+ *     row's value from there as integer words: nothing is computed, NaN payloads and -0.0 survive.  No byte of an output row
+ *     depends on what the buffers held.  Output columns are aligned to their element (8 bytes positions and GPS times, 4
+ *     normals, 2 intensities and point source ids).  SWZ_ERR_BAD_ARG before anything is launched for: rows that do not
+ *     ascend contiguously from 0, a segment whose image passes raw_bytes, a mask bit that does not exist, more than 2^32 -
+ *     65536 rows.  Zero segments or zero rows launches nothing.  The kernel trusts the table: whoever reads the files checks
+ *     their 12-byte headers against it (swz_convert_dataset does).
+ *   swz_convert_dataset: scans src_dir, refuses what can be refused before anything is written -- what
+ *     swz_tiler_write_output refuses of `out`, a 3DTILES source (its positions are floats and it carries no attribute beyond
+ *     RGB and intensity), dst_dir equal to src_dir, a mask outside the source's, no root box and spacing from the metadata
+ *     files or the parameters, reserved words that are not 0 --, plans the target layout for the (depth-limited) table from
+ *     the source's root box and spacing, and streams chunks of whole consecutive nodes of at most out.chunk_points points
+ *     (the cuts of swz_output_chunks): reader threads (SWZ_INPUT_READER_THREADS) read the chunk's files back to back, each
+ *     at a multiple of 8, into one of two page-locked buffers (BINZ files are inflated into it, LAS files contribute their
+ *     record ranges, BIN headers are checked against the scanned table), a copy stream moves the buffer to the device, the
+ *     unpack kernel (LAS sources: the segment kernel of swz_las_decode_segments_device, one layout per file, so the result
+ *     is swz_las_read_node's) fills chunk-local positions and columns, and the target format's pack kernel, the copy back
+ *     and the writer threads (SWZ_BIN_WRITER_THREADS) produce the files exactly as swz_tiler_write_output does, tight
+ *     bounds included.  Chunk k + 1 is read while chunk k is packed and written.  Device and host hold a bounded number of
+ *     chunk images whatever the size of the data set; row numbers are chunk-local, so a data set may hold more than 2^32
+ *     points: only a chunk, and therefore a node, is bound by 2^32 - 65536.  At the end: the format's metadata for the
+ *     table as swz_tiler_write_output writes it, and properties.json into dst_dir for every target (processed_points: the
+ *     converted table's total).  out.attribute_mask: a subset of the source's, ~0u = all it has.  root_given != 0:
+ *     root_min / root_max / spacing_at_root override the metadata files.  A file that changed since the scan or cannot be
+ *     read stops the stream after the running chunk and is reported by name.  The call never writes to or deletes from
+ *     src_dir.  Not offered (the reference's --delete-source, --source-projection inside the converter, LAZ, .pnts or
+ *     cloud.js sources, a multi-GPU driver): project while tiling, and delete what you no longer need yourself. */
+enum { SWZ_DATASET_ROOT_ABSENT = 0, SWZ_DATASET_ROOT_PROPERTIES = 1, SWZ_DATASET_ROOT_EPT = 2 };
+typedef struct {
+  int32_t format;          /* SWZ_OUT_* */
+  uint32_t attribute_mask; /* bits SWZ_ATTR_*, the same in every file */
+  uint32_t root_source;    /* SWZ_DATASET_ROOT_* */
+  float spacing_at_root;
+  double root_min[3], root_max[3];
+  uint64_t num_nodes, points; /* of the (depth-limited) table */
+  int32_t max_level;          /* deepest level of the table; -1: the root alone, or no node */
+  uint32_t reserved;
+} swz_dataset_info;
+typedef struct {
+  uint64_t first_row;   /* output row of the segment's first point */
+  uint64_t count;       /* points */
+  uint64_t byte_offset; /* of the file image in d_raw */
+  uint32_t mask;        /* bits SWZ_ATTR_*: the arrays the image holds */
+  uint32_t reserved;
+} swz_bin_segment;
+typedef struct {
+  swz_output_params out;
+  int32_t max_depth;   /* < 0: every node */
+  uint32_t root_given; /* != 0: root_min, root_max and spacing_at_root below override the metadata files */
+  double root_min[3], root_max[3];
+  float spacing_at_root;
+  uint32_t reserved[3]; /* 0 */
+} swz_convert_params;
+typedef struct {
+  uint64_t nodes, points, bytes_read, bytes_written, chunks;
+  double read_ms, unpack_ms, pack_ms, copy_ms, write_ms, wall_ms;
+} swz_convert_stats;
+int swz_properties_json_write(swz_ctx* ctx, const char* dir, const double root_min[3], const double root_max[3],
+                              float spacing_at_root, uint64_t processed_points);
+int swz_properties_json_read(swz_ctx* ctx, const char* dir, double root_min_out[3], double root_max_out[3], float* spacing_out,
+                             uint64_t* points_out);
+int swz_tiler_write_properties(swz_tiler* tiler, const char* dir);
+int swz_dataset_scan(swz_ctx* ctx, const char* dir, int32_t max_depth, swz_dataset_info* info_out, uint64_t max_nodes,
+                     int8_t* node_level_out, uint64_t* node_key_out, uint64_t* node_count_out, uint64_t* num_nodes_out);
+/* swz_dataset_scan without a context: the text of a refusal goes into why_out (why_bytes bytes, may be NULL) */
+int swz_dataset_scan_why(const char* dir, int32_t max_depth, swz_dataset_info* info_out, uint64_t max_nodes, int8_t* node_level_out,
+                         uint64_t* node_key_out, uint64_t* node_count_out, uint64_t* num_nodes_out, char* why_out, uint64_t why_bytes);
+uint32_t swz_bin_unpack_tile(void); /* rows one workgroup takes; tests place their edges by it */
+int swz_bin_unpack_segments_device(swz_ctx* ctx, const uint8_t* d_raw, uint64_t raw_bytes, const swz_bin_segment* segments /* host */,
+                                   uint64_t num_segments, double* d_xyz_out, const swz_attribute_columns* d_out);
+int swz_convert_dataset(swz_ctx* ctx, const char* src_dir, const char* dst_dir, const swz_convert_params* params,
+                        swz_convert_stats* stats);
 /* ---- a source projection (the reference's --source-projection: Proj4Transform, core/util/Transformation.cpp:74-211, source
  * -> "+proj=geocent +datum=WGS84").  PROJ is not linked: the library maps the projection families LAS data comes in itself,
  * in double, and refuses every other definition by name.

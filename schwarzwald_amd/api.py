@@ -662,6 +662,120 @@ def ept_json_write(path, bounds, conforming_bounds, points, attrs=(), span=0.0, 
 
 
 LAS_FILE_OK, LAS_FILE_UNREADABLE, LAS_FILE_BAD_HEADER, LAS_FILE_COMPRESSED = 0, 1, 2, 3
+# ---- a written data set found again and converted (swz_dataset_scan, swz_convert_dataset)
+DATASET_ROOT_ABSENT, DATASET_ROOT_PROPERTIES, DATASET_ROOT_EPT = 0, 1, 2
+
+
+class _DatasetInfo(C.Structure):
+    _fields_ = [("format", C.c_int32), ("attribute_mask", C.c_uint32), ("root_source", C.c_uint32), ("spacing_at_root", C.c_float),
+                ("root_min", C.c_double * 3), ("root_max", C.c_double * 3), ("num_nodes", C.c_uint64), ("points", C.c_uint64),
+                ("max_level", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class _BinSegment(C.Structure):
+    _fields_ = [("first_row", C.c_uint64), ("count", C.c_uint64), ("byte_offset", C.c_uint64), ("mask", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class _ConvertParams(C.Structure):
+    _fields_ = [("out", _OutputParams), ("max_depth", C.c_int32), ("root_given", C.c_uint32), ("root_min", C.c_double * 3),
+                ("root_max", C.c_double * 3), ("spacing_at_root", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+class _ConvertStats(C.Structure):
+    _fields_ = [("nodes", C.c_uint64), ("points", C.c_uint64), ("bytes_read", C.c_uint64), ("bytes_written", C.c_uint64),
+                ("chunks", C.c_uint64), ("read_ms", C.c_double), ("unpack_ms", C.c_double), ("pack_ms", C.c_double),
+                ("copy_ms", C.c_double), ("write_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+def properties_json_write(directory, root_min, root_max, spacing_at_root, processed_points):
+    """swz_properties_json_write: directory/properties.json as the reference's tiler writes it (host only)."""
+    st = load_library().swz_properties_json_write(None, os.fsencode(directory), _vec3(root_min), _vec3(root_max), float(spacing_at_root),
+                                                  int(processed_points))
+    if st != 0:
+        raise SwzError(st, "swz_properties_json_write(%s) failed" % directory)
+
+
+def properties_json_read(directory):
+    """swz_properties_json_read: dict(root_min, root_max, spacing_at_root, processed_points) of directory/properties.json."""
+    mn, mx = (C.c_double * 3)(), (C.c_double * 3)()
+    spacing, points = C.c_float(), C.c_uint64()
+    st = load_library().swz_properties_json_read(None, os.fsencode(directory), mn, mx, C.byref(spacing), C.byref(points))
+    if st != 0:
+        raise SwzError(st, "swz_properties_json_read(%s) failed" % directory)
+    return dict(root_min=np.array(list(mn)), root_max=np.array(list(mx)), spacing_at_root=float(spacing.value),
+                processed_points=int(points.value))
+
+
+def dataset_scan(directory, max_depth=None):
+    """swz_dataset_scan (host, no GPU): the written data set in directory as a dict -- format (a key of OUTPUT_FORMATS),
+    attrs / attribute_mask, nodes (level, key, count in the order of Tiler.node_table), points, max_level, root_source
+    (DATASET_ROOT_*), and root_min / root_max / spacing_at_root unless the source is DATASET_ROOT_ABSENT.  max_depth: only
+    the nodes of depth (level + 1) <= max_depth; None: all.  A refusal raises SwzError with the library's text."""
+    L = load_library()
+    depth = -1 if max_depth is None else int(max_depth)
+    info, num = _DatasetInfo(), C.c_uint64()
+    why = C.create_string_buffer(4096)
+    st = L.swz_dataset_scan_why(os.fsencode(directory), depth, C.byref(info), 0, None, None, None, C.byref(num), why, len(why))
+    if st != 0:
+        raise SwzError(st, why.value.decode(errors="replace"))
+    cap = max(int(num.value), 1)
+    nl, nk, nc = np.empty(cap, dtype=np.int8), np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint64)
+    st = L.swz_dataset_scan_why(os.fsencode(directory), depth, C.byref(info), cap, nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p),
+                                nc.ctypes.data_as(_u64p), C.byref(num), why, len(why))
+    if st != 0:
+        raise SwzError(st, why.value.decode(errors="replace"))
+    m = int(num.value)
+    names = {v: k for k, v in OUTPUT_FORMATS.items()}
+    out = dict(format=names[int(info.format)], attribute_mask=int(info.attribute_mask), attrs=attribute_names(info.attribute_mask),
+               nodes=dict(level=nl[:m].copy(), key=nk[:m].copy(), count=nc[:m].copy()), points=int(info.points),
+               max_level=int(info.max_level), root_source=int(info.root_source))
+    if info.root_source != DATASET_ROOT_ABSENT:
+        out.update(root_min=np.array(list(info.root_min)), root_max=np.array(list(info.root_max)),
+                   spacing_at_root=float(info.spacing_at_root))
+    return out
+
+
+def bin_unpack_tile():
+    """Output rows one workgroup of bin_unpack_segments_device takes (tests place their edges by it)."""
+    return int(load_library().swz_bin_unpack_tile())
+
+
+def _ept_struct(ept):
+    srs = ept.get("srs") or {}
+    return _EptJson(_vec3(ept["bounds"][0]), _vec3(ept["bounds"][1]), _vec3(ept["conforming_bounds"][0]),
+                    _vec3(ept["conforming_bounds"][1]), int(ept["points"]), _las_mask(ept.get("attrs", ())), 0,
+                    float(ept.get("span", 0.0)), srs.get("authority", "").encode(), srs.get("horizontal", "").encode(),
+                    srs.get("wkt", "").encode(), ept.get("version", "").encode())
+
+
+def convert_dataset(ctx, src, dst, format, attrs=None, max_depth=None, rgb_from=RGB_FROM_COLOR, global_offset=None, chunk_points=0,
+                    ept=None, tight_bounds=False, root_box=None, spacing=None, flags=0):
+    """swz_convert_dataset: the written data set in src (BIN, BINZ, LAS or ENTWINE_LAS node files) converted into dst in
+    another format, node files unpacked and packed on the device.  format, rgb_from, global_offset, chunk_points, ept,
+    tight_bounds, flags: as in Tiler.write_output; attrs: the columns to write, a subset of the source's (None: all it has);
+    max_depth: only the nodes of depth <= max_depth; root_box ((min, max)) and spacing: the root box and spacing_at_root,
+    overriding properties.json / ept.json of src -- required when src has neither.  Returns the stats as a dict (nodes,
+    points, bytes_read, bytes_written, chunks, read_ms, unpack_ms, pack_ms, copy_ms, write_ms, wall_ms)."""
+    fmt = OUTPUT_FORMATS[format] if isinstance(format, str) else int(format)
+    out = _OutputParams(fmt, 0xFFFFFFFF if attrs is None else _las_mask(attrs), int(rgb_from),
+                        int(flags) | (OUT_TIGHT_BOUNDS if tight_bounds else 0),
+                        _vec3(global_offset if global_offset is not None else (0, 0, 0)), int(chunk_points), None)
+    keep = None
+    if ept is not None:
+        keep = _ept_struct(ept)
+        out.ept = C.pointer(keep)
+    if (root_box is None) != (spacing is None):
+        raise ValueError("convert_dataset: root_box and spacing go together")
+    given = root_box is not None
+    p = _ConvertParams(out, -1 if max_depth is None else int(max_depth), 1 if given else 0,
+                       _vec3(root_box[0] if given else (0, 0, 0)), _vec3(root_box[1] if given else (0, 0, 0)),
+                       float(spacing) if given else 0.0, (C.c_uint32 * 3)(0, 0, 0))
+    stats = _ConvertStats()
+    ctx._check(ctx._lib.swz_convert_dataset(ctx._ctx, os.fsencode(src), os.fsencode(dst), C.byref(p), C.byref(stats)))
+    return {k: getattr(stats, k) for k, _ in _ConvertStats._fields_}
+
+
 LAS_SCAN_SKIP_UNREADABLE = 1
 
 
@@ -930,6 +1044,16 @@ def load_library():
     L.swz_bin_pack_tile.restype = C.c_uint32
     L.swz_bin_pack_device.argtypes = [vp, vp, vp, C.c_uint64, vp, cols, C.c_uint64, _u64p, _u64p, C.c_uint32, vp, C.c_uint64]
     L.swz_bin_persist_nodes_image.argtypes = [vp, C.c_char_p, C.c_uint64, _i8p, _u64p, _u64p, vp, C.c_uint64, C.c_uint32, C.c_int]
+    L.swz_properties_json_write.argtypes = [vp, C.c_char_p, _dp, _dp, C.c_float, C.c_uint64]
+    L.swz_properties_json_read.argtypes = [vp, C.c_char_p, _dp, _dp, C.POINTER(C.c_float), _u64p]
+    L.swz_tiler_write_properties.argtypes = [vp, C.c_char_p]
+    L.swz_dataset_scan.argtypes = [vp, C.c_char_p, C.c_int32, C.POINTER(_DatasetInfo), C.c_uint64, _i8p, _u64p, _u64p, _u64p]
+    L.swz_dataset_scan_why.argtypes = [C.c_char_p, C.c_int32, C.POINTER(_DatasetInfo), C.c_uint64, _i8p, _u64p, _u64p, _u64p, C.c_char_p,
+                                       C.c_uint64]
+    L.swz_bin_unpack_tile.argtypes = []
+    L.swz_bin_unpack_tile.restype = C.c_uint32
+    L.swz_bin_unpack_segments_device.argtypes = [vp, vp, C.c_uint64, C.POINTER(_BinSegment), C.c_uint64, vp, cols]
+    L.swz_convert_dataset.argtypes = [vp, C.c_char_p, C.c_char_p, C.POINTER(_ConvertParams), C.POINTER(_ConvertStats)]
     L.swz_tiler_write_output.argtypes = [vp, C.c_char_p, C.POINTER(_OutputParams), C.POINTER(_OutputStats)]
     L.swz_output_chunks.argtypes = [C.c_uint64, _u64p, C.c_uint64, C.c_uint64, _u64p, _u64p]
     L.swz_merge_shard_node_tables.argtypes = [C.c_int, _u64p, C.POINTER(_i8p), C.POINTER(_u64p), C.POINTER(_u64p), C.c_uint64, _i8p,
@@ -1343,6 +1467,22 @@ class Context:
         self._check(self._lib.swz_las_decode_segments_device(self._ctx, C.c_void_p(d_raw), int(raw_bytes), len(segments), segs, center,
                                                              C.c_void_p(d_xyz), C.byref(cols)))
 
+    def bin_unpack_segments_device(self, d_raw, raw_bytes, segments, d_xyz, d_attrs=None):
+        """swz_bin_unpack_segments_device: uncompressed BIN file images (device memory, any alignment) -> positions and
+        attribute columns in one launch.  segments: dicts of first_row, count, byte_offset and attrs (names or a mask: the
+        arrays the image holds).  d_xyz may be None; d_attrs: dict name -> device pointer of the columns to fill (zeros where
+        a segment lacks the array)."""
+        segs = (_BinSegment * max(len(segments), 1))()
+        for i, g in enumerate(segments):
+            segs[i] = _BinSegment(int(g["first_row"]), int(g["count"]), int(g["byte_offset"]), _las_mask(g.get("attrs", ())), 0)
+        cols = device_columns(d_attrs)
+        self._check(self._lib.swz_bin_unpack_segments_device(self._ctx, C.c_void_p(d_raw), int(raw_bytes), segs, len(segments),
+                                                             C.c_void_p(d_xyz), C.byref(cols)))
+
+    def convert_dataset(self, src, dst, format, **kwargs):
+        """convert_dataset(self, src, dst, format, ...)"""
+        return convert_dataset(self, src, dst, format, **kwargs)
+
     def bin_persist_nodes(self, directory, nodes, xyz, attrs=None, compressed=False):
         """bin_persist_nodes with this context's writer threads and error text."""
         bin_persist_nodes(directory, nodes, xyz, attrs, compressed, ctx=self._ctx)
@@ -1731,6 +1871,11 @@ class Tiler:
         stats = _OutputStats()
         self._ctx._check(self._lib.swz_tiler_write_output(self._t, os.fsencode(directory), C.byref(p), C.byref(stats)))
         return {k: getattr(stats, k) for k, _ in _OutputStats._fields_}
+
+    def write_properties(self, directory):
+        """swz_tiler_write_properties: directory/properties.json (root box, spacing_at_root, points added) -- what
+        convert_dataset and the reference's converter find the root of a BIN, BINZ, LAS or 3DTILES data set with."""
+        self._ctx._check(self._lib.swz_tiler_write_properties(self._t, os.fsencode(directory)))
 
     def set_source_srs(self, srs):
         """swz_tiler_set_source_srs: add_las_files projects its input to ECEF (a string or an Srs; None clears).  Refused once

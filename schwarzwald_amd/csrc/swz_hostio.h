@@ -3,11 +3,14 @@
 // of writer threads and the attribute arrays of a BIN node file.
 #pragma once
 
+#include <fcntl.h>
+#include <unistd.h>
 #include <zlib.h>
 
 #include <atomic>
 #include <chrono>
 #include <charconv>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <algorithm>
@@ -44,6 +47,27 @@ inline int read_whole_file(swz_ctx* c, const char* path, std::vector<unsigned ch
   fclose(f);
   return SWZ_OK;
 }
+
+// `bytes` bytes at `offset` of the file, all of them or an error
+inline bool pread_all(int fd, void* dst, uint64_t bytes, uint64_t offset) {
+  unsigned char* out = static_cast<unsigned char*>(dst);
+  while (bytes) {
+    const ssize_t got = pread(fd, out, (size_t)std::min<uint64_t>(bytes, 1ull << 30), (off_t)offset);
+    if (got < 0 && errno == EINTR) continue;
+    if (got <= 0) return false;
+    out += got;
+    offset += (uint64_t)got;
+    bytes -= (uint64_t)got;
+  }
+  return true;
+}
+
+struct Fd {
+  int fd = -1;
+  ~Fd() {
+    if (fd >= 0) (void)close(fd);
+  }
+};
 
 // A file out of pieces that go out as they lie in memory, one behind the other.  No context: the files of a table are
 // written by several threads (run_tickets).

@@ -225,27 +225,6 @@ static double get_f64(const unsigned char* p) {
   return v;
 }
 
-// `bytes` bytes at `offset` of the file, all of them or an error
-static bool pread_all(int fd, void* dst, uint64_t bytes, uint64_t offset) {
-  unsigned char* out = static_cast<unsigned char*>(dst);
-  while (bytes) {
-    const ssize_t got = pread(fd, out, (size_t)std::min<uint64_t>(bytes, 1ull << 30), (off_t)offset);
-    if (got < 0 && errno == EINTR) continue;
-    if (got <= 0) return false;
-    out += got;
-    offset += (uint64_t)got;
-    bytes -= (uint64_t)got;
-  }
-  return true;
-}
-
-struct Fd {
-  int fd = -1;
-  ~Fd() {
-    if (fd >= 0) (void)close(fd);
-  }
-};
-
 // the public header block of one file (LAS 1.0 - 1.4); SWZ_LAS_FILE_* and, unless OK, the reason
 static int scan_one(const char* path, swz_las_file_info* info, std::string* why) {
   *info = swz_las_file_info{};

@@ -3,6 +3,7 @@
 // OutputImages, output_stream), write the metadata from a table (output_metadata).  swz_group_write_output
 // (swz_goutput.hip) runs the middle part per shard and the other two once.
 #pragma once
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -67,10 +68,13 @@ int output_create_dirs(swz_ctx* c, const char* who, OutputPlan* p, const char* d
 // the chunks of the nodes [k0, k1) of a plan: first->at(j) .. first->at(j + 1) are chunk j's nodes; the largest chunk image
 void output_cuts(swz_ctx* c, const OutputPlan& p, uint64_t k0, uint64_t k1, uint64_t chunk_points, std::vector<uint64_t>* first,
                  uint64_t* image_max);
+// A source that exists chunk by chunk (swz_convert_dataset): called before chunk j is packed, while the files of chunk j - 1
+// are being written; it may change *src.  A failure (c's error) stops the stream after the running chunk.
+using OutputChunkFeed = std::function<int(uint64_t j, OutputSource* src)>;
 // packs, copies and writes chunk after chunk; writer_threads 0: option SWZ_BIN_WRITER_THREADS.  A failure is c's error.
-// A tight plan also gets its chunk's boxes (swz_node_boxes_device beside the pack call).
+// A tight plan also gets its chunk's boxes (swz_node_boxes_device beside the pack call).  feed (may be NULL): see above.
 int output_stream(swz_ctx* c, OutputPlan& p, const std::vector<uint64_t>& first, const OutputSource& src, OutputImages& img,
-                  long writer_threads, OutputStreamStats* st);
+                  long writer_threads, OutputStreamStats* st, const OutputChunkFeed* feed = nullptr);
 int output_metadata(swz_ctx* c, const char* who, const OutputPlan& p, const char* dir, const swz_output_params* params);
 
 // the node table of a tiler into a plan; refuses a poisoned tiler and one with a batch staged or open

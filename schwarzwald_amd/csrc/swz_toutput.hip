@@ -221,8 +221,9 @@ void output_cuts(swz_ctx* c, const OutputPlan& p, uint64_t k0, uint64_t k1, uint
   for (uint64_t j = 0; j < num_chunks; ++j) *image_max = std::max(*image_max, image_at(p, (*first)[j + 1]) - image_at(p, (*first)[j]));
 }
 
-int output_stream(swz_ctx* c, OutputPlan& p, const std::vector<uint64_t>& first, const OutputSource& src, OutputImages& ob,
-                  long writer_threads, OutputStreamStats* stats) {
+int output_stream(swz_ctx* c, OutputPlan& p, const std::vector<uint64_t>& first, const OutputSource& source, OutputImages& ob,
+                  long writer_threads, OutputStreamStats* stats, const OutputChunkFeed* feed) {
+  OutputSource src = source;
   const uint64_t num_chunks = first.empty() ? 0 : first.size() - 1;
   int status = SWZ_OK;
   std::string why;
@@ -243,6 +244,14 @@ int output_stream(swz_ctx* c, OutputPlan& p, const std::vector<uint64_t>& first,
     const int b = ob.device[1] ? (int)(j & 1) : 0;
     const uint64_t k0 = first[j], k1 = first[j + 1];
     const uint64_t at0 = image_at(p, k0), bytes = image_at(p, k1) - at0;
+    if (feed && *feed) {
+      const int st = (*feed)(j, &src);
+      if (st != SWZ_OK) {
+        status = st;
+        why = c->err;
+        break;
+      }
+    }
     const uint64_t row0 = p.offset[k0];
     const uint64_t rows = p.offset[k1 - 1] + p.count[k1 - 1] - row0;
     // buffer b, device and host: chunk j - 2 has been copied out of the one and written out of the other (with one buffer

@@ -16,7 +16,7 @@
 //   sample_points                    Sampling.h:799-821       sample_points (returns the partition point)
 //   TilerMetaParameters              process/Tiler.h:64-75    TilerMetaParameters
 //   PointsPersistence::persist_points io/PointsPersistence.h  PointsSink::persist_points
-//   TilingAlgorithmBase              TilingAlgorithms.h:70    TilingAlgorithmGPU::tile_batch / add_las_files / finalize / write_output
+//   TilingAlgorithmBase              TilingAlgorithms.h:70    TilingAlgorithmGPU::tile_batch / add_las_files / finalize / write_output / write_properties
 //   get_octant_bounds                OctreeAlgorithms.cpp:3   get_octant_bounds
 //
 // Errors: every failing ABI call becomes std::runtime_error carrying swz_last_error(), the way the
@@ -150,6 +150,17 @@ public:
 private:
   swz_ctx* _ctx = nullptr;
 };
+
+// ConverterProcess::run (core/process/ConverterProcess.cpp) in one call: the written data set in src_dir (BIN, BINZ, LAS or
+// ENTWINE_LAS node files; root box and spacing from its properties.json or ept.json unless params gives them) converted into
+// dst_dir in the format of params.out, node files unpacked and packed on the device (swz_convert_dataset).  A refusal -- a
+// .pnts source, dst_dir equal to src_dir, a mask outside the source's, no root box -- throws with the library's text.
+inline swz_convert_stats convert_dataset(Context& ctx, const std::string& src_dir, const std::string& dst_dir,
+                                         const swz_convert_params& params) {
+  swz_convert_stats stats{};
+  ctx.check(swz_convert_dataset(ctx.get(), src_dir.c_str(), dst_dir.c_str(), &params, &stats));
+  return stats;
+}
 
 // index_points<21> -- OctreeAlgorithms.h:181-197.  positions: n x 3 doubles (PointBuffer::positions().data());
 // outliers are clamped in place, like index_point does.
@@ -437,6 +448,13 @@ public:
     swz_output_stats stats{};
     _ctx.check(swz_tiler_write_output(_tiler, dir.c_str(), &params, &stats));
     return stats;
+  }
+
+  // dir/properties.json (write_properties_json, TilerProcess.cpp:76-151): the root box, spacing_at_root and the points added --
+  // what convert_dataset, and the reference's converter, find the root of a BIN, BINZ, LAS or 3DTILES data set with.
+  void write_properties(const std::string& dir) {
+    if (!_tiler) throw std::runtime_error{"TilingAlgorithmGPU: write_properties before the first batch"};
+    _ctx.check(swz_tiler_write_properties(_tiler, dir.c_str()));
   }
 
   // The boxes of the nodes' POINTS (3 doubles per node, in the order of the node table; a node without points: +inf / -inf),
