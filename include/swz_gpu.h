@@ -446,6 +446,36 @@ int swz_pnts_read_node(swz_ctx* ctx, const char* path, double* xyz_out, const sw
 /* one value of the grey table (0 for SWZ_PNTS_RGB_FROM_COLOR) */
 uint8_t swz_pnts_rgb_from_intensity(int rgb_mapping, uint16_t intensity);
 int swz_tileset_write(swz_ctx* ctx, const swz_tileset_node* nodes, uint64_t num, const char* dir);
+/* ---- 3D Tiles in a world frame: node files relative to their own origin, tile volumes as oriented boxes (what
+ * swz_convert_dataset_world writes; struct swz_srs: see "a source projection" below).
+ *   swz_pnts_pack_origin_device: swz_pnts_pack_device with an origin per node (node_origin: host, 3 doubles per node of the
+ *     table): a position is stored as (float)(pos[c] - origin[c]), the subtraction in double, then the plain cast -- what
+ *     setOriginToSmallestPoint + PNTSWriter do (Transformation.cpp:213-227).  A second instantiation of the pack kernel that
+ *     keeps the origins of its window's nodes beside their bases; layout, RGB mapping and padding are swz_pnts_pack_device's,
+ *     whose own instantiation and output are untouched.  Refuses what swz_pnts_pack_device refuses, and an origin that is
+ *     not finite for a node that holds points (for an empty node it is not looked at).
+ *   swz_pnts_persist_nodes_rtc: swz_pnts_persist_nodes with an RTC_CENTER per node (3 doubles per node; must be finite for
+ *     a node that holds points).
+ *   swz_tileset_oriented_boxes (host): boundingBoxFromAABB(aabb, transform) (core/pointcloud/Tileset.cpp:52-92) for every
+ *     entry: with c = bounds_min + (bounds_max - bounds_min) / 2 the four points c, (max.x, c.y, c.z), (c.x, max.y, c.z),
+ *     (c.x, c.y, max.z) go through swz_srs_transform to SWZ_SRS_ECEF; obb_out gets 12 doubles per entry: the mapped centre,
+ *     then the three differences to it.  srs == NULL maps nothing: the centre and the axis-aligned HALF extents on the
+ *     diagonal -- what the reference's converter writes with its IdentityTransform, and not the full extents its tiler
+ *     writes (swz_tileset_write keeps those).  The four-point box follows the reference; it does not enclose the bulge of
+ *     a flat tile's image.
+ *   swz_tileset_write_oriented: swz_tileset_write with boundingVolume.box taken from obb (12 per entry, finite); an entry
+ *     marked `tight` keeps its own axis-aligned centre and half-axes.  Everything else in the files is swz_tileset_write's. */
+struct swz_srs_s;
+int swz_pnts_pack_origin_device(swz_ctx* ctx, const uint32_t* d_perm, const uint32_t* d_order, uint64_t n, const double* d_xyz,
+                                const swz_attribute_columns* d_in, uint64_t num_nodes, const uint64_t* node_offset,
+                                const uint64_t* node_count, uint32_t mask, int rgb_mapping, void* d_image_out, uint64_t image_bytes,
+                                const double* node_origin /* host, 3 per node */);
+int swz_pnts_persist_nodes_rtc(swz_ctx* ctx, const char* dir, uint64_t num_nodes, const int8_t* node_level, const uint64_t* node_key,
+                               const uint64_t* node_count, const void* image, uint64_t image_bytes, uint32_t mask,
+                               const double* node_rtc_center /* 3 per node */);
+int swz_tileset_oriented_boxes(const struct swz_srs_s* srs /* NULL: identity */, const swz_tileset_node* nodes, uint64_t num,
+                               double* obb_out /* 12 per entry */);
+int swz_tileset_write_oriented(swz_ctx* ctx, const swz_tileset_node* nodes, uint64_t num, const double* obb, const char* dir);
 
 /* ---- LAS point records -> positions + attribute columns: the step right in
  * front of the path.  The reference reads points through LASzip into a laszip_point and converts them in
@@ -992,8 +1022,9 @@ int swz_tiler_add_las_files(swz_tiler* tiler, const char* const* paths, uint64_t
  *     converted table's total).  out.attribute_mask: a subset of the source's, ~0u = all it has.  root_given != 0:
  *     root_min / root_max / spacing_at_root override the metadata files.  A file that changed since the scan or cannot be
  *     read stops the stream after the running chunk and is reported by name.  The call never writes to or deletes from
- *     src_dir.  Not offered (the reference's --delete-source, --source-projection inside the converter, LAZ, .pnts or
- *     cloud.js sources, a multi-GPU driver): project while tiling, and delete what you no longer need yourself. */
+ *     src_dir.  --source-projection inside the converter is swz_convert_dataset_world (below, behind the projection).  Not
+ *     offered (the reference's --delete-source, LAZ, .pnts or cloud.js sources, a multi-GPU driver): delete what you no
+ *     longer need yourself. */
 enum { SWZ_DATASET_ROOT_ABSENT = 0, SWZ_DATASET_ROOT_PROPERTIES = 1, SWZ_DATASET_ROOT_EPT = 2 };
 typedef struct {
   int32_t format;          /* SWZ_OUT_* */
@@ -1085,7 +1116,7 @@ int swz_convert_dataset(swz_ctx* ctx, const char* src_dir, const char* dst_dir, 
  *     for swz_group_add_las_files, between swz_group_tiler_open and the first batch (the close forgets it). */
 enum { SWZ_SRS_LONGLAT = 0, SWZ_SRS_TMERC = 1 };
 enum { SWZ_SRS_ECEF = 0, SWZ_SRS_WGS84 = 1 };
-typedef struct {
+typedef struct swz_srs_s {
   int32_t kind; /* SWZ_SRS_LONGLAT / SWZ_SRS_TMERC (utm is a tmerc) */
   int32_t reserved;
   double a, f, e2, n;      /* the source ellipsoid: semi-major axis, flattening, e^2 = f (2 - f), n = f / (2 - f) */
@@ -1110,6 +1141,41 @@ int swz_las_decode_segments_srs_device(swz_ctx* ctx, const uint8_t* d_raw, uint6
                                        const swz_las_segment* segments /* host */, const double shift_center[3] /* or NULL */,
                                        double* d_xyz_out, const swz_attribute_columns* d_out, const swz_srs* srs /* or NULL */);
 int swz_tiler_set_source_srs(swz_tiler* tiler, const swz_srs* srs /* NULL clears */);
+/* ---- a written data set converted to georeferenced 3D Tiles: the conversion the reference's --converter mode exists for
+ * (convert_to_pnts_file, core/process/ConverterProcess.cpp:505-530).  Tile once in the source CRS into BIN, derive the
+ * Cesium tileset from those files.
+ *   swz_srs_project_node_boxes_device: n rows of 24 bytes at d_xyz, IN STORED ORDER (no perm or order indirection: the
+ *     converter's chunk-local arrays), mapped in place to SWZ_SRS_ECEF, and the exact box of every node's mapped rows, in ONE
+ *     launch (plus the preset of the table).  A workgroup stages a tile of swz_srs_tile() rows through LDS as
+ *     swz_srs_transform_device does and every lane maps its row with the same inlined map, contraction off: the stored bits
+ *     are swz_srs_transform_device's.  The block finds the nodes of its rows like the pack kernels do, a wave reduces the
+ *     runs of lanes of one node with shuffles on the order-preserving codes of swz_node_boxes_device, and one 64-bit atomic
+ *     min and max per run, axis and wave go into the table, which starts at +inf / -inf.  ALL n rows are mapped, rows
+ *     outside every node range included.  node_offset / node_count / box_min_out / box_max_out: host, as in
+ *     swz_node_boxes_device; a node of count 0 gets min = +inf, max = -inf.  srs == NULL maps nothing and only reduces.
+ *     Refused before anything is launched: what swz_node_boxes_device refuses of the table (SWZ_ERR_BAD_ARG), a struct
+ *     swz_srs_parse did not make, more than 2^32 - 65536 rows (SWZ_ERR_TOO_MANY_POINTS).  n == 0, or no node that holds
+ *     points and no projection, launches nothing.
+ *   swz_convert_dataset_world: swz_convert_dataset for the target SWZ_OUT_3DTILES only, sources BIN, BINZ, LAS and
+ *     ENTWINE_LAS as there.  Between the unpack and the pack of every chunk swz_srs_project_node_boxes_device maps the
+ *     chunk's positions to ECEF (srs == NULL: they stay, and only the origins apply); the box minima are the origins of the
+ *     chunk's nodes (setOriginToSmallestPoint, Transformation.cpp:213-227), the pack goes through
+ *     swz_pnts_pack_origin_device, and every file carries its node's origin as RTC_CENTER: a float offset within a node
+ *     instead of a float at 6.4e6 m.  Metadata: the tileset tree is built on the SOURCE root box (swz_tileset_build) and
+ *     written with swz_tileset_oriented_boxes / swz_tileset_write_oriented.  With SWZ_OUT_TIGHT_BOUNDS the ECEF boxes of the
+ *     kernel, collected over the chunks and widened to what the files hold (origin + the narrowed float of the largest
+ *     offset), go through swz_tileset_build_boxes (unions bottom-up, half-axes): those boxes are axis-aligned in ECEF and DO
+ *     enclose the points, which the reference's four-point oriented box does not where a flat tile bulges.  properties.json
+ *     keeps the source's box and spacing.  Refused by name before anything is written: everything swz_convert_dataset
+ *     refuses, a format other than 3DTILES, a non-zero out.global_offset (the origin is the node's), a struct swz_srs_parse
+ *     did not make.  swz_convert_stats does not grow: the projection's time is part of pack_ms.  Not offered: LAS or BIN
+ *     targets with a projection (the reference's convert_to_las_file takes the transformation and never uses it),
+ *     boundingRegion, --delete-source, .pnts and LAZ sources, a multi-GPU driver. */
+int swz_srs_project_node_boxes_device(swz_ctx* ctx, const swz_srs* srs /* NULL: identity */, double* d_xyz, uint64_t n,
+                                      uint64_t num_nodes, const uint64_t* node_offset, const uint64_t* node_count /* host */,
+                                      double* box_min_out, double* box_max_out /* host, 3 per node */);
+int swz_convert_dataset_world(swz_ctx* ctx, const char* src_dir, const char* dst_dir, const swz_convert_params* params,
+                              const swz_srs* srs /* NULL: no projection, per-node origins only */, swz_convert_stats* stats);
 /* ---- one tiler per GPU of a multi-GPU run (BASELINE config 5: sharded + multi-batch).  Points are owned by their
  * level-0 octant as in swz_shard_* above; every shard keeps the subtrees of its octants and ITS part of the root's
  * file.  Per batch, after the exchange of the batch's points (and attribute columns) by octant:

@@ -355,17 +355,45 @@ def pnts_read_node(path):
     return xyz, keep, list(rtc)
 
 
-def tileset_write(tiles, directory):
-    """swz_tileset_write: the tileset JSON files of tileset_build's output (the list of dicts it returns)."""
+def _tileset_buffer(tiles):
     buf = (_TilesetNode * max(len(tiles), 1))()
     for t, d in zip(buf, tiles):
         t.level, t.key, t.has_content, t.is_tileset_root = d["level"], d["key"], int(d["has_content"]), int(d["is_tileset_root"])
         t.num_children, t.parent, t.first_child, t.geometric_error = d["num_children"], d["parent"], d["first_child"], d["geometric_error"]
         t.bounds_min, t.bounds_max = _vec3(d["bounds_min"]), _vec3(d["bounds_max"])
         t.tight = int(bool(d.get("tight", False)))
-    st = load_library().swz_tileset_write(None, buf, len(tiles), os.fsencode(directory))
+    return buf
+
+
+def tileset_write(tiles, directory):
+    """swz_tileset_write: the tileset JSON files of tileset_build's output (the list of dicts it returns)."""
+    st = load_library().swz_tileset_write(None, _tileset_buffer(tiles), len(tiles), os.fsencode(directory))
     if st != 0:
         raise SwzError(st, "swz_tileset_write(%s) failed" % directory)
+
+
+def tileset_oriented_boxes(srs, tiles):
+    """swz_tileset_oriented_boxes: (len(tiles), 12) float64 -- per entry of tileset_build's output the centre of its bounds
+    and the three vectors to the centres of its upper x, y and z faces, all four points mapped to ECEF through srs (a
+    definition string or an Srs; boundingBoxFromAABB, Tileset.cpp:52-92).  srs None maps nothing: centre and half extents."""
+    srs = _as_srs(srs)
+    obb = np.empty((len(tiles), 12), dtype=np.float64)
+    st = load_library().swz_tileset_oriented_boxes(srs._ref() if srs is not None else None, _tileset_buffer(tiles), len(tiles),
+                                                   obb.ctypes.data_as(_dp))
+    if st != 0:
+        raise SwzError(st, "swz_tileset_oriented_boxes failed")
+    return obb
+
+
+def tileset_write_oriented(tiles, obb, directory):
+    """swz_tileset_write_oriented: tileset_write with boundingVolume.box of every entry taken from obb (len(tiles) x 12); an
+    entry marked `tight` keeps its own axis-aligned half-axes."""
+    o = np.ascontiguousarray(obb, dtype=np.float64).reshape(-1)
+    if o.shape[0] != 12 * len(tiles):
+        raise ValueError("obb must hold 12 values per entry")
+    st = load_library().swz_tileset_write_oriented(None, _tileset_buffer(tiles), len(tiles), o.ctypes.data_as(_dp), os.fsencode(directory))
+    if st != 0:
+        raise SwzError(st, "swz_tileset_write_oriented(%s) failed" % directory)
 
 
 # LAS node files and Entwine metadata (include/swz_gpu.h, swz_las_* / swz_ept_*)
@@ -750,7 +778,7 @@ def _ept_struct(ept):
 
 
 def convert_dataset(ctx, src, dst, format, attrs=None, max_depth=None, rgb_from=RGB_FROM_COLOR, global_offset=None, chunk_points=0,
-                    ept=None, tight_bounds=False, root_box=None, spacing=None, flags=0):
+                    ept=None, tight_bounds=False, root_box=None, spacing=None, flags=0, _world=None):
     """swz_convert_dataset: the written data set in src (BIN, BINZ, LAS or ENTWINE_LAS node files) converted into dst in
     another format, node files unpacked and packed on the device.  format, rgb_from, global_offset, chunk_points, ept,
     tight_bounds, flags: as in Tiler.write_output; attrs: the columns to write, a subset of the source's (None: all it has);
@@ -772,8 +800,22 @@ def convert_dataset(ctx, src, dst, format, attrs=None, max_depth=None, rgb_from=
                        _vec3(root_box[0] if given else (0, 0, 0)), _vec3(root_box[1] if given else (0, 0, 0)),
                        float(spacing) if given else 0.0, (C.c_uint32 * 3)(0, 0, 0))
     stats = _ConvertStats()
-    ctx._check(ctx._lib.swz_convert_dataset(ctx._ctx, os.fsencode(src), os.fsencode(dst), C.byref(p), C.byref(stats)))
+    if _world is not None:   # convert_dataset_world: (srs,)
+        srs = _world[0]
+        ctx._check(ctx._lib.swz_convert_dataset_world(ctx._ctx, os.fsencode(src), os.fsencode(dst), C.byref(p),
+                                                      srs._ref() if srs is not None else None, C.byref(stats)))
+    else:
+        ctx._check(ctx._lib.swz_convert_dataset(ctx._ctx, os.fsencode(src), os.fsencode(dst), C.byref(p), C.byref(stats)))
     return {k: getattr(stats, k) for k, _ in _ConvertStats._fields_}
+
+
+def convert_dataset_world(ctx, src, dst, source_projection=None, format="3DTILES", **kwargs):
+    """swz_convert_dataset_world: the written data set in src converted into georeferenced 3D Tiles in dst -- every chunk's
+    positions mapped to ECEF on the device (source_projection: a definition string or an Srs, as in Tiler.add_las_files;
+    None: no projection), every .pnts file relative to its node's own origin (RTC_CENTER = the per-axis minimum of the
+    node's mapped positions), the tileset with oriented boxes.  The other arguments and the returned stats are
+    convert_dataset's; format must be 3DTILES and global_offset zero (both are refused by the library otherwise)."""
+    return convert_dataset(ctx, src, dst, format, _world=(_as_srs(source_projection),), **kwargs)
 
 
 LAS_SCAN_SKIP_UNREADABLE = 1
@@ -1094,6 +1136,15 @@ def load_library():
     L.swz_pnts_rgb_from_intensity.argtypes = [C.c_int, C.c_uint16]
     L.swz_pnts_rgb_from_intensity.restype = C.c_uint8
     L.swz_tileset_write.argtypes = [vp, C.POINTER(_TilesetNode), C.c_uint64, C.c_char_p]
+    L.swz_pnts_pack_origin_device.argtypes = L.swz_pnts_pack_device.argtypes + [_dp]
+    L.swz_pnts_persist_nodes_rtc.argtypes = [vp, C.c_char_p, C.c_uint64, _i8p, _u64p, _u64p, vp, C.c_uint64, C.c_uint32, _dp]
+    L.swz_tileset_oriented_boxes.argtypes = [C.POINTER(_Srs), C.POINTER(_TilesetNode), C.c_uint64, _dp]
+    L.swz_tileset_write_oriented.argtypes = [vp, C.POINTER(_TilesetNode), C.c_uint64, _dp, C.c_char_p]
+    L.swz_srs_project_node_boxes_device.argtypes = [vp, C.POINTER(_Srs), vp, C.c_uint64, C.c_uint64, _u64p, _u64p, _dp, _dp]
+    L.swz_convert_dataset_world.argtypes = [vp, C.c_char_p, C.c_char_p, C.POINTER(_ConvertParams), C.POINTER(_Srs), C.POINTER(_ConvertStats)]
+    for name in ("swz_pnts_pack_origin_device", "swz_pnts_persist_nodes_rtc", "swz_tileset_oriented_boxes", "swz_tileset_write_oriented",
+                 "swz_srs_project_node_boxes_device", "swz_convert_dataset_world"):
+        getattr(L, name).restype = C.c_int
     for name in ("swz_pnts_layout", "swz_pnts_pack_device", "swz_pnts_write_node", "swz_pnts_write_node_rows",
                  "swz_pnts_persist_nodes", "swz_pnts_read_header", "swz_pnts_read_node", "swz_tileset_write"):
         getattr(L, name).restype = C.c_int
@@ -1482,6 +1533,49 @@ class Context:
     def convert_dataset(self, src, dst, format, **kwargs):
         """convert_dataset(self, src, dst, format, ...)"""
         return convert_dataset(self, src, dst, format, **kwargs)
+
+    def convert_dataset_world(self, src, dst, source_projection=None, **kwargs):
+        """convert_dataset_world(self, src, dst, source_projection, ...)"""
+        return convert_dataset_world(self, src, dst, source_projection, **kwargs)
+
+    def srs_project_node_boxes_device(self, srs, d_xyz, n, nodes):
+        """swz_srs_project_node_boxes_device: n rows of 24 bytes at d_xyz (a device pointer), in stored order, mapped in place
+        to ECEF through srs (a string or an Srs; None: they stay), and (box_min, box_max), num_nodes x 3 float64 each: the
+        exact componentwise min and max of the mapped rows [offset, offset + count) of every node of the table; a node
+        without points has +inf / -inf.  All n rows are mapped, those outside every node too."""
+        srs = _as_srs(srs)
+        no, nc = _node_columns(nodes, "offset", "count")
+        lo = np.empty((nc.shape[0], 3), dtype=np.float64)
+        hi = np.empty((nc.shape[0], 3), dtype=np.float64)
+        self._check(self._lib.swz_srs_project_node_boxes_device(self._ctx, srs._ref() if srs is not None else None, C.c_void_p(d_xyz),
+                                                                int(n), nc.shape[0], no.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p),
+                                                                lo.ctypes.data_as(_dp), hi.ctypes.data_as(_dp)))
+        return lo, hi
+
+    def pnts_pack_origin_device(self, d_perm, d_order, n, d_xyz, d_attrs, nodes, d_image, image_bytes, node_origin, attrs=(),
+                                rgb_from=RGB_FROM_COLOR):
+        """swz_pnts_pack_origin_device: pnts_pack_device with positions stored relative to node_origin (num_nodes x 3): the
+        subtraction in double, then the narrowing."""
+        cin = device_columns(d_attrs)
+        no, nc = _node_columns(nodes, "offset", "count")
+        org = np.ascontiguousarray(node_origin, dtype=np.float64).reshape(-1)
+        if org.shape[0] != 3 * nc.shape[0]:
+            raise ValueError("node_origin must hold 3 values per node")
+        self._check(self._lib.swz_pnts_pack_origin_device(self._ctx, C.c_void_p(d_perm), C.c_void_p(d_order), int(n), C.c_void_p(d_xyz),
+                                                          C.byref(cin), nc.shape[0], no.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p),
+                                                          _pnts_mask(attrs), int(rgb_from), C.c_void_p(d_image), int(image_bytes),
+                                                          org.ctypes.data_as(_dp)))
+
+    def pnts_persist_nodes_rtc(self, directory, nodes, image, node_rtc_center, attrs=()):
+        """swz_pnts_persist_nodes_rtc: pnts_persist_nodes with an RTC_CENTER per node (num_nodes x 3)."""
+        img = np.ascontiguousarray(image, dtype=np.uint8).reshape(-1)
+        nl, nk, nc = _node_columns(nodes, "level", "key", "count")
+        rtc = np.ascontiguousarray(node_rtc_center, dtype=np.float64).reshape(-1)
+        if rtc.shape[0] != 3 * nc.shape[0]:
+            raise ValueError("node_rtc_center must hold 3 values per node")
+        self._check(self._lib.swz_pnts_persist_nodes_rtc(self._ctx, os.fsencode(directory), nl.shape[0], nl.ctypes.data_as(_i8p),
+                                                         nk.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p), img.ctypes.data, img.shape[0],
+                                                         _pnts_mask(attrs), rtc.ctypes.data_as(_dp)))
 
     def bin_persist_nodes(self, directory, nodes, xyz, attrs=None, compressed=False):
         """bin_persist_nodes with this context's writer threads and error text."""

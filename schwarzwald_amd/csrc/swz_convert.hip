@@ -14,11 +14,13 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
 #include "swz_convert.h"
 #include "swz_hostio.h"
+#include "swz_srs.h"
 #include "swz_tinput.h"
 #include "swz_toutput.h"
 
@@ -167,16 +169,10 @@ static bool same_dir(const char* a, const char* b) {
   return realpath(a, ra) && realpath(b, rb) && strcmp(ra, rb) == 0;
 }
 
-}  // namespace swz
-
-using namespace swz;
-
-extern "C" {
-
-int swz_convert_dataset(swz_ctx* c, const char* src_dir, const char* dst_dir, const swz_convert_params* params,
-                        swz_convert_stats* stats) {
-  if (!c) return SWZ_ERR_BAD_ARG;
-  const char* who = "swz_convert_dataset";
+// swz_convert_dataset, and swz_convert_dataset_world (world: every chunk projected with srs, which may be null, between
+// its unpack and its pack, the files relative to their nodes' origins, the tileset with oriented boxes)
+static int convert(swz_ctx* c, const char* who, const char* src_dir, const char* dst_dir, const swz_convert_params* params, bool world,
+                   const swz_srs* srs, swz_convert_stats* stats) {
   auto refuse = [&](const std::string& what) { return c->fail(SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
   if (!src_dir || !dst_dir || !params) return refuse("NULL argument");
   const auto t_wall = std::chrono::steady_clock::now();
@@ -185,13 +181,20 @@ int swz_convert_dataset(swz_ctx* c, const char* src_dir, const char* dst_dir, co
 
   // ---- the source, then everything that is refused before anything is written
   if (params->reserved[0] || params->reserved[1] || params->reserved[2])
-    return refuse("reserved must be 0 (--delete-source and --source-projection are not offered: project while tiling)");
+    return refuse(world ? "reserved must be 0 (--delete-source is not offered)"
+                        : "reserved must be 0 (--delete-source and --source-projection are not offered: project while tiling)");
   DatasetScan scan;
   SWZ_TRY(dataset_scan(c, who, src_dir, params->max_depth, &scan));
   const int src_format = scan.info.format;
   if (src_format == SWZ_OUT_3DTILES) return refuse("a 3DTILES source is not converted: .pnts files hold float positions and no attribute beyond RGB and intensity");
   if (same_dir(src_dir, dst_dir)) return refuse("dst_dir is src_dir");
   swz_output_params op = params->out;
+  if (world) {
+    if (op.format != SWZ_OUT_3DTILES) return refuse("only 3DTILES is written in the world frame (a LAS or BIN target keeps the source's coordinates: swz_convert_dataset)");
+    if (op.global_offset[0] != 0.0 || op.global_offset[1] != 0.0 || op.global_offset[2] != 0.0)
+      return refuse("global_offset must be 0: every file is relative to its own node's origin");
+    if (srs && !srs_valid(srs)) return refuse("not a definition swz_srs_parse made");
+  }
   if (op.attribute_mask == ~0u) op.attribute_mask = scan.info.attribute_mask;
   if (op.attribute_mask & ~scan.info.attribute_mask) return refuse("the attribute_mask names a column the source does not hold");
   double bmin[3], bmax[3];
@@ -216,6 +219,12 @@ int swz_convert_dataset(swz_ctx* c, const char* src_dir, const char* dst_dir, co
   p.count = scan.count;
   p.offset.assign(nn, 0);
   SWZ_TRY(output_plan(c, who, &op, scan.info.attribute_mask, bmin, bmax, spacing, dst_dir, &p));
+  if (world) {
+    p.world = true;
+    p.world_srs = srs;
+    p.world_min.assign(3 * nn, std::numeric_limits<double>::infinity());
+    p.world_max.assign(3 * nn, -std::numeric_limits<double>::infinity());
+  }
   SWZ_TRY(output_create_dirs(c, who, &p, dst_dir));
 
   // ---- the chunks; rows are chunk-local: a node's offset is what its chunk holds in front of it
@@ -259,6 +268,7 @@ int swz_convert_dataset(swz_ctx* c, const char* src_dir, const char* dst_dir, co
     }
     src.ids = d_ids;
     src.xyz = d_xyz;
+    src.world_xyz = d_xyz;
     hipLaunchKernelGGL(iota_kernel, dim3(div_up(rows_max, 256)), dim3(256), 0, c->stream, d_ids, (uint32_t)rows_max);
     SWZ_LAUNCH_CHECK(c);
     SWZ_HIP(c, hipStreamSynchronize(c->stream));
@@ -331,6 +341,24 @@ int swz_convert_dataset(swz_ctx* c, const char* src_dir, const char* dst_dir, co
     stats->wall_ms = ms_since(t_wall);
   }
   return status;
+}
+
+}  // namespace swz
+
+using namespace swz;
+
+extern "C" {
+
+int swz_convert_dataset(swz_ctx* c, const char* src_dir, const char* dst_dir, const swz_convert_params* params,
+                        swz_convert_stats* stats) {
+  if (!c) return SWZ_ERR_BAD_ARG;
+  return convert(c, "swz_convert_dataset", src_dir, dst_dir, params, false, nullptr, stats);
+}
+
+int swz_convert_dataset_world(swz_ctx* c, const char* src_dir, const char* dst_dir, const swz_convert_params* params,
+                              const swz_srs* srs, swz_convert_stats* stats) {
+  if (!c) return SWZ_ERR_BAD_ARG;
+  return convert(c, "swz_convert_dataset_world", src_dir, dst_dir, params, true, srs, stats);
 }
 
 }  // extern "C"

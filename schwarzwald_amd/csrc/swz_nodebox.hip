@@ -16,20 +16,12 @@
 
 #include "swz_internal.h"
 #include "swz_device.h"
+#include "swz_nodebox.h"
 #include "swz_nodepack.h"
 
 namespace swz {
 
 constexpr int BOX_TILE = 256;  // stored rows per block, one per thread
-constexpr uint64_t BOX_MAX_POINTS = 0xFFFFFFFFull - 65535ull;  // the library's limit of points per batch (2^32 - 65536)
-constexpr uint32_t BOX_NO_ENTRY = 0xFFFFFFFFu;
-constexpr uint64_t BOX_CODE_POS_INF = 0xFFF0000000000000ull;  // box_code(+inf): what a minimum starts from
-constexpr uint64_t BOX_CODE_NEG_INF = 0x000FFFFFFFFFFFFFull;  // box_code(-inf): what a maximum starts from
-
-struct BoxNode {  // an entry of the pack table (swz_nodepack.h)
-  uint32_t start, count;
-  uint64_t base;  // of the node's six codes in the table, in bytes: 48 x its place among the nodes that hold points
-};
 
 struct BoxArgs {
   const uint32_t* perm;
@@ -40,22 +32,6 @@ struct BoxArgs {
   uint32_t num_nodes;
   uint64_t* table;  // per listed node: min x, y, z, max x, y, z as codes
 };
-
-__host__ __device__ inline uint64_t box_code(double v) {
-#ifdef __HIP_DEVICE_COMPILE__
-  const uint64_t b = (uint64_t)__double_as_longlong(v);
-#else
-  uint64_t b;
-  memcpy(&b, &v, 8);
-#endif
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-static double box_decode(uint64_t code) {
-  const uint64_t b = (code >> 63) ? (code & 0x7FFFFFFFFFFFFFFFull) : ~code;
-  double v;
-  memcpy(&v, &b, 8);
-  return v;
-}
 
 __global__ void node_boxes_preset_kernel(uint64_t* table, uint32_t entries) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -124,6 +100,12 @@ __global__ __launch_bounds__(BOX_TILE) void node_boxes_kernel(BoxArgs a) {
   }
 }
 
+int node_boxes_preset(swz_ctx* c, uint64_t* d_table, uint32_t entries) {
+  hipLaunchKernelGGL(node_boxes_preset_kernel, dim3(div_up(entries, 256)), dim3(256), 0, c->stream, d_table, entries);
+  SWZ_LAUNCH_CHECK(c);
+  return SWZ_OK;
+}
+
 }  // namespace swz
 
 using namespace swz;
@@ -174,8 +156,7 @@ int swz_node_boxes_device(swz_ctx* c, const uint32_t* d_perm, const uint32_t* d_
   {
     ProfScope ps(c, "node_boxes", prev_end * (d_order ? 8 : 4) + prev_end * 24 + listed * (sizeof(BoxNode) + 96), 2);
     const uint32_t entries = (uint32_t)(listed * 6);
-    hipLaunchKernelGGL(node_boxes_preset_kernel, dim3(div_up(entries, 256)), dim3(256), 0, c->stream, d_table, entries);
-    SWZ_LAUNCH_CHECK(c);
+    SWZ_TRY(node_boxes_preset(c, d_table, entries));
     // rows behind the last node belong to no node: the grid ends with it
     hipLaunchKernelGGL(node_boxes_kernel, dim3(div_up(prev_end, BOX_TILE)), dim3(BOX_TILE), 0, c->stream, a);
     SWZ_LAUNCH_CHECK(c);

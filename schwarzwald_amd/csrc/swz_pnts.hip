@@ -27,6 +27,7 @@
 #include "swz_device.h"
 #include "swz_hostio.h"
 #include "swz_nodepack.h"
+#include "swz_srs.h"
 
 namespace swz {
 
@@ -102,6 +103,7 @@ struct PntsPackArgs {
   uint32_t num_nodes;
   uint32_t mask;
   uint8_t* image;
+  const double* origin;  // swz_pnts_pack_origin_device: 3 per entry of `nodes`, else null
 };
 
 // The part of one byte array (rows of RB bytes) of a node that this thread writes.  `body` is the node's body in the image,
@@ -137,6 +139,9 @@ __device__ __forceinline__ void pnts_emit_bytes(uint8_t* __restrict__ body, cons
 // table, walks forward from there (swz_nodepack.h), loads its rows -- scattered 24-byte position reads, the narrowing is
 // the plain cast (round to nearest even) -- into LDS and writes from there:
 // positions as dwords in the order of the image, the 3- and 2-byte rows as aligned dwords put together from LDS.
+// ORIGIN (swz_pnts_pack_origin_device): the window also keeps every node's origin, and a position is narrowed after the
+// origin has been subtracted from it in double; nothing else differs.
+template <bool ORIGIN>
 __global__ __launch_bounds__(PNTS_TILE) void pnts_pack_kernel(PntsPackArgs a) {
   __shared__ uint32_t s_start[PNTS_TILE];
   __shared__ uint32_t s_count[PNTS_TILE];
@@ -145,6 +150,7 @@ __global__ __launch_bounds__(PNTS_TILE) void pnts_pack_kernel(PntsPackArgs a) {
   __shared__ uint32_t s_rgb[PNTS_TILE * 3 / 4];
   __shared__ uint16_t s_int[PNTS_TILE];
   __shared__ uint16_t s_node[PNTS_TILE];
+  __shared__ double s_origin[ORIGIN ? PNTS_TILE * 3 : 1];
   const uint32_t t = threadIdx.x;
   const uint32_t r0 = blockIdx.x * (uint32_t)PNTS_TILE;
   const uint32_t r1 = (uint32_t)min((uint64_t)r0 + PNTS_TILE, (uint64_t)a.n);
@@ -152,6 +158,10 @@ __global__ __launch_bounds__(PNTS_TILE) void pnts_pack_kernel(PntsPackArgs a) {
   const uint32_t k0 = pack_first_node(a.nodes, a.num_nodes, r0);
   const PntsNode* const listed = pack_fill_window(a.nodes, a.num_nodes, k0, r1, s_start, s_count);
   s_base[t] = listed ? listed->base : 0ull;
+  if constexpr (ORIGIN) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s_origin[3 * t + k] = listed ? a.origin[3 * (size_t)(k0 + t) + k] : 0.0;
+  }
   __syncthreads();
 
   const uint32_t r = r0 + t;
@@ -161,6 +171,10 @@ __global__ __launch_bounds__(PNTS_TILE) void pnts_pack_kernel(PntsPackArgs a) {
   if (in_node) {
     double pos[3];
     const uint32_t src = pack_source_row(a.perm, a.order, a.xyz, r, pos);
+    if constexpr (ORIGIN) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) pos[k] = pos[k] - s_origin[3 * e + k];
+    }
     s_pos[3 * t + 0] = __float_as_uint((float)pos[0]);
     s_pos[3 * t + 1] = __float_as_uint((float)pos[1]);
     s_pos[3 * t + 2] = __float_as_uint((float)pos[2]);
@@ -443,12 +457,9 @@ static int pnts_parse(swz_ctx* c, const char* path, PntsFile* f) {
 }
 
 // ---------------------------------------------------------------------------------- tileset JSON
-static void put_tile(std::string& s, const swz_tileset_node* nodes, uint64_t i, uint32_t remaining_levels) {
-  const swz_tileset_node& t = nodes[i];
-  char name[24];
-  (void)swz_node_name(t.level, t.key, name);
-  // boundingBoxFromAABB (Tileset.cpp:94-118): centre = min + extent / 2 (AABB.h:70) and the FULL extent on the diagonal
-  s += "{\"boundingVolume\":{\"box\":[";
+// the axis-aligned box of an entry: boundingBoxFromAABB (Tileset.cpp:94-118): centre = min + extent / 2 (AABB.h:70) and the
+// FULL extent on the diagonal; a `tight` entry the half extent
+static void put_box(std::string& s, const swz_tileset_node& t) {
   double e[3];
   for (int k = 0; k < 3; ++k) {
     e[k] = t.bounds_max[k] - t.bounds_min[k];
@@ -470,6 +481,22 @@ static void put_tile(std::string& s, const swz_tileset_node* nodes, uint64_t i, 
     put_number(s, k % 4 == 0 ? e[k / 4] : 0.0);
     if (k < 8) s += ",";
   }
+}
+
+// obb (may be null; swz_tileset_write_oriented): 12 numbers per entry, written as they are for every entry that is not `tight`
+static void put_tile(std::string& s, const swz_tileset_node* nodes, const double* obb, uint64_t i, uint32_t remaining_levels) {
+  const swz_tileset_node& t = nodes[i];
+  char name[24];
+  (void)swz_node_name(t.level, t.key, name);
+  s += "{\"boundingVolume\":{\"box\":[";
+  if (obb && !t.tight) {
+    for (int k = 0; k < 12; ++k) {
+      put_number(s, obb[12 * i + k]);
+      if (k < 11) s += ",";
+    }
+  } else {
+    put_box(s, t);
+  }
   s += "]},\"geometricError\":";
   put_number(s, t.geometric_error);
   // write_tileset (TileSetWriter.cpp:42-79): at the bottom of a file the entry refers to the next file and has no children
@@ -478,7 +505,7 @@ static void put_tile(std::string& s, const swz_tileset_node* nodes, uint64_t i, 
     s += ",\"children\":[";
     for (uint32_t k = 0; k < t.num_children; ++k) {
       if (k) s += ",";
-      put_tile(s, nodes, (uint64_t)t.first_child + k, remaining_levels - 1);
+      put_tile(s, nodes, obb, (uint64_t)t.first_child + k, remaining_levels - 1);
     }
     s += "]";
   }
@@ -514,18 +541,25 @@ int swz_pnts_layout(uint64_t num_nodes, const uint64_t* node_count, uint32_t mas
   return SWZ_OK;
 }
 
-int swz_pnts_pack_device(swz_ctx* c, const uint32_t* d_perm, const uint32_t* d_order, uint64_t n, const double* d_xyz,
-                         const swz_attribute_columns* d_in, uint64_t num_nodes, const uint64_t* node_offset,
-                         const uint64_t* node_count, uint32_t mask, int rgb_mapping, void* d_image_out, uint64_t image_bytes) {
-  if (!c) return SWZ_ERR_BAD_ARG;
+// swz_pnts_pack_device (node_origin null) and swz_pnts_pack_origin_device: the checks, the table and the launch
+static int pnts_pack(swz_ctx* c, const char* who, const uint32_t* d_perm, const uint32_t* d_order, uint64_t n, const double* d_xyz,
+                     const swz_attribute_columns* d_in, uint64_t num_nodes, const uint64_t* node_offset, const uint64_t* node_count,
+                     uint32_t mask, int rgb_mapping, void* d_image_out, uint64_t image_bytes, const double* node_origin) {
   // everything is checked on the host before anything is launched
-  if (n > PNTS_MAX_POINTS) return c->fail(SWZ_ERR_BAD_ARG, "swz_pnts_pack_device: more than 2^32-65536 rows");
-  SWZ_TRY(check_columns(c, "swz_pnts_pack_device", d_in, mask, rgb_mapping));
-  if (num_nodes && (!node_offset || !node_count)) return c->fail(SWZ_ERR_BAD_ARG, "swz_pnts_pack_device: NULL node table");
-  const PackNames names{"swz_pnts_pack_device", "swz_pnts_layout", "pnts_nodes"};
+  if (n > PNTS_MAX_POINTS) return c->fail(SWZ_ERR_BAD_ARG, std::string(who) + ": more than 2^32-65536 rows");
+  SWZ_TRY(check_columns(c, who, d_in, mask, rgb_mapping));
+  if (num_nodes && (!node_offset || !node_count)) return c->fail(SWZ_ERR_BAD_ARG, std::string(who) + ": NULL node table");
+  const PackNames names{who, "swz_pnts_layout", "pnts_nodes"};
   PackTable<PntsNode> table;
+  std::vector<double> origins;  // of the nodes that hold points, in the table's order
   SWZ_TRY(pack_build_table(
-    c, names, n, num_nodes, node_offset, node_count, [](uint64_t, PntsNode*) -> const char* { return nullptr; },
+    c, names, n, num_nodes, node_offset, node_count,
+    [&](uint64_t k, PntsNode*) -> const char* {
+      if (!node_origin || node_count[k] == 0) return nullptr;
+      if (!finite3(node_origin + 3 * k)) return "the origin of a node that holds points is not finite";
+      origins.insert(origins.end(), node_origin + 3 * k, node_origin + 3 * k + 3);
+      return nullptr;
+    },
     [&](uint64_t cnt, uint64_t* bytes) -> const char* {
       if (cnt > PNTS_MAX_BODY / 17) return "a node too large for a .pnts file";
       *bytes = pnts_body<uint64_t>(cnt, mask).size;
@@ -553,15 +587,41 @@ int swz_pnts_pack_device(swz_ctx* c, const uint32_t* d_perm, const uint32_t* d_o
     SWZ_HIP(c, hipMemcpyAsync(d_grey, grey_table(rgb_mapping), 65536, hipMemcpyHostToDevice, c->stream));
     a.grey = d_grey;
   }
+  if (node_origin) {
+    double* d_origin = nullptr;
+    SWZ_TRY(c->get("pnts_origins", origins.size(), &d_origin));
+    SWZ_HIP(c, hipMemcpyAsync(d_origin, origins.data(), origins.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    a.origin = d_origin;
+  }
   {
     const uint64_t row = 24 + ((mask & SWZ_PNTS_RGB) ? 3 : 0) + ((mask & SWZ_PNTS_INTENSITY) || a.grey ? 2 : 0);
     ProfScope ps(c, "pnts_pack", n * (d_order ? 8 : 4) + prev_end * row + at, 1);
     // rows behind the last node belong to no body: the grid ends with it
-    hipLaunchKernelGGL(pnts_pack_kernel, dim3(div_up(prev_end, PNTS_TILE)), dim3(PNTS_TILE), 0, c->stream, a);
+    if (node_origin) hipLaunchKernelGGL(pnts_pack_kernel<true>, dim3(div_up(prev_end, PNTS_TILE)), dim3(PNTS_TILE), 0, c->stream, a);
+    else hipLaunchKernelGGL(pnts_pack_kernel<false>, dim3(div_up(prev_end, PNTS_TILE)), dim3(PNTS_TILE), 0, c->stream, a);
     SWZ_LAUNCH_CHECK(c);
   }
   SWZ_HIP(c, hipStreamSynchronize(c->stream));
   return SWZ_OK;
+}
+
+int swz_pnts_pack_device(swz_ctx* c, const uint32_t* d_perm, const uint32_t* d_order, uint64_t n, const double* d_xyz,
+                         const swz_attribute_columns* d_in, uint64_t num_nodes, const uint64_t* node_offset,
+                         const uint64_t* node_count, uint32_t mask, int rgb_mapping, void* d_image_out, uint64_t image_bytes) {
+  if (!c) return SWZ_ERR_BAD_ARG;
+  return pnts_pack(c, "swz_pnts_pack_device", d_perm, d_order, n, d_xyz, d_in, num_nodes, node_offset, node_count, mask, rgb_mapping,
+                   d_image_out, image_bytes, nullptr);
+}
+
+int swz_pnts_pack_origin_device(swz_ctx* c, const uint32_t* d_perm, const uint32_t* d_order, uint64_t n, const double* d_xyz,
+                                const swz_attribute_columns* d_in, uint64_t num_nodes, const uint64_t* node_offset,
+                                const uint64_t* node_count, uint32_t mask, int rgb_mapping, void* d_image_out, uint64_t image_bytes,
+                                const double* node_origin) {
+  if (!c) return SWZ_ERR_BAD_ARG;
+  if (num_nodes && !node_origin) return c->fail(SWZ_ERR_BAD_ARG, "swz_pnts_pack_origin_device: NULL origins");
+  static const double none[3] = {0, 0, 0};  // (no nodes: the instantiation is chosen by the pointer, nothing is read)
+  return pnts_pack(c, "swz_pnts_pack_origin_device", d_perm, d_order, n, d_xyz, d_in, num_nodes, node_offset, node_count, mask,
+                   rgb_mapping, d_image_out, image_bytes, node_origin ? node_origin : none);
 }
 
 int swz_pnts_write_node(swz_ctx* c, const char* path, uint64_t count, const void* body, uint64_t body_bytes, uint32_t mask,
@@ -606,18 +666,20 @@ int swz_pnts_write_node_rows(swz_ctx* c, const char* path, uint64_t count, const
   return st == SWZ_OK ? SWZ_OK : fail(c, st, err);
 }
 
-int swz_pnts_persist_nodes(swz_ctx* c, const char* dir, uint64_t num_nodes, const int8_t* node_level, const uint64_t* node_key,
-                           const uint64_t* node_count, const void* image, uint64_t image_bytes, uint32_t mask,
-                           const double rtc_center[3]) {
-  if (!dir || (num_nodes && (!node_level || !node_key || !node_count)))
-    return fail(c, SWZ_ERR_BAD_ARG, "swz_pnts_persist_nodes: NULL argument");
-  if (!mask_ok(mask)) return fail(c, SWZ_ERR_BAD_ARG, "swz_pnts_persist_nodes: the mask names an attribute a .pnts file does not hold");
-  if (rtc_center && !finite3(rtc_center)) return fail(c, SWZ_ERR_BAD_ARG, "swz_pnts_persist_nodes: RTC_CENTER is not finite");
+// swz_pnts_persist_nodes (one centre, may be null) and swz_pnts_persist_nodes_rtc (node_rtc: 3 per node)
+static int pnts_persist(swz_ctx* c, const std::string& who, const char* dir, uint64_t num_nodes, const int8_t* node_level,
+                        const uint64_t* node_key, const uint64_t* node_count, const void* image, uint64_t image_bytes, uint32_t mask,
+                        const double* rtc_center, const double* node_rtc) {
+  if (!dir || (num_nodes && (!node_level || !node_key || !node_count))) return fail(c, SWZ_ERR_BAD_ARG, who + ": NULL argument");
+  if (!mask_ok(mask)) return fail(c, SWZ_ERR_BAD_ARG, who + ": the mask names an attribute a .pnts file does not hold");
+  if (rtc_center && !finite3(rtc_center)) return fail(c, SWZ_ERR_BAD_ARG, who + ": RTC_CENTER is not finite");
+  for (uint64_t k = 0; node_rtc && k < num_nodes; ++k)
+    if (node_count[k] && !finite3(node_rtc + 3 * k)) return fail(c, SWZ_ERR_BAD_ARG, who + ": the RTC_CENTER of a node that holds points is not finite");
   std::vector<uint64_t> at(num_nodes), size(num_nodes);
   uint64_t total = 0;
   if (swz_pnts_layout(num_nodes, node_count, mask, SWZ_PNTS_RGB_FROM_COLOR, at.data(), size.data(), nullptr, nullptr, &total) != SWZ_OK)
-    return fail(c, SWZ_ERR_BAD_ARG, "swz_pnts_persist_nodes: a node too large for a .pnts file");
-  if (total > image_bytes || (total && !image)) return fail(c, SWZ_ERR_BAD_ARG, "swz_pnts_persist_nodes: the image is smaller than the table's layout");
+    return fail(c, SWZ_ERR_BAD_ARG, who + ": a node too large for a .pnts file");
+  if (total > image_bytes || (total && !image)) return fail(c, SWZ_ERR_BAD_ARG, who + ": the image is smaller than the table's layout");
   for (uint64_t k = 0; k < num_nodes; ++k) {
     char name[24];
     if (swz_node_name(node_level[k], node_key[k], name) != SWZ_OK) return fail(c, SWZ_ERR_BAD_ARG, "bad node level");
@@ -628,9 +690,26 @@ int swz_pnts_persist_nodes(swz_ctx* c, const char* dir, uint64_t num_nodes, cons
     char name[24];
     (void)swz_node_name(node_level[k], node_key[k], name);
     const std::string path = std::string(dir) + "/" + name + ".pnts";
-    return pnts_write_file(path.c_str(), node_count[k], static_cast<const unsigned char*>(image) + at[k], size[k], mask, rtc_center, err);
+    return pnts_write_file(path.c_str(), node_count[k], static_cast<const unsigned char*>(image) + at[k], size[k], mask,
+                           node_rtc ? node_rtc + 3 * k : rtc_center, err);
   }, &first_err);
   return st == SWZ_OK ? SWZ_OK : fail(c, st, first_err);
+}
+
+int swz_pnts_persist_nodes(swz_ctx* c, const char* dir, uint64_t num_nodes, const int8_t* node_level, const uint64_t* node_key,
+                           const uint64_t* node_count, const void* image, uint64_t image_bytes, uint32_t mask,
+                           const double rtc_center[3]) {
+  return pnts_persist(c, "swz_pnts_persist_nodes", dir, num_nodes, node_level, node_key, node_count, image, image_bytes, mask, rtc_center,
+                      nullptr);
+}
+
+int swz_pnts_persist_nodes_rtc(swz_ctx* c, const char* dir, uint64_t num_nodes, const int8_t* node_level, const uint64_t* node_key,
+                               const uint64_t* node_count, const void* image, uint64_t image_bytes, uint32_t mask,
+                               const double* node_rtc_center) {
+  if (num_nodes && !node_rtc_center) return fail(c, SWZ_ERR_BAD_ARG, "swz_pnts_persist_nodes_rtc: NULL argument");
+  static const double none[3] = {0, 0, 0};
+  return pnts_persist(c, "swz_pnts_persist_nodes_rtc", dir, num_nodes, node_level, node_key, node_count, image, image_bytes, mask, nullptr,
+                      node_rtc_center ? node_rtc_center : none);
 }
 
 int swz_pnts_read_header(swz_ctx* c, const char* path, uint64_t* count_out, uint32_t* mask_out, double rtc_center_out[3]) {
@@ -707,8 +786,10 @@ int swz_tileset_build_boxes(uint64_t num_nodes, const int8_t* node_level, const 
   return SWZ_OK;
 }
 
-int swz_tileset_write(swz_ctx* c, const swz_tileset_node* nodes, uint64_t num, const char* dir) {
-  if (!dir || (num && !nodes)) return fail(c, SWZ_ERR_BAD_ARG, "swz_tileset_write: NULL argument");
+// swz_tileset_write (obb null) and swz_tileset_write_oriented
+static int tileset_write(swz_ctx* c, const std::string& who, const swz_tileset_node* nodes, uint64_t num, const double* obb,
+                         const char* dir) {
+  if (!dir || (num && !nodes)) return fail(c, SWZ_ERR_BAD_ARG, who + ": NULL argument");
   // the array must be what swz_tileset_build hands out: children behind their parent, inside the array, one level down
   for (uint64_t i = 0; i < num; ++i) {
     const swz_tileset_node& t = nodes[i];
@@ -717,7 +798,9 @@ int swz_tileset_write(swz_ctx* c, const swz_tileset_node* nodes, uint64_t num, c
       ok = t.first_child > (int64_t)i && (uint64_t)t.first_child < num && t.num_children <= num - (uint64_t)t.first_child;
     for (uint32_t k = 0; ok && k < t.num_children; ++k) ok = nodes[t.first_child + k].level == t.level + 1;
     if (!ok || !std::isfinite(t.geometric_error) || !finite3(t.bounds_min) || !finite3(t.bounds_max))
-      return fail(c, SWZ_ERR_BAD_ARG, "swz_tileset_write: not a tileset tree of swz_tileset_build");
+      return fail(c, SWZ_ERR_BAD_ARG, who + ": not a tileset tree of swz_tileset_build");
+    for (int k = 0; obb && !t.tight && k < 12; ++k)
+      if (!std::isfinite(obb[12 * i + k])) return fail(c, SWZ_ERR_BAD_ARG, who + ": an oriented box is not finite");
   }
   std::vector<uint64_t> roots;
   for (uint64_t i = 0; i < num; ++i)
@@ -729,7 +812,7 @@ int swz_tileset_write(swz_ctx* c, const swz_tileset_node* nodes, uint64_t num, c
     std::string s = "{\"asset\":{\"version\":\"0.0\"},\"geometricError\":";
     put_number(s, t.geometric_error);
     s += ",\"root\":";
-    put_tile(s, nodes, roots[k], 3);
+    put_tile(s, nodes, obb, roots[k], 3);
     s += "}";
     char name[24];
     (void)swz_node_name(t.level, t.key, name);
@@ -737,6 +820,34 @@ int swz_tileset_write(swz_ctx* c, const swz_tileset_node* nodes, uint64_t num, c
     return write_file(path, {{s.data(), s.size()}}, err);
   }, &first_err);
   return st == SWZ_OK ? SWZ_OK : fail(c, st, first_err);
+}
+
+int swz_tileset_write(swz_ctx* c, const swz_tileset_node* nodes, uint64_t num, const char* dir) {
+  return tileset_write(c, "swz_tileset_write", nodes, num, nullptr, dir);
+}
+
+int swz_tileset_write_oriented(swz_ctx* c, const swz_tileset_node* nodes, uint64_t num, const double* obb, const char* dir) {
+  if (num && !obb) return fail(c, SWZ_ERR_BAD_ARG, "swz_tileset_write_oriented: NULL argument");
+  static const double none[12] = {0};
+  return tileset_write(c, "swz_tileset_write_oriented", nodes, num, obb ? obb : none, dir);
+}
+
+int swz_tileset_oriented_boxes(const swz_srs* srs, const swz_tileset_node* nodes, uint64_t num, double* obb_out) {
+  if ((srs && !srs_valid(srs)) || (num && (!nodes || !obb_out))) return SWZ_ERR_BAD_ARG;
+  for (uint64_t i = 0; i < num; ++i) {
+    const swz_tileset_node& t = nodes[i];
+    // boundingBoxFromAABB(aabb, transform) (Tileset.cpp:52-92): the centre (min + extent / 2, AABB.h:70) and the centres of
+    // the three upper faces
+    double c3[3];
+    for (int k = 0; k < 3; ++k) c3[k] = t.bounds_min[k] + (t.bounds_max[k] - t.bounds_min[k]) / 2;
+    double p[12] = {c3[0], c3[1], c3[2], t.bounds_max[0], c3[1], c3[2], c3[0], t.bounds_max[1], c3[2], c3[0], c3[1], t.bounds_max[2]};
+    if (srs) (void)swz_srs_transform(srs, SWZ_SRS_ECEF, p, 4);
+    double* out = obb_out + 12 * i;
+    for (int k = 0; k < 3; ++k) out[k] = p[k];
+    for (int v = 1; v < 4; ++v)
+      for (int k = 0; k < 3; ++k) out[3 * v + k] = p[3 * v + k] - p[k];
+  }
+  return SWZ_OK;
 }
 
 }  // extern "C"

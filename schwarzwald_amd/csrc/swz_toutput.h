@@ -28,6 +28,12 @@ struct OutputPlan {
   // a node without points).  output_stream fills them chunk by chunk, before the chunk's files are written.
   bool tight = false;
   std::vector<double> tight_min, tight_max;
+  // swz_convert_dataset_world (3DTILES): every chunk's positions are projected in place (world_srs, may be null: they stay)
+  // and every file is relative to its node's own origin, the per-axis minimum of its projected rows: world_min, which
+  // output_stream fills with world_max chunk by chunk like the tight boxes (3 per node; +inf / -inf for a node without points)
+  bool world = false;
+  const swz_srs* world_srs = nullptr;
+  std::vector<double> world_min, world_max;
 };
 
 // where the rows of a plan's nodes come from: row i of a node = row ids[offset + i] of xyz and of the columns
@@ -35,6 +41,7 @@ struct OutputSource {
   const uint32_t* ids = nullptr;
   const double* xyz = nullptr;
   swz_attribute_columns in{};
+  double* world_xyz = nullptr;  // a world plan: xyz, writable -- rows in stored order (ids the identity), projected in place
 };
 
 struct OutputStreamStats {

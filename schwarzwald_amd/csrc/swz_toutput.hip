@@ -67,7 +67,7 @@ static int write_node_file(const OutputPlan& p, uint64_t k, const unsigned char*
     case SWZ_OUT_BINZ: return write_file_zlib(stem + ".binz", body, (size_t)p.file_size[k], err);
     case SWZ_OUT_3DTILES:
       path = stem + ".pnts";
-      st = swz_pnts_write_node(nullptr, path.c_str(), p.count[k], body, p.body_size[k], p.mask, p.rtc);
+      st = swz_pnts_write_node(nullptr, path.c_str(), p.count[k], body, p.body_size[k], p.mask, p.world ? &p.world_min[3 * k] : p.rtc);
       break;
     default:
       path = stem + ".las";
@@ -268,6 +268,15 @@ int output_stream(swz_ctx* c, OutputPlan& p, const std::vector<uint64_t>& first,
                                    ob.device[b], bytes);
           break;
         case SWZ_OUT_3DTILES:
+          if (p.world) {
+            // the chunk's rows to ECEF in place and the boxes of its nodes' projected rows; their minima are the files' origins
+            st = swz_srs_project_node_boxes_device(c, p.world_srs, src.world_xyz + 3 * row0, rows, k1 - k0, rel_offset.data(),
+                                                   &p.count[k0], &p.world_min[3 * k0], &p.world_max[3 * k0]);
+            if (st == SWZ_OK)
+              st = swz_pnts_pack_origin_device(c, src.ids + row0, nullptr, rows, src.xyz, &src.in, k1 - k0, rel_offset.data(),
+                                               &p.count[k0], p.mask, p.rgb_mapping, ob.device[b], bytes, &p.world_min[3 * k0]);
+            break;
+          }
           st = swz_pnts_pack_device(c, src.ids + row0, nullptr, rows, src.xyz, &src.in, k1 - k0, rel_offset.data(), &p.count[k0], p.mask,
                                     p.rgb_mapping, ob.device[b], bytes);
           break;
@@ -277,7 +286,7 @@ int output_stream(swz_ctx* c, OutputPlan& p, const std::vector<uint64_t>& first,
           break;
       }
       // (the boxes of chunk j's nodes: the writers of chunk j - 1 read other entries, and chunk j's start after this)
-      if (st == SWZ_OK && p.tight)
+      if (st == SWZ_OK && p.tight && !p.world)  // (a world plan has its boxes already)
         st = swz_node_boxes_device(c, src.ids + row0, nullptr, rows, src.xyz, k1 - k0, rel_offset.data(), &p.count[k0],
                                    &p.tight_min[3 * k0], &p.tight_max[3 * k0]);
       stats->pack_ms += ms_since(t_pack);
@@ -321,7 +330,26 @@ int output_stream(swz_ctx* c, OutputPlan& p, const std::vector<uint64_t>& first,
 
 int output_metadata(swz_ctx* c, const char* who, const OutputPlan& p, const char* dir, const swz_output_params* params) {
   const uint64_t nn = p.count.size();
-  if (p.format == SWZ_OUT_3DTILES && nn) {
+  if (p.format == SWZ_OUT_3DTILES && nn && p.world) {
+    // the tree on the SOURCE root box, its cubes as oriented boxes in the target; with tight bounds the entries that hold
+    // points below them get the axis-aligned box of what the files hold instead: origin + the floats, evaluated in double
+    // like a reader does (narrowing and the sum are monotonic, so the largest offset bounds every point's)
+    uint64_t num = 0;
+    int st = swz_tileset_build(nn, p.level.data(), p.key.data(), p.bmin, p.bmax, p.spacing_at_root, nullptr, 0, nullptr, &num);
+    std::vector<swz_tileset_node> tiles(num);
+    if (st == SWZ_OK) st = swz_tileset_build(nn, p.level.data(), p.key.data(), p.bmin, p.bmax, p.spacing_at_root, nullptr, num, tiles.data(), &num);
+    std::vector<double> obb(12 * num);
+    if (st == SWZ_OK) st = swz_tileset_oriented_boxes(p.world_srs, tiles.data(), num, obb.data());
+    if (st == SWZ_OK && p.tight) {
+      std::vector<double> hi(p.world_max);
+      for (size_t i = 0; i < hi.size(); ++i)
+        if (p.world_min[i] <= p.world_max[i]) hi[i] = p.world_min[i] + (double)(float)(p.world_max[i] - p.world_min[i]);
+      st = swz_tileset_build_boxes(nn, p.level.data(), p.key.data(), p.world_min.data(), hi.data(), p.bmin, p.bmax, p.spacing_at_root,
+                                   nullptr, num, tiles.data(), &num);
+    }
+    if (st != SWZ_OK) return c->fail(st, std::string(who) + ": swz_tileset_build failed");
+    SWZ_TRY(swz_tileset_write_oriented(c, tiles.data(), num, obb.data(), dir));
+  } else if (p.format == SWZ_OUT_3DTILES && nn) {
     uint64_t num = 0;
     std::vector<swz_tileset_node> tiles;
     int st = swz_tileset_build(nn, p.level.data(), p.key.data(), p.bmin, p.bmax, p.spacing_at_root, p.rtc, 0, nullptr, &num);

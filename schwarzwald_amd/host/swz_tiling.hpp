@@ -162,6 +162,19 @@ inline swz_convert_stats convert_dataset(Context& ctx, const std::string& src_di
   return stats;
 }
 
+// The conversion the reference's --converter mode exists for (convert_to_pnts_file, ConverterProcess.cpp:505-530;
+// ConverterArguments::source_projection): src_dir converted into 3D Tiles in the world frame -- positions mapped to ECEF on the
+// device, every .pnts file relative to its node's own origin, tile volumes as oriented boxes (swz_convert_dataset_world).
+// projection == nullptr is the reference's IdentityTransform.  params.out.format must be SWZ_OUT_3DTILES and
+// params.out.global_offset zero; a refusal throws with the library's text.
+inline swz_convert_stats convert_dataset_world(Context& ctx, const std::string& src_dir, const std::string& dst_dir,
+                                               const swz_convert_params& params, const SourceProjection* projection = nullptr) {
+  swz_convert_stats stats{};
+  ctx.check(swz_convert_dataset_world(ctx.get(), src_dir.c_str(), dst_dir.c_str(), &params, projection ? projection->srs() : nullptr,
+                                      &stats));
+  return stats;
+}
+
 // index_points<21> -- OctreeAlgorithms.h:181-197.  positions: n x 3 doubles (PointBuffer::positions().data());
 // outliers are clamped in place, like index_point does.
 inline void index_points(Context& ctx, double* positions, size_t n, IndexedPoint64* indexed_points_begin,

@@ -5,9 +5,13 @@ intensity) writes a BIN data set with write_output + write_properties; then, per
   (w) Tiler.write_output of the same format from the live tiler: the ceiling -- conversion adds the read and the unpack;
   (h) the host recipe: bin_read_node of every source file, then the format's *_write_node_rows writer, node by node
       (--host-nodes N: only the first N nodes, and the time scaled to the whole table by points; 0: all).
+--source-projection DEF: the 3DTILES leg is also timed through convert_dataset_world (positions mapped to ECEF with DEF, files
+relative to their nodes' origins, oriented boxes), beside the existing call: row["convert_world"].  The unit cube is read as
+coordinates of DEF (for a UTM zone: a metre beside the false origin, on the equator); the map costs what it costs anywhere.
 Everything goes into fresh directories under --dir (default: the system's temporary directory).  The work runs in one child
 process under `timeout`.
-usage: convert_probe.py [points] [--batches K] [--formats BIN,LAS,...] [--dir DIR] [--host-nodes N] [--json FILE]"""
+usage: convert_probe.py [points] [--batches K] [--formats BIN,LAS,...] [--dir DIR] [--host-nodes N] [--json FILE]
+                        [--source-projection DEF]"""
 import json
 import os
 import shutil
@@ -49,7 +53,7 @@ def host_recipe(swz, src, dst, fmt, nodes, bmin, bmax, limit):
     return time.perf_counter() - t0, done
 
 
-def step(n, batches, formats, base, host_nodes):
+def step(n, batches, formats, base, host_nodes, projection):
     import numpy as np
     import schwarzwald_amd as swz
     ctx = swz.Context(0)
@@ -74,8 +78,11 @@ def step(n, batches, formats, base, host_nodes):
     print("CONVERT_PROBE " + json.dumps(dict(source=out)), flush=True)
     for fmt in formats:
         row = dict(format=fmt)
-        for name, fn in (("convert", lambda d: swz.convert_dataset(ctx, src, d, fmt, attrs=NAMES)),
-                         ("write_output", lambda d: t.write_output(d, fmt, attrs=NAMES))):
+        legs = [("convert", lambda d: swz.convert_dataset(ctx, src, d, fmt, attrs=NAMES)),
+                ("write_output", lambda d: t.write_output(d, fmt, attrs=NAMES))]
+        if projection and fmt == "3DTILES":
+            legs.append(("convert_world", lambda d: swz.convert_dataset_world(ctx, src, d, projection, attrs=NAMES)))
+        for name, fn in legs:
             for rep in ("warm", "timed"):   # the first run pays allocations and the page cache
                 d = os.path.join(work, name + "_" + fmt)
                 shutil.rmtree(d, ignore_errors=True)
@@ -87,6 +94,8 @@ def step(n, batches, formats, base, host_nodes):
         row["host_recipe"] = dict(measured_s=secs, points=done, scaled_to_all_s=secs * stored / max(done, 1))
         row["convert_over_write_output"] = row["convert"]["wall_ms"] / row["write_output"]["wall_ms"]
         row["host_over_convert"] = row["host_recipe"]["scaled_to_all_s"] * 1e3 / row["convert"]["wall_ms"]
+        if "convert_world" in row:
+            row["world_over_convert"] = row["convert_world"]["wall_ms"] / row["convert"]["wall_ms"]
         print("CONVERT_PROBE " + json.dumps(row), flush=True)
     shutil.rmtree(work, ignore_errors=True)
     t.close()
@@ -96,7 +105,7 @@ def step(n, batches, formats, base, host_nodes):
 def main():
     args = sys.argv[1:]
     if args and args[0] == "--step":
-        return step(int(args[1]), int(args[2]), args[3].split(","), args[4] or None, int(args[5]))
+        return step(int(args[1]), int(args[2]), args[3].split(","), args[4] or None, int(args[5]), args[6] or None)
 
     def option(name, default):
         return args[args.index(name) + 1] if name in args else default
@@ -104,7 +113,7 @@ def main():
     limit = str(max(300, n // 50_000))
     # one child under its own time limit; check=True: a failure ends the script here
     r = subprocess.run(["timeout", "-k", "10", limit, sys.executable, os.path.abspath(__file__), "--step", str(n), option("--batches", "10"),
-                        option("--formats", ",".join(FORMATS)), option("--dir", ""), option("--host-nodes", "0")], check=True,
+                        option("--formats", ",".join(FORMATS)), option("--dir", ""), option("--host-nodes", "0"), option("--source-projection", "")], check=True,
                        stdout=subprocess.PIPE, text=True)
     results = [json.loads(l[len("CONVERT_PROBE "):]) for l in r.stdout.splitlines() if l.startswith("CONVERT_PROBE ")]
     for row in results:
