@@ -415,7 +415,11 @@ int swz_node_boxes_device(swz_ctx* ctx, const uint32_t* d_perm, const uint32_t* 
  *   swz_pnts_read_header / swz_pnts_read_node: retrieve_points.  Positions come back as the stored floats widened to double
  *     (the format is lossy), RGB and intensity into the non-NULL columns if the file has them.  The arrays are found through
  *     the offsets in the file's JSON, whatever their order.  SWZ_ERR_BAD_ARG, without reading outside the file, for a short
- *     file, a wrong magic, lengths that do not add up, an array that passes the binary, a JSON that cannot be read.
+ *     file, a wrong magic, lengths that do not add up, an array that passes the binary, a JSON that cannot be read, a
+ *     feature table without POSITION (POSITION_QUANTIZED is not read).  swz_pnts_read_header reads the header and the JSON
+ *     only.  swz_pnts_parse_image: the same checks on a file image in memory, never reading outside [file, file +
+ *     file_bytes); the three offsets count from the first byte of the image (0 for an array the file lacks), members other
+ *     than POINTS_LENGTH, RTC_CENTER, POSITION, RGB and INTENSITY and a batch table are ignored; any output may be NULL.
  *   swz_tileset_write: the JSON files of swz_tileset_build's output (write_tilesets, Cesium3DTilesPersistence.cpp:173-210;
  *     writeTilesetJSON, core/io/TileSetWriter.cpp:42-210): "<name>.json" per is_tileset_root entry with asset.version "0.0",
  *     the entry's geometricError and its tile as root.  A tile holds boundingVolume.box = [centre, then the FULL extent on the
@@ -443,6 +447,9 @@ int swz_pnts_persist_nodes(swz_ctx* ctx, const char* dir, uint64_t num_nodes, co
                            const double rtc_center[3]);
 int swz_pnts_read_header(swz_ctx* ctx, const char* path, uint64_t* count_out, uint32_t* mask_out, double rtc_center_out[3]);
 int swz_pnts_read_node(swz_ctx* ctx, const char* path, double* xyz_out, const swz_attribute_columns* columns_out);
+int swz_pnts_parse_image(swz_ctx* ctx, const void* file, uint64_t file_bytes, uint64_t* count_out, uint32_t* mask_out,
+                         double rtc_center_out[3], uint64_t* position_offset_out, uint64_t* rgb_offset_out,
+                         uint64_t* intensity_offset_out);
 /* one value of the grey table (0 for SWZ_PNTS_RGB_FROM_COLOR) */
 uint8_t swz_pnts_rgb_from_intensity(int rgb_mapping, uint16_t intensity);
 int swz_tileset_write(swz_ctx* ctx, const swz_tileset_node* nodes, uint64_t num, const char* dir);
@@ -1004,16 +1011,31 @@ int swz_tiler_add_las_files(swz_tiler* tiler, const char* const* paths, uint64_t
  *     ascend contiguously from 0, a segment whose image passes raw_bytes, a mask bit that does not exist, more than 2^32 -
  *     65536 rows.  Zero segments or zero rows launches nothing.  The kernel trusts the table: whoever reads the files checks
  *     their 12-byte headers against it (swz_convert_dataset does).
+ *   swz_pnts_unpack_segments_device: the inverse of swz_pnts_pack_device, shaped like swz_bin_unpack_segments_device.  A
+ *     segment names where its arrays lie in d_raw (swz_pnts_parse_image's offsets plus the file's place in the image), each
+ *     AT ANY BYTE ALIGNMENT and in any order.  Row first_row + i of d_xyz_out gets (double)f of the three stored floats --
+ *     exact, nothing is added, the sign of zero, denormals and infinities survive, a NaN stays a NaN --, its RGB column the
+ *     three stored bytes, its intensity column the stored u16; a column of d_out outside the segment's mask gets zeros for
+ *     the segment's rows, any other column in d_out is refused (the format cannot carry it), d_xyz_out may be NULL.  One
+ *     kernel with the staging of the BIN unpack (swz_pnts_unpack_tile() rows per workgroup; whole dwords only inside [d_raw,
+ *     d_raw + raw_bytes), single bytes at the two ends); the widened positions of a tile are put together in LDS and leave
+ *     as consecutive 16-byte pieces.  SWZ_ERR_BAD_ARG before anything is launched for: rows that do not ascend contiguously
+ *     from 0, an array that passes raw_bytes, a mask bit outside RGB | INTENSITY, reserved != 0, an output column the format
+ *     lacks, more than 2^32 - 65536 rows.  Zero segments or zero rows launches nothing.
  *   swz_convert_dataset: scans src_dir, refuses what can be refused before anything is written -- what
- *     swz_tiler_write_output refuses of `out`, a 3DTILES source (its positions are floats and it carries no attribute beyond
- *     RGB and intensity), dst_dir equal to src_dir, a mask outside the source's, no root box and spacing from the metadata
+ *     swz_tiler_write_output refuses of `out`, a 3DTILES source without SWZ_CONVERT_LOSSY_SOURCE in source_flags (its
+ *     positions are floats and it carries no attribute beyond RGB and intensity: converting it is opt-in; the flag does
+ *     nothing for another source, any other bit is refused), a 3DTILES source whose files do not all carry the same
+ *     RTC_CENTER (a data set of swz_convert_dataset_world; the first file that differs is named), dst_dir equal to src_dir, a mask outside the source's, no root box and spacing from the metadata
  *     files or the parameters, reserved words that are not 0 --, plans the target layout for the (depth-limited) table from
  *     the source's root box and spacing, and streams chunks of whole consecutive nodes of at most out.chunk_points points
  *     (the cuts of swz_output_chunks): reader threads (SWZ_INPUT_READER_THREADS) read the chunk's files back to back, each
  *     at a multiple of 8, into one of two page-locked buffers (BINZ files are inflated into it, LAS files contribute their
- *     record ranges, BIN headers are checked against the scanned table), a copy stream moves the buffer to the device, the
+ *     record ranges, BIN headers are checked against the scanned table, .pnts files are read whole, run through
+ *     swz_pnts_parse_image and checked against the scanned table), a copy stream moves the buffer to the device, the
  *     unpack kernel (LAS sources: the segment kernel of swz_las_decode_segments_device, one layout per file, so the result
- *     is swz_las_read_node's) fills chunk-local positions and columns, and the target format's pack kernel, the copy back
+ *     is swz_las_read_node's; .pnts sources: swz_pnts_unpack_segments_device's kernel, so the result is swz_pnts_read_node's
+ *     and nothing is inferred from the source's RTC_CENTER) fills chunk-local positions and columns, and the target format's pack kernel, the copy back
  *     and the writer threads (SWZ_BIN_WRITER_THREADS) produce the files exactly as swz_tiler_write_output does, tight
  *     bounds included.  Chunk k + 1 is read while chunk k is packed and written.  Device and host hold a bounded number of
  *     chunk images whatever the size of the data set; row numbers are chunk-local, so a data set may hold more than 2^32
@@ -1023,7 +1045,7 @@ int swz_tiler_add_las_files(swz_tiler* tiler, const char* const* paths, uint64_t
  *     root_min / root_max / spacing_at_root override the metadata files.  A file that changed since the scan or cannot be
  *     read stops the stream after the running chunk and is reported by name.  The call never writes to or deletes from
  *     src_dir.  --source-projection inside the converter is swz_convert_dataset_world (below, behind the projection).  Not
- *     offered (the reference's --delete-source, LAZ, .pnts or cloud.js sources, a multi-GPU driver): delete what you no
+ *     offered (the reference's --delete-source, LAZ or cloud.js sources, a multi-GPU driver): delete what you no
  *     longer need yourself. */
 enum { SWZ_DATASET_ROOT_ABSENT = 0, SWZ_DATASET_ROOT_PROPERTIES = 1, SWZ_DATASET_ROOT_EPT = 2 };
 typedef struct {
@@ -1044,12 +1066,20 @@ typedef struct {
   uint32_t reserved;
 } swz_bin_segment;
 typedef struct {
+  uint64_t first_row, count;                              /* output rows [first_row, first_row + count) */
+  uint64_t position_offset, rgb_offset, intensity_offset; /* absolute in d_raw, any byte alignment */
+  uint32_t mask;                                          /* SWZ_PNTS_RGB | SWZ_PNTS_INTENSITY: the arrays the segment holds */
+  uint32_t reserved;                                      /* 0 */
+} swz_pnts_segment;
+enum { SWZ_CONVERT_LOSSY_SOURCE = 1u }; /* admits a 3DTILES source: float positions, RGB and intensity only */
+typedef struct {
   swz_output_params out;
   int32_t max_depth;   /* < 0: every node */
   uint32_t root_given; /* != 0: root_min, root_max and spacing_at_root below override the metadata files */
   double root_min[3], root_max[3];
   float spacing_at_root;
-  uint32_t reserved[3]; /* 0 */
+  uint32_t source_flags; /* SWZ_CONVERT_* */
+  uint32_t reserved[2];  /* 0 */
 } swz_convert_params;
 typedef struct {
   uint64_t nodes, points, bytes_read, bytes_written, chunks;
@@ -1068,6 +1098,9 @@ int swz_dataset_scan_why(const char* dir, int32_t max_depth, swz_dataset_info* i
 uint32_t swz_bin_unpack_tile(void); /* rows one workgroup takes; tests place their edges by it */
 int swz_bin_unpack_segments_device(swz_ctx* ctx, const uint8_t* d_raw, uint64_t raw_bytes, const swz_bin_segment* segments /* host */,
                                    uint64_t num_segments, double* d_xyz_out, const swz_attribute_columns* d_out);
+uint32_t swz_pnts_unpack_tile(void); /* rows one workgroup takes */
+int swz_pnts_unpack_segments_device(swz_ctx* ctx, const uint8_t* d_raw, uint64_t raw_bytes, const swz_pnts_segment* segments /* host */,
+                                    uint64_t num_segments, double* d_xyz_out, const swz_attribute_columns* d_out);
 int swz_convert_dataset(swz_ctx* ctx, const char* src_dir, const char* dst_dir, const swz_convert_params* params,
                         swz_convert_stats* stats);
 /* ---- a source projection (the reference's --source-projection: Proj4Transform, core/util/Transformation.cpp:74-211, source
@@ -1156,8 +1189,8 @@ int swz_tiler_set_source_srs(swz_tiler* tiler, const swz_srs* srs /* NULL clears
  *     Refused before anything is launched: what swz_node_boxes_device refuses of the table (SWZ_ERR_BAD_ARG), a struct
  *     swz_srs_parse did not make, more than 2^32 - 65536 rows (SWZ_ERR_TOO_MANY_POINTS).  n == 0, or no node that holds
  *     points and no projection, launches nothing.
- *   swz_convert_dataset_world: swz_convert_dataset for the target SWZ_OUT_3DTILES only, sources BIN, BINZ, LAS and
- *     ENTWINE_LAS as there.  Between the unpack and the pack of every chunk swz_srs_project_node_boxes_device maps the
+ *   swz_convert_dataset_world: swz_convert_dataset for the target SWZ_OUT_3DTILES only, sources BIN, BINZ, LAS,
+ *     ENTWINE_LAS and (SWZ_CONVERT_LOSSY_SOURCE) 3DTILES as there.  Between the unpack and the pack of every chunk swz_srs_project_node_boxes_device maps the
  *     chunk's positions to ECEF (srs == NULL: they stay, and only the origins apply); the box minima are the origins of the
  *     chunk's nodes (setOriginToSmallestPoint, Transformation.cpp:213-227), the pack goes through
  *     swz_pnts_pack_origin_device, and every file carries its node's origin as RTC_CENTER: a float offset within a node

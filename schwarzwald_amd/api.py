@@ -355,6 +355,24 @@ def pnts_read_node(path):
     return xyz, keep, list(rtc)
 
 
+def pnts_parse_image(image):
+    """swz_pnts_parse_image: where the arrays of a .pnts file image (bytes, or a uint8 array) are -- a dict of count, mask,
+    attrs, rtc_center and position_offset / rgb_offset / intensity_offset, counted from the first byte of the image (0 for
+    an array the file lacks).  Host only; a refusal raises SwzError."""
+    b = np.frombuffer(bytes(image), dtype=np.uint8) if isinstance(image, (bytes, bytearray, memoryview)) else \
+        np.ascontiguousarray(image, dtype=np.uint8).reshape(-1)
+    count, mask, rtc = C.c_uint64(), C.c_uint32(), (C.c_double * 3)()
+    pos, rgb, inten = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    keep = b if b.shape[0] else np.zeros(1, dtype=np.uint8)
+    st = load_library().swz_pnts_parse_image(None, C.c_void_p(keep.ctypes.data), int(b.shape[0]), C.byref(count), C.byref(mask), rtc,
+                                             C.byref(pos), C.byref(rgb), C.byref(inten))
+    if st != 0:
+        raise SwzError(st, "swz_pnts_parse_image failed")
+    m = int(mask.value)
+    return dict(count=int(count.value), mask=m, attrs=[k for k, bit in (("rgb", PNTS_RGB), ("intensity", PNTS_INTENSITY)) if m & bit],
+                rtc_center=list(rtc), position_offset=int(pos.value), rgb_offset=int(rgb.value), intensity_offset=int(inten.value))
+
+
 def _tileset_buffer(tiles):
     buf = (_TilesetNode * max(len(tiles), 1))()
     for t, d in zip(buf, tiles):
@@ -705,9 +723,18 @@ class _BinSegment(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class _PntsSegment(C.Structure):
+    _fields_ = [("first_row", C.c_uint64), ("count", C.c_uint64), ("position_offset", C.c_uint64), ("rgb_offset", C.c_uint64),
+                ("intensity_offset", C.c_uint64), ("mask", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+CONVERT_LOSSY_SOURCE = 1
+
+
 class _ConvertParams(C.Structure):
     _fields_ = [("out", _OutputParams), ("max_depth", C.c_int32), ("root_given", C.c_uint32), ("root_min", C.c_double * 3),
-                ("root_max", C.c_double * 3), ("spacing_at_root", C.c_float), ("reserved", C.c_uint32 * 3)]
+                ("root_max", C.c_double * 3), ("spacing_at_root", C.c_float), ("source_flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
 
 
 class _ConvertStats(C.Structure):
@@ -769,6 +796,11 @@ def bin_unpack_tile():
     return int(load_library().swz_bin_unpack_tile())
 
 
+def pnts_unpack_tile():
+    """Output rows one workgroup of pnts_unpack_segments_device takes."""
+    return int(load_library().swz_pnts_unpack_tile())
+
+
 def _ept_struct(ept):
     srs = ept.get("srs") or {}
     return _EptJson(_vec3(ept["bounds"][0]), _vec3(ept["bounds"][1]), _vec3(ept["conforming_bounds"][0]),
@@ -778,9 +810,11 @@ def _ept_struct(ept):
 
 
 def convert_dataset(ctx, src, dst, format, attrs=None, max_depth=None, rgb_from=RGB_FROM_COLOR, global_offset=None, chunk_points=0,
-                    ept=None, tight_bounds=False, root_box=None, spacing=None, flags=0, _world=None):
-    """swz_convert_dataset: the written data set in src (BIN, BINZ, LAS or ENTWINE_LAS node files) converted into dst in
-    another format, node files unpacked and packed on the device.  format, rgb_from, global_offset, chunk_points, ept,
+                    ept=None, tight_bounds=False, root_box=None, spacing=None, flags=0, lossy_source=False, source_flags=None,
+                    _world=None):
+    """swz_convert_dataset: the written data set in src (BIN, BINZ, LAS or ENTWINE_LAS node files; with lossy_source=True
+    also 3DTILES, whose .pnts files hold float positions, RGB and intensity only) converted into dst in another format, node
+    files unpacked and packed on the device.  source_flags: the raw word, instead of lossy_source.  format, rgb_from, global_offset, chunk_points, ept,
     tight_bounds, flags: as in Tiler.write_output; attrs: the columns to write, a subset of the source's (None: all it has);
     max_depth: only the nodes of depth <= max_depth; root_box ((min, max)) and spacing: the root box and spacing_at_root,
     overriding properties.json / ept.json of src -- required when src has neither.  Returns the stats as a dict (nodes,
@@ -798,7 +832,9 @@ def convert_dataset(ctx, src, dst, format, attrs=None, max_depth=None, rgb_from=
     given = root_box is not None
     p = _ConvertParams(out, -1 if max_depth is None else int(max_depth), 1 if given else 0,
                        _vec3(root_box[0] if given else (0, 0, 0)), _vec3(root_box[1] if given else (0, 0, 0)),
-                       float(spacing) if given else 0.0, (C.c_uint32 * 3)(0, 0, 0))
+                       float(spacing) if given else 0.0,
+                       int(source_flags) if source_flags is not None else (CONVERT_LOSSY_SOURCE if lossy_source else 0),
+                       (C.c_uint32 * 2)(0, 0))
     stats = _ConvertStats()
     if _world is not None:   # convert_dataset_world: (srs,)
         srs = _world[0]
@@ -1095,6 +1131,12 @@ def load_library():
     L.swz_bin_unpack_tile.argtypes = []
     L.swz_bin_unpack_tile.restype = C.c_uint32
     L.swz_bin_unpack_segments_device.argtypes = [vp, vp, C.c_uint64, C.POINTER(_BinSegment), C.c_uint64, vp, cols]
+    L.swz_pnts_unpack_tile.argtypes = []
+    L.swz_pnts_unpack_tile.restype = C.c_uint32
+    L.swz_pnts_unpack_segments_device.argtypes = [vp, vp, C.c_uint64, C.POINTER(_PntsSegment), C.c_uint64, vp, cols]
+    L.swz_pnts_unpack_segments_device.restype = C.c_int
+    L.swz_pnts_parse_image.argtypes = [vp, vp, C.c_uint64, _u64p, _u32p, _dp, _u64p, _u64p, _u64p]
+    L.swz_pnts_parse_image.restype = C.c_int
     L.swz_convert_dataset.argtypes = [vp, C.c_char_p, C.c_char_p, C.POINTER(_ConvertParams), C.POINTER(_ConvertStats)]
     L.swz_tiler_write_output.argtypes = [vp, C.c_char_p, C.POINTER(_OutputParams), C.POINTER(_OutputStats)]
     L.swz_output_chunks.argtypes = [C.c_uint64, _u64p, C.c_uint64, C.c_uint64, _u64p, _u64p]
@@ -1529,6 +1571,22 @@ class Context:
         cols = device_columns(d_attrs)
         self._check(self._lib.swz_bin_unpack_segments_device(self._ctx, C.c_void_p(d_raw), int(raw_bytes), segs, len(segments),
                                                              C.c_void_p(d_xyz), C.byref(cols)))
+
+    def pnts_unpack_segments_device(self, d_raw, raw_bytes, segments, d_xyz, d_attrs=None):
+        """swz_pnts_unpack_segments_device: the arrays of .pnts files (device memory, any alignment and order) -> positions
+        (the stored floats widened) and the rgb / intensity columns in one launch.  segments: dicts of first_row, count,
+        position_offset, rgb_offset, intensity_offset (absolute in d_raw) and attrs (names or a mask: the arrays the segment
+        holds); `reserved` is passed on.  d_xyz may be None; d_attrs: dict name -> device pointer of the columns to fill
+        (zeros where a segment lacks the array)."""
+        segs = (_PntsSegment * max(len(segments), 1))()
+        for i, g in enumerate(segments):
+            attrs = g.get("attrs", ())
+            mask = int(attrs) if isinstance(attrs, (int, np.integer)) else _pnts_mask(attrs)
+            segs[i] = _PntsSegment(int(g["first_row"]), int(g["count"]), int(g["position_offset"]), int(g.get("rgb_offset", 0)),
+                                   int(g.get("intensity_offset", 0)), mask, int(g.get("reserved", 0)))
+        cols = device_columns(d_attrs)
+        self._check(self._lib.swz_pnts_unpack_segments_device(self._ctx, C.c_void_p(d_raw), int(raw_bytes), segs, len(segments),
+                                                              C.c_void_p(d_xyz), C.byref(cols)))
 
     def convert_dataset(self, src, dst, format, **kwargs):
         """convert_dataset(self, src, dst, format, ...)"""

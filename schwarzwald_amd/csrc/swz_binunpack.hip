@@ -17,6 +17,7 @@
 #include "swz_convert.h"
 #include "swz_device.h"
 #include "swz_hostio.h"
+#include "swz_unpackstage.h"
 
 namespace swz {
 
@@ -24,8 +25,7 @@ constexpr uint32_t BINU_TILE = 256;                      // output rows per work
 constexpr uint32_t BINU_PIECES = SWZ_ATTR_COUNT + 1;     // positions, then the attribute arrays in file order
 constexpr uint64_t BINU_MAX_POINTS = 0xFFFFFFFFull - 65535ull;
 constexpr uint32_t BINU_MASK_ALL = (1u << SWZ_ATTR_COUNT) - 1u;
-// run e of a piece of width w begins at dword (w * rel_e) / 4 + 2 e of the stage (rel_e: its first row in the tile): a run
-// of L bytes is covered by at most (L + 6) / 4 <= L / 4 + 2 dwords, so the runs do not meet; one spare dword for the shifts
+// the stage of the widest piece (swz_unpackstage.h)
 constexpr uint32_t BINU_STAGE = 24 * BINU_TILE / 4 + 2 * BINU_TILE + 4;
 // nibble j: bytes of a row of the j-th attribute array in file order (FILE_ORDER / ATTR_BYTES of swz_hostio.h)
 constexpr uint64_t BINU_WIDTHS = 0x1112118112C3ull;
@@ -51,12 +51,6 @@ __device__ __host__ __forceinline__ uint32_t binu_prefix(uint32_t file_mask, uin
   return at;
 }
 
-// the four bytes at byte q of the stage
-__device__ __forceinline__ uint32_t binu_word(const uint32_t* stage, uint32_t q) {
-  const uint32_t w0 = stage[q >> 2], w1 = stage[(q >> 2) + 1u];
-  return (uint32_t)((((uint64_t)w1 << 32) | w0) >> (8u * (q & 3u)));
-}
-
 __global__ __launch_bounds__(BINU_TILE) void bin_unpack_kernel(BinUnpackArgs a) {
   __shared__ uint32_t s_first[BINU_TILE];  // first rows of the segments k0 .. k0 + BINU_TILE - 1 (past the table: no row)
   __shared__ uint32_t s_count[BINU_TILE];
@@ -67,12 +61,7 @@ __global__ __launch_bounds__(BINU_TILE) void bin_unpack_kernel(BinUnpackArgs a) 
   const uint32_t r0 = blockIdx.x * BINU_TILE;
   const uint32_t r1 = (uint32_t)min((uint64_t)r0 + BINU_TILE, (uint64_t)a.n);
 
-  // the segment of the tile's first row: the last one that begins at or before it (segment 0 begins at row 0)
-  uint32_t k0 = 0;
-  for (uint32_t hi = a.num_segs; hi - k0 > 1;) {
-    const uint32_t mid = k0 + (hi - k0) / 2;
-    if (a.segs[mid].first_row <= r0) k0 = mid; else hi = mid;
-  }
+  const uint32_t k0 = unpack_first_segment(a.segs, a.num_segs, r0);
   {
     const bool listed = k0 + t < a.num_segs;
     const BinUnpackSeg* sg = a.segs + k0 + t;
@@ -83,25 +72,11 @@ __global__ __launch_bounds__(BINU_TILE) void bin_unpack_kernel(BinUnpackArgs a) 
   }
   __syncthreads();
 
-  // the entries that hold rows of the tile: those that begin in front of r1 (every segment holds a point)
-  uint32_t nwin;
-  {
-    uint32_t l = 0, h = BINU_TILE;
-    while (l < h) {
-      const uint32_t mid = (l + h) / 2;
-      if (s_first[mid] < r1) l = mid + 1; else h = mid;
-    }
-    nwin = l;
-  }
+  const uint32_t nwin = unpack_window_size<BINU_TILE>(s_first, r1);
   // this lane's row and its entry
   const uint32_t r = r0 + t;
   const bool live = r < r1;
-  uint32_t my = 0;
-  if (live)
-    for (uint32_t hi = nwin; hi - my > 1;) {
-      const uint32_t mid = my + (hi - my) / 2;
-      if (s_first[mid] <= r) my = mid; else hi = mid;
-    }
+  const uint32_t my = live ? unpack_row_entry(s_first, nwin, r) : 0u;
   const uintptr_t raw_begin = (uintptr_t)a.raw, raw_end = raw_begin + a.raw_bytes;
 
   for (uint32_t piece = 0; piece < BINU_PIECES; ++piece) {
@@ -120,34 +95,7 @@ __global__ __launch_bounds__(BINU_TILE) void bin_unpack_kernel(BinUnpackArgs a) 
       *S = ((w * (*lo - r0)) >> 2) + 2u * e;
     };
 
-    // ---- the covering dwords of every run into the stage
-    const uint32_t span = ((w * (r1 - r0)) >> 2) + 2u * nwin + 2u;
-    for (uint32_t x = t; x < span; x += BINU_TILE) {
-      // the last entry whose run begins at or before stage dword x (entry 0's begins at 0)
-      uint32_t e = 0;
-      for (uint32_t hi = nwin; hi - e > 1;) {
-        const uint32_t mid = e + (hi - e) / 2;
-        if (((w * (max(s_first[mid], r0) - r0)) >> 2) + 2u * mid <= x) e = mid; else hi = mid;
-      }
-      uint32_t lo, len, S;
-      uintptr_t G;
-      run(e, &lo, &len, &G, &S);
-      if (len == 0u) continue;
-      const uintptr_t word0 = G & ~(uintptr_t)3;
-      const uint32_t slots = (uint32_t)((((G + (uintptr_t)w * len + 3u) & ~(uintptr_t)3) - word0) >> 2);
-      const uint32_t s = x - S;
-      if (s >= slots) continue;
-      const uintptr_t at = word0 + 4u * (uintptr_t)s;
-      uint32_t v;
-      if (at >= raw_begin && at + 4u <= raw_end) {
-        v = *reinterpret_cast<const uint32_t*>(at);
-      } else {  // the first or the last dword of the buffer: only the bytes inside it
-        v = 0;
-        for (uint32_t b = 0; b < 4u; ++b)
-          if (at + b >= raw_begin && at + b < raw_end) v |= (uint32_t)*reinterpret_cast<const uint8_t*>(at + b) << (8u * b);
-      }
-      s_stage[x] = v;
-    }
+    stage_fill<BINU_TILE>(s_stage, s_first, nwin, w, r0, r1, raw_begin, raw_end, run);
     __syncthreads();
 
     // ---- every lane its row's value: bit copies out of the stage, zeros where the segment lacks the array
@@ -163,26 +111,26 @@ __global__ __launch_bounds__(BINU_TILE) void bin_unpack_kernel(BinUnpackArgs a) 
           uint64_t* const o8 = reinterpret_cast<uint64_t*>(o);
 #pragma unroll
           for (uint32_t i = 0; i < 3u; ++i)
-            o8[i] = present ? ((uint64_t)binu_word(s_stage, q + 8u * i + 4u) << 32) | binu_word(s_stage, q + 8u * i) : 0ull;
+            o8[i] = present ? ((uint64_t)stage_word(s_stage, q + 8u * i + 4u) << 32) | stage_word(s_stage, q + 8u * i) : 0ull;
           break;
         }
         case 12: {
           uint32_t* const o4 = reinterpret_cast<uint32_t*>(o);
 #pragma unroll
-          for (uint32_t i = 0; i < 3u; ++i) o4[i] = present ? binu_word(s_stage, q + 4u * i) : 0u;
+          for (uint32_t i = 0; i < 3u; ++i) o4[i] = present ? stage_word(s_stage, q + 4u * i) : 0u;
           break;
         }
         case 8:
-          *reinterpret_cast<uint64_t*>(o) = present ? ((uint64_t)binu_word(s_stage, q + 4u) << 32) | binu_word(s_stage, q) : 0ull;
+          *reinterpret_cast<uint64_t*>(o) = present ? ((uint64_t)stage_word(s_stage, q + 4u) << 32) | stage_word(s_stage, q) : 0ull;
           break;
         case 3: {
-          const uint32_t v = present ? binu_word(s_stage, q) : 0u;
+          const uint32_t v = present ? stage_word(s_stage, q) : 0u;
           o[0] = (uint8_t)v;
           o[1] = (uint8_t)(v >> 8);
           o[2] = (uint8_t)(v >> 16);
           break;
         }
-        case 2: *reinterpret_cast<uint16_t*>(o) = present ? (uint16_t)binu_word(s_stage, q) : (uint16_t)0; break;
+        case 2: *reinterpret_cast<uint16_t*>(o) = present ? (uint16_t)stage_word(s_stage, q) : (uint16_t)0; break;
         default: o[0] = present ? reinterpret_cast<const uint8_t*>(s_stage)[q] : (uint8_t)0; break;
       }
     }

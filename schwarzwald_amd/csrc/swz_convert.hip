@@ -1,14 +1,17 @@
 // swz_convert.hip -- a written data set converted to another format in one call (swz_convert_dataset): the reference's
 // --converter mode (ConverterProcess::run, core/process/ConverterProcess.cpp).  The source is scanned (swz_dataset.hip), the
 // target is planned with the parts of swz_tiler_write_output (swz_toutput.h), and the node table is streamed chunk by chunk:
-// reader threads fill one of two page-locked images with the chunk's files (BINZ inflated, LAS as record ranges), the copy
-// stream moves it to the device, the unpack kernel (swz_binunpack.hip; LAS sources: the segment kernel of swz_tinput.hip)
-// makes chunk-local positions and columns of it, and output_stream packs, copies back and writes them in the target format.
+// reader threads fill one of two page-locked images with the chunk's files (BINZ inflated, LAS as record ranges, .pnts whole),
+// the copy stream moves it to the device, the unpack kernel (swz_binunpack.hip; LAS sources: the segment kernel of
+// swz_tinput.hip; .pnts sources, which SWZ_CONVERT_LOSSY_SOURCE admits: swz_pntsunpack.hip) makes chunk-local positions and columns of it, and output_stream packs, copies back and writes them in the target format.
 // The readers of chunk k + 1 run while chunk k is packed and written.
 //
 // Size limit: row numbers are chunk-local, so a data set may hold more than 2^32 points; only a chunk, and therefore a
 // node, is bound by 2^32 - 65536.  Device and host hold two raw images, one set of chunk-local arrays and two output images.
+#include <sys/stat.h>
+
 #include <climits>
+#include <cstddef>
 #include <cstdlib>
 
 #include <algorithm>
@@ -24,7 +27,7 @@
 #include "swz_tinput.h"
 #include "swz_toutput.h"
 
-static_assert(sizeof(swz_convert_params) == 128 && sizeof(swz_bin_segment) == 32 && sizeof(swz_dataset_info) == 88,
+static_assert(sizeof(swz_convert_params) == 128 && offsetof(swz_convert_params, source_flags) == 116 && sizeof(swz_bin_segment) == 32 && sizeof(swz_dataset_info) == 88,
               "the structs of the converter as include/swz_gpu.h and the bindings lay them out");
 
 namespace swz {
@@ -45,7 +48,8 @@ struct ConvertChunk {
   uint64_t rows = 0, raw_bytes = 0, table_at = 0, image_bytes = 0;
   InputBatch las;                  // LAS sources: segments and pieces as swz_tiler_add_las_files cuts them
   std::vector<BinUnpackSeg> segs;  // BIN, BINZ
-  std::vector<ReadPiece> pieces;   // BIN: parts of files; BINZ: whole files (bytes: what the stream inflates to)
+  std::vector<ReadPiece> pieces;   // BIN: parts of files; BINZ: whole files (bytes: what the stream inflates to); 3DTILES: whole files
+  std::vector<uint64_t> piece_row; // 3DTILES: the first row of a piece's file; its segment is filled by the piece's reader
 };
 
 static void build_chunk(const DatasetScan& scan, uint64_t k0, uint64_t k1, ConvertChunk* out) {
@@ -53,12 +57,17 @@ static void build_chunk(const DatasetScan& scan, uint64_t k0, uint64_t k1, Conve
   ch = ConvertChunk{};
   const int format = scan.info.format;
   const bool las = format == SWZ_OUT_LAS || format == SWZ_OUT_ENTWINE_LAS;
+  const bool pnts = format == SWZ_OUT_3DTILES;
   uint64_t at = 0;
   for (uint64_t k = k0; k < k1; ++k) {
     const uint64_t cnt = scan.count[k];
     if (!cnt) continue;
     uint64_t bytes;
-    if (las) {
+    if (pnts) {
+      bytes = scan.file_bytes[k];
+      ch.pieces.push_back({k, 0, bytes, at});
+      ch.piece_row.push_back(ch.rows);
+    } else if (las) {
       bytes = cnt * scan.layout[k].record_bytes;
       swz_las_segment sg{};
       sg.first_row = ch.rows;
@@ -83,7 +92,9 @@ static void build_chunk(const DatasetScan& scan, uint64_t k0, uint64_t k1, Conve
   }
   ch.raw_bytes = at;
   ch.table_at = (at + 15) & ~15ull;
-  ch.image_bytes = ch.table_at + (las ? ch.las.segs.size() * sizeof(swz_las_segment) : ch.segs.size() * sizeof(BinUnpackSeg));
+  ch.image_bytes = ch.table_at + (las    ? ch.las.segs.size() * sizeof(swz_las_segment)
+                                  : pnts ? ch.pieces.size() * sizeof(swz_pnts_segment)
+                                         : ch.segs.size() * sizeof(BinUnpackSeg));
   ch.las.points = ch.rows;
   ch.las.raw_bytes = ch.raw_bytes;
   ch.las.table_at = ch.table_at;
@@ -163,6 +174,42 @@ static void start_read(TicketRun& run, swz_ctx* c, const char* who, const Datase
   }, threads);
 }
 
+// the reader threads of a 3DTILES chunk: every file whole into the image, parsed there and checked against the scan; piece i
+// fills segment i of the table behind the files
+static void start_read_pnts(TicketRun& run, swz_ctx* c, const char* who, const DatasetScan* scan, const ConvertChunk* ch,
+                            unsigned char* image, long threads) {
+  run.start(c, ch->pieces.size(), [who, scan, ch, image](uint64_t i, std::string* err) {
+    const ReadPiece& p = ch->pieces[i];
+    const std::string& path = scan->path[p.file];
+    Fd f;
+    f.fd = open(path.c_str(), O_RDONLY | O_CLOEXEC);
+    struct stat sb;
+    if (f.fd < 0 || fstat(f.fd, &sb) != 0 || (uint64_t)sb.st_size != p.bytes || !pread_all(f.fd, image + p.image_at, p.bytes, 0)) {
+      *err = std::string(who) + ": cannot read " + path + ", or it is not the file that was scanned";
+      return (int)SWZ_ERR_BAD_ARG;
+    }
+    PntsImage pi;
+    std::string why;
+    if (pnts_parse_image(image + p.image_at, p.bytes, &pi, &why) != SWZ_OK) {
+      *err = std::string(who) + ": " + why + " in " + path;
+      return (int)SWZ_ERR_BAD_ARG;
+    }
+    if (pi.mask != scan->info.attribute_mask || pi.count != scan->count[p.file]) {
+      *err = std::string(who) + ": the header of " + path + " is not the one that was scanned";
+      return (int)SWZ_ERR_BAD_ARG;
+    }
+    swz_pnts_segment sg{};
+    sg.first_row = ch->piece_row[i];
+    sg.count = pi.count;
+    sg.position_offset = p.image_at + pi.position;
+    sg.rgb_offset = p.image_at + pi.rgb;
+    sg.intensity_offset = p.image_at + pi.intensity;
+    sg.mask = pi.mask;
+    memcpy(image + ch->table_at + i * sizeof(swz_pnts_segment), &sg, sizeof(sg));
+    return (int)SWZ_OK;
+  }, threads);
+}
+
 static bool same_dir(const char* a, const char* b) {
   if (strcmp(a, b) == 0) return true;
   char ra[PATH_MAX], rb[PATH_MAX];
@@ -180,13 +227,33 @@ static int convert(swz_ctx* c, const char* who, const char* src_dir, const char*
   SWZ_HIP(c, hipSetDevice(c->device));
 
   // ---- the source, then everything that is refused before anything is written
-  if (params->reserved[0] || params->reserved[1] || params->reserved[2])
+  if (params->source_flags & ~(uint32_t)SWZ_CONVERT_LOSSY_SOURCE) return refuse("an unknown bit in source_flags");
+  if (params->reserved[0] || params->reserved[1])
     return refuse(world ? "reserved must be 0 (--delete-source is not offered)"
                         : "reserved must be 0 (--delete-source and --source-projection are not offered: project while tiling)");
   DatasetScan scan;
   SWZ_TRY(dataset_scan(c, who, src_dir, params->max_depth, &scan));
   const int src_format = scan.info.format;
-  if (src_format == SWZ_OUT_3DTILES) return refuse("a 3DTILES source is not converted: .pnts files hold float positions and no attribute beyond RGB and intensity");
+  const bool pnts = src_format == SWZ_OUT_3DTILES;
+  if (pnts && !(params->source_flags & SWZ_CONVERT_LOSSY_SOURCE))
+    return refuse("a 3DTILES source is converted only with SWZ_CONVERT_LOSSY_SOURCE in source_flags: .pnts files hold float positions and no attribute beyond RGB and intensity");
+  if (pnts) {
+    // one frame for all files: a data set of swz_convert_dataset_world keeps every node relative to an origin of its own
+    bool have = false;
+    double rtc[3] = {0, 0, 0};
+    scan.file_bytes.assign(scan.path.size(), 0);
+    for (size_t k = 0; k < scan.path.size(); ++k) {
+      PntsImage pi;
+      std::string why;
+      const int st = pnts_read_head(scan.path[k].c_str(), &pi, &why);
+      if (st != SWZ_OK) return c->fail(st, std::string(who) + ": " + why);
+      if (have && memcmp(rtc, pi.rtc, sizeof(rtc)) != 0)
+        return refuse("the RTC_CENTER differs from the files before it (the positions of a data set of swz_convert_dataset_world are relative to an origin per node): " + scan.path[k]);
+      have = true;
+      memcpy(rtc, pi.rtc, sizeof(rtc));
+      scan.file_bytes[k] = pi.file_bytes;
+    }
+  }
   if (same_dir(src_dir, dst_dir)) return refuse("dst_dir is src_dir");
   swz_output_params op = params->out;
   if (world) {
@@ -287,6 +354,7 @@ static int convert(swz_ctx* c, const char* who, const char* src_dir, const char*
       build_chunk(scan, first[j], first[j + 1], &cc);
       unsigned char* image = static_cast<unsigned char*>(ib.host[ib.host[1] ? (j & 1) : 0]);
       if (las) las_start_read(readers, c, who, &cc.las, image, paths.data(), threads);
+      else if (pnts) start_read_pnts(readers, c, who, &scan, &cc, image, threads);
       else start_read(readers, c, who, &scan, &cc, image, threads);
     };
     // chunk j: its image is read -> to the device -> unpacked into the chunk-local arrays; then the readers go on with
@@ -305,6 +373,9 @@ static int convert(swz_ctx* c, const char* who, const char* src_dir, const char*
       SWZ_HIP(c, hipEventRecord(ib.copied[b], images.copy));
       if (las) {
         SWZ_TRY(las_launch_image(c, images.copy, ib.device[b], cc.las, nullptr, d_xyz, &src.in, op.attribute_mask, nullptr));
+      } else if (pnts) {
+        SWZ_TRY(pnts_unpack_launch(c, images.copy, ib.device[b], cc.raw_bytes, reinterpret_cast<const swz_pnts_segment*>(ib.device[b] + cc.table_at),
+                                   (uint32_t)cc.pieces.size(), (uint32_t)cc.rows, d_xyz, &src.in));
       } else {
         SWZ_TRY(bin_unpack_launch(c, images.copy, ib.device[b], cc.raw_bytes, reinterpret_cast<const BinUnpackSeg*>(ib.device[b] + cc.table_at),
                                   (uint32_t)cc.segs.size(), (uint32_t)cc.rows, d_xyz, &src.in));

@@ -23,7 +23,10 @@
 #include <string>
 #include <vector>
 
+#include <sys/stat.h>
+
 #include "swz_internal.h"
+#include "swz_convert.h"
 #include "swz_device.h"
 #include "swz_hostio.h"
 #include "swz_nodepack.h"
@@ -365,15 +368,6 @@ struct JsonCursor {
   }
 };
 
-struct PntsFile {
-  std::vector<unsigned char> data;
-  uint64_t count = 0;
-  uint32_t mask = 0;
-  double rtc[3] = {0, 0, 0};
-  uint64_t binary_at = 0, binary_bytes = 0;
-  uint64_t position = 0, rgb = 0, intensity = 0;  // offsets in the binary
-};
-
 static bool offset_ok(double v, uint64_t bytes, uint64_t binary_bytes, uint64_t* out) {
   if (!(v >= 0) || v != std::floor(v) || v > 4294967295.0) return false;
   const uint64_t o = (uint64_t)v;
@@ -382,20 +376,27 @@ static bool offset_ok(double v, uint64_t bytes, uint64_t binary_bytes, uint64_t*
   return true;
 }
 
-static int pnts_parse(swz_ctx* c, const char* path, PntsFile* f) {
-  SWZ_TRY(read_whole_file(c, path, &f->data));
-  const std::string where = std::string(" in ") + path;
-  if (f->data.size() < 28) return fail(c, SWZ_ERR_BAD_ARG, "shorter than a .pnts header" + where);
-  if (memcmp(f->data.data(), "pnts", 4) != 0) return fail(c, SWZ_ERR_BAD_ARG, "not a .pnts file (magic)" + where);
+// Every check of a .pnts file, on the first head_bytes bytes of a file of file_bytes bytes: head_bytes reaches at least to
+// the end of the feature-table JSON wherever the header's lengths add up to file_bytes (the whole file, or what pnts_read_head
+// read of it).  Nothing outside [head, head + head_bytes) is read.  What is wrong goes to *why; no context: reader threads
+// call this.
+static int pnts_parse_bytes(const unsigned char* head, uint64_t head_bytes, uint64_t file_bytes, PntsImage* f, std::string* why) {
+  auto refuse = [&](const char* what) {
+    *why = what;
+    return (int)SWZ_ERR_BAD_ARG;
+  };
+  *f = PntsImage{};
+  if (file_bytes < 28 || head_bytes < 28) return refuse("shorter than a .pnts header");
+  if (memcmp(head, "pnts", 4) != 0) return refuse("not a .pnts file (magic)");
   uint32_t h[6];
-  memcpy(h, f->data.data() + 4, 24);
-  if (h[0] != 1u) return fail(c, SWZ_ERR_BAD_ARG, "unknown .pnts version" + where);
+  memcpy(h, head + 4, 24);
+  if (h[0] != 1u) return refuse("unknown .pnts version");
   const uint64_t json_bytes = h[2], binary_bytes = h[3];
-  if ((uint64_t)h[1] != f->data.size() || 28ull + json_bytes + binary_bytes + h[4] + h[5] != (uint64_t)h[1])
-    return fail(c, SWZ_ERR_BAD_ARG, "the lengths of the header do not add up to the file" + where);
-  f->binary_at = 28 + json_bytes;
-  f->binary_bytes = binary_bytes;
-  JsonCursor js{reinterpret_cast<const char*>(f->data.data()) + 28, reinterpret_cast<const char*>(f->data.data()) + 28 + json_bytes};
+  if ((uint64_t)h[1] != file_bytes || 28ull + json_bytes + binary_bytes + h[4] + h[5] != (uint64_t)h[1])
+    return refuse("the lengths of the header do not add up to the file");
+  if (head_bytes < 28 + json_bytes) return refuse("the feature-table JSON was not read to its end");
+  const uint64_t binary_at = 28 + json_bytes;
+  JsonCursor js{reinterpret_cast<const char*>(head) + 28, reinterpret_cast<const char*>(head) + 28 + json_bytes};
   bool have_count = false, have_pos = false, have_rgb = false, have_int = false;
   double o_pos = 0, o_rgb = 0, o_int = 0;
   bool ok = js.eat('{');
@@ -447,13 +448,57 @@ static int pnts_parse(swz_ctx* c, const char* path, PntsFile* f) {
     js.ws();
     ok = js.p == js.end;  // only the padding may follow
   }
-  if (!ok || !have_count || !have_pos) return fail(c, SWZ_ERR_BAD_ARG, "cannot read the feature-table JSON" + where);
+  if (!ok || !have_count) return refuse("cannot read the feature-table JSON");
+  if (!have_pos) return refuse("the feature table has no POSITION array (POSITION_QUANTIZED is not read)");
   if (!offset_ok(o_pos, 12 * f->count, binary_bytes, &f->position) ||
       (have_rgb && !offset_ok(o_rgb, 3 * f->count, binary_bytes, &f->rgb)) ||
       (have_int && !offset_ok(o_int, 2 * f->count, binary_bytes, &f->intensity)))
-    return fail(c, SWZ_ERR_BAD_ARG, "an attribute array passes the end of the binary" + where);
+    return refuse("an attribute array passes the end of the binary");
+  f->position += binary_at;  // from the first byte of the file on
+  if (have_rgb) f->rgb += binary_at;
+  if (have_int) f->intensity += binary_at;
   f->mask = (have_rgb ? SWZ_PNTS_RGB : 0u) | (have_int ? SWZ_PNTS_INTENSITY : 0u);
+  f->file_bytes = file_bytes;
   return SWZ_OK;
+}
+
+int pnts_parse_image(const unsigned char* file, uint64_t file_bytes, PntsImage* out, std::string* why) {
+  return pnts_parse_bytes(file, file_bytes, file_bytes, out, why);
+}
+
+// the header and the feature-table JSON of a file, not its arrays; *why names the file
+int pnts_read_head(const char* path, PntsImage* out, std::string* why) {
+  Fd f;
+  f.fd = open(path, O_RDONLY | O_CLOEXEC);
+  struct stat sb;
+  if (f.fd < 0 || fstat(f.fd, &sb) != 0) {
+    *why = std::string("cannot open ") + path;
+    return SWZ_ERR_BAD_ARG;
+  }
+  const uint64_t file_bytes = (uint64_t)sb.st_size;
+  std::vector<unsigned char> head((size_t)std::min<uint64_t>(file_bytes, 28));
+  uint32_t json_bytes = 0;
+  bool ok = pread_all(f.fd, head.data(), head.size(), 0);
+  if (ok && head.size() == 28) {
+    memcpy(&json_bytes, head.data() + 12, 4);
+    head.resize((size_t)std::min<uint64_t>(file_bytes, 28ull + json_bytes));
+    ok = pread_all(f.fd, head.data() + 28, head.size() - 28, 28);
+  }
+  if (!ok) {
+    *why = std::string("cannot read the header of ") + path;
+    return SWZ_ERR_BAD_ARG;
+  }
+  const int st = pnts_parse_bytes(head.data(), head.size(), file_bytes, out, why);
+  if (st != SWZ_OK) *why += std::string(" in ") + path;
+  return st;
+}
+
+// the whole file and where its arrays are
+static int pnts_parse(swz_ctx* c, const char* path, std::vector<unsigned char>* data, PntsImage* f) {
+  SWZ_TRY(read_whole_file(c, path, data));
+  std::string why;
+  const int st = pnts_parse_bytes(data->data(), data->size(), data->size(), f, &why);
+  return st == SWZ_OK ? SWZ_OK : fail(c, st, why + " in " + path);
 }
 
 // ---------------------------------------------------------------------------------- tileset JSON
@@ -714,8 +759,10 @@ int swz_pnts_persist_nodes_rtc(swz_ctx* c, const char* dir, uint64_t num_nodes, 
 
 int swz_pnts_read_header(swz_ctx* c, const char* path, uint64_t* count_out, uint32_t* mask_out, double rtc_center_out[3]) {
   if (!path || !count_out || !mask_out) return fail(c, SWZ_ERR_BAD_ARG, "swz_pnts_read_header: NULL argument");
-  PntsFile f;
-  SWZ_TRY(pnts_parse(c, path, &f));
+  PntsImage f;
+  std::string why;
+  const int st = pnts_read_head(path, &f, &why);
+  if (st != SWZ_OK) return fail(c, st, why);
   *count_out = f.count;
   *mask_out = f.mask;
   if (rtc_center_out)
@@ -723,22 +770,41 @@ int swz_pnts_read_header(swz_ctx* c, const char* path, uint64_t* count_out, uint
   return SWZ_OK;
 }
 
+int swz_pnts_parse_image(swz_ctx* c, const void* file, uint64_t file_bytes, uint64_t* count_out, uint32_t* mask_out,
+                         double rtc_center_out[3], uint64_t* position_offset_out, uint64_t* rgb_offset_out,
+                         uint64_t* intensity_offset_out) {
+  if (!file && file_bytes) return fail(c, SWZ_ERR_BAD_ARG, "swz_pnts_parse_image: NULL image");
+  PntsImage f;
+  std::string why;
+  const int st = pnts_parse_image(static_cast<const unsigned char*>(file), file_bytes, &f, &why);
+  if (st != SWZ_OK) return fail(c, st, "swz_pnts_parse_image: " + why);
+  if (count_out) *count_out = f.count;
+  if (mask_out) *mask_out = f.mask;
+  if (rtc_center_out)
+    for (int k = 0; k < 3; ++k) rtc_center_out[k] = f.rtc[k];
+  if (position_offset_out) *position_offset_out = f.position;
+  if (rgb_offset_out) *rgb_offset_out = f.rgb;
+  if (intensity_offset_out) *intensity_offset_out = f.intensity;
+  return SWZ_OK;
+}
+
 int swz_pnts_read_node(swz_ctx* c, const char* path, double* xyz_out, const swz_attribute_columns* columns_out) {
   if (!path) return fail(c, SWZ_ERR_BAD_ARG, "swz_pnts_read_node: NULL path");
-  PntsFile f;
-  SWZ_TRY(pnts_parse(c, path, &f));
-  const unsigned char* bin = f.data.data() + f.binary_at;
+  std::vector<unsigned char> data;
+  PntsImage f;
+  SWZ_TRY(pnts_parse(c, path, &data, &f));
+  const unsigned char* file = data.data();
   if (xyz_out) {
     for (uint64_t i = 0; i < 3 * f.count; ++i) {
       float v;
-      memcpy(&v, bin + f.position + 4 * i, 4);
+      memcpy(&v, file + f.position + 4 * i, 4);
       xyz_out[i] = v;  // the format is lossy: the stored float, widened
     }
   }
   if (columns_out && columns_out->column[SWZ_ATTR_RGB] && (f.mask & SWZ_PNTS_RGB))
-    memcpy(columns_out->column[SWZ_ATTR_RGB], bin + f.rgb, (size_t)(3 * f.count));
+    memcpy(columns_out->column[SWZ_ATTR_RGB], file + f.rgb, (size_t)(3 * f.count));
   if (columns_out && columns_out->column[SWZ_ATTR_INTENSITY] && (f.mask & SWZ_PNTS_INTENSITY))
-    memcpy(columns_out->column[SWZ_ATTR_INTENSITY], bin + f.intensity, (size_t)(2 * f.count));
+    memcpy(columns_out->column[SWZ_ATTR_INTENSITY], file + f.intensity, (size_t)(2 * f.count));
   return SWZ_OK;
 }
 

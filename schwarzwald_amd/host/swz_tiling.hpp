@@ -153,12 +153,16 @@ private:
 
 // ConverterProcess::run (core/process/ConverterProcess.cpp) in one call: the written data set in src_dir (BIN, BINZ, LAS or
 // ENTWINE_LAS node files; root box and spacing from its properties.json or ept.json unless params gives them) converted into
-// dst_dir in the format of params.out, node files unpacked and packed on the device (swz_convert_dataset).  A refusal -- a
-// .pnts source, dst_dir equal to src_dir, a mask outside the source's, no root box -- throws with the library's text.
+// dst_dir in the format of params.out, node files unpacked and packed on the device (swz_convert_dataset).  lossy_source (or
+// SWZ_CONVERT_LOSSY_SOURCE in params.source_flags) admits a 3DTILES source, whose .pnts files hold float positions, RGB and
+// intensity only (the reference's converter reads them through Cesium3DTilesPersistence).  A refusal -- a .pnts source
+// without the switch, dst_dir equal to src_dir, a mask outside the source's, no root box -- throws with the library's text.
 inline swz_convert_stats convert_dataset(Context& ctx, const std::string& src_dir, const std::string& dst_dir,
-                                         const swz_convert_params& params) {
+                                         const swz_convert_params& params, bool lossy_source = false) {
+  swz_convert_params p = params;
+  if (lossy_source) p.source_flags |= SWZ_CONVERT_LOSSY_SOURCE;
   swz_convert_stats stats{};
-  ctx.check(swz_convert_dataset(ctx.get(), src_dir.c_str(), dst_dir.c_str(), &params, &stats));
+  ctx.check(swz_convert_dataset(ctx.get(), src_dir.c_str(), dst_dir.c_str(), &p, &stats));
   return stats;
 }
 
@@ -166,11 +170,14 @@ inline swz_convert_stats convert_dataset(Context& ctx, const std::string& src_di
 // ConverterArguments::source_projection): src_dir converted into 3D Tiles in the world frame -- positions mapped to ECEF on the
 // device, every .pnts file relative to its node's own origin, tile volumes as oriented boxes (swz_convert_dataset_world).
 // projection == nullptr is the reference's IdentityTransform.  params.out.format must be SWZ_OUT_3DTILES and
-// params.out.global_offset zero; a refusal throws with the library's text.
+// params.out.global_offset zero; lossy_source as in convert_dataset; a refusal throws with the library's text.
 inline swz_convert_stats convert_dataset_world(Context& ctx, const std::string& src_dir, const std::string& dst_dir,
-                                               const swz_convert_params& params, const SourceProjection* projection = nullptr) {
+                                               const swz_convert_params& params, const SourceProjection* projection = nullptr,
+                                               bool lossy_source = false) {
+  swz_convert_params p = params;
+  if (lossy_source) p.source_flags |= SWZ_CONVERT_LOSSY_SOURCE;
   swz_convert_stats stats{};
-  ctx.check(swz_convert_dataset_world(ctx.get(), src_dir.c_str(), dst_dir.c_str(), &params, projection ? projection->srs() : nullptr,
+  ctx.check(swz_convert_dataset_world(ctx.get(), src_dir.c_str(), dst_dir.c_str(), &p, projection ? projection->srs() : nullptr,
                                       &stats));
   return stats;
 }

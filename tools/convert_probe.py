@@ -8,10 +8,12 @@ intensity) writes a BIN data set with write_output + write_properties; then, per
 --source-projection DEF: the 3DTILES leg is also timed through convert_dataset_world (positions mapped to ECEF with DEF, files
 relative to their nodes' origins, oriented boxes), beside the existing call: row["convert_world"].  The unit cube is read as
 coordinates of DEF (for a UTM zone: a metre beside the false origin, on the equator); the map costs what it costs anywhere.
+--source-format 3DTILES: the tiler also writes a 3DTILES data set, and every target is converted from it as well
+(convert_dataset(..., lossy_source=True)), timed beside the BIN source: row["convert_from_3DTILES"].
 Everything goes into fresh directories under --dir (default: the system's temporary directory).  The work runs in one child
 process under `timeout`.
 usage: convert_probe.py [points] [--batches K] [--formats BIN,LAS,...] [--dir DIR] [--host-nodes N] [--json FILE]
-                        [--source-projection DEF]"""
+                        [--source-projection DEF] [--source-format 3DTILES]"""
 import json
 import os
 import shutil
@@ -53,7 +55,7 @@ def host_recipe(swz, src, dst, fmt, nodes, bmin, bmax, limit):
     return time.perf_counter() - t0, done
 
 
-def step(n, batches, formats, base, host_nodes, projection):
+def step(n, batches, formats, base, host_nodes, projection, source_format=None):
     import numpy as np
     import schwarzwald_amd as swz
     ctx = swz.Context(0)
@@ -75,6 +77,12 @@ def step(n, batches, formats, base, host_nodes, projection):
     out = dict(points=n, batches=batches, stored=stored, nodes=int(info["num_nodes"]), tile_s=time.perf_counter() - t0,
                write_bin=t.write_output(src, "BIN", attrs=NAMES))
     t.write_properties(src)
+    src_tiles = os.path.join(work, "src_tiles")
+    if source_format == "3DTILES":
+        out["write_3dtiles"] = t.write_output(src_tiles, "3DTILES", attrs=NAMES)
+        t.write_properties(src_tiles)
+    elif source_format:
+        raise SystemExit("--source-format: only 3DTILES is timed beside the BIN source")
     print("CONVERT_PROBE " + json.dumps(dict(source=out)), flush=True)
     for fmt in formats:
         row = dict(format=fmt)
@@ -82,6 +90,8 @@ def step(n, batches, formats, base, host_nodes, projection):
                 ("write_output", lambda d: t.write_output(d, fmt, attrs=NAMES))]
         if projection and fmt == "3DTILES":
             legs.append(("convert_world", lambda d: swz.convert_dataset_world(ctx, src, d, projection, attrs=NAMES)))
+        if source_format == "3DTILES":
+            legs.append(("convert_from_3DTILES", lambda d: swz.convert_dataset(ctx, src_tiles, d, fmt, attrs=NAMES, lossy_source=True)))
         for name, fn in legs:
             for rep in ("warm", "timed"):   # the first run pays allocations and the page cache
                 d = os.path.join(work, name + "_" + fmt)
@@ -94,6 +104,8 @@ def step(n, batches, formats, base, host_nodes, projection):
         row["host_recipe"] = dict(measured_s=secs, points=done, scaled_to_all_s=secs * stored / max(done, 1))
         row["convert_over_write_output"] = row["convert"]["wall_ms"] / row["write_output"]["wall_ms"]
         row["host_over_convert"] = row["host_recipe"]["scaled_to_all_s"] * 1e3 / row["convert"]["wall_ms"]
+        if "convert_from_3DTILES" in row:
+            row["from_3dtiles_over_from_bin"] = row["convert_from_3DTILES"]["wall_ms"] / row["convert"]["wall_ms"]
         if "convert_world" in row:
             row["world_over_convert"] = row["convert_world"]["wall_ms"] / row["convert"]["wall_ms"]
         print("CONVERT_PROBE " + json.dumps(row), flush=True)
@@ -105,7 +117,8 @@ def step(n, batches, formats, base, host_nodes, projection):
 def main():
     args = sys.argv[1:]
     if args and args[0] == "--step":
-        return step(int(args[1]), int(args[2]), args[3].split(","), args[4] or None, int(args[5]), args[6] or None)
+        return step(int(args[1]), int(args[2]), args[3].split(","), args[4] or None, int(args[5]), args[6] or None,
+                    (args[7] if len(args) > 7 else "") or None)
 
     def option(name, default):
         return args[args.index(name) + 1] if name in args else default
@@ -113,7 +126,8 @@ def main():
     limit = str(max(300, n // 50_000))
     # one child under its own time limit; check=True: a failure ends the script here
     r = subprocess.run(["timeout", "-k", "10", limit, sys.executable, os.path.abspath(__file__), "--step", str(n), option("--batches", "10"),
-                        option("--formats", ",".join(FORMATS)), option("--dir", ""), option("--host-nodes", "0"), option("--source-projection", "")], check=True,
+                        option("--formats", ",".join(FORMATS)), option("--dir", ""), option("--host-nodes", "0"), option("--source-projection", ""),
+                        option("--source-format", "")], check=True,
                        stdout=subprocess.PIPE, text=True)
     results = [json.loads(l[len("CONVERT_PROBE "):]) for l in r.stdout.splitlines() if l.startswith("CONVERT_PROBE ")]
     for row in results:
