@@ -1103,6 +1103,67 @@ int swz_pnts_unpack_segments_device(swz_ctx* ctx, const uint8_t* d_raw, uint64_t
                                     uint64_t num_segments, double* d_xyz_out, const swz_attribute_columns* d_out);
 int swz_convert_dataset(swz_ctx* ctx, const char* src_dir, const char* dst_dir, const swz_convert_params* params,
                         swz_convert_stats* stats);
+/* ---- a written data set queried: the points of a closed box down to a chosen depth, selected on the device.
+ *   swz_box_select_device: the stable compaction of the rows with box_min[a] <= p[a] <= box_max[a] on all three axes -- plain
+ *     double compares on the stored positions, no tolerance, a NaN coordinate is outside.  Output row i is the i-th selected
+ *     input row: its position, every column of attribute_mask (rows of 1, 2, 3, 8 and 12 bytes; columns aligned to their
+ *     element as for swz_bin_unpack_segments_device) and, where d_row_out is given, its input row number.  Two launches
+ *     around the library's scan: a count per tile of swz_box_select_tile() rows (wave ballot and popcount), the exclusive
+ *     scan of the tile counts, whose total the host reads, and a scatter that evaluates the predicate again, ranks inside
+ *     the tile and stores the tile's compacted positions out of LDS as consecutive words.  No atomic decides a place: the
+ *     same bytes on every run.  Exactly the rows [0, *count_out) of every output are written, nothing is read from them.
+ *     d_xyz_out == NULL with capacity == 0 counts only.  *count_out > capacity is SWZ_ERR_BAD_ARG ("capacity ..."):
+ *     *count_out holds the needed number and no byte of the outputs is touched.  SWZ_ERR_BAD_ARG before anything is
+ *     launched for: n above 2^32 - 65536, a mask bit that does not exist or lacks its input or (unless counting) output
+ *     column, box_min > box_max or a bound that is not finite, an output (capacity rows) that overlaps an input (n rows),
+ *     a misaligned array.  n == 0 launches nothing and counts 0.
+ *   swz_dataset_query_nodes (host; ctx only carries the error text): the nodes of dir a query reads, in the scanned table's
+ *     order (level, Morton index).  Depth is as swz_dataset_scan counts it.  A node is dropped only if its box cannot hold a
+ *     point of the query box: the box is swz_node_bounds on the root box of properties.json / ept.json, widened on every
+ *     face by two key cells (2^-20 of the root's side: positions are tiled by their key, whose cell edges are rounded) and
+ *     by the rounding of its own bounds; for LAS sources also by the file's scale on that axis (stored points are rounded
+ *     to the scale's grid), for a 3DTILES source moved by the files' RTC_CENTER -- the stored positions are relative to it
+ *     -- and widened by the float rounding of the bounds.  points_bound_out: the sum of the kept nodes' counts, the
+ *     capacity that always suffices.  level_out / key_out / count_out may all be NULL (only the numbers), else max_nodes
+ *     must hold the kept nodes.  Refused: everything swz_dataset_scan and swz_convert_dataset refuse of a source (LAZ,
+ *     cloud.js, a 3DTILES source without SWZ_CONVERT_LOSSY_SOURCE, .pnts files whose RTC_CENTER differ, ...), a source
+ *     without a root box, box_min > box_max or a bound that is not finite, an unknown bit in source_flags, reserved != 0.
+ *   swz_dataset_query: streams the kept nodes as swz_convert_dataset streams its source -- chunks of whole nodes of at most
+ *     chunk_points points (0: the default of swz_output_params), reader threads into two page-locked images, the copy
+ *     stream, the source format's unpack into chunk-local arrays, chunk j + 1 read while chunk j is selected -- and runs
+ *     swz_box_select_device on every chunk into the caller's arrays at the running offset.  The output order is the node
+ *     table's, then the file's: defined byte for byte.  attribute_mask: a subset of the source's, ~0u = all it holds.
+ *     d_node_out (may be NULL): per output point the index of its node in swz_dataset_query_nodes' table.  If the running
+ *     total would pass capacity the stream stops after that chunk's count with the "capacity" refusal (*count_out: the
+ *     total up to and including that chunk); nothing is written at or beyond capacity rows.  d_xyz_out == NULL with
+ *     capacity == 0 counts only.  A file that changed since the scan or cannot be read stops the stream and is named.
+ *     Device and host hold two raw images and one set of chunk-local arrays whatever the data set's size.  Not offered: a
+ *     multi-GPU driver, frustum or polygon queries. */
+typedef struct {
+  double box_min[3], box_max[3]; /* closed */
+  int32_t max_depth;             /* < 0: every node; else nodes of depth <= max_depth, as swz_dataset_scan counts depth */
+  uint32_t attribute_mask;       /* ~0u: all the source holds */
+  uint32_t source_flags;         /* SWZ_CONVERT_LOSSY_SOURCE admits a 3DTILES source, as in the converter */
+  uint32_t reserved;             /* 0 */
+  uint64_t chunk_points;         /* 0: the library's default, as in swz_output_params */
+} swz_query_params;
+typedef struct {
+  uint64_t nodes_scanned, nodes_read, points_read, points_out, bytes_read, chunks;
+  double read_ms, unpack_ms, select_ms, copy_ms, wall_ms;
+} swz_query_stats;
+uint32_t swz_box_select_tile(void); /* rows one workgroup takes; tests place their edges by it */
+int swz_box_select_device(swz_ctx* ctx, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t attribute_mask,
+                          const double box_min[3], const double box_max[3], uint64_t capacity, double* d_xyz_out,
+                          const swz_attribute_columns* d_out, uint32_t* d_row_out /* may be NULL: the input row of every output row */,
+                          uint64_t* count_out);
+int swz_dataset_query_nodes(swz_ctx* ctx, const char* dir, const swz_query_params* params, uint64_t max_nodes, int8_t* level_out,
+                            uint64_t* key_out, uint64_t* count_out, uint64_t* num_out, uint64_t* points_bound_out);
+/* swz_dataset_query_nodes without a context: the text of a refusal goes into why_out (why_bytes bytes, may be NULL) */
+int swz_dataset_query_nodes_why(const char* dir, const swz_query_params* params, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out,
+                                uint64_t* count_out, uint64_t* num_out, uint64_t* points_bound_out, char* why_out, uint64_t why_bytes);
+int swz_dataset_query(swz_ctx* ctx, const char* dir, const swz_query_params* params, uint64_t capacity, double* d_xyz_out,
+                      const swz_attribute_columns* d_out, uint32_t* d_node_out /* may be NULL */, uint64_t* count_out,
+                      swz_query_stats* stats);
 /* ---- a source projection (the reference's --source-projection: Proj4Transform, core/util/Transformation.cpp:74-211, source
  * -> "+proj=geocent +datum=WGS84").  PROJ is not linked: the library maps the projection families LAS data comes in itself,
  * in double, and refuses every other definition by name.

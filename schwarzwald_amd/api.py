@@ -854,6 +854,85 @@ def convert_dataset_world(ctx, src, dst, source_projection=None, format="3DTILES
     return convert_dataset(ctx, src, dst, format, _world=(_as_srs(source_projection),), **kwargs)
 
 
+# ---- a written data set queried by box and depth (swz_box_select_device, swz_dataset_query_nodes, swz_dataset_query)
+class _QueryParams(C.Structure):
+    _fields_ = [("box_min", C.c_double * 3), ("box_max", C.c_double * 3), ("max_depth", C.c_int32), ("attribute_mask", C.c_uint32),
+                ("source_flags", C.c_uint32), ("reserved", C.c_uint32), ("chunk_points", C.c_uint64)]
+
+
+class _QueryStats(C.Structure):
+    _fields_ = [("nodes_scanned", C.c_uint64), ("nodes_read", C.c_uint64), ("points_read", C.c_uint64), ("points_out", C.c_uint64),
+                ("bytes_read", C.c_uint64), ("chunks", C.c_uint64), ("read_ms", C.c_double), ("unpack_ms", C.c_double),
+                ("select_ms", C.c_double), ("copy_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+def box_select_tile():
+    """Rows one workgroup of box_select_device takes (tests place their edges by it)."""
+    return int(load_library().swz_box_select_tile())
+
+
+def _query_params(box_min, box_max, max_depth, attrs, lossy_source, chunk_points, source_flags=None, reserved=0):
+    return _QueryParams(_vec3(box_min), _vec3(box_max), -1 if max_depth is None else int(max_depth),
+                        0xFFFFFFFF if attrs is None else _las_mask(attrs),
+                        int(source_flags) if source_flags is not None else (CONVERT_LOSSY_SOURCE if lossy_source else 0),
+                        int(reserved), int(chunk_points))
+
+
+def dataset_query_nodes(directory, box_min, box_max, max_depth=None, lossy_source=False, source_flags=None, reserved=0):
+    """swz_dataset_query_nodes (host, no GPU): the nodes of the written data set in directory that a query of the closed box
+    [box_min, box_max] reads, as dict(level, key, count -- in the order of dataset_scan --, points_bound: the sum of the
+    counts, the capacity that always suffices).  A node drops out only if its widened box misses the query box.  max_depth:
+    only the nodes of depth <= max_depth; lossy_source: admits a 3DTILES source (source_flags: the raw word instead;
+    reserved is passed on).  A refusal raises SwzError with the library's text."""
+    L = load_library()
+    p = _query_params(box_min, box_max, max_depth, None, lossy_source, 0, source_flags, reserved)
+    num, bound = C.c_uint64(), C.c_uint64()
+    why = C.create_string_buffer(4096)
+    st = L.swz_dataset_query_nodes_why(os.fsencode(directory), C.byref(p), 0, None, None, None, C.byref(num), C.byref(bound), why, len(why))
+    if st != 0:
+        raise SwzError(st, why.value.decode(errors="replace"))
+    cap = max(int(num.value), 1)
+    nl, nk, nc = np.empty(cap, dtype=np.int8), np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint64)
+    st = L.swz_dataset_query_nodes_why(os.fsencode(directory), C.byref(p), cap, nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p),
+                                       nc.ctypes.data_as(_u64p), C.byref(num), C.byref(bound), why, len(why))
+    if st != 0:
+        raise SwzError(st, why.value.decode(errors="replace"))
+    m = int(num.value)
+    return dict(level=nl[:m].copy(), key=nk[:m].copy(), count=nc[:m].copy(), points_bound=int(bound.value))
+
+
+def dataset_query(ctx, directory, box_min, box_max, max_depth=None, attrs=None, lossy_source=False, chunk_points=0, return_nodes=False,
+                  capacity=None):
+    """swz_dataset_query: the points of the written data set in directory inside the closed box [box_min, box_max], of the nodes
+    of depth <= max_depth (None: all), streamed from the node files and selected on the device.  attrs: the columns wanted, a
+    subset of the source's (None: all it has); lossy_source: admits a 3DTILES source; chunk_points: as in Tiler.write_output.
+    The outputs are torch tensors on the context's device with points_bound rows (dataset_query_nodes; capacity: another row
+    count -- one that is too small is refused), trimmed to the count: dict(xyz, <column names>, node (with return_nodes: per
+    point the index into dataset_query_nodes' table, else None), count, stats (the fields of swz_query_stats))."""
+    import torch
+
+    table = dataset_query_nodes(directory, box_min, box_max, max_depth, lossy_source)
+    names = attribute_names(dataset_scan(directory, max_depth)["attribute_mask"]) if attrs is None else list(attrs)
+    rows = int(table["points_bound"]) if capacity is None else int(capacity)
+    dev = torch.device("cuda", ctx.device)
+    xyz = torch.empty((max(rows, 1), 3), dtype=torch.float64, device=dev)
+    cols = {}
+    for name in names:
+        _, dt, width = ATTRIBUTES[name]
+        cols[name] = torch.empty((max(rows, 1), width) if width > 1 else (max(rows, 1),), dtype=getattr(torch, np.dtype(dt).name), device=dev)
+    node = torch.empty(max(rows, 1), dtype=torch.int32, device=dev) if return_nodes else None
+    p = _query_params(box_min, box_max, max_depth, names, lossy_source, chunk_points)
+    d_cols = device_columns({k: v.data_ptr() for k, v in cols.items()})
+    count, stats = C.c_uint64(), _QueryStats()
+    ctx._check(ctx._lib.swz_dataset_query(ctx._ctx, os.fsencode(directory), C.byref(p), rows, C.c_void_p(xyz.data_ptr()), C.byref(d_cols),
+                                          C.c_void_p(node.data_ptr()) if return_nodes else None, C.byref(count), C.byref(stats)))
+    m = int(count.value)
+    out = dict(xyz=xyz[:m], node=node[:m] if return_nodes else None, count=m,
+               stats={k: getattr(stats, k) for k, _ in _QueryStats._fields_})
+    out.update({k: v[:m] for k, v in cols.items()})
+    return out
+
+
 LAS_SCAN_SKIP_UNREADABLE = 1
 
 
@@ -1138,6 +1217,15 @@ def load_library():
     L.swz_pnts_parse_image.argtypes = [vp, vp, C.c_uint64, _u64p, _u32p, _dp, _u64p, _u64p, _u64p]
     L.swz_pnts_parse_image.restype = C.c_int
     L.swz_convert_dataset.argtypes = [vp, C.c_char_p, C.c_char_p, C.POINTER(_ConvertParams), C.POINTER(_ConvertStats)]
+    L.swz_box_select_tile.argtypes = []
+    L.swz_box_select_tile.restype = C.c_uint32
+    L.swz_box_select_device.argtypes = [vp, vp, C.c_uint64, cols, C.c_uint32, _dp, _dp, C.c_uint64, vp, cols, vp, _u64p]
+    L.swz_dataset_query_nodes.argtypes = [vp, C.c_char_p, C.POINTER(_QueryParams), C.c_uint64, _i8p, _u64p, _u64p, _u64p, _u64p]
+    L.swz_dataset_query_nodes_why.argtypes = [C.c_char_p, C.POINTER(_QueryParams), C.c_uint64, _i8p, _u64p, _u64p, _u64p, _u64p, C.c_char_p,
+                                              C.c_uint64]
+    L.swz_dataset_query.argtypes = [vp, C.c_char_p, C.POINTER(_QueryParams), C.c_uint64, vp, cols, vp, _u64p, C.POINTER(_QueryStats)]
+    for name in ("swz_box_select_device", "swz_dataset_query_nodes", "swz_dataset_query_nodes_why", "swz_dataset_query"):
+        getattr(L, name).restype = C.c_int
     L.swz_tiler_write_output.argtypes = [vp, C.c_char_p, C.POINTER(_OutputParams), C.POINTER(_OutputStats)]
     L.swz_output_chunks.argtypes = [C.c_uint64, _u64p, C.c_uint64, C.c_uint64, _u64p, _u64p]
     L.swz_merge_shard_node_tables.argtypes = [C.c_int, _u64p, C.POINTER(_i8p), C.POINTER(_u64p), C.POINTER(_u64p), C.c_uint64, _i8p,
@@ -1324,6 +1412,7 @@ class Context:
     def __init__(self, device=0):
         self._lib = load_library()
         self._ctx = C.c_void_p()
+        self.device = int(device)
         st = self._lib.swz_create(C.byref(self._ctx), int(device))
         if st != 0:
             raise SwzError(st, self._lib.swz_last_error(None).decode())
@@ -1587,6 +1676,28 @@ class Context:
         cols = device_columns(d_attrs)
         self._check(self._lib.swz_pnts_unpack_segments_device(self._ctx, C.c_void_p(d_raw), int(raw_bytes), segs, len(segments),
                                                               C.c_void_p(d_xyz), C.byref(cols)))
+
+    def box_select_device(self, d_xyz, n, box_min, box_max, capacity, d_xyz_out, d_attrs=None, d_attrs_out=None, attrs=None,
+                          d_row_out=None):
+        """swz_box_select_device: the rows of d_xyz (n rows on the device) inside the closed box [box_min, box_max], compacted
+        in their order into d_xyz_out, with the columns attrs (names or a mask; None: those of d_attrs) moved from d_attrs to
+        d_attrs_out (dicts name -> device pointer) and, where d_row_out is given, every output row's input row (u32).
+        d_xyz_out None with capacity 0 counts only.  Returns the count; a count above capacity raises SwzError ("capacity")
+        whose `needed` attribute is the count, and touches no output."""
+        mask = _las_mask(d_attrs.keys() if d_attrs else ()) if attrs is None else (int(attrs) if isinstance(attrs, (int, np.integer)) else _las_mask(attrs))
+        cin, cout = device_columns(d_attrs), device_columns(d_attrs_out)
+        count = C.c_uint64()
+        st = self._lib.swz_box_select_device(self._ctx, C.c_void_p(d_xyz), int(n), C.byref(cin), mask, _vec3(box_min), _vec3(box_max),
+                                             int(capacity), C.c_void_p(d_xyz_out), C.byref(cout), C.c_void_p(d_row_out), C.byref(count))
+        if st != 0:
+            err = SwzError(st, self._lib.swz_last_error(self._ctx).decode())
+            err.needed = int(count.value)
+            raise err
+        return int(count.value)
+
+    def dataset_query(self, directory, box_min, box_max, **kwargs):
+        """dataset_query(self, directory, box_min, box_max, ...)"""
+        return dataset_query(self, directory, box_min, box_max, **kwargs)
 
     def convert_dataset(self, src, dst, format, **kwargs):
         """convert_dataset(self, src, dst, format, ...)"""

@@ -1,10 +1,12 @@
 // swz_convert.h -- what the parts of swz_convert_dataset share: the scanned source (swz_dataset.hip), the launch of the BIN
-// unpack kernel on a stream (swz_binunpack.hip) and the call itself (swz_convert.hip).
+// unpack kernel on a stream (swz_binunpack.hip), the stream of a source's chunks onto the device (swz_source.hip), which
+// swz_dataset_query (swz_query.hip) runs as well, and the call itself (swz_convert.hip).
 #pragma once
 #include <string>
 #include <vector>
 
 #include "swz_internal.h"
+#include "swz_tinput.h"
 
 namespace swz {
 
@@ -52,5 +54,56 @@ int pnts_read_head(const char* path, PntsImage* out, std::string* why);
 // the .pnts unpack kernel (swz_pntsunpack.hip) on `stream` for a checked table on the device whose segments all hold points
 int pnts_unpack_launch(swz_ctx* c, hipStream_t stream, const uint8_t* d_raw, uint64_t raw_bytes, const swz_pnts_segment* d_table,
                        uint32_t num_segs, uint32_t rows, double* d_xyz_out, const swz_attribute_columns* d_out);
+
+// ---- the source half of swz_convert_dataset (swz_source.hip), shared with swz_dataset_query
+// dataset_scan, then what is refused of a 3DTILES source: one without SWZ_CONVERT_LOSSY_SOURCE in source_flags, files whose
+// RTC_CENTER differ.  Fills scan->file_bytes of such a source; rtc_out (may be NULL): the files' common RTC_CENTER, else 0.
+int source_open(swz_ctx* c, const char* who, const char* dir, int32_t max_depth, uint32_t source_flags, DatasetScan* scan,
+                double rtc_out[3]);
+
+// the raw image of one chunk: the files of its nodes back to back, each at a multiple of 8, then the kernel's segment table
+struct SourceChunk {
+  uint64_t rows = 0, raw_bytes = 0, table_at = 0, image_bytes = 0;
+  InputBatch las;                  // LAS sources: segments and pieces as swz_tiler_add_las_files cuts them
+  std::vector<BinUnpackSeg> segs;  // BIN, BINZ
+  std::vector<ReadPiece> pieces;   // BIN: parts of files; BINZ: whole files (bytes: what the stream inflates to); 3DTILES: whole files
+  std::vector<uint64_t> piece_row; // 3DTILES: the first row of a piece's file; its segment is filled by the piece's reader
+};
+
+// Chunk after chunk of a scanned source as chunk-local positions and columns on the device: reader threads
+// (SWZ_INPUT_READER_THREADS) fill one of two page-locked images with the chunk's files (BINZ inflated, LAS as record ranges,
+// .pnts whole; headers checked against the scan), `copy` moves it to the device and the source format's unpack kernel runs
+// behind it on the same stream.  next(j) returns when chunk j lies in xyz / cols and the readers of chunk j + 1 have been
+// started: they run while the caller works on chunk j.  The arrays are "out_cv_*" of the workspace (an OutputWorkspace of
+// the caller gives them back).  The scan, `first` and the stream outlive the object; its readers are joined when it ends.
+struct SourceStream {
+  swz_ctx* c = nullptr;
+  const char* who = nullptr;
+  const DatasetScan* scan = nullptr;
+  const std::vector<uint64_t>* first = nullptr;  // chunk j: the nodes [first[j], first[j + 1]) of the scan
+  hipStream_t copy = nullptr;
+  uint32_t mask = 0;
+  uint64_t num_chunks = 0, image_max = 0, rows_max = 0;
+  double* xyz = nullptr;
+  swz_attribute_columns cols{};
+  uint64_t bytes_read = 0;
+  double read_ms = 0, unpack_ms = 0, copy_ms = 0;
+
+  // sizes the images and the arrays over all chunks; nothing is allocated
+  void plan(swz_ctx* ctx, const char* who_c, const DatasetScan* s, const std::vector<uint64_t>* first_nodes, uint32_t attribute_mask);
+  // the arrays and the images (a plan with rows); then the readers of chunk 0
+  int start(hipStream_t copy_stream);
+  int next(uint64_t j);
+  uint64_t rows(uint64_t j) const { return ch_[j & 1].rows; }  // of the chunk next(j) delivered
+  ~SourceStream() { (void)readers_.wait(nullptr, nullptr); }  // (they write into ib_'s host images)
+
+private:
+  void read_chunk(uint64_t j);
+  TicketRun readers_;
+  InputBuffers ib_;
+  SourceChunk ch_[2];
+  std::vector<const char*> paths_;
+  long threads_ = 1;
+};
 
 }  // namespace swz

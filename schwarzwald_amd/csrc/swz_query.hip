@@ -1,0 +1,253 @@
+// swz_query.hip -- a written data set queried by box and depth (swz_dataset_query_nodes, swz_dataset_query).  The source is
+// opened as the converter opens it (source_open, swz_source.hip), the nodes whose widened boxes miss the query box drop out
+// of the table (host only), and the rest is streamed chunk by chunk with the converter's SourceStream: every chunk's
+// chunk-local positions and columns go through the selection kernel (swz_select.hip) into the caller's arrays at the running
+// offset.  The readers of chunk j + 1 run while chunk j is selected.
+#include <chrono>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "swz_convert.h"
+#include "swz_hostio.h"
+#include "swz_select.h"
+#include "swz_toutput.h"
+
+static_assert(sizeof(swz_query_params) == 72 && offsetof(swz_query_params, max_depth) == 48 && offsetof(swz_query_params, chunk_points) == 64 &&
+                sizeof(swz_query_stats) == 88 && offsetof(swz_query_stats, read_ms) == 48,
+              "the structs of the query as include/swz_gpu.h and the bindings lay them out");
+
+namespace swz {
+
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// per selected row of a chunk its node: the last node of the chunk whose first row is not behind the row (nodes without
+// points share their first row with the node behind them)
+__global__ __launch_bounds__(256) void query_row_nodes_kernel(const uint32_t* __restrict__ rows, uint32_t cnt, const uint32_t* __restrict__ node_first,
+                                                              uint32_t nodes, uint32_t node0, uint32_t* __restrict__ node_out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= cnt) return;
+  const uint32_t r = rows[i];
+  uint32_t lo = 0, hi = nodes;  // node_first[lo] <= r < node_first[hi] (node_first[nodes]: the chunk's rows)
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (node_first[mid] <= r) lo = mid;
+    else hi = mid;
+  }
+  node_out[i] = node0 + lo;
+}
+
+// The table a query reads: `kept` holds the nodes of the (depth-limited) scan whose widened boxes meet the query box, in the
+// scan's order; *scanned: the nodes of the scan.
+static int query_plan(swz_ctx* c, const char* who, const char* dir, const swz_query_params* q, DatasetScan* kept, uint64_t* scanned) {
+  auto refuse = [&](const std::string& what) { return fail(c, SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
+  if (!dir || !q) return refuse("NULL argument");
+  if (!finite3(q->box_min) || !finite3(q->box_max)) return refuse("a bound of the box is not finite");
+  for (int a = 0; a < 3; ++a)
+    if (q->box_min[a] > q->box_max[a]) return refuse("box_min > box_max");
+  if (q->source_flags & ~(uint32_t)SWZ_CONVERT_LOSSY_SOURCE) return refuse("an unknown bit in source_flags");
+  if (q->reserved) return refuse("reserved must be 0");
+  DatasetScan scan;
+  double rtc[3];
+  SWZ_TRY(source_open(c, who, dir, q->max_depth, q->source_flags, &scan, rtc));
+  if (scan.info.root_source == SWZ_DATASET_ROOT_ABSENT)
+    return refuse("no root box: the source has neither properties.json nor ept.json");
+  const double* rmin = scan.info.root_min;
+  const double* rmax = scan.info.root_max;
+  if (!finite3(rmin) || !finite3(rmax)) return refuse("the root box of the source is not finite");
+  const int format = scan.info.format;
+  const bool las = format == SWZ_OUT_LAS || format == SWZ_OUT_ENTWINE_LAS;
+  const bool pnts = format == SWZ_OUT_3DTILES;
+  const uint64_t nn = scan.count.size();
+  *scanned = nn;
+  *kept = DatasetScan{};
+  kept->info = scan.info;
+  kept->info.points = 0;
+  for (uint64_t k = 0; k < nn; ++k) {
+    double lo[3], hi[3];
+    if (swz_node_bounds(scan.level[k], scan.key[k], rmin, rmax, lo, hi) != SWZ_OK) return refuse("no box for the node " + scan.path[k]);
+    bool meets = true;
+    for (int a = 0; a < 3; ++a) {
+      // a point lies in the node of its KEY: two key cells cover the rounding of the cell edges against the halved boxes,
+      // four ulps of the largest bound the rounding of the bounds themselves
+      const double big = std::max(std::max(std::fabs(rmin[a]), std::fabs(rmax[a])), std::max(std::fabs(lo[a]), std::fabs(hi[a])));
+      double room = std::ldexp(std::fabs(rmax[a] - rmin[a]), -20) + 4 * std::numeric_limits<double>::epsilon() * big;
+      if (las) room += std::fabs(scan.layout[k].scale[a]);  // stored on the scale's grid: half a step off at the most
+      if (pnts) {  // stored as floats relative to RTC_CENTER
+        lo[a] -= rtc[a];
+        hi[a] -= rtc[a];
+        room += std::ldexp(std::max(std::fabs(lo[a]), std::fabs(hi[a])), -23) + 4 * std::numeric_limits<double>::epsilon() * std::fabs(rtc[a]);
+      }
+      if (!(lo[a] - room <= q->box_max[a] && q->box_min[a] <= hi[a] + room)) meets = false;
+    }
+    if (!meets) continue;
+    kept->level.push_back(scan.level[k]);
+    kept->key.push_back(scan.key[k]);
+    kept->count.push_back(scan.count[k]);
+    kept->path.push_back(scan.path[k]);
+    kept->layout.push_back(scan.layout[k]);
+    kept->data_at.push_back(scan.data_at[k]);
+    if (pnts) kept->file_bytes.push_back(scan.file_bytes[k]);
+    kept->info.points += scan.count[k];
+  }
+  kept->info.num_nodes = kept->count.size();
+  return SWZ_OK;
+}
+
+struct CopyStream {
+  hipStream_t s = nullptr;
+  ~CopyStream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+
+static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_params* q, uint64_t capacity, double* d_xyz_out,
+                 const swz_attribute_columns* d_out, uint32_t* d_node_out, uint64_t* count_out, swz_query_stats* stats) {
+  auto refuse = [&](const std::string& what) { return c->fail(SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
+  const auto t_wall = std::chrono::steady_clock::now();
+  if (stats) *stats = swz_query_stats{};
+  if (!count_out) return refuse("NULL argument");
+  *count_out = 0;
+  DatasetScan kept;
+  uint64_t scanned = 0;
+  SWZ_TRY(query_plan(c, who, dir, q, &kept, &scanned));
+  const bool count_only = !d_xyz_out && capacity == 0;
+  if (!d_xyz_out && !count_only) return refuse("NULL d_xyz_out with a capacity (count only: NULL and capacity 0)");
+  uint32_t mask = q->attribute_mask == ~0u ? kept.info.attribute_mask : q->attribute_mask;
+  if (mask & ~kept.info.attribute_mask) return refuse("the attribute_mask names a column the source does not hold");
+  if (count_only) mask = 0;  // positions decide
+  for (int a = 0; a < SWZ_ATTR_COUNT; ++a)
+    if (((mask >> a) & 1u) && (!d_out || !d_out->column[a])) return refuse("a bit of the mask without an output column");
+  SWZ_HIP(c, hipSetDevice(c->device));
+
+  // ---- the chunks: whole nodes of the kept table, as the converter cuts its source
+  const uint64_t nn = kept.count.size();
+  std::vector<uint64_t> first;
+  {
+    const uint64_t chunk_points = output_chunk_points(c, q->chunk_points);
+    uint64_t num_chunks = 0;
+    (void)swz_output_chunks(nn, kept.count.data(), chunk_points, 0, nullptr, &num_chunks);
+    first.assign(num_chunks + 1, 0);
+    (void)swz_output_chunks(nn, kept.count.data(), chunk_points, num_chunks, first.data(), &num_chunks);
+  }
+  OutputWorkspace ow{c};  // the chunk-local arrays ("out_*") are the call's part of the workspace
+  CopyStream copy;
+  SourceStream source;
+  source.plan(c, who, &kept, &first, mask);
+  uint64_t total = 0, chunks = 0;
+  double select_ms = 0;
+  int status = SWZ_OK;
+  if (source.rows_max) {
+    uint64_t nodes_max = 0;
+    for (uint64_t j = 0; j < source.num_chunks; ++j) nodes_max = std::max(nodes_max, first[j + 1] - first[j]);
+    uint32_t *d_rows = nullptr, *d_first = nullptr;
+    if (d_node_out && !count_only) {
+      SWZ_TRY(c->get("out_q_rows", (size_t)source.rows_max, &d_rows));
+      SWZ_TRY(c->get("out_q_first", (size_t)nodes_max + 1, &d_first));
+    }
+    std::vector<uint32_t> node_first;
+    SWZ_HIP(c, hipStreamCreateWithFlags(&copy.s, hipStreamNonBlocking));
+    SWZ_TRY(source.start(copy.s));
+    for (uint64_t j = 0; j < source.num_chunks; ++j) {
+      SWZ_TRY(source.next(j));  // (a read error: the stream stops here, the file is named)
+      ++chunks;
+      const uint64_t rows = source.rows(j);
+      const auto t_select = std::chrono::steady_clock::now();
+      swz_attribute_columns at{};
+      for (int a = 0; a < SWZ_ATTR_COUNT; ++a)
+        if ((mask >> a) & 1u) at.column[a] = static_cast<uint8_t*>(d_out->column[a]) + total * ATTR_BYTES[a];
+      const uint64_t room = count_only ? 0 : capacity - total;
+      uint64_t cnt = 0;
+      // (a chunk selects its rows at the most: the capacity the kernel's checks see ends with the chunk-local row array)
+      status = box_select(c, who, source.xyz, rows, &source.cols, mask, q->box_min, q->box_max, std::min(room, rows),
+                          count_only ? nullptr : d_xyz_out + 3 * total, &at, d_rows, &cnt);
+      if (status != SWZ_OK) {
+        if (!count_only && cnt > room) {  // the stream stops after this chunk's count
+          *count_out = total + cnt;
+          return refuse("capacity " + std::to_string(capacity) + " is less than the " + std::to_string(total + cnt) +
+                        " rows selected up to chunk " + std::to_string(j));
+        }
+        return status;
+      }
+      if (d_rows && cnt) {
+        const uint64_t k0 = first[j], k1 = first[j + 1];
+        node_first.assign(k1 - k0 + 1, 0);
+        for (uint64_t k = k0; k < k1; ++k) node_first[k - k0 + 1] = node_first[k - k0] + (uint32_t)kept.count[k];
+        SWZ_HIP(c, hipMemcpyAsync(d_first, node_first.data(), node_first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(query_row_nodes_kernel, dim3(div_up(cnt, 256)), dim3(256), 0, c->stream, d_rows, (uint32_t)cnt, d_first,
+                           (uint32_t)(k1 - k0), (uint32_t)k0, d_node_out + total);
+        SWZ_LAUNCH_CHECK(c);
+        SWZ_HIP(c, hipStreamSynchronize(c->stream));  // (node_first is the next chunk's)
+      }
+      total += cnt;
+      select_ms += ms_since(t_select);
+    }
+  }
+  *count_out = total;
+  if (stats) {
+    stats->nodes_scanned = scanned;
+    stats->nodes_read = nn;
+    stats->points_read = kept.info.points;
+    stats->points_out = total;
+    stats->bytes_read = source.bytes_read;
+    stats->chunks = chunks;
+    stats->read_ms = source.read_ms;
+    stats->unpack_ms = source.unpack_ms;
+    stats->select_ms = select_ms;
+    stats->copy_ms = source.copy_ms;
+    stats->wall_ms = ms_since(t_wall);
+  }
+  return SWZ_OK;
+}
+
+}  // namespace swz
+
+using namespace swz;
+
+extern "C" {
+
+int swz_dataset_query_nodes(swz_ctx* c, const char* dir, const swz_query_params* params, uint64_t max_nodes, int8_t* level_out,
+                            uint64_t* key_out, uint64_t* count_out, uint64_t* num_out, uint64_t* points_bound_out) {
+  swz_ctx text;  // (a NULL context: only the status comes back; no device is touched either way)
+  if (!c) c = &text;
+  if (!num_out) return c->fail(SWZ_ERR_BAD_ARG, "swz_dataset_query_nodes: NULL argument");
+  DatasetScan kept;
+  uint64_t scanned = 0;
+  SWZ_TRY(query_plan(c, "swz_dataset_query_nodes", dir, params, &kept, &scanned));
+  const uint64_t nn = kept.count.size();
+  *num_out = nn;
+  if (points_bound_out) *points_bound_out = kept.info.points;
+  if (!level_out && !key_out && !count_out) return SWZ_OK;
+  if (nn > max_nodes) return c->fail(SWZ_ERR_BAD_ARG, "swz_dataset_query_nodes: max_nodes too small");
+  for (uint64_t k = 0; k < nn; ++k) {
+    if (level_out) level_out[k] = kept.level[k];
+    if (key_out) key_out[k] = kept.key[k];
+    if (count_out) count_out[k] = kept.count[k];
+  }
+  return SWZ_OK;
+}
+
+int swz_dataset_query_nodes_why(const char* dir, const swz_query_params* params, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out,
+                                uint64_t* count_out, uint64_t* num_out, uint64_t* points_bound_out, char* why_out, uint64_t why_bytes) {
+  swz_ctx text;  // (only its error text is used: no device is touched)
+  const int st = swz_dataset_query_nodes(&text, dir, params, max_nodes, level_out, key_out, count_out, num_out, points_bound_out);
+  if (why_out && why_bytes) {
+    const size_t len = std::min<size_t>(st == SWZ_OK ? 0 : text.err.size(), (size_t)why_bytes - 1);
+    memcpy(why_out, text.err.data(), len);
+    why_out[len] = 0;
+  }
+  return st;
+}
+
+int swz_dataset_query(swz_ctx* c, const char* dir, const swz_query_params* params, uint64_t capacity, double* d_xyz_out,
+                      const swz_attribute_columns* d_out, uint32_t* d_node_out, uint64_t* count_out, swz_query_stats* stats) {
+  if (!c) return SWZ_ERR_BAD_ARG;
+  return query(c, "swz_dataset_query", dir, params, capacity, d_xyz_out, d_out, d_node_out, count_out, stats);
+}
+
+}  // extern "C"

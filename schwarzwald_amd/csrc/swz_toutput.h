@@ -72,6 +72,8 @@ struct OutputWorkspace {
 int output_plan(swz_ctx* c, const char* who, const swz_output_params* params, uint32_t attr_mask, const double bmin[3],
                 const double bmax[3], float spacing_at_root, const char* dir, OutputPlan* p);
 int output_create_dirs(swz_ctx* c, const char* who, OutputPlan* p, const char* dir);
+// chunk_points of swz_output_params as the cuts take it: 0 is the library's default (option SWZ_OUTPUT_CHUNK_POINTS)
+uint64_t output_chunk_points(swz_ctx* c, uint64_t chunk_points);
 // the chunks of the nodes [k0, k1) of a plan: first->at(j) .. first->at(j + 1) are chunk j's nodes; the largest chunk image
 void output_cuts(swz_ctx* c, const OutputPlan& p, uint64_t k0, uint64_t k1, uint64_t chunk_points, std::vector<uint64_t>* first,
                  uint64_t* image_max);

@@ -208,9 +208,13 @@ static uint64_t image_at(const OutputPlan& p, uint64_t node) {
   return node < nn ? p.body_at[node] : (nn ? p.body_at[nn - 1] + p.body_size[nn - 1] : 0);
 }
 
+uint64_t output_chunk_points(swz_ctx* c, uint64_t chunk_points) {
+  return chunk_points ? chunk_points : (uint64_t)std::max(1L, c->opt_int("SWZ_OUTPUT_CHUNK_POINTS", (long)OUTPUT_CHUNK_POINTS));
+}
+
 void output_cuts(swz_ctx* c, const OutputPlan& p, uint64_t k0, uint64_t k1, uint64_t chunk_points, std::vector<uint64_t>* first,
                  uint64_t* image_max) {
-  if (!chunk_points) chunk_points = (uint64_t)std::max(1L, c->opt_int("SWZ_OUTPUT_CHUNK_POINTS", (long)OUTPUT_CHUNK_POINTS));
+  chunk_points = output_chunk_points(c, chunk_points);
   uint64_t num_chunks = 0;
   const uint64_t* counts = p.count.data() + k0;
   (void)swz_output_chunks(k1 - k0, counts, chunk_points, 0, nullptr, &num_chunks);

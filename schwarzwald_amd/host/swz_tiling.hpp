@@ -182,6 +182,65 @@ inline swz_convert_stats convert_dataset_world(Context& ctx, const std::string& 
   return stats;
 }
 
+// The points of a written data set inside a closed box, of the nodes down to params.max_depth (swz_dataset_query): the kept
+// nodes' files are streamed and unpacked as convert_dataset does, the rows of the box selected on the device into arrays of
+// swz_dataset_query_nodes' points_bound rows, and the result copied to the host -- positions (3 doubles per point), the
+// columns of params.attribute_mask (~0u: all the source holds) as raw rows, and with want_nodes per point the index of its
+// node in swz_dataset_query_nodes' table.  The order is the node table's, then the file's.  lossy_source as in
+// convert_dataset.  A refusal -- a bad box, a .pnts source without the switch, no root box -- throws with the library's text.
+struct QueryResult {
+  uint64_t count = 0;
+  std::vector<double> positions;
+  std::vector<uint8_t> columns[SWZ_ATTR_COUNT];  // empty: not asked for, or not in the source
+  std::vector<uint32_t> nodes;
+  swz_query_stats stats{};
+};
+inline QueryResult query_dataset(Context& ctx, const std::string& dir, const swz_query_params& params, bool lossy_source = false,
+                                 bool want_nodes = false) {
+  static const uint32_t widths[SWZ_ATTR_COUNT] = {3, 12, 2, 1, 1, 8, 1, 1, 2, 1, 1, 1};
+  swz_query_params p = params;
+  if (lossy_source) p.source_flags |= SWZ_CONVERT_LOSSY_SOURCE;
+  uint64_t kept = 0, bound = 0;
+  ctx.check(swz_dataset_query_nodes(ctx.get(), dir.c_str(), &p, 0, nullptr, nullptr, nullptr, &kept, &bound));
+  if (p.attribute_mask == ~0u) {
+    swz_dataset_info info{};
+    uint64_t scanned = 0;
+    ctx.check(swz_dataset_scan(ctx.get(), dir.c_str(), p.max_depth, &info, 0, nullptr, nullptr, nullptr, &scanned));
+    p.attribute_mask = info.attribute_mask;
+  }
+  struct Device {  // freed however the call ends
+    std::vector<void*> ptrs;
+    ~Device() {
+      for (void* d : ptrs) (void)swz_device_free(d);
+    }
+  } device;
+  auto alloc = [&](uint64_t bytes) {
+    void* d = nullptr;
+    ctx.check(swz_device_alloc_on(ctx.get(), bytes ? bytes : 1, &d));
+    device.ptrs.push_back(d);
+    return d;
+  };
+  QueryResult out;
+  double* d_xyz = static_cast<double*>(alloc(24 * bound));
+  swz_attribute_columns d_cols{};
+  for (int a = 0; a < SWZ_ATTR_COUNT; ++a)
+    if ((p.attribute_mask >> a) & 1u) d_cols.column[a] = alloc(widths[a] * bound);
+  uint32_t* d_nodes = want_nodes ? static_cast<uint32_t*>(alloc(4 * bound)) : nullptr;
+  ctx.check(swz_dataset_query(ctx.get(), dir.c_str(), &p, bound, d_xyz, &d_cols, d_nodes, &out.count, &out.stats));
+  out.positions.resize(3 * out.count);
+  if (out.count) ctx.check(swz_copy_to_host(ctx.get(), out.positions.data(), d_xyz, 24 * out.count));
+  for (int a = 0; a < SWZ_ATTR_COUNT; ++a) {
+    if (!d_cols.column[a]) continue;
+    out.columns[a].resize(widths[a] * out.count);
+    if (out.count) ctx.check(swz_copy_to_host(ctx.get(), out.columns[a].data(), d_cols.column[a], widths[a] * out.count));
+  }
+  if (want_nodes) {
+    out.nodes.resize(out.count);
+    if (out.count) ctx.check(swz_copy_to_host(ctx.get(), out.nodes.data(), d_nodes, 4 * out.count));
+  }
+  return out;
+}
+
 // index_points<21> -- OctreeAlgorithms.h:181-197.  positions: n x 3 doubles (PointBuffer::positions().data());
 // outliers are clamped in place, like index_point does.
 inline void index_points(Context& ctx, double* positions, size_t n, IndexedPoint64* indexed_points_begin,
