@@ -91,7 +91,8 @@ int swz_set_stream(swz_ctx* ctx, void* hip_stream);
  *   occupied grid cells from which a level is numbered directly), SWZ_MD_DIRECT_MAX_CELLS (the largest grid that is numbered
  *   directly; default: what fits the free device memory); chains of dense levels that share one active set:
  *   SWZ_MD_DEFER=0 (every level compacts its survivors, as the other paths do), SWZ_MD_DEFER_MAX_GONE (1/8: the share of
- *   taken points in the shared arrays from which a chain ends);
+ *   taken points in the shared arrays from which a chain ends), SWZ_MD_PREBUILD=0 (no level of a chain builds the next
+ *   level's cell tables ahead, under its own rounds: every level builds all of its tables itself);
  *   the frontier sweeps: SWZ_MD_PATIENT, SWZ_MD_LAZY, SWZ_MD_LAZY_FRAC, SWZ_MD_BIG, SWZ_MD_GROUPS, SWZ_MD_GRID,
  *   SWZ_MD_NBR_GRID, SWZ_MD_BATCH, SWZ_MD_COARSEN, SWZ_MD_COARSEN_MIN, SWZ_MD_FF_MIN, SWZ_MD_NO_DEAD_TEST=1 (blocker scans
  *   without the dead-point test), SWZ_MD_CHAIN, SWZ_MD_KEYS_RG, SWZ_MD_DENSE_MIN;
@@ -1504,7 +1505,12 @@ typedef struct {
 } swz_kernel_stat;
 int swz_profile_enable(swz_ctx* ctx, int enabled);
 int swz_profile_reset(swz_ctx* ctx);
-/* Copies up to max_stats entries; returns the number of kernel classes via *num_out. */
+/* Copies up to max_stats entries; returns the number of kernel classes via *num_out.
+ * Five entries are COUNTS, not timed classes (total_ms and algorithmic_bytes stay 0): what the key sweep did with the cell
+ * tables of a chain of dense MIN_DISTANCE levels -- mq_tables_ahead (kernels that built a next level's early tables on the
+ * build stream, two per level), mq_prebuild_taken / mq_prebuild_dropped (levels that took such tables / tables nobody could
+ * use), mq_tables_late (the two late kernels of a level that took them), mq_tables_at_setup (the two table kernels of a
+ * directly numbered level that built everything itself). */
 int swz_profile_get(swz_ctx* ctx, swz_kernel_stat* stats_out, uint32_t max_stats, uint32_t* num_out);
 
 #ifdef __cplusplus

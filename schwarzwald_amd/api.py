@@ -1470,6 +1470,8 @@ class Context:
         self._check(self._lib.swz_profile_reset(self._ctx))
 
     def profile_get(self):
+        """{class: launches, total_ms, algorithmic_bytes}.  mq_tables_ahead, mq_prebuild_taken, mq_prebuild_dropped,
+        mq_tables_late and mq_tables_at_setup are counts only (swz_profile_get in include/swz_gpu.h): their times are 0."""
         buf = (_KernelStat * 64)()
         num = C.c_uint32()
         self._check(self._lib.swz_profile_get(self._ctx, buf, 64, C.byref(num)))

@@ -103,6 +103,8 @@ void swz_ctx::release_all() {
 void swz_ctx::free_buf(swz::DevBuf& b) {
   if (b.ptr && b.ptr == sbi_clean_ptr) sbi_clean_ptr = nullptr;  // (what comes back at this address later is not known to be zero)
   if (b.ptr && b.ptr == mq_qpos_buf) mq_qpos_buf = nullptr;      // (... nor to hold anybody's key coordinates)
+  if (b.ptr && (b.ptr == mq_pre.cinfo || b.ptr == mq_pre.qnbr || b.ptr == mq_pre.rec || b.ptr == mq_pre.slot || b.ptr == mq_pre.qst))
+    mq_pre.valid = false;                                        // (... nor tables built ahead)
   if (b.ptr) (void)(b.host ? hipHostFree(b.ptr) : hipFree(b.ptr));
   b.ptr = nullptr;
   b.cap = 0;
@@ -284,6 +286,7 @@ int swz_destroy(swz_ctx* c) {
   c->prof_collect();
   for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
   for (hipStream_t st : c->aux_streams) (void)hipStreamDestroy(st);
+  if (c->mq_build_stream) (void)hipStreamDestroy(c->mq_build_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
   return SWZ_OK;

@@ -36,6 +36,24 @@ struct PendingEvent {
   uint64_t bytes;
 };
 
+// The key sweep's early per-cell tables of the NEXT level of a chain, built on a side stream under the running level's rounds
+// (swz_mqbuild.hip, mq_prebuild_launch).  A guess that costs only time: the next level compares `key` fields
+// with what it really is (mq_prebuilt_matches) and builds everything itself when one differs.
+struct MqPrebuild {
+  // the request: session_run_levels in front of a level that may leave its survivors in place, for the level after it
+  bool wanted = false;
+  uint32_t want_node_shift = 0, want_cl = 0, want_rg = 0;
+  // the product: which keys, which grid, which set of per-cell buffers ("" / "_b") and where they were when it was built
+  bool valid = false;
+  uint32_t serial = 0;  // counts the products: tells the one a level found from the one it built
+  int set = 0;
+  const void* akey = nullptr;
+  uint32_t m = 0, node_shift = 0, cl = 0, rg = 0, ncells = 0, nodes = 0;
+  const void *cinfo = nullptr, *qnbr = nullptr, *rec = nullptr, *slot = nullptr, *qst = nullptr;
+  hipEvent_t done = nullptr;  // behind the last early kernel on the build stream; null: the context's stream has waited for it
+  hipEvent_t t0 = nullptr, t1 = nullptr;  // SWZ_DEBUG: around the early kernels
+};
+
 }  // namespace swz
 
 struct swz_ctx {
@@ -94,6 +112,13 @@ struct swz_ctx {
   const void* mq_qpos_buf = nullptr;
   const void* mq_qpos_keys = nullptr;
   uint32_t mq_qpos_m = 0;
+  // ... and its tables built ahead: the build stream (made on demand, lowest priority) and the one product in flight;
+  // free_buf forgets a product whose buffer it frees
+  hipStream_t mq_build_stream = nullptr;
+  swz::MqPrebuild mq_pre;
+  void prof_count(const char* name, uint64_t launches) {  // launches that no event pair brackets (another stream's, or skipped ones)
+    if (profile) kstats[name].launches += launches;
+  }
   bool tiler_active = false;  // a swz_tiler lives on this context: its node store is part of the workspace
   swz_tiler* nodes_tiler = nullptr;  // the tiler of an open swz_tile_nodes_begin_device / _end_device pair
   // no batch of the tiler is open: its per-batch scratch ("tl_*") holds nothing anybody will read again, and get() may free

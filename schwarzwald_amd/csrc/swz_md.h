@@ -93,6 +93,13 @@ int md_active_positions(swz_ctx* c, const MdLevel& L, size_t per_point, const do
 // with direct numbering or not at all.
 int min_distance_keys_level(swz_ctx* c, const MdLevel& L, int cl, uint32_t* rounds_out, bool* used,
                             const MdShardRoot* shard_root = nullptr, bool* direct = nullptr);
+// granules per record buffer (4 or 8) for cells of 2^cell_bits key cells at a spacing of T key cells
+uint32_t key_sweep_record_granules(const swz_ctx* c, uint32_t cell_bits, double T);
+// The grid the key sweep would most likely be given for the level of `plan` if about `points` points, spread evenly,
+// reached it inside a chain: the ladder's rules of min_distance_level (swz_md.hip) on an estimate instead of a survey.
+// false: the level would probably go elsewhere (take-all nodes, a sparse level, no key metric, compacted cells).  Only
+// a guess -- it decides what mq_prebuild_launch builds ahead, never what the level does.
+bool md_guess_chained_level(const swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp, uint32_t points, MqPrebuild* want);
 // Sparse levels by blocks of 8^3 cells staged in LDS, blocks in Morton order, decisions in the same launch
 // (swz_mdblock.hip); *done = false: the level does not qualify or a block did not fit, nothing is lost.
 int min_distance_block_level(swz_ctx* c, const MdLevel& L, bool* done);

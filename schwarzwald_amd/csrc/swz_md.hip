@@ -221,6 +221,36 @@ static int sweep_cell_levels(const swz_ctx* c, const MdLevel& L) {
   return cl;
 }
 
+bool md_guess_chained_level(const swz_ctx* c, const LevelPlan& plan, const SortedPoints& sp, uint32_t points, MqPrebuild* want) {
+  want->wanted = false;
+  if (plan.node_shift >= 63u || plan.node_shift < 3u || plan.node_shift % 3u != 0u || plan.terminal || plan.reroot || plan.md_property) return false;
+  const KeyMetric km = key_metric(c, plan, sp);
+  if (!km.ok) return false;
+  const uint32_t levels = (63u - plan.node_shift) / 3u;  // below the root: every one of the 8^levels nodes is assumed to exist
+  if (levels > 6u) return false;
+  const double nodes = std::ldexp(1.0, 3 * (int)levels);
+  if (plan.force_sample ? points == 0u : (double)points / nodes <= (double)plan.max_points) return false;  // (the nodes would keep what they hold)
+  // occupied cells at cell level cl of evenly spread points: a cell is empty with probability exp(-points / cells)
+  auto occupied = [&](int cl) {
+    const double cells = nodes * std::ldexp(1.0, 3 * cl);
+    return std::max(1.0, cells * -std::expm1(-(double)points / cells));
+  };
+  const int cl_sparse = md_clamp_cell_levels((uint32_t)nodes, plan.cell_levels_geo);
+  if ((double)points / occupied(cl_sparse) < c->opt_num("SWZ_MD_SPARSE_LIMIT", 2.0)) return false;
+  int cl = plan.cell_levels_geo;  // sweep_cell_levels without its population test
+  while (cl > 0 && plan.cell_levels_geo - cl < 3 && (double)points / occupied(cl) < 8.0) --cl;
+  cl = md_clamp_cell_levels((uint32_t)nodes, cl);
+  const double cells = nodes * std::ldexp(1.0, 3 * cl);
+  if (cells > 2147483632.0 || occupied(cl) / cells < c->opt_num("SWZ_MD_DIRECT_MIN_OCCUPANCY", 0.5)) return false;
+  const uint32_t cell_shift = plan.node_shift - 3u * (uint32_t)cl;
+  if (cell_shift / 3u > 21u) return false;
+  want->want_node_shift = plan.node_shift;
+  want->want_cl = (uint32_t)cl;
+  want->want_rg = key_sweep_record_granules(c, cell_shift / 3u, km.T);
+  want->wanted = true;
+  return true;
+}
+
 // The coloured phases: one wavefront per cell.  Coarser cells are better filled, but a cell of side r spacings can hold
 // about 0.75 r^3 taken points (points that are pairwise a spacing apart, and never more than it has points) and every
 // point is tested against those of 27 cells: go one level coarser only when the finest cells are poorly filled and the

@@ -136,6 +136,8 @@ struct MqLevel {
   uint32_t ncells = 0;             // entries of the per-cell arrays
   uint32_t occ_cells = 0;          // occupied cells, for the scheduling rules: counted, or the caller's estimate
   uint32_t* d_cell_sums = nullptr; // compacted numbering: the count's block sums, for the build
+  int set = 0;                     // which set of per-cell buffers the level runs on ("" / "_b"; 1 only after a build ahead)
+  bool prebuilt = false;           // the early tables were built under the level before (mq_prebuild_launch): only the late ones are due
   bool coded = false;              // the taken bytes carry a code: see mq_commit_kernel
   bool lazy = false, big_cells = false;
   uint32_t groups = 1, ndense = 0;
@@ -151,6 +153,10 @@ int mq_alloc_arrays(swz_ctx* c, MqLevel& q);
 int mq_build_cell_tables(swz_ctx* c, MqLevel& q);
 int mq_list_dense_cells(swz_ctx* c, MqLevel& q);
 int mq_start_groups(swz_ctx* c, MqLevel& q);
+// ... and the early tables of the level after this one (swz_internal.h, MqPrebuild): launched on the build stream once this
+// level's own tables are on their way, joined -- the context's stream waits for them -- behind this level's rounds
+int mq_prebuild_launch(swz_ctx* c, MqLevel& q);
+int mq_prebuild_join(swz_ctx* c);
 // swz_mqsweep.hip: the rounds and what follows them
 uint32_t mq_sweep_grid(swz_ctx* c, const MqLevel& q);
 void mq_launch_round(const MqLevel& q, uint32_t g, uint32_t sweep_grid);

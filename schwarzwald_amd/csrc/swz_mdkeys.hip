@@ -147,15 +147,19 @@ static int mq_fill_args(const swz_ctx* c, MqLevel& q) {
   return SWZ_OK;
 }
 
+// A cell r spacings wide ends with about 0.75 r^3 accepted points: records of 3 or 7 inline ones, the rest in the
+// overflow.  (Small records win well beyond their capacity -- level 1 at 1 B points, cells two spacings wide with ~6
+// accepted points each: 78 ms with records of 3, 84 with records of 7: less to stage, more wavefronts per CU.)
+uint32_t key_sweep_record_granules(const swz_ctx* c, uint32_t cell_bits, double T) {
+  const double r_cell = std::ldexp(1.0, (int)cell_bits) / T;
+  const uint32_t rg = (0.75 * r_cell * r_cell * r_cell <= 12.0) ? 4u : 8u;
+  return c->opt_int("SWZ_MD_KEYS_RG", rg) >= 8 ? 8u : 4u;
+}
+
 // Record size and how the cells are numbered; over when a level inside a chain would not get direct numbering.
 static int mq_choose_records_and_numbering(const swz_ctx* c, MqLevel& q, bool* direct_out) {
   MqArgs& a = q.a;
-  // A cell r spacings wide ends with about 0.75 r^3 accepted points: records of 3 or 7 inline ones, the rest in the
-  // overflow.  (Small records win well beyond their capacity -- level 1 at 1 B points, cells two spacings wide with ~6
-  // accepted points each: 78 ms with records of 3, 84 with records of 7: less to stage, more wavefronts per CU.)
-  const double r_cell = std::ldexp(1.0, (int)a.cell_bits) / q.L.km.T;
-  a.rg = (0.75 * r_cell * r_cell * r_cell <= 12.0) ? 4u : 8u;
-  a.rg = c->opt_int("SWZ_MD_KEYS_RG", a.rg) >= 8 ? 8u : 4u;
+  a.rg = key_sweep_record_granules(c, a.cell_bits, q.L.km.T);
   a.rg2_shift = a.rg == 4u ? 3u : 4u;
   // How the cells are numbered (MqArgs::direct).  By their place in the grid when most of the grid is occupied -- the
   // caller's estimate from THIS call's keys (from half of it on) -- and the per-cell arrays of the whole
@@ -170,7 +174,9 @@ static int mq_choose_records_and_numbering(const swz_ctx* c, MqLevel& q, bool* d
     size_t free_b = 0, total_b = 0, held = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
     for (const auto& kv : c->bufs)
-      if (!kv.second.host && kv.first.compare(0, 4, "md_q") == 0) held += kv.second.cap;
+      if (!kv.second.host && kv.first.compare(0, 4, "md_q") == 0 &&
+          !(kv.first.size() > 2 && kv.first.compare(kv.first.size() - 2, 2, "_b") == 0))  // (not the second set of tables built ahead: a level that builds its own never runs on it)
+        held += kv.second.cap;
     max_cells = std::min<uint64_t>(max_cells, (uint64_t)((double)(free_b + held) * 0.9 / (double)per_cell));
   }
   const double occupancy = (double)q.L.occupied[q.cl] / (double)std::max<uint64_t>(1, q.grid_entries);
@@ -342,8 +348,19 @@ static int mq_run_rounds(swz_ctx* c, MqLevel& q) {
     }
   }
   if (fork) c->event_pool.push_back(fork);
-  return SWZ_OK;
+  return mq_prebuild_join(c);  // (long done as a rule: what follows the rounds on the context's stream is ordered behind it)
 }
+
+// every way out of a level between the launch of the tables built ahead and the end of its rounds joins them
+struct MqPrebuildGuard {
+  swz_ctx* c;
+  ~MqPrebuildGuard() {
+    if (c->mq_pre.done) {
+      (void)mq_prebuild_join(c);
+      c->mq_pre.valid = false;
+    }
+  }
+};
 
 // SWZ_DEBUG: what the level starts with, and -- the event pair around the sweep -- how long it took
 struct MqTrace {
@@ -417,6 +434,8 @@ int min_distance_keys_level(swz_ctx* c, const MdLevel& L, int cl, uint32_t* roun
   mq_schedule(c, q);
   SWZ_TRY(mq_list_dense_cells(c, q));
   SWZ_TRY(mq_start_groups(c, q));
+  MqPrebuildGuard prebuild_guard{c};
+  SWZ_TRY(mq_prebuild_launch(c, q));
   MqTrace trace;
   mq_trace_begin(c, q, trace);
   SWZ_TRY(mq_run_rounds(c, q));

@@ -102,6 +102,8 @@ int session_run_levels(swz_ctx* c, TileSession& t, int last_level, int first_mod
   const bool chain_static = chains && first_mode < 0 && t.params.sampler == SWZ_MIN_DISTANCE &&
                             !(t.params.flags & SWZ_FLAG_MIN_DISTANCE_PROPERTY) && !t.sp.ghosts && !t.front && !c->shard &&
                             !c->md_shard_root && c->opt_on("SWZ_MD_DEFER", true);
+  const bool prebuild = chain_static && c->opt_on("SWZ_MD_PREBUILD", true);
+  c->mq_pre.valid = false;  // (tables built ahead never outlive the call that built them)
   LevelChain chain;
   chain.max_gone = c->opt_num("SWZ_MD_DEFER_MAX_GONE", 0.125);
   for (int level = t.next_level; (t.as.gone ? t.as.live : t.as.m) > 0 && level <= last_level; ++level) {
@@ -114,10 +116,15 @@ int session_run_levels(swz_ctx* c, TileSession& t, int last_level, int first_mod
                                t.params.max_depth, t.bmin, t.bmax, false, true);
     plan.md_property = (t.params.flags & SWZ_FLAG_MIN_DISTANCE_PROPERTY) != 0;
     chain.may_defer = false;
+    c->mq_pre.wanted = false;
     if (chain_static && level < 20) {
       const LevelPlan next = make_plan(level + 1, t.params.sampler, t.params.max_points_per_node, t.params.spacing_at_root,
                                        t.params.max_depth, t.bmin, t.bmax, false, true);
       chain.may_defer = !plan.terminal && !plan.reroot && !next.terminal && !next.reroot;
+      // A level that may leave its survivors in place is followed by one on the same keys: should the key sweep take this
+      // level, it builds that level's early tables under its own rounds (mq_prebuild_launch), for the grid guessed here from
+      // the geometry and the points still open.  SWZ_MD_PREBUILD=0: never.
+      if (chain.may_defer && prebuild) (void)md_guess_chained_level(c, next, t.sp, t.as.gone ? t.as.live : t.as.m, &c->mq_pre);
     }
     if (chain.may_defer || t.as.gone) plan.take_code = (uint8_t)(level + 2);
     // (the root of a sharded batch spans the shards: it is sampled exactly -- the lower shards' samples as ghosts, or all
@@ -134,7 +141,14 @@ int session_run_levels(swz_ctx* c, TileSession& t, int last_level, int first_mod
     LevelResult r;
     t.as.parent_prefix = pprefix;
     t.as.parents = pprefix ? parents : 0u;
-    SWZ_TRY(level_step(c, plan, t.as, t.sp, t.lb, t.level, t.key_buf[t.which], t.idx_buf[t.which], &r, &chain));
+    const uint32_t found_tables = c->mq_pre.valid ? c->mq_pre.serial : 0u;
+    const int step_status = level_step(c, plan, t.as, t.sp, t.lb, t.level, t.key_buf[t.which], t.idx_buf[t.which], &r, &chain);
+    c->mq_pre.wanted = false;  // (a request no key sweep picked up ends with its level)
+    SWZ_TRY(step_status);
+    if (found_tables && c->mq_pre.valid && c->mq_pre.serial == found_tables && !r.needs_flush) {
+      c->mq_pre.valid = false;  // tables built ahead for a level that went to no key sweep (take-all nodes, the block kernel after the flush)
+      c->prof_count("mq_prebuild_dropped", 1);
+    }
     if (r.needs_flush) {
       // the chain ends in front of this level: its one compaction, then the level again on the survivors
       if (!t.as.gone) return c->fail(SWZ_ERR_INTERNAL, "a level outside a chain asked for the chain's compaction");
