@@ -1138,8 +1138,42 @@ int swz_convert_dataset(swz_ctx* ctx, const char* src_dir, const char* dst_dir, 
  *     total would pass capacity the stream stops after that chunk's count with the "capacity" refusal (*count_out: the
  *     total up to and including that chunk); nothing is written at or beyond capacity rows.  d_xyz_out == NULL with
  *     capacity == 0 counts only.  A file that changed since the scan or cannot be read stops the stream and is named.
- *     Device and host hold two raw images and one set of chunk-local arrays whatever the data set's size.  Not offered: a
- *     multi-GPU driver, frustum or polygon queries. */
+ *     Device and host hold two raw images and one set of chunk-local arrays whatever the data set's size.
+ *   A region (swz_region; swz_region_select_device, swz_dataset_query_region_nodes[_why], swz_dataset_query_region) is the
+ *     closed box of the call cut by one more test on the stored positions.  A row is in the region iff it passes the box test
+ *     above AND the test of the region's kind -- the box test keeps NaN coordinates out of the kind tests.  Every *, + and -
+ *     below is ONE rounded double operation, in the order written (no fused multiply-add, no tolerance, no division):
+ *       SWZ_REGION_BOX (count 0, values ignored; so is region == NULL): nothing more -- the bytes of the box calls.
+ *       SWZ_REGION_PLANES, 1..SWZ_REGION_MAX_PLANES rows (a, b, c, d): for every plane  ((a*x + b*y) + c*z) + d >= 0.
+ *         A frustum is six.  A row whose expression is exactly 0 is in.
+ *       SWZ_REGION_POLYGON, 3..SWZ_REGION_MAX_VERTICES vertices (x, y) of one outline in the x-y plane, extruded over the
+ *         box's z range; even-odd rule, so concave and self-intersecting outlines are defined.  With vertex i = (x0, y0) and
+ *         vertex (i+1) mod m = (x1, y1), edge i counts for the row (px, py, .) iff  (y0 > py) != (y1 > py)  and, with
+ *         t = (x1 - x0)*(py - y0) - (px - x0)*(y1 - y0),  (t > 0) == (y1 > y0).  The row is inside iff an odd number of
+ *         edges count.  Rows on an edge, on a vertex or level with a vertex are decided by exactly that: a horizontal edge
+ *         never counts (its two compares agree); a row level with a vertex sees the vertex on one side only (y > py is
+ *         false for it on both edges that share it), so a crossing there is counted once, not twice; reversing an edge
+ *         negates t and swaps y0, y1, so both vertex orders give the same set for every row with t != 0 on the edges whose
+ *         y range holds it -- a row exactly ON a non-horizontal edge (t == 0) counts that edge iff it runs downwards
+ *         (y1 < y0), which makes such rows outside for a counter-clockwise simple outline and inside for a clockwise one.
+ *     values is HOST memory, read before the call returns.  Coordinates are the stored ones: for a 3DTILES source relative to
+ *     the files' RTC_CENTER, as the box.  SWZ_ERR_BAD_ARG with a message, before anything is launched or any file is read:
+ *     an unknown kind, reserved != 0, a count outside 1..16 (planes) or 3..1024 (polygon) or not 0 (box), values == NULL, a
+ *     coefficient or vertex that is not finite, a plane with a = b = c = 0.
+ *   swz_region_select_device is swz_box_select_device with a region: the same output order, count-only mode, capacity refusal
+ *     that touches no output, aliasing and alignment refusals, n == 0 and determinism.  Planes travel in the kernel
+ *     arguments; a polygon's vertices are uploaded once per call and staged in LDS by every workgroup of the count pass (a
+ *     lane runs the edge loop only if its row passed the box test).  For these two kinds the count pass stores every wave's
+ *     ballot (8 bytes per 64 rows) and the scatter reads it back: the predicate is evaluated once per row.
+ *   swz_dataset_query_region_nodes / swz_dataset_query_region are swz_dataset_query_nodes / swz_dataset_query with a region,
+ *     word for word; the vertices are uploaded once per query.  The node rule starts from the same widened node box and drops
+ *     a node iff it misses the query box or cannot hold a row the kind's test accepts: for planes, if for some plane the
+ *     largest value of its expression over the widened box (the corner the coefficients' signs choose) plus a bound on the
+ *     expression's rounding is < 0; for a polygon, if no edge touches the widened x-y rectangle (segment against rectangle,
+ *     widened again by the rounding of t) and the rectangle's centre is outside by the formula above.  The rule errs
+ *     towards reading a file.
+ *   Not offered: a multi-GPU driver, polygons with holes or several rings, a shortcut that copies nodes wholly inside a
+ *     region without testing their rows, depth chosen by screen-space error. */
 typedef struct {
   double box_min[3], box_max[3]; /* closed */
   int32_t max_depth;             /* < 0: every node; else nodes of depth <= max_depth, as swz_dataset_scan counts depth */
@@ -1165,6 +1199,28 @@ int swz_dataset_query_nodes_why(const char* dir, const swz_query_params* params,
 int swz_dataset_query(swz_ctx* ctx, const char* dir, const swz_query_params* params, uint64_t capacity, double* d_xyz_out,
                       const swz_attribute_columns* d_out, uint32_t* d_node_out /* may be NULL */, uint64_t* count_out,
                       swz_query_stats* stats);
+enum { SWZ_REGION_BOX = 0, SWZ_REGION_PLANES = 1, SWZ_REGION_POLYGON = 2 };
+#define SWZ_REGION_MAX_PLANES 16
+#define SWZ_REGION_MAX_VERTICES 1024
+typedef struct {
+  int32_t kind;         /* SWZ_REGION_* */
+  uint32_t count;       /* planes or vertices; 0 for SWZ_REGION_BOX */
+  const double* values; /* HOST memory: count x (a, b, c, d) or count x (x, y) */
+  uint64_t reserved;    /* 0 */
+} swz_region;
+int swz_region_select_device(swz_ctx* ctx, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t attribute_mask,
+                             const double box_min[3], const double box_max[3], const swz_region* region /* NULL: the box alone */,
+                             uint64_t capacity, double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_row_out,
+                             uint64_t* count_out);
+int swz_dataset_query_region_nodes(swz_ctx* ctx, const char* dir, const swz_query_params* params, const swz_region* region,
+                                   uint64_t max_nodes, int8_t* level_out, uint64_t* key_out, uint64_t* count_out, uint64_t* num_out,
+                                   uint64_t* points_bound_out);
+int swz_dataset_query_region_nodes_why(const char* dir, const swz_query_params* params, const swz_region* region, uint64_t max_nodes,
+                                       int8_t* level_out, uint64_t* key_out, uint64_t* count_out, uint64_t* num_out,
+                                       uint64_t* points_bound_out, char* why_out, uint64_t why_bytes);
+int swz_dataset_query_region(swz_ctx* ctx, const char* dir, const swz_query_params* params, const swz_region* region, uint64_t capacity,
+                             double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_node_out /* may be NULL */,
+                             uint64_t* count_out, swz_query_stats* stats);
 /* ---- a source projection (the reference's --source-projection: Proj4Transform, core/util/Transformation.cpp:74-211, source
  * -> "+proj=geocent +datum=WGS84").  PROJ is not linked: the library maps the projection families LAS data comes in itself,
  * in double, and refuses every other definition by name.

@@ -902,7 +902,7 @@ def dataset_query_nodes(directory, box_min, box_max, max_depth=None, lossy_sourc
 
 
 def dataset_query(ctx, directory, box_min, box_max, max_depth=None, attrs=None, lossy_source=False, chunk_points=0, return_nodes=False,
-                  capacity=None):
+                  capacity=None, _region=None):
     """swz_dataset_query: the points of the written data set in directory inside the closed box [box_min, box_max], of the nodes
     of depth <= max_depth (None: all), streamed from the node files and selected on the device.  attrs: the columns wanted, a
     subset of the source's (None: all it has); lossy_source: admits a 3DTILES source; chunk_points: as in Tiler.write_output.
@@ -911,7 +911,10 @@ def dataset_query(ctx, directory, box_min, box_max, max_depth=None, attrs=None, 
     point the index into dataset_query_nodes' table, else None), count, stats (the fields of swz_query_stats))."""
     import torch
 
-    table = dataset_query_nodes(directory, box_min, box_max, max_depth, lossy_source)
+    if _region is not None:   # dataset_query_region: (region,)
+        table = dataset_query_region_nodes(directory, box_min, box_max, _region[0], max_depth, lossy_source)
+    else:
+        table = dataset_query_nodes(directory, box_min, box_max, max_depth, lossy_source)
     names = attribute_names(dataset_scan(directory, max_depth)["attribute_mask"]) if attrs is None else list(attrs)
     rows = int(table["points_bound"]) if capacity is None else int(capacity)
     dev = torch.device("cuda", ctx.device)
@@ -924,13 +927,116 @@ def dataset_query(ctx, directory, box_min, box_max, max_depth=None, attrs=None, 
     p = _query_params(box_min, box_max, max_depth, names, lossy_source, chunk_points)
     d_cols = device_columns({k: v.data_ptr() for k, v in cols.items()})
     count, stats = C.c_uint64(), _QueryStats()
-    ctx._check(ctx._lib.swz_dataset_query(ctx._ctx, os.fsencode(directory), C.byref(p), rows, C.c_void_p(xyz.data_ptr()), C.byref(d_cols),
-                                          C.c_void_p(node.data_ptr()) if return_nodes else None, C.byref(count), C.byref(stats)))
+    d_node = C.c_void_p(node.data_ptr()) if return_nodes else None
+    if _region is not None:
+        rg = None if _region[0] is None else _region[0]._struct()
+        ctx._check(ctx._lib.swz_dataset_query_region(ctx._ctx, os.fsencode(directory), C.byref(p), None if rg is None else C.byref(rg), rows,
+                                                     C.c_void_p(xyz.data_ptr()), C.byref(d_cols), d_node, C.byref(count), C.byref(stats)))
+    else:
+        ctx._check(ctx._lib.swz_dataset_query(ctx._ctx, os.fsencode(directory), C.byref(p), rows, C.c_void_p(xyz.data_ptr()), C.byref(d_cols),
+                                              d_node, C.byref(count), C.byref(stats)))
     m = int(count.value)
     out = dict(xyz=xyz[:m], node=node[:m] if return_nodes else None, count=m,
                stats={k: getattr(stats, k) for k, _ in _QueryStats._fields_})
     out.update({k: v[:m] for k, v in cols.items()})
     return out
+
+
+# ---- the same by region: the box cut by planes or by a polygon in x-y (swz_region_select_device, swz_dataset_query_region*)
+REGION_BOX, REGION_PLANES, REGION_POLYGON = 0, 1, 2
+REGION_MAX_PLANES, REGION_MAX_VERTICES = 16, 1024
+
+
+class _Region(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("count", C.c_uint32), ("values", C.POINTER(C.c_double)), ("reserved", C.c_uint64)]
+
+
+class Region:
+    """A swz_region: what cuts the closed box of a query further.  Region.planes(k x 4 rows a, b, c, d): the rows with
+    ((a*x + b*y) + c*z) + d >= 0 for every plane (1 to 16; a frustum is six, frustum_planes).  Region.polygon(m x 2 vertices):
+    the rows inside one outline in the x-y plane by the even-odd rule (3 to 1024 vertices; concave and self-intersecting
+    outlines are defined), over the box's z range.  Region.box(): nothing more.  The formulas, operation for operation, are in
+    include/swz_gpu.h.  Nothing is checked here: the library refuses what it does not take (count, reserved and a None for the
+    values are passed on as they are)."""
+
+    def __init__(self, kind, values=None, count=None, reserved=0):
+        self.kind, self.reserved = int(kind), int(reserved)
+        self.values = None if values is None else np.ascontiguousarray(values, dtype=np.float64)
+        self.count = int(count) if count is not None else 0 if self.values is None or self.kind == REGION_BOX else len(self.values)
+
+    @classmethod
+    def box(cls):
+        return cls(REGION_BOX)
+
+    @classmethod
+    def planes(cls, array_k4):
+        return cls(REGION_PLANES, np.asarray(array_k4, dtype=np.float64).reshape(-1, 4))
+
+    @classmethod
+    def polygon(cls, array_m2):
+        return cls(REGION_POLYGON, np.asarray(array_m2, dtype=np.float64).reshape(-1, 2))
+
+    def _struct(self):
+        """the ctypes struct; it points into self.values, which lives as long as self"""
+        return _Region(self.kind, self.count, None if self.values is None else self.values.ctypes.data_as(_dp), self.reserved)
+
+
+def frustum_planes(view_proj):
+    """The six inward planes (rows a, b, c, d) of a row-major 4 x 4 view-projection matrix M, clip = M (x, y, z, 1), with the
+    clip volume -w <= x, y, z <= w: the usual sums and differences of M's rows with its last row -- left, right, bottom, top,
+    near, far --, every row divided by the length of its normal.  The doubles returned are the planes a query takes; nothing
+    is promised about how exactly they follow the matrix."""
+    m = np.asarray(view_proj, dtype=np.float64).reshape(4, 4)
+    rows = np.array([m[3] + m[0], m[3] - m[0], m[3] + m[1], m[3] - m[1], m[3] + m[2], m[3] - m[2]])
+    return rows / np.sqrt((rows[:, :3] ** 2).sum(axis=1))[:, None]
+
+
+def _region_box(directory, box_min, box_max, region, max_depth):
+    """the box of a region query: given, or for a polygon its x-y bounds and the root box's z"""
+    if box_min is not None and box_max is not None:
+        return box_min, box_max
+    if region is None or region.kind != REGION_POLYGON or region.values is None or (box_min is None) != (box_max is None):
+        raise ValueError("a region query needs box_min and box_max (only a polygon may leave both out)")
+    scan = dataset_scan(directory, max_depth)
+    if scan["root_source"] == DATASET_ROOT_ABSENT or scan["format"] == "3DTILES":
+        raise ValueError("no box to derive: the source has no root box, or stores positions relative to an RTC_CENTER")
+    xy = region.values.reshape(-1, 2)
+    return ([xy[:, 0].min(), xy[:, 1].min(), scan["root_min"][2]], [xy[:, 0].max(), xy[:, 1].max(), scan["root_max"][2]])
+
+
+def dataset_query_region_nodes(directory, box_min, box_max, region, max_depth=None, lossy_source=False, source_flags=None, reserved=0):
+    """swz_dataset_query_region_nodes (host, no GPU): dataset_query_nodes for the box cut by region (a Region; None: the box
+    alone).  A node drops out only if its widened box misses the query box or cannot hold a row the region accepts.  box_min
+    and box_max may both be None for a polygon: its x-y bounds and the root box's z.  The dict is dataset_query_nodes'."""
+    L = load_library()
+    box_min, box_max = _region_box(directory, box_min, box_max, region, max_depth)
+    p = _query_params(box_min, box_max, max_depth, None, lossy_source, 0, source_flags, reserved)
+    rg = None if region is None else region._struct()
+    ref = None if rg is None else C.byref(rg)
+    num, bound = C.c_uint64(), C.c_uint64()
+    why = C.create_string_buffer(4096)
+    st = L.swz_dataset_query_region_nodes_why(os.fsencode(directory), C.byref(p), ref, 0, None, None, None, C.byref(num), C.byref(bound), why,
+                                              len(why))
+    if st != 0:
+        raise SwzError(st, why.value.decode(errors="replace"))
+    cap = max(int(num.value), 1)
+    nl, nk, nc = np.empty(cap, dtype=np.int8), np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint64)
+    st = L.swz_dataset_query_region_nodes_why(os.fsencode(directory), C.byref(p), ref, cap, nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p),
+                                              nc.ctypes.data_as(_u64p), C.byref(num), C.byref(bound), why, len(why))
+    if st != 0:
+        raise SwzError(st, why.value.decode(errors="replace"))
+    m = int(num.value)
+    return dict(level=nl[:m].copy(), key=nk[:m].copy(), count=nc[:m].copy(), points_bound=int(bound.value))
+
+
+def dataset_query_region(ctx, directory, box_min, box_max, region, max_depth=None, attrs=None, lossy_source=False, chunk_points=0,
+                         return_nodes=False, capacity=None):
+    """swz_dataset_query_region: dataset_query for the box cut by region (a Region; None: the box alone) -- the same keywords,
+    the same result dict; node indexes dataset_query_region_nodes' table.  box_min and box_max may both be None for a polygon:
+    its x-y bounds and the root box's z; planes need the box."""
+    box_min, box_max = _region_box(directory, box_min, box_max, region, max_depth)
+    return dataset_query(ctx, directory, box_min, box_max, max_depth, attrs, lossy_source, chunk_points, return_nodes, capacity,
+                         _region=(region,))
 
 
 LAS_SCAN_SKIP_UNREADABLE = 1
@@ -1224,6 +1330,14 @@ def load_library():
     L.swz_dataset_query_nodes_why.argtypes = [C.c_char_p, C.POINTER(_QueryParams), C.c_uint64, _i8p, _u64p, _u64p, _u64p, _u64p, C.c_char_p,
                                               C.c_uint64]
     L.swz_dataset_query.argtypes = [vp, C.c_char_p, C.POINTER(_QueryParams), C.c_uint64, vp, cols, vp, _u64p, C.POINTER(_QueryStats)]
+    rgp = C.POINTER(_Region)
+    L.swz_region_select_device.argtypes = [vp, vp, C.c_uint64, cols, C.c_uint32, _dp, _dp, rgp, C.c_uint64, vp, cols, vp, _u64p]
+    L.swz_dataset_query_region_nodes.argtypes = [vp, C.c_char_p, C.POINTER(_QueryParams), rgp, C.c_uint64, _i8p, _u64p, _u64p, _u64p, _u64p]
+    L.swz_dataset_query_region_nodes_why.argtypes = [C.c_char_p, C.POINTER(_QueryParams), rgp, C.c_uint64, _i8p, _u64p, _u64p, _u64p, _u64p,
+                                                     C.c_char_p, C.c_uint64]
+    L.swz_dataset_query_region.argtypes = [vp, C.c_char_p, C.POINTER(_QueryParams), rgp, C.c_uint64, vp, cols, vp, _u64p, C.POINTER(_QueryStats)]
+    for name in ("swz_region_select_device", "swz_dataset_query_region_nodes", "swz_dataset_query_region_nodes_why", "swz_dataset_query_region"):
+        getattr(L, name).restype = C.c_int
     for name in ("swz_box_select_device", "swz_dataset_query_nodes", "swz_dataset_query_nodes_why", "swz_dataset_query"):
         getattr(L, name).restype = C.c_int
     L.swz_tiler_write_output.argtypes = [vp, C.c_char_p, C.POINTER(_OutputParams), C.POINTER(_OutputStats)]
@@ -1696,6 +1810,28 @@ class Context:
             err.needed = int(count.value)
             raise err
         return int(count.value)
+
+    def region_select_device(self, d_xyz, n, box_min, box_max, region, capacity, d_xyz_out, d_attrs=None, d_attrs_out=None, attrs=None,
+                             d_row_out=None):
+        """swz_region_select_device: box_select_device for the box cut by region (a Region; None: the box alone, the bytes of
+        box_select_device).  Everything else -- order, count-only mode, the capacity refusal and its `needed` -- is
+        box_select_device's."""
+        mask = _las_mask(d_attrs.keys() if d_attrs else ()) if attrs is None else (int(attrs) if isinstance(attrs, (int, np.integer)) else _las_mask(attrs))
+        cin, cout = device_columns(d_attrs), device_columns(d_attrs_out)
+        count = C.c_uint64()
+        rg = None if region is None else region._struct()
+        st = self._lib.swz_region_select_device(self._ctx, C.c_void_p(d_xyz), int(n), C.byref(cin), mask, _vec3(box_min), _vec3(box_max),
+                                                None if rg is None else C.byref(rg), int(capacity), C.c_void_p(d_xyz_out), C.byref(cout),
+                                                C.c_void_p(d_row_out), C.byref(count))
+        if st != 0:
+            err = SwzError(st, self._lib.swz_last_error(self._ctx).decode())
+            err.needed = int(count.value)
+            raise err
+        return int(count.value)
+
+    def dataset_query_region(self, directory, box_min, box_max, region, **kwargs):
+        """dataset_query_region(self, directory, box_min, box_max, region, ...)"""
+        return dataset_query_region(self, directory, box_min, box_max, region, **kwargs)
 
     def dataset_query(self, directory, box_min, box_max, **kwargs):
         """dataset_query(self, directory, box_min, box_max, ...)"""

@@ -1,6 +1,7 @@
-// swz_query.hip -- a written data set queried by box and depth (swz_dataset_query_nodes, swz_dataset_query).  The source is
-// opened as the converter opens it (source_open, swz_source.hip), the nodes whose widened boxes miss the query box drop out
-// of the table (host only), and the rest is streamed chunk by chunk with the converter's SourceStream: every chunk's
+// swz_query.hip -- a written data set queried by box and depth (swz_dataset_query_nodes, swz_dataset_query) or by a region,
+// the box cut by planes or by a polygon in x-y (swz_dataset_query_region_nodes, swz_dataset_query_region).  The source is
+// opened as the converter opens it (source_open, swz_source.hip), the nodes whose widened boxes miss the query box or cannot
+// hold a row of the region drop out of the table (host only), and the rest is streamed chunk by chunk with the converter's SourceStream: every chunk's
 // chunk-local positions and columns go through the selection kernel (swz_select.hip) into the caller's arrays at the running
 // offset.  The readers of chunk j + 1 run while chunk j is selected.
 #include <chrono>
@@ -42,9 +43,73 @@ __global__ __launch_bounds__(256) void query_row_nodes_kernel(const uint32_t* __
   node_out[i] = node0 + lo;
 }
 
-// The table a query reads: `kept` holds the nodes of the (depth-limited) scan whose widened boxes meet the query box, in the
-// scan's order; *scanned: the nodes of the scan.
-static int query_plan(swz_ctx* c, const char* who, const char* dir, const swz_query_params* q, DatasetScan* kept, uint64_t* scanned) {
+// ---- the node rule of a region, on the node's widened box [lo, hi] (every room term of the box rule already in it)
+
+// Planes.  The kernel evaluates f^(p) = ((a*x + b*y) + c*z) + d in four rounded operations.  With u = 2^-53 a term passes
+// through four roundings at the most (a*x: its product and three sums), so |f^(p) - f(p)| <= g4 S(p) with g4 = 4u / (1 - 4u)
+// and S(p) = |a||x| + |b||y| + |c||z| + |d| (the usual bound of a recursive sum).  Over the box, f(p) <= F = f(corner), the
+// corner the coefficients' signs choose, and S(p) <= S = |a| max|x| + ... + |d|.  The host evaluates F^ at that corner the
+// same way, |F^ - F| <= g4 S.  Hence f^(p) <= F^ + 2 g4 S for every p of the box, and 2 g4 < 8u = 4 eps; the rule takes
+// 8 eps S (the rounding of S and of the product itself lies far inside the spare factor) and the smallest normal double for
+// products that underflow.  A node is dropped iff F^ + that bound < 0 for some plane.
+static bool planes_miss(const RegionHost& r, const double lo[3], const double hi[3]) {
+  const double eps = std::numeric_limits<double>::epsilon();
+  for (uint32_t k = 0; k < r.count; ++k) {
+    const double* p = &r.v[4 * k];
+    double at[3], s = std::fabs(p[3]);
+    for (int a = 0; a < 3; ++a) {
+      at[a] = p[a] >= 0.0 ? hi[a] : lo[a];
+      s += std::fabs(p[a]) * std::max(std::fabs(lo[a]), std::fabs(hi[a]));
+    }
+    const double f = ((p[0] * at[0] + p[1] * at[1]) + p[2] * at[2]) + p[3];
+    if (f + (8.0 * eps * s + std::numeric_limits<double>::min()) < 0.0) return true;
+  }
+  return false;
+}
+
+// does the segment touch the closed rectangle?  Separating axes: x, y and the segment's normal (the four corners strictly on
+// one side of its line).  The side is the sign of a cross product computed in double; a value within its own rounding
+// (8 eps of the sum of its two products' magnitudes) counts as touching.
+static bool segment_touches(double x0, double y0, double x1, double y1, const double lo[2], const double hi[2]) {
+  if (std::max(x0, x1) < lo[0] || std::min(x0, x1) > hi[0] || std::max(y0, y1) < lo[1] || std::min(y0, y1) > hi[1]) return false;
+  const double eps = std::numeric_limits<double>::epsilon();
+  const double dx = x1 - x0, dy = y1 - y0;
+  int above = 0, below = 0;
+  for (int corner = 0; corner < 4; ++corner) {
+    const double cx = (corner & 1) ? hi[0] : lo[0], cy = (corner & 2) ? hi[1] : lo[1];
+    const double m0 = dx * (cy - y0), m1 = (cx - x0) * dy;
+    const double t = m0 - m1, tol = 8.0 * eps * (std::fabs(m0) + std::fabs(m1));
+    if (t > tol) ++above;
+    else if (t < -tol) ++below;
+  }
+  return !(above == 4 || below == 4);
+}
+
+// Polygon.  Where no edge touches a rectangle the exact parity is one value over all of it, the centre's.  The kernel's
+// parity of a row differs from the exact one only if an edge whose y range holds the row has the wrong sign of t there; t is
+// off by at most 3 eps (|x1 - x0||py - y0| + |px - x0||y1 - y0|) and |py - y0| <= |y1 - y0| for such an edge, so the row lies
+// within 3 eps (|x1 - x0| + |px - x0|) of the edge along x: less than 12 eps of the largest |x| in play.  The rectangle is
+// therefore widened once more, by 32 eps of the largest coordinate of the rectangle and the outline on either axis; then no
+// edge touching it means every row of the node gets the centre's parity, by the formula as by the exact rule.
+static bool polygon_misses(const RegionHost& r, const double lo[3], const double hi[3]) {
+  const double eps = std::numeric_limits<double>::epsilon();
+  double big = 0;
+  for (int a = 0; a < 2; ++a) big = std::max(big, std::max(std::fabs(lo[a]), std::fabs(hi[a])));
+  for (double v : r.v) big = std::max(big, std::fabs(v));
+  const double more = 32.0 * eps * big;
+  const double wlo[2] = {lo[0] - more, lo[1] - more}, whi[2] = {hi[0] + more, hi[1] + more};
+  const uint32_t m = r.count;
+  for (uint32_t i = 0; i < m; ++i) {
+    const uint32_t j = (i + 1) % m;
+    if (segment_touches(r.v[2 * i], r.v[2 * i + 1], r.v[2 * j], r.v[2 * j + 1], wlo, whi)) return false;
+  }
+  return !region_polygon_inside(r, lo[0] + 0.5 * (hi[0] - lo[0]), lo[1] + 0.5 * (hi[1] - lo[1]));
+}
+
+// The table a query reads: `kept` holds the nodes of the (depth-limited) scan whose widened boxes meet the query box and can
+// hold a row of the region, in the scan's order; *scanned: the nodes of the scan; *region_out: the region, checked.
+static int query_plan(swz_ctx* c, const char* who, const char* dir, const swz_query_params* q, const swz_region* region, DatasetScan* kept,
+                      uint64_t* scanned, RegionHost* region_out) {
   auto refuse = [&](const std::string& what) { return fail(c, SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
   if (!dir || !q) return refuse("NULL argument");
   if (!finite3(q->box_min) || !finite3(q->box_max)) return refuse("a bound of the box is not finite");
@@ -52,6 +117,8 @@ static int query_plan(swz_ctx* c, const char* who, const char* dir, const swz_qu
     if (q->box_min[a] > q->box_max[a]) return refuse("box_min > box_max");
   if (q->source_flags & ~(uint32_t)SWZ_CONVERT_LOSSY_SOURCE) return refuse("an unknown bit in source_flags");
   if (q->reserved) return refuse("reserved must be 0");
+  SWZ_TRY(region_check(c, who, region, region_out));  // (before any file is read)
+  const RegionHost& rh = *region_out;
   DatasetScan scan;
   double rtc[3];
   SWZ_TRY(source_open(c, who, dir, q->max_depth, q->source_flags, &scan, rtc));
@@ -72,6 +139,7 @@ static int query_plan(swz_ctx* c, const char* who, const char* dir, const swz_qu
     double lo[3], hi[3];
     if (swz_node_bounds(scan.level[k], scan.key[k], rmin, rmax, lo, hi) != SWZ_OK) return refuse("no box for the node " + scan.path[k]);
     bool meets = true;
+    double wlo[3], whi[3];  // the widened box, for the region's rule
     for (int a = 0; a < 3; ++a) {
       // a point lies in the node of its KEY: two key cells cover the rounding of the cell edges against the halved boxes,
       // four ulps of the largest bound the rounding of the bounds themselves
@@ -84,8 +152,12 @@ static int query_plan(swz_ctx* c, const char* who, const char* dir, const swz_qu
         room += std::ldexp(std::max(std::fabs(lo[a]), std::fabs(hi[a])), -23) + 4 * std::numeric_limits<double>::epsilon() * std::fabs(rtc[a]);
       }
       if (!(lo[a] - room <= q->box_max[a] && q->box_min[a] <= hi[a] + room)) meets = false;
+      wlo[a] = lo[a] - room;
+      whi[a] = hi[a] + room;
     }
     if (!meets) continue;
+    if (rh.kind == SWZ_REGION_PLANES && planes_miss(rh, wlo, whi)) continue;
+    if (rh.kind == SWZ_REGION_POLYGON && polygon_misses(rh, wlo, whi)) continue;
     kept->level.push_back(scan.level[k]);
     kept->key.push_back(scan.key[k]);
     kept->count.push_back(scan.count[k]);
@@ -106,8 +178,8 @@ struct CopyStream {
   }
 };
 
-static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_params* q, uint64_t capacity, double* d_xyz_out,
-                 const swz_attribute_columns* d_out, uint32_t* d_node_out, uint64_t* count_out, swz_query_stats* stats) {
+static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_params* q, const swz_region* region, uint64_t capacity,
+                 double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_node_out, uint64_t* count_out, swz_query_stats* stats) {
   auto refuse = [&](const std::string& what) { return c->fail(SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
   const auto t_wall = std::chrono::steady_clock::now();
   if (stats) *stats = swz_query_stats{};
@@ -115,7 +187,8 @@ static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_p
   *count_out = 0;
   DatasetScan kept;
   uint64_t scanned = 0;
-  SWZ_TRY(query_plan(c, who, dir, q, &kept, &scanned));
+  RegionHost region_host;
+  SWZ_TRY(query_plan(c, who, dir, q, region, &kept, &scanned, &region_host));
   const bool count_only = !d_xyz_out && capacity == 0;
   if (!d_xyz_out && !count_only) return refuse("NULL d_xyz_out with a capacity (count only: NULL and capacity 0)");
   uint32_t mask = q->attribute_mask == ~0u ? kept.info.attribute_mask : q->attribute_mask;
@@ -151,6 +224,8 @@ static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_p
       SWZ_TRY(c->get("out_q_first", (size_t)nodes_max + 1, &d_first));
     }
     std::vector<uint32_t> node_first;
+    RegionDev region_dev;  // a polygon's vertices go up once, not per chunk
+    SWZ_TRY(region_upload(c, region_host, &region_dev));
     SWZ_HIP(c, hipStreamCreateWithFlags(&copy.s, hipStreamNonBlocking));
     SWZ_TRY(source.start(copy.s));
     for (uint64_t j = 0; j < source.num_chunks; ++j) {
@@ -164,8 +239,8 @@ static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_p
       const uint64_t room = count_only ? 0 : capacity - total;
       uint64_t cnt = 0;
       // (a chunk selects its rows at the most: the capacity the kernel's checks see ends with the chunk-local row array)
-      status = box_select(c, who, source.xyz, rows, &source.cols, mask, q->box_min, q->box_max, std::min(room, rows),
-                          count_only ? nullptr : d_xyz_out + 3 * total, &at, d_rows, &cnt);
+      status = region_select(c, who, source.xyz, rows, &source.cols, mask, q->box_min, q->box_max, &region_dev, nullptr, std::min(room, rows),
+                             count_only ? nullptr : d_xyz_out + 3 * total, &at, d_rows, &cnt);
       if (status != SWZ_OK) {
         if (!count_only && cnt > room) {  // the stream stops after this chunk's count
           *count_out = total + cnt;
@@ -211,19 +286,22 @@ using namespace swz;
 
 extern "C" {
 
-int swz_dataset_query_nodes(swz_ctx* c, const char* dir, const swz_query_params* params, uint64_t max_nodes, int8_t* level_out,
-                            uint64_t* key_out, uint64_t* count_out, uint64_t* num_out, uint64_t* points_bound_out) {
+// swz_dataset_query_nodes and swz_dataset_query_region_nodes
+static int query_nodes(swz_ctx* c, const std::string& who, const char* dir, const swz_query_params* params, const swz_region* region,
+                       uint64_t max_nodes, int8_t* level_out, uint64_t* key_out, uint64_t* count_out, uint64_t* num_out,
+                       uint64_t* points_bound_out) {
   swz_ctx text;  // (a NULL context: only the status comes back; no device is touched either way)
   if (!c) c = &text;
-  if (!num_out) return c->fail(SWZ_ERR_BAD_ARG, "swz_dataset_query_nodes: NULL argument");
+  if (!num_out) return c->fail(SWZ_ERR_BAD_ARG, who + ": NULL argument");
   DatasetScan kept;
   uint64_t scanned = 0;
-  SWZ_TRY(query_plan(c, "swz_dataset_query_nodes", dir, params, &kept, &scanned));
+  RegionHost region_host;
+  SWZ_TRY(query_plan(c, who.c_str(), dir, params, region, &kept, &scanned, &region_host));
   const uint64_t nn = kept.count.size();
   *num_out = nn;
   if (points_bound_out) *points_bound_out = kept.info.points;
   if (!level_out && !key_out && !count_out) return SWZ_OK;
-  if (nn > max_nodes) return c->fail(SWZ_ERR_BAD_ARG, "swz_dataset_query_nodes: max_nodes too small");
+  if (nn > max_nodes) return c->fail(SWZ_ERR_BAD_ARG, who + ": max_nodes too small");
   for (uint64_t k = 0; k < nn; ++k) {
     if (level_out) level_out[k] = kept.level[k];
     if (key_out) key_out[k] = kept.key[k];
@@ -232,10 +310,18 @@ int swz_dataset_query_nodes(swz_ctx* c, const char* dir, const swz_query_params*
   return SWZ_OK;
 }
 
-int swz_dataset_query_nodes_why(const char* dir, const swz_query_params* params, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out,
-                                uint64_t* count_out, uint64_t* num_out, uint64_t* points_bound_out, char* why_out, uint64_t why_bytes) {
-  swz_ctx text;  // (only its error text is used: no device is touched)
-  const int st = swz_dataset_query_nodes(&text, dir, params, max_nodes, level_out, key_out, count_out, num_out, points_bound_out);
+int swz_dataset_query_nodes(swz_ctx* c, const char* dir, const swz_query_params* params, uint64_t max_nodes, int8_t* level_out,
+                            uint64_t* key_out, uint64_t* count_out, uint64_t* num_out, uint64_t* points_bound_out) {
+  return query_nodes(c, "swz_dataset_query_nodes", dir, params, nullptr, max_nodes, level_out, key_out, count_out, num_out, points_bound_out);
+}
+
+int swz_dataset_query_region_nodes(swz_ctx* c, const char* dir, const swz_query_params* params, const swz_region* region, uint64_t max_nodes,
+                                   int8_t* level_out, uint64_t* key_out, uint64_t* count_out, uint64_t* num_out, uint64_t* points_bound_out) {
+  return query_nodes(c, "swz_dataset_query_region_nodes", dir, params, region, max_nodes, level_out, key_out, count_out, num_out,
+                     points_bound_out);
+}
+
+static int why_text(int st, const swz_ctx& text, char* why_out, uint64_t why_bytes) {
   if (why_out && why_bytes) {
     const size_t len = std::min<size_t>(st == SWZ_OK ? 0 : text.err.size(), (size_t)why_bytes - 1);
     memcpy(why_out, text.err.data(), len);
@@ -244,10 +330,32 @@ int swz_dataset_query_nodes_why(const char* dir, const swz_query_params* params,
   return st;
 }
 
+int swz_dataset_query_nodes_why(const char* dir, const swz_query_params* params, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out,
+                                uint64_t* count_out, uint64_t* num_out, uint64_t* points_bound_out, char* why_out, uint64_t why_bytes) {
+  swz_ctx text;  // (only its error text is used: no device is touched)
+  const int st = swz_dataset_query_nodes(&text, dir, params, max_nodes, level_out, key_out, count_out, num_out, points_bound_out);
+  return why_text(st, text, why_out, why_bytes);
+}
+
+int swz_dataset_query_region_nodes_why(const char* dir, const swz_query_params* params, const swz_region* region, uint64_t max_nodes,
+                                       int8_t* level_out, uint64_t* key_out, uint64_t* count_out, uint64_t* num_out,
+                                       uint64_t* points_bound_out, char* why_out, uint64_t why_bytes) {
+  swz_ctx text;
+  const int st = swz_dataset_query_region_nodes(&text, dir, params, region, max_nodes, level_out, key_out, count_out, num_out, points_bound_out);
+  return why_text(st, text, why_out, why_bytes);
+}
+
 int swz_dataset_query(swz_ctx* c, const char* dir, const swz_query_params* params, uint64_t capacity, double* d_xyz_out,
                       const swz_attribute_columns* d_out, uint32_t* d_node_out, uint64_t* count_out, swz_query_stats* stats) {
   if (!c) return SWZ_ERR_BAD_ARG;
-  return query(c, "swz_dataset_query", dir, params, capacity, d_xyz_out, d_out, d_node_out, count_out, stats);
+  return query(c, "swz_dataset_query", dir, params, nullptr, capacity, d_xyz_out, d_out, d_node_out, count_out, stats);
+}
+
+int swz_dataset_query_region(swz_ctx* c, const char* dir, const swz_query_params* params, const swz_region* region, uint64_t capacity,
+                             double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_node_out, uint64_t* count_out,
+                             swz_query_stats* stats) {
+  if (!c) return SWZ_ERR_BAD_ARG;
+  return query(c, "swz_dataset_query_region", dir, params, region, capacity, d_xyz_out, d_out, d_node_out, count_out, stats);
 }
 
 }  // extern "C"

@@ -1,13 +1,42 @@
-// swz_select.h -- the box selection (swz_select.hip) for the callers inside the library: swz_box_select_device itself and
-// swz_dataset_query (swz_query.hip), which runs it chunk by chunk.
+// swz_select.h -- the selection (swz_select.hip) for the callers inside the library: swz_box_select_device and
+// swz_region_select_device themselves and the data-set query (swz_query.hip), which runs it chunk by chunk.
 #pragma once
+#include <vector>
+
 #include "swz_internal.h"
 
 namespace swz {
 
-// swz_box_select_device as include/swz_gpu.h describes it; `who` starts the messages.  Synchronises c's stream.
-int box_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t mask,
-               const double box_min[3], const double box_max[3], uint64_t capacity, double* d_xyz_out,
-               const swz_attribute_columns* d_out, uint32_t* d_row_out, uint64_t* count_out);
+// a swz_region checked and copied (host only): what the node rule of swz_query.hip reads
+struct RegionHost {
+  int kind = SWZ_REGION_BOX;
+  uint32_t count = 0;
+  std::vector<double> v;  // count x (a, b, c, d) or count x (x, y)
+};
+// the refusals of include/swz_gpu.h, `who` in front; region == NULL is the box.  c may be NULL (only the status comes back).
+int region_check(swz_ctx* c, const char* who, const swz_region* region, RegionHost* out);
+// the polygon test of include/swz_gpu.h on the host, operation for operation what the kernel evaluates
+bool region_polygon_inside(const RegionHost& r, double px, double py);
+
+// what the kernels take: planes by value, a polygon's vertices in the workspace buffer "sel_poly"
+struct RegionPlanes {
+  double p[SWZ_REGION_MAX_PLANES][4];
+  uint32_t count;
+};
+struct RegionDev {
+  int kind = SWZ_REGION_BOX;
+  RegionPlanes planes{};
+  const double* d_xy = nullptr;  // polygon: count x (x, y)
+  uint32_t vertices = 0;
+};
+// uploads a polygon's vertices (once per call; once per query); synchronises c's stream
+int region_upload(swz_ctx* c, const RegionHost& r, RegionDev* out);
+
+// swz_region_select_device as include/swz_gpu.h describes it; `who` starts the messages.  The region: `region`, already on
+// the device (the query: once for all chunks), or `upload`, a checked one still on the host, which goes up once every other
+// check has passed; neither: the box alone, swz_box_select_device.  Synchronises c's stream.
+int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t mask,
+                  const double box_min[3], const double box_max[3], const RegionDev* region, const RegionHost* upload, uint64_t capacity,
+                  double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_row_out, uint64_t* count_out);
 
 }  // namespace swz

@@ -10,9 +10,16 @@
 // run leaves as consecutive doubles.  The source row of every output row stays in LDS: lane t then moves output row t of the
 // tile column by column -- 8- and 12-byte rows as whole words, consecutive lanes consecutive addresses; the 1-, 2- and
 // 3-byte rows as plain per-row stores (putting them together into dwords has not been measured).
+//
+// A region (swz_region_select_device) is the box cut by planes or by a polygon in x-y (the formulas: include/swz_gpu.h).  Its
+// count pass, region_count_kernel<planes | polygon>, ranks like the box's and also stores every wave's ballot; its scatter,
+// select_scatter_kernel<true>, is the box's scatter with the ballot read back in place of the predicate, so the edge loop of
+// a polygon (up to 1024 iterations of FP64 per row) runs once per row, in a kernel that holds no other LDS to speak of.  The
+// box kernels are what they were: select_count_kernel untouched, select_scatter_kernel<false> the same instructions.
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 #include "swz_device.h"
 #include "swz_hostio.h"
@@ -46,9 +53,10 @@ __device__ __forceinline__ bool select_inside(const SelectBox& b, double x, doub
 }
 
 // the rank of this lane's row among the tile's selected rows, and their number; every lane of the workgroup calls it
-__device__ __forceinline__ uint32_t select_rank(bool in, uint32_t* s_wave, uint32_t* total) {
+__device__ __forceinline__ uint32_t select_rank(bool in, uint32_t* s_wave, uint32_t* total, uint64_t* ballot = nullptr) {
   const uint32_t lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
   const uint64_t bal = __ballot(in);
+  if (ballot) *ballot = bal;
   if (lane == 0) s_wave[wave] = (uint32_t)__popcll(bal);
   __syncthreads();
   uint32_t before = 0, all = 0;
@@ -92,7 +100,10 @@ __device__ __forceinline__ void select_move(const uint8_t* __restrict__ in, uint
   }
 }
 
-__global__ __launch_bounds__(SEL_TILE) void select_scatter_kernel(SelectArgs a) {
+// The scatter, instantiated over who decides a row.  BALLOTS false: the box test, here (swz_box_select_device; `ballots` is
+// not read).  BALLOTS true: the count pass of a region has decided every row and left its waves' ballots.
+template <bool BALLOTS>
+__global__ __launch_bounds__(SEL_TILE) void select_scatter_kernel(SelectArgs a, const uint64_t* __restrict__ ballots) {
   __shared__ double s_xyz[3 * SEL_TILE];
   __shared__ uint32_t s_src[SEL_TILE];
   __shared__ uint32_t s_wave[SEL_WAVES];
@@ -107,7 +118,8 @@ __global__ __launch_bounds__(SEL_TILE) void select_scatter_kernel(SelectArgs a) 
     x = s_xyz[3 * t];
     y = s_xyz[3 * t + 1];
     z = s_xyz[3 * t + 2];
-    in = select_inside(a.box, x, y, z);
+    if constexpr (BALLOTS) in = ((ballots[(uint64_t)blockIdx.x * SEL_WAVES + t / WAVE] >> (t % WAVE)) & 1ull) != 0;
+    else in = select_inside(a.box, x, y, z);
   }
   uint32_t cnt;
   const uint32_t rank = select_rank(in, s_wave, &cnt);  // (its barrier: every lane holds its row before the array is reused)
@@ -138,15 +150,136 @@ __global__ __launch_bounds__(SEL_TILE) void select_scatter_kernel(SelectArgs a) 
   }
 }
 
+// ---- regions: the box cut by planes or by a polygon in x-y
+struct RegionPolygon {
+  const double* xy;  // vertices x (x, y)
+  uint32_t vertices;
+};
+
+// every plane: ((a*x + b*y) + c*z) + d >= 0, four separately rounded operations (the library is built without contraction)
+__device__ __forceinline__ bool planes_inside(const RegionPlanes& P, double x, double y, double z) {
+  bool in = true;
+  for (uint32_t k = 0; k < P.count; ++k) in = in && ((P.p[k][0] * x + P.p[k][1] * y) + P.p[k][2] * z) + P.p[k][3] >= 0.0;
+  return in;
+}
+
+// even-odd over the edges (v[i], v[(i+1) mod m]); the parity does not care that the closing edge comes first.  Every lane
+// reads the same LDS address: a broadcast.
+__device__ __forceinline__ bool polygon_inside(const double* s_xy, uint32_t m, double px, double py) {
+  bool odd = false;
+  double x0 = s_xy[2 * (m - 1)], y0 = s_xy[2 * (m - 1) + 1];
+  for (uint32_t i = 0; i < m; ++i) {
+    const double x1 = s_xy[2 * i], y1 = s_xy[2 * i + 1];
+    if ((y0 > py) != (y1 > py)) {
+      const double t = (x1 - x0) * (py - y0) - (px - x0) * (y1 - y0);
+      odd ^= (t > 0.0) == (y1 > y0);
+    }
+    x0 = x1;
+    y0 = y1;
+  }
+  return odd;
+}
+
+// the count pass of a region: R is RegionPlanes (in the kernel arguments) or RegionPolygon (staged in LDS: 16 KiB at the
+// most, which with the 16 bytes of the ranking leaves the 32 waves of a CU their room in its 160 KiB).  ballots: one word per
+// wave of every tile, what select_scatter_kernel<true> reads back.
+template <class R>
+__global__ __launch_bounds__(SEL_TILE) void region_count_kernel(const double* __restrict__ xyz, uint32_t n, SelectBox box, R region,
+                                                                uint32_t* __restrict__ tile_count, uint64_t* __restrict__ ballots) {
+  __shared__ uint32_t s_wave[SEL_WAVES];
+  const uint64_t r = (uint64_t)blockIdx.x * SEL_TILE + threadIdx.x;
+  double x = 0, y = 0, z = 0;
+  bool in = false;
+  if (r < n) {
+    x = xyz[3 * r];
+    y = xyz[3 * r + 1];
+    z = xyz[3 * r + 2];
+    in = select_inside(box, x, y, z);  // (keeps NaN out of the tests below)
+  }
+  if constexpr (std::is_same_v<R, RegionPolygon>) {
+    __shared__ double s_xy[2 * SWZ_REGION_MAX_VERTICES];
+    for (uint32_t i = threadIdx.x; i < 2u * region.vertices; i += SEL_TILE) s_xy[i] = region.xy[i];
+    __syncthreads();
+    if (in) in = polygon_inside(s_xy, region.vertices, x, y);  // only the rows of the box walk the edges
+  } else {
+    if (in) in = planes_inside(region, x, y, z);
+  }
+  uint32_t total;
+  uint64_t bal;
+  (void)select_rank(in, s_wave, &total, &bal);
+  if (threadIdx.x % WAVE == 0) ballots[(uint64_t)blockIdx.x * SEL_WAVES + threadIdx.x / WAVE] = bal;
+  if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
+}
+
+int region_check(swz_ctx* c, const char* who, const swz_region* region, RegionHost* out) {
+  auto refuse = [&](const std::string& what) { return fail(c, SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
+  *out = RegionHost{};
+  if (!region) return SWZ_OK;
+  if (region->kind != SWZ_REGION_BOX && region->kind != SWZ_REGION_PLANES && region->kind != SWZ_REGION_POLYGON)
+    return refuse("an unknown kind of region");
+  if (region->reserved) return refuse("the region's reserved must be 0");
+  if (region->kind == SWZ_REGION_BOX) {
+    if (region->count) return refuse("a box region with a count that is not 0");
+    return SWZ_OK;
+  }
+  const bool planes = region->kind == SWZ_REGION_PLANES;
+  if (planes && (region->count < 1 || region->count > SWZ_REGION_MAX_PLANES)) return refuse("a region of planes holds 1 to 16 of them");
+  if (!planes && (region->count < 3 || region->count > SWZ_REGION_MAX_VERTICES)) return refuse("a polygon region holds 3 to 1024 vertices");
+  if (!region->values) return refuse("a region with NULL values");
+  const size_t len = (size_t)region->count * (planes ? 4 : 2);
+  for (size_t i = 0; i < len; ++i)
+    if (!std::isfinite(region->values[i])) return refuse(planes ? "a coefficient of a plane is not finite" : "a vertex of the polygon is not finite");
+  if (planes)
+    for (uint32_t k = 0; k < region->count; ++k)
+      if (region->values[4 * k] == 0.0 && region->values[4 * k + 1] == 0.0 && region->values[4 * k + 2] == 0.0)
+        return refuse("a plane with a = b = c = 0");
+  out->kind = region->kind;
+  out->count = region->count;
+  out->v.assign(region->values, region->values + len);
+  return SWZ_OK;
+}
+
+bool region_polygon_inside(const RegionHost& r, double px, double py) {
+  const uint32_t m = r.count;
+  bool odd = false;
+  for (uint32_t i = 0; i < m; ++i) {
+    const double x0 = r.v[2 * i], y0 = r.v[2 * i + 1], x1 = r.v[2 * ((i + 1) % m)], y1 = r.v[2 * ((i + 1) % m) + 1];
+    if ((y0 > py) != (y1 > py)) {
+      const double t = (x1 - x0) * (py - y0) - (px - x0) * (y1 - y0);
+      odd ^= (t > 0.0) == (y1 > y0);
+    }
+  }
+  return odd;
+}
+
+int region_upload(swz_ctx* c, const RegionHost& r, RegionDev* out) {
+  *out = RegionDev{};
+  out->kind = r.kind;
+  if (r.kind == SWZ_REGION_PLANES) {
+    out->planes.count = r.count;
+    memcpy(out->planes.p, r.v.data(), r.v.size() * sizeof(double));
+  } else if (r.kind == SWZ_REGION_POLYGON) {
+    double* d_xy = nullptr;
+    SWZ_HIP(c, hipSetDevice(c->device));
+    SWZ_TRY(c->get("sel_poly", (size_t)2 * SWZ_REGION_MAX_VERTICES, &d_xy));
+    SWZ_HIP(c, hipMemcpyAsync(d_xy, r.v.data(), r.v.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    SWZ_HIP(c, hipStreamSynchronize(c->stream));  // (r.v is the caller's)
+    out->d_xy = d_xy;
+    out->vertices = r.count;
+  }
+  return SWZ_OK;
+}
+
 static bool overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
   if (!a || !b || !a_bytes || !b_bytes) return false;
   const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
   return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
-int box_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t mask,
-               const double box_min[3], const double box_max[3], uint64_t capacity, double* d_xyz_out,
-               const swz_attribute_columns* d_out, uint32_t* d_row_out, uint64_t* count_out) {
+int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t mask,
+                  const double box_min[3], const double box_max[3], const RegionDev* region, const RegionHost* upload, uint64_t capacity,
+                  double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_row_out, uint64_t* count_out) {
+  const int kind = upload ? upload->kind : region ? region->kind : SWZ_REGION_BOX;
   auto refuse = [&](const std::string& what) { return c->fail(SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
   static_assert(SEL_BYTES[SWZ_ATTR_RGB] == 3 && SEL_BYTES[SWZ_ATTR_NORMAL] == 12 && SEL_BYTES[SWZ_ATTR_INTENSITY] == 2 &&
                   SEL_BYTES[SWZ_ATTR_POINT_SOURCE_ID] == 2 && SEL_BYTES[SWZ_ATTR_GPS_TIME] == 8,
@@ -195,6 +328,11 @@ int box_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, con
   if (n == 0) return SWZ_OK;
 
   SWZ_HIP(c, hipSetDevice(c->device));
+  RegionDev uploaded;
+  if (upload) {
+    SWZ_TRY(region_upload(c, *upload, &uploaded));
+    region = &uploaded;
+  }
   const uint32_t nb = div_up(n, SEL_TILE);
   uint32_t *d_tiles = nullptr, *d_total = nullptr;
   SWZ_TRY(c->get("sel_tiles", (size_t)nb, &d_tiles));
@@ -206,10 +344,24 @@ int box_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, con
     a.box.lo[k] = box_min[k];
     a.box.hi[k] = box_max[k];
   }
-  {
+  uint64_t* d_ballots = nullptr;
+  if (kind == SWZ_REGION_BOX) {
     ProfScope ps(c, "box_select_count", 24 * n, 1);
     hipLaunchKernelGGL(select_count_kernel, dim3(nb), dim3(SEL_TILE), 0, c->stream, d_xyz, a.n, a.box, d_tiles);
     SWZ_LAUNCH_CHECK(c);
+  } else {
+    SWZ_TRY(c->get("sel_ballots", (size_t)nb * SEL_WAVES, &d_ballots));
+    if (kind == SWZ_REGION_PLANES) {
+      ProfScope ps(c, "planes_select_count", 24 * n + 8ull * nb * SEL_WAVES, 1);
+      hipLaunchKernelGGL(region_count_kernel<RegionPlanes>, dim3(nb), dim3(SEL_TILE), 0, c->stream, d_xyz, a.n, a.box, region->planes, d_tiles,
+                         d_ballots);
+      SWZ_LAUNCH_CHECK(c);
+    } else {
+      ProfScope ps(c, "polygon_select_count", 24 * n + 8ull * nb * SEL_WAVES, 1);
+      hipLaunchKernelGGL(region_count_kernel<RegionPolygon>, dim3(nb), dim3(SEL_TILE), 0, c->stream, d_xyz, a.n, a.box,
+                         RegionPolygon{region->d_xy, region->vertices}, d_tiles, d_ballots);
+      SWZ_LAUNCH_CHECK(c);
+    }
   }
   SWZ_TRY(scan_exclusive_u32(c, d_tiles, d_tiles, nb, d_total, "sel"));
   uint32_t total = 0;
@@ -217,7 +369,8 @@ int box_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, con
   *count_out = total;
   if (count_only || total == 0) return SWZ_OK;
   if (total > capacity)
-    return refuse("capacity " + std::to_string(capacity) + " is less than the " + std::to_string(total) + " rows of the box");
+    return refuse("capacity " + std::to_string(capacity) + " is less than the " + std::to_string(total) +
+                  (kind == SWZ_REGION_BOX ? " rows of the box" : " rows of the region"));
   a.tile_first = d_tiles;
   a.xyz_out = d_xyz_out;
   a.row_out = d_row_out;
@@ -228,9 +381,14 @@ int box_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, con
     a.out[k] = static_cast<uint8_t*>(d_out->column[k]);
     row_bytes += 2 * ATTR_BYTES[k];
   }
-  {
+  if (kind == SWZ_REGION_BOX) {
     ProfScope ps(c, "box_select_scatter", 24 * n + row_bytes * total, 1);
-    hipLaunchKernelGGL(select_scatter_kernel, dim3(nb), dim3(SEL_TILE), 0, c->stream, a);
+    hipLaunchKernelGGL(select_scatter_kernel<false>, dim3(nb), dim3(SEL_TILE), 0, c->stream, a, (const uint64_t*)nullptr);
+    SWZ_LAUNCH_CHECK(c);
+  } else {
+    ProfScope ps(c, kind == SWZ_REGION_PLANES ? "planes_select_scatter" : "polygon_select_scatter",
+                 24 * n + 8ull * nb * SEL_WAVES + row_bytes * total, 1);
+    hipLaunchKernelGGL(select_scatter_kernel<true>, dim3(nb), dim3(SEL_TILE), 0, c->stream, a, (const uint64_t*)d_ballots);
     SWZ_LAUNCH_CHECK(c);
   }
   SWZ_HIP(c, hipStreamSynchronize(c->stream));
@@ -249,8 +407,19 @@ int swz_box_select_device(swz_ctx* c, const double* d_xyz, uint64_t n, const swz
                           const double box_min[3], const double box_max[3], uint64_t capacity, double* d_xyz_out,
                           const swz_attribute_columns* d_out, uint32_t* d_row_out, uint64_t* count_out) {
   if (!c) return SWZ_ERR_BAD_ARG;
-  return box_select(c, "swz_box_select_device", d_xyz, n, d_in, attribute_mask, box_min, box_max, capacity, d_xyz_out, d_out, d_row_out,
-                    count_out);
+  return region_select(c, "swz_box_select_device", d_xyz, n, d_in, attribute_mask, box_min, box_max, nullptr, nullptr, capacity, d_xyz_out,
+                       d_out, d_row_out, count_out);
+}
+
+int swz_region_select_device(swz_ctx* c, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t attribute_mask,
+                             const double box_min[3], const double box_max[3], const swz_region* region, uint64_t capacity,
+                             double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_row_out, uint64_t* count_out) {
+  if (!c) return SWZ_ERR_BAD_ARG;
+  const char* who = "swz_region_select_device";
+  RegionHost host;
+  SWZ_TRY(region_check(c, who, region, &host));
+  return region_select(c, who, d_xyz, n, d_in, attribute_mask, box_min, box_max, nullptr, &host, capacity, d_xyz_out, d_out, d_row_out,
+                       count_out);
 }
 
 }  // extern "C"

@@ -24,6 +24,8 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
+#include <cmath>
 #include <cstdint>
 #include <map>
 #include <memory>
@@ -195,13 +197,17 @@ struct QueryResult {
   std::vector<uint32_t> nodes;
   swz_query_stats stats{};
 };
-inline QueryResult query_dataset(Context& ctx, const std::string& dir, const swz_query_params& params, bool lossy_source = false,
-                                 bool want_nodes = false) {
+// query_dataset for the box cut by a region (swz_dataset_query_region): planes (a frustum: frustum_planes) or a polygon in
+// x-y; region == nullptr is the box alone.  Everything else is query_dataset's; nodes index swz_dataset_query_region_nodes'
+// table.
+inline QueryResult query_dataset_region(Context& ctx, const std::string& dir, const swz_query_params& params, const swz_region* region,
+                                        bool lossy_source = false, bool want_nodes = false) {
   static const uint32_t widths[SWZ_ATTR_COUNT] = {3, 12, 2, 1, 1, 8, 1, 1, 2, 1, 1, 1};
   swz_query_params p = params;
   if (lossy_source) p.source_flags |= SWZ_CONVERT_LOSSY_SOURCE;
   uint64_t kept = 0, bound = 0;
-  ctx.check(swz_dataset_query_nodes(ctx.get(), dir.c_str(), &p, 0, nullptr, nullptr, nullptr, &kept, &bound));
+  if (region) ctx.check(swz_dataset_query_region_nodes(ctx.get(), dir.c_str(), &p, region, 0, nullptr, nullptr, nullptr, &kept, &bound));
+  else ctx.check(swz_dataset_query_nodes(ctx.get(), dir.c_str(), &p, 0, nullptr, nullptr, nullptr, &kept, &bound));
   if (p.attribute_mask == ~0u) {
     swz_dataset_info info{};
     uint64_t scanned = 0;
@@ -226,7 +232,8 @@ inline QueryResult query_dataset(Context& ctx, const std::string& dir, const swz
   for (int a = 0; a < SWZ_ATTR_COUNT; ++a)
     if ((p.attribute_mask >> a) & 1u) d_cols.column[a] = alloc(widths[a] * bound);
   uint32_t* d_nodes = want_nodes ? static_cast<uint32_t*>(alloc(4 * bound)) : nullptr;
-  ctx.check(swz_dataset_query(ctx.get(), dir.c_str(), &p, bound, d_xyz, &d_cols, d_nodes, &out.count, &out.stats));
+  if (region) ctx.check(swz_dataset_query_region(ctx.get(), dir.c_str(), &p, region, bound, d_xyz, &d_cols, d_nodes, &out.count, &out.stats));
+  else ctx.check(swz_dataset_query(ctx.get(), dir.c_str(), &p, bound, d_xyz, &d_cols, d_nodes, &out.count, &out.stats));
   out.positions.resize(3 * out.count);
   if (out.count) ctx.check(swz_copy_to_host(ctx.get(), out.positions.data(), d_xyz, 24 * out.count));
   for (int a = 0; a < SWZ_ATTR_COUNT; ++a) {
@@ -237,6 +244,26 @@ inline QueryResult query_dataset(Context& ctx, const std::string& dir, const swz
   if (want_nodes) {
     out.nodes.resize(out.count);
     if (out.count) ctx.check(swz_copy_to_host(ctx.get(), out.nodes.data(), d_nodes, 4 * out.count));
+  }
+  return out;
+}
+inline QueryResult query_dataset(Context& ctx, const std::string& dir, const swz_query_params& params, bool lossy_source = false,
+                                 bool want_nodes = false) {
+  return query_dataset_region(ctx, dir, params, nullptr, lossy_source, want_nodes);
+}
+
+// The six inward planes of a row-major 4 x 4 view-projection matrix m (clip = m (x, y, z, 1), clip volume -w <= x, y, z <= w),
+// as rows (a, b, c, d) for a swz_region of SWZ_REGION_PLANES: the sums and differences of m's rows with its last row -- left,
+// right, bottom, top, near, far --, every row divided by the length of its normal.  The doubles returned are the planes the
+// query takes; nothing is promised about how exactly they follow the matrix.
+inline std::array<double, 24> frustum_planes(const double m[16]) {
+  std::array<double, 24> out{};
+  for (int k = 0; k < 6; ++k) {
+    const double sign = (k & 1) ? -1.0 : 1.0;
+    double row[4];
+    for (int j = 0; j < 4; ++j) row[j] = m[12 + j] + sign * m[4 * (k / 2) + j];
+    const double len = std::sqrt(row[0] * row[0] + row[1] * row[1] + row[2] * row[2]);
+    for (int j = 0; j < 4; ++j) out[4 * k + j] = row[j] / len;
   }
   return out;
 }

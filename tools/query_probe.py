@@ -9,7 +9,11 @@ wall), and the host recipe -- bin_read_node of EVERY node file plus a numpy mask
 time scaled to the whole table by points; 0: all).  The times are printed, none is asserted; the counts of the two must agree
 when the host recipe ran over all nodes.  Everything goes into a fresh directory under --dir (default: the system's temporary
 directory).  The work runs in one child process under `timeout`.
-usage: query_probe.py [points] [--batches K] [--dir DIR] [--host-nodes N] [--json FILE]"""
+--polygon M: every box is cut by the regular M-gon inscribed in its x-y rectangle (dataset_query_region); --planes: by the
+frustum of a fixed camera above the corner (-0.6, -0.4, 1.2) looking at (0.5, 0.5, 0.3).  Per box then: the stats of the region
+query, beside them those of the box query of the region's bounding box (`box_query`), and the host recipe with the region's
+formula in numpy.
+usage: query_probe.py [points] [--batches K] [--dir DIR] [--host-nodes N] [--json FILE] [--polygon M | --planes]"""
 import json
 import os
 import shutil
@@ -24,7 +28,51 @@ NAMES = ("rgb", "intensity")
 BOXES = dict(whole=([0.0] * 3, [1.0] * 3), eighth=([0.0] * 3, [0.5] * 3), slab=([0.0, 0.0, 0.5], [1.0, 1.0, 0.5 + 2.0 ** -10]))
 
 
-def host_recipe(swz, np, src, nodes, box, limit):
+def camera_planes(swz, np):
+    """the six planes of the fixed camera: an OpenGL-style look-at and perspective, through frustum_planes"""
+    eye, target, up = np.array([-0.6, -0.4, 1.2]), np.array([0.5, 0.5, 0.3]), np.array([0.0, 0.0, 1.0])
+    f = (target - eye) / np.linalg.norm(target - eye)
+    s = np.cross(f, up) / np.linalg.norm(np.cross(f, up))
+    view = np.eye(4)
+    view[0, :3], view[1, :3], view[2, :3] = s, np.cross(s, f), -f
+    view[:3, 3] = -view[:3, :3] @ eye
+    t, aspect, near, far = 1.0 / np.tan(np.radians(40.0) / 2), 1.25, 0.1, 3.0
+    proj = np.array([[t / aspect, 0, 0, 0], [0, t, 0, 0], [0, 0, (far + near) / (near - far), 2 * far * near / (near - far)], [0, 0, -1, 0]])
+    return swz.frustum_planes(proj @ view)
+
+
+def make_region(swz, np, spec, box):
+    """spec: "", "planes" or "polygon:M" -> (Region or None, the region's bounding box, its mask over rows already in the box)"""
+    if not spec:
+        return None, box, lambda xyz: np.ones(len(xyz), bool)
+    if spec == "planes":
+        planes = camera_planes(swz, np)
+
+        def inside(xyz):
+            m = np.ones(len(xyz), bool)
+            for a, b, c, d in planes:
+                m &= ((a * xyz[:, 0] + b * xyz[:, 1]) + c * xyz[:, 2]) + d >= 0.0
+            return m
+        return swz.Region.planes(planes), box, inside
+    m = int(spec.split(":")[1])
+    ang = 2 * np.pi * np.arange(m) / m
+    cx, cy = (box[0][0] + box[1][0]) / 2, (box[0][1] + box[1][1]) / 2
+    v = np.stack([cx + (box[1][0] - box[0][0]) / 2 * np.cos(ang), cy + (box[1][1] - box[0][1]) / 2 * np.sin(ang)], axis=1)
+
+    def inside(xyz):
+        px, py = xyz[:, 0], xyz[:, 1]
+        odd = np.zeros(len(xyz), bool)
+        for i in range(m):
+            (x0, y0), (x1, y1) = v[i], v[(i + 1) % m]
+            t = (x1 - x0) * (py - y0) - (px - x0) * (y1 - y0)
+            odd ^= ((y0 > py) != (y1 > py)) & ((t > 0.0) == (y1 > y0))
+        return odd
+    bound = ([max(box[0][0], v[:, 0].min()), max(box[0][1], v[:, 1].min()), box[0][2]],
+             [min(box[1][0], v[:, 0].max()), min(box[1][1], v[:, 1].max()), box[1][2]])
+    return swz.Region.polygon(v), bound, inside
+
+
+def host_recipe(swz, np, src, nodes, box, limit, region_mask=None):
     """bin_read_node of the first `limit` nodes (0: all) and a numpy mask; seconds, points read, points inside"""
     lo, hi = np.asarray(box[0]), np.asarray(box[1])
     done = inside = 0
@@ -32,13 +80,16 @@ def host_recipe(swz, np, src, nodes, box, limit):
     for k in range(len(nodes["count"]) if not limit else min(limit, len(nodes["count"]))):
         xyz, cols = swz.bin_read_node(os.path.join(src, swz.node_name(int(nodes["level"][k]), int(nodes["key"][k])) + ".bin"))
         sel = ((xyz >= lo) & (xyz <= hi)).all(axis=1)
+        if region_mask is not None:
+            at = np.flatnonzero(sel)
+            sel[at] = region_mask(xyz[at])
         kept = (xyz[sel], {name: v[sel] for name, v in cols.items()})
         done += len(xyz)
         inside += len(kept[0])
     return time.perf_counter() - t0, done, inside
 
 
-def step(n, batches, base, host_nodes):
+def step(n, batches, base, host_nodes, spec=""):
     import numpy as np
     import schwarzwald_amd as swz
     ctx = swz.Context(0)
@@ -61,12 +112,18 @@ def step(n, batches, base, host_nodes):
     t.close()
     print("QUERY_PROBE " + json.dumps(dict(source=out)), flush=True)
     for name, box in BOXES.items():
-        row = dict(box=name)
+        row = dict(box=name, region=spec or "box")
+        region, bound, mask = make_region(swz, np, spec, box)
         for rep in ("warm", "timed"):   # the first run pays allocations and the page cache
-            got = swz.dataset_query(ctx, src, box[0], box[1], attrs=NAMES)
+            got = swz.dataset_query_region(ctx, src, box[0], box[1], region, attrs=NAMES) if region is not None else \
+                swz.dataset_query(ctx, src, box[0], box[1], attrs=NAMES)
             row["query"] = dict(got["stats"], count=got["count"])
             del got
-        secs, done, inside = host_recipe(swz, np, src, nodes, box, host_nodes)
+            if region is not None:   # beside it: what the caller asked for before, the region's bounding box
+                got = swz.dataset_query(ctx, src, bound[0], bound[1], attrs=NAMES)
+                row["box_query"] = dict(got["stats"], count=got["count"])
+                del got
+        secs, done, inside = host_recipe(swz, np, src, nodes, box, host_nodes, mask if region is not None else None)
         row["host_recipe"] = dict(measured_s=secs, points=done, inside=inside, scaled_to_all_s=secs * stored / max(done, 1))
         row["host_over_query"] = row["host_recipe"]["scaled_to_all_s"] * 1e3 / row["query"]["wall_ms"]
         if done == stored:
@@ -79,15 +136,16 @@ def step(n, batches, base, host_nodes):
 def main():
     args = sys.argv[1:]
     if args and args[0] == "--step":
-        return step(int(args[1]), int(args[2]), args[3] or None, int(args[4]))
+        return step(int(args[1]), int(args[2]), args[3] or None, int(args[4]), args[5] if len(args) > 5 else "")
 
     def option(name, default):
         return args[args.index(name) + 1] if name in args else default
     n = int(args[0]) if args and not args[0].startswith("--") else 100_000_000
     limit = str(max(300, n // 50_000))
+    spec = "planes" if "--planes" in args else "polygon:" + option("--polygon", "0") if "--polygon" in args else ""
     # one child under its own time limit; check=True: a failure ends the script here
     r = subprocess.run(["timeout", "-k", "10", limit, sys.executable, os.path.abspath(__file__), "--step", str(n), option("--batches", "10"),
-                        option("--dir", ""), option("--host-nodes", "0")], check=True, stdout=subprocess.PIPE, text=True)
+                        option("--dir", ""), option("--host-nodes", "0"), spec], check=True, stdout=subprocess.PIPE, text=True)
     results = [json.loads(l[len("QUERY_PROBE "):]) for l in r.stdout.splitlines() if l.startswith("QUERY_PROBE ")]
     for row in results:
         print(json.dumps(row), flush=True)
