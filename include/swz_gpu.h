@@ -1172,8 +1172,41 @@ int swz_convert_dataset(swz_ctx* ctx, const char* src_dir, const char* dst_dir, 
  *     expression's rounding is < 0; for a polygon, if no edge touches the widened x-y rectangle (segment against rectangle,
  *     widened again by the rounding of t) and the rectangle's centre is outside by the formula above.  The rule errs
  *     towards reading a file.
+ *   A filter (swz_filter; swz_filter_check, swz_filter_select_device, swz_dataset_query_filtered) is a predicate over the
+ *     attribute columns, evaluated behind the region: a row is selected iff it is in the region AND passes EVERY one of the
+ *     filter's 1..SWZ_FILTER_MAX_CLAUSES clauses.  Two clauses may name the same attribute.  count == 0 and filter == NULL both
+ *     mean no filter: the bytes of the region calls.  A clause tests the value v its `attribute` column holds for the row:
+ *       SWZ_FILTER_RANGE, on every scalar column -- INTENSITY and POINT_SOURCE_ID (uint16), GPS_TIME (double),
+ *         SCAN_ANGLE_RANK (int8, compared as its signed value) and the uint8 columns: v is converted to double, which is
+ *         exact for every one of these types, and the row passes iff  lo <= (double)v && (double)v <= hi,  two plain double
+ *         compares, closed at both ends.  lo and hi may be -infinity and +infinity, which gives an open end.  A NaN GPS time
+ *         fails both compares, so it fails a RANGE and passes a RANGE with SWZ_FILTER_NOT.
+ *       SWZ_FILTER_SET, on the one-byte columns only: the row passes iff bit b of the 256-bit map is set, b the stored byte
+ *         read as unsigned (bit b is bit b % 64 of set[b / 64]); scan-angle rank -1 is bit 255.
+ *       SWZ_FILTER_NOT in `kind` inverts the clause's test.
+ *     The fields a kind does not use are 0, so that they can mean something later.  SWZ_ERR_BAD_ARG with a message that names
+ *     the clause ("clause 3: ..."), before anything is launched or any file is read: count > 8, reserved != 0, an attribute
+ *     outside the table, SWZ_ATTR_RGB or SWZ_ATTR_NORMAL (not scalars), an unknown kind or flag bit, SET on a column wider
+ *     than a byte, a RANGE with lo > hi or a NaN bound, a SET with a nonzero lo or hi, a RANGE with a nonzero set.
+ *     swz_filter_check is the one place these rules live (host only, no context; the text goes into why_out, which may be
+ *     NULL); every call that takes a filter goes through it.
+ *   swz_filter_select_device is swz_region_select_device with a filter: the same output order, count-only mode, capacity
+ *     refusal that touches no output, aliasing and alignment refusals, n == 0 and determinism.  d_in must hold every column
+ *     that attribute_mask OR the filter names, d_out every column attribute_mask names; a filtered column outside
+ *     attribute_mask is read and never written.  With a filter the count pass of all three kinds is one kernel: a lane does the
+ *     box test, then the kind's test, then the clauses in order, and loads a clause's column element only while its row is
+ *     still in -- rows outside the region cost no column traffic.  The filter travels in the kernel arguments; the ballots go
+ *     to the scatter of the region call, so every test, the box's included, is evaluated once per row.
+ *   swz_dataset_query_filtered is swz_dataset_query_region with a filter.  The stream unpacks attribute_mask | the filter's
+ *     attributes into its chunk-local arrays and hands the caller attribute_mask (~0u: all the source holds).  The filter sees
+ *     exactly the values an unfiltered query of that source returns (a LAS source: what its decode yields).  Refused before any
+ *     file of points is read: a filtered attribute the source does not hold (named, with the source's mask) and, for a
+ *     3DTILES source, any filtered attribute .pnts files do not carry.  The data set holds no per-node summary of its
+ *     attributes, so no node is dropped for a filter: the node table is swz_dataset_query_region_nodes', d_node_out indexes it,
+ *     points_bound stays the safe capacity, and points_read less points_out shows what region and filter refused.
  *   Not offered: a multi-GPU driver, polygons with holes or several rings, a shortcut that copies nodes wholly inside a
- *     region without testing their rows, depth chosen by screen-space error. */
+ *     region without testing their rows, depth chosen by screen-space error, per-node attribute summaries that would let a
+ *     filter drop whole nodes. */
 typedef struct {
   double box_min[3], box_max[3]; /* closed */
   int32_t max_depth;             /* < 0: every node; else nodes of depth <= max_depth, as swz_dataset_scan counts depth */
@@ -1221,6 +1254,29 @@ int swz_dataset_query_region_nodes_why(const char* dir, const swz_query_params* 
 int swz_dataset_query_region(swz_ctx* ctx, const char* dir, const swz_query_params* params, const swz_region* region, uint64_t capacity,
                              double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_node_out /* may be NULL */,
                              uint64_t* count_out, swz_query_stats* stats);
+enum { SWZ_FILTER_RANGE = 0, SWZ_FILTER_SET = 1 };
+#define SWZ_FILTER_NOT 0x100u /* in `kind`: the clause's test is inverted */
+#define SWZ_FILTER_MAX_CLAUSES 8
+typedef struct {
+  int32_t attribute; /* SWZ_ATTR_* */
+  uint32_t kind;     /* SWZ_FILTER_RANGE | SWZ_FILTER_SET, optionally | SWZ_FILTER_NOT */
+  double lo, hi;     /* RANGE: lo <= (double)v && (double)v <= hi, closed; SET: 0 */
+  uint64_t set[4];   /* SET: bit (uint8_t)v of the 256-bit map; RANGE: 0 */
+} swz_filter_clause;
+typedef struct {
+  uint32_t count;    /* 0: no filter */
+  uint32_t reserved; /* 0 */
+  swz_filter_clause clause[SWZ_FILTER_MAX_CLAUSES];
+} swz_filter;
+/* SWZ_OK, or SWZ_ERR_BAD_ARG with the refusal in why_out (why_bytes bytes, may be NULL).  NULL and count == 0 are in order. */
+int swz_filter_check(const swz_filter* filter, char* why_out, uint64_t why_bytes);
+int swz_filter_select_device(swz_ctx* ctx, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t attribute_mask,
+                             const double box_min[3], const double box_max[3], const swz_region* region /* NULL: the box alone */,
+                             const swz_filter* filter /* NULL: no filter */, uint64_t capacity, double* d_xyz_out,
+                             const swz_attribute_columns* d_out, uint32_t* d_row_out, uint64_t* count_out);
+int swz_dataset_query_filtered(swz_ctx* ctx, const char* dir, const swz_query_params* params, const swz_region* region,
+                               const swz_filter* filter, uint64_t capacity, double* d_xyz_out, const swz_attribute_columns* d_out,
+                               uint32_t* d_node_out /* may be NULL */, uint64_t* count_out, swz_query_stats* stats);
 /* ---- a source projection (the reference's --source-projection: Proj4Transform, core/util/Transformation.cpp:74-211, source
  * -> "+proj=geocent +datum=WGS84").  PROJ is not linked: the library maps the projection families LAS data comes in itself,
  * in double, and refuses every other definition by name.

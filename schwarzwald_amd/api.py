@@ -902,7 +902,7 @@ def dataset_query_nodes(directory, box_min, box_max, max_depth=None, lossy_sourc
 
 
 def dataset_query(ctx, directory, box_min, box_max, max_depth=None, attrs=None, lossy_source=False, chunk_points=0, return_nodes=False,
-                  capacity=None, _region=None):
+                  capacity=None, _region=None, _filter=None):
     """swz_dataset_query: the points of the written data set in directory inside the closed box [box_min, box_max], of the nodes
     of depth <= max_depth (None: all), streamed from the node files and selected on the device.  attrs: the columns wanted, a
     subset of the source's (None: all it has); lossy_source: admits a 3DTILES source; chunk_points: as in Tiler.write_output.
@@ -928,7 +928,13 @@ def dataset_query(ctx, directory, box_min, box_max, max_depth=None, attrs=None, 
     d_cols = device_columns({k: v.data_ptr() for k, v in cols.items()})
     count, stats = C.c_uint64(), _QueryStats()
     d_node = C.c_void_p(node.data_ptr()) if return_nodes else None
-    if _region is not None:
+    if _filter is not None:   # dataset_query_filtered: (filter,), beside _region
+        rg = None if _region[0] is None else _region[0]._struct()
+        fl = None if _filter[0] is None else _filter[0]._struct()
+        ctx._check(ctx._lib.swz_dataset_query_filtered(ctx._ctx, os.fsencode(directory), C.byref(p), None if rg is None else C.byref(rg),
+                                                       None if fl is None else C.byref(fl), rows, C.c_void_p(xyz.data_ptr()), C.byref(d_cols),
+                                                       d_node, C.byref(count), C.byref(stats)))
+    elif _region is not None:
         rg = None if _region[0] is None else _region[0]._struct()
         ctx._check(ctx._lib.swz_dataset_query_region(ctx._ctx, os.fsencode(directory), C.byref(p), None if rg is None else C.byref(rg), rows,
                                                      C.c_void_p(xyz.data_ptr()), C.byref(d_cols), d_node, C.byref(count), C.byref(stats)))
@@ -1037,6 +1043,94 @@ def dataset_query_region(ctx, directory, box_min, box_max, region, max_depth=Non
     box_min, box_max = _region_box(directory, box_min, box_max, region, max_depth)
     return dataset_query(ctx, directory, box_min, box_max, max_depth, attrs, lossy_source, chunk_points, return_nodes, capacity,
                          _region=(region,))
+
+
+# ---- the same with a filter: clauses over the attribute columns, evaluated on the device behind the region
+FILTER_RANGE, FILTER_SET, FILTER_NOT, FILTER_MAX_CLAUSES = 0, 1, 0x100, 8
+
+
+class _FilterClause(C.Structure):
+    _fields_ = [("attribute", C.c_int32), ("kind", C.c_uint32), ("lo", C.c_double), ("hi", C.c_double), ("set", C.c_uint64 * 4)]
+
+
+class _Filter(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("reserved", C.c_uint32), ("clause", _FilterClause * FILTER_MAX_CLAUSES)]
+
+
+class Filter:
+    """A swz_filter: up to 8 clauses over the scalar attribute columns; a row passes iff it passes every clause.
+    Filter().range("gps_time", lo, hi): lo <= value <= hi as doubles, closed, +-inf for an open end (a NaN value fails);
+    .any_of("classification", [2, 9]): the value is one of these (one-byte columns; scan_angle_rank -1 is bit 255);
+    .none_of("classification", [7, 18]): it is none of them.  An attribute is a name of ATTRIBUTES or its index.  The methods
+    return self.  Nothing is checked here beyond what cannot be stored (a ninth clause, a set value outside a byte): the library
+    refuses what it does not take (check()), and clause(...) appends a raw one."""
+
+    def __init__(self, reserved=0):
+        self.clauses, self.reserved, self.count = [], int(reserved), None   # count: None is len(clauses)
+
+    @staticmethod
+    def _index(attribute):
+        return int(attribute) if isinstance(attribute, (int, np.integer)) else ATTRIBUTES[attribute][0]
+
+    def clause(self, attribute, kind, lo=0.0, hi=0.0, bits=(0, 0, 0, 0)):
+        if len(self.clauses) >= FILTER_MAX_CLAUSES:
+            raise ValueError("a filter holds %d clauses at the most" % FILTER_MAX_CLAUSES)
+        self.clauses.append((self._index(attribute), int(kind), float(lo), float(hi), tuple(int(w) for w in bits)))
+        return self
+
+    def range(self, attribute, lo, hi, negate=False):
+        return self.clause(attribute, FILTER_RANGE | (FILTER_NOT if negate else 0), lo, hi)
+
+    @staticmethod
+    def _bits(values):
+        words = [0, 0, 0, 0]
+        for v in values:
+            v = int(v)
+            if not -128 <= v <= 255:
+                raise ValueError("a set holds the values of one byte")
+            words[(v & 255) >> 6] |= 1 << (v & 63)
+        return words
+
+    def any_of(self, attribute, values):
+        return self.clause(attribute, FILTER_SET, bits=self._bits(values))
+
+    def none_of(self, attribute, values):
+        return self.clause(attribute, FILTER_SET | FILTER_NOT, bits=self._bits(values))
+
+    def attributes(self):
+        """the mask of the attributes the clauses name"""
+        mask = 0
+        for c in self.clauses:
+            mask |= 1 << c[0] if 0 <= c[0] < 32 else 0
+        return mask
+
+    def _struct(self):
+        f = _Filter(len(self.clauses) if self.count is None else int(self.count), self.reserved)
+        for k, (attribute, kind, lo, hi, bits) in enumerate(self.clauses):
+            f.clause[k] = _FilterClause(attribute, kind, lo, hi, (C.c_uint64 * 4)(*bits))
+        return f
+
+    def check(self):
+        """swz_filter_check (host, no GPU): raises SwzError with the library's text if the library refuses the filter"""
+        why = C.create_string_buffer(1024)
+        f = self._struct()
+        st = load_library().swz_filter_check(C.byref(f), why, len(why))
+        if st != 0:
+            raise SwzError(st, why.value.decode(errors="replace"))
+        return self
+
+
+def dataset_query_filtered(ctx, directory, box_min, box_max, region=None, filter=None, max_depth=None, attrs=None, lossy_source=False,
+                           chunk_points=0, return_nodes=False, capacity=None):
+    """swz_dataset_query_filtered: dataset_query_region for the rows that also pass filter (a Filter; None: no filter) -- the same
+    keywords, the same result dict.  attrs are the columns returned; the columns the filter names are read for it whether
+    attrs holds them or not.  No node drops out for a filter: node indexes dataset_query_region_nodes' table, and
+    stats["points_read"] - stats["points_out"] is what region and filter refused."""
+    box_min, box_max = _region_box(directory, box_min, box_max, region, max_depth)
+    if filter is not None:
+        filter.check()   # (before dataset_query scans the directory for its table)
+    return dataset_query(ctx, directory, box_min, box_max, max_depth, attrs, lossy_source, chunk_points, return_nodes, capacity,
+                         _region=(region,), _filter=(filter,))
 
 
 LAS_SCAN_SKIP_UNREADABLE = 1
@@ -1336,6 +1430,13 @@ def load_library():
     L.swz_dataset_query_region_nodes_why.argtypes = [C.c_char_p, C.POINTER(_QueryParams), rgp, C.c_uint64, _i8p, _u64p, _u64p, _u64p, _u64p,
                                                      C.c_char_p, C.c_uint64]
     L.swz_dataset_query_region.argtypes = [vp, C.c_char_p, C.POINTER(_QueryParams), rgp, C.c_uint64, vp, cols, vp, _u64p, C.POINTER(_QueryStats)]
+    flp = C.POINTER(_Filter)
+    L.swz_filter_check.argtypes = [flp, C.c_char_p, C.c_uint64]
+    L.swz_filter_select_device.argtypes = [vp, vp, C.c_uint64, cols, C.c_uint32, _dp, _dp, rgp, flp, C.c_uint64, vp, cols, vp, _u64p]
+    L.swz_dataset_query_filtered.argtypes = [vp, C.c_char_p, C.POINTER(_QueryParams), rgp, flp, C.c_uint64, vp, cols, vp, _u64p,
+                                             C.POINTER(_QueryStats)]
+    for name in ("swz_filter_check", "swz_filter_select_device", "swz_dataset_query_filtered"):
+        getattr(L, name).restype = C.c_int
     for name in ("swz_region_select_device", "swz_dataset_query_region_nodes", "swz_dataset_query_region_nodes_why", "swz_dataset_query_region"):
         getattr(L, name).restype = C.c_int
     for name in ("swz_box_select_device", "swz_dataset_query_nodes", "swz_dataset_query_nodes_why", "swz_dataset_query"):
@@ -1828,6 +1929,29 @@ class Context:
             err.needed = int(count.value)
             raise err
         return int(count.value)
+
+    def filter_select_device(self, d_xyz, n, box_min, box_max, region, filter, capacity, d_xyz_out, d_attrs=None, d_attrs_out=None,
+                             attrs=None, d_row_out=None):
+        """swz_filter_select_device: region_select_device for the rows that also pass filter (a Filter; None: the bytes of
+        region_select_device).  d_attrs holds the columns of attrs (default: those of d_attrs_out) and the filter's; only the
+        columns of attrs are written."""
+        mask = _las_mask(d_attrs_out.keys() if d_attrs_out else ()) if attrs is None else _las_mask(attrs)
+        cin, cout = device_columns(d_attrs), device_columns(d_attrs_out)
+        count = C.c_uint64()
+        rg = None if region is None else region._struct()
+        fl = None if filter is None else filter._struct()
+        st = self._lib.swz_filter_select_device(self._ctx, C.c_void_p(d_xyz), int(n), C.byref(cin), mask, _vec3(box_min), _vec3(box_max),
+                                                None if rg is None else C.byref(rg), None if fl is None else C.byref(fl), int(capacity),
+                                                C.c_void_p(d_xyz_out), C.byref(cout), C.c_void_p(d_row_out), C.byref(count))
+        if st != 0:
+            err = SwzError(st, self._lib.swz_last_error(self._ctx).decode())
+            err.needed = int(count.value)
+            raise err
+        return int(count.value)
+
+    def dataset_query_filtered(self, directory, box_min, box_max, region=None, filter=None, **kwargs):
+        """dataset_query_filtered(self, directory, box_min, box_max, region, filter, ...)"""
+        return dataset_query_filtered(self, directory, box_min, box_max, region, filter, **kwargs)
 
     def dataset_query_region(self, directory, box_min, box_max, region, **kwargs):
         """dataset_query_region(self, directory, box_min, box_max, region, ...)"""

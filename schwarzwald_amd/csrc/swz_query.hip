@@ -3,7 +3,8 @@
 // opened as the converter opens it (source_open, swz_source.hip), the nodes whose widened boxes miss the query box or cannot
 // hold a row of the region drop out of the table (host only), and the rest is streamed chunk by chunk with the converter's SourceStream: every chunk's
 // chunk-local positions and columns go through the selection kernel (swz_select.hip) into the caller's arrays at the running
-// offset.  The readers of chunk j + 1 run while chunk j is selected.
+// offset.  The readers of chunk j + 1 run while chunk j is selected.  With a filter (swz_dataset_query_filtered) the stream
+// unpacks the caller's columns and the filter's, the selection reads the latter, and no node drops out for it.
 #include <chrono>
 #include <cmath>
 #include <cstddef>
@@ -109,7 +110,7 @@ static bool polygon_misses(const RegionHost& r, const double lo[3], const double
 // The table a query reads: `kept` holds the nodes of the (depth-limited) scan whose widened boxes meet the query box and can
 // hold a row of the region, in the scan's order; *scanned: the nodes of the scan; *region_out: the region, checked.
 static int query_plan(swz_ctx* c, const char* who, const char* dir, const swz_query_params* q, const swz_region* region, DatasetScan* kept,
-                      uint64_t* scanned, RegionHost* region_out) {
+                      uint64_t* scanned, RegionHost* region_out, const swz_filter* filter = nullptr, uint32_t* filter_attrs = nullptr) {
   auto refuse = [&](const std::string& what) { return fail(c, SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
   if (!dir || !q) return refuse("NULL argument");
   if (!finite3(q->box_min) || !finite3(q->box_max)) return refuse("a bound of the box is not finite");
@@ -118,10 +119,24 @@ static int query_plan(swz_ctx* c, const char* who, const char* dir, const swz_qu
   if (q->source_flags & ~(uint32_t)SWZ_CONVERT_LOSSY_SOURCE) return refuse("an unknown bit in source_flags");
   if (q->reserved) return refuse("reserved must be 0");
   SWZ_TRY(region_check(c, who, region, region_out));  // (before any file is read)
+  uint32_t fattrs = 0;
+  SWZ_TRY(filter_check(c, who, filter, &fattrs));
+  if (filter_attrs) *filter_attrs = fattrs;
   const RegionHost& rh = *region_out;
   DatasetScan scan;
   double rtc[3];
   SWZ_TRY(source_open(c, who, dir, q->max_depth, q->source_flags, &scan, rtc));
+  // the filter's columns: known from the scan (and, for .pnts, from what the format carries), before a node file is opened
+  for (int a = 0; a < SWZ_ATTR_COUNT; ++a) {
+    if (!((fattrs >> a) & 1u)) continue;
+    if (scan.info.format == SWZ_OUT_3DTILES && a != SWZ_ATTR_INTENSITY)
+      return refuse(std::string("the filter names ") + attribute_name(a) + ", which .pnts files do not carry (a 3DTILES source holds RGB and intensity)");
+    if (!((scan.info.attribute_mask >> a) & 1u)) {
+      char hex[16];
+      snprintf(hex, sizeof(hex), "0x%x", scan.info.attribute_mask);
+      return refuse(std::string("the filter names ") + attribute_name(a) + ", which the source does not hold (its attribute mask is " + hex + ")");
+    }
+  }
   if (scan.info.root_source == SWZ_DATASET_ROOT_ABSENT)
     return refuse("no root box: the source has neither properties.json nor ept.json");
   const double* rmin = scan.info.root_min;
@@ -179,7 +194,8 @@ struct CopyStream {
 };
 
 static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_params* q, const swz_region* region, uint64_t capacity,
-                 double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_node_out, uint64_t* count_out, swz_query_stats* stats) {
+                 double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_node_out, uint64_t* count_out, swz_query_stats* stats,
+                 const swz_filter* filter = nullptr) {
   auto refuse = [&](const std::string& what) { return c->fail(SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
   const auto t_wall = std::chrono::steady_clock::now();
   if (stats) *stats = swz_query_stats{};
@@ -188,7 +204,8 @@ static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_p
   DatasetScan kept;
   uint64_t scanned = 0;
   RegionHost region_host;
-  SWZ_TRY(query_plan(c, who, dir, q, region, &kept, &scanned, &region_host));
+  uint32_t fattrs = 0;  // the columns the filter reads: unpacked for it, handed to the caller only if the mask names them too
+  SWZ_TRY(query_plan(c, who, dir, q, region, &kept, &scanned, &region_host, filter, &fattrs));
   const bool count_only = !d_xyz_out && capacity == 0;
   if (!d_xyz_out && !count_only) return refuse("NULL d_xyz_out with a capacity (count only: NULL and capacity 0)");
   uint32_t mask = q->attribute_mask == ~0u ? kept.info.attribute_mask : q->attribute_mask;
@@ -211,7 +228,7 @@ static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_p
   OutputWorkspace ow{c};  // the chunk-local arrays ("out_*") are the call's part of the workspace
   CopyStream copy;
   SourceStream source;
-  source.plan(c, who, &kept, &first, mask);
+  source.plan(c, who, &kept, &first, mask | fattrs);
   uint64_t total = 0, chunks = 0;
   double select_ms = 0;
   int status = SWZ_OK;
@@ -240,7 +257,7 @@ static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_p
       uint64_t cnt = 0;
       // (a chunk selects its rows at the most: the capacity the kernel's checks see ends with the chunk-local row array)
       status = region_select(c, who, source.xyz, rows, &source.cols, mask, q->box_min, q->box_max, &region_dev, nullptr, std::min(room, rows),
-                             count_only ? nullptr : d_xyz_out + 3 * total, &at, d_rows, &cnt);
+                             count_only ? nullptr : d_xyz_out + 3 * total, &at, d_rows, &cnt, filter);
       if (status != SWZ_OK) {
         if (!count_only && cnt > room) {  // the stream stops after this chunk's count
           *count_out = total + cnt;
@@ -356,6 +373,13 @@ int swz_dataset_query_region(swz_ctx* c, const char* dir, const swz_query_params
                              swz_query_stats* stats) {
   if (!c) return SWZ_ERR_BAD_ARG;
   return query(c, "swz_dataset_query_region", dir, params, region, capacity, d_xyz_out, d_out, d_node_out, count_out, stats);
+}
+
+int swz_dataset_query_filtered(swz_ctx* c, const char* dir, const swz_query_params* params, const swz_region* region,
+                               const swz_filter* filter, uint64_t capacity, double* d_xyz_out, const swz_attribute_columns* d_out,
+                               uint32_t* d_node_out, uint64_t* count_out, swz_query_stats* stats) {
+  if (!c) return SWZ_ERR_BAD_ARG;
+  return query(c, "swz_dataset_query_filtered", dir, params, region, capacity, d_xyz_out, d_out, d_node_out, count_out, stats, filter);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// swz_select.h -- the selection (swz_select.hip) for the callers inside the library: swz_box_select_device and
-// swz_region_select_device themselves and the data-set query (swz_query.hip), which runs it chunk by chunk.
+// swz_select.h -- the selection (swz_select.hip) for the callers inside the library: swz_box_select_device,
+// swz_region_select_device and swz_filter_select_device themselves and the data-set query (swz_query.hip), which runs it chunk by chunk.
 #pragma once
 #include <vector>
 
@@ -32,11 +32,19 @@ struct RegionDev {
 // uploads a polygon's vertices (once per call; once per query); synchronises c's stream
 int region_upload(swz_ctx* c, const RegionHost& r, RegionDev* out);
 
+// swz_filter_check for the callers inside the library: `who` in front of the text, c may be NULL (only the status comes
+// back).  *attrs_out: the mask of the attributes the clauses name (0 without a filter).
+int filter_check(swz_ctx* c, const char* who, const swz_filter* filter, uint32_t* attrs_out);
+// "SWZ_ATTR_CLASSIFICATION", for the refusals
+const char* attribute_name(int attribute);
+
 // swz_region_select_device as include/swz_gpu.h describes it; `who` starts the messages.  The region: `region`, already on
 // the device (the query: once for all chunks), or `upload`, a checked one still on the host, which goes up once every other
-// check has passed; neither: the box alone, swz_box_select_device.  Synchronises c's stream.
+// check has passed; neither: the box alone, swz_box_select_device.  `filter`: one that filter_check has passed, or NULL; with
+// clauses the count pass is filter_count_kernel for every kind (swz_filter_select_device).  Synchronises c's stream.
 int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t mask,
                   const double box_min[3], const double box_max[3], const RegionDev* region, const RegionHost* upload, uint64_t capacity,
-                  double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_row_out, uint64_t* count_out);
+                  double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_row_out, uint64_t* count_out,
+                  const swz_filter* filter = nullptr);
 
 }  // namespace swz

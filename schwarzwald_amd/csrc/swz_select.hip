@@ -16,6 +16,12 @@
 // select_scatter_kernel<true>, is the box's scatter with the ballot read back in place of the predicate, so the edge loop of
 // a polygon (up to 1024 iterations of FP64 per row) runs once per row, in a kernel that holds no other LDS to speak of.  The
 // box kernels are what they were: select_count_kernel untouched, select_scatter_kernel<false> the same instructions.
+//
+// A filter (swz_filter_select_device) is up to eight clauses over the attribute columns behind the region.  Its count pass,
+// filter_count_kernel<none | planes | polygon>, is one more kernel for all three kinds: box, the kind's test, then the clauses in
+// order, a column element loaded only for a row that is still in; the filter travels in the kernel arguments.  It leaves the
+// ballots for select_scatter_kernel<true>, which is unchanged -- so are the count kernels of the calls without a filter.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -211,6 +217,109 @@ __global__ __launch_bounds__(SEL_TILE) void region_count_kernel(const double* __
   if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
 }
 
+// ---- filters: clauses over the attribute columns, behind the region (swz_filter_select_device)
+struct RegionNone {};  // the box alone
+
+struct FilterCols {
+  const uint8_t* col[SWZ_FILTER_MAX_CLAUSES];  // clause k's column
+};
+
+// one clause on row r.  Every field of cl and col are the same for all lanes (kernel arguments: scalar registers); only the
+// element is per lane.  The four words of a set are chosen by compares, not by an index a lane computes.
+__device__ __forceinline__ bool clause_passes(const swz_filter_clause& cl, const uint8_t* __restrict__ col, uint64_t r) {
+  bool pass;
+  if ((cl.kind & 0xFFu) == SWZ_FILTER_SET) {
+    const uint32_t b = col[r];  // the stored byte, unsigned
+    const uint64_t w01 = (b & 64u) ? cl.set[1] : cl.set[0], w23 = (b & 64u) ? cl.set[3] : cl.set[2];
+    pass = ((((b & 128u) ? w23 : w01) >> (b & 63u)) & 1ull) != 0;
+  } else {
+    double v;  // exact for every type
+    switch (cl.attribute) {
+      case SWZ_ATTR_GPS_TIME: v = reinterpret_cast<const double*>(col)[r]; break;
+      case SWZ_ATTR_INTENSITY:
+      case SWZ_ATTR_POINT_SOURCE_ID: v = (double)reinterpret_cast<const uint16_t*>(col)[r]; break;
+      case SWZ_ATTR_SCAN_ANGLE_RANK: v = (double)reinterpret_cast<const int8_t*>(col)[r]; break;
+      default: v = (double)col[r]; break;
+    }
+    pass = cl.lo <= v && v <= cl.hi;  // (a NaN fails both)
+  }
+  return pass != ((cl.kind & SWZ_FILTER_NOT) != 0u);
+}
+
+// the count pass with a filter, for all three kinds: R is RegionNone, RegionPlanes or RegionPolygon.  Box, then the kind's
+// test, then the clauses in order -- a lane loads a clause's element only while its row is still in (r < n then).  The loop
+// over the clauses is the same for the whole wave.  Ballots and tile counts as region_count_kernel leaves them.
+template <class R>
+__global__ __launch_bounds__(SEL_TILE) void filter_count_kernel(const double* __restrict__ xyz, uint32_t n, SelectBox box, R region,
+                                                                swz_filter filter, FilterCols cols, uint32_t* __restrict__ tile_count,
+                                                                uint64_t* __restrict__ ballots) {
+  __shared__ uint32_t s_wave[SEL_WAVES];
+  const uint64_t r = (uint64_t)blockIdx.x * SEL_TILE + threadIdx.x;
+  double x = 0, y = 0, z = 0;
+  bool in = false;
+  if (r < n) {
+    x = xyz[3 * r];
+    y = xyz[3 * r + 1];
+    z = xyz[3 * r + 2];
+    in = select_inside(box, x, y, z);
+  }
+  if constexpr (std::is_same_v<R, RegionPolygon>) {
+    __shared__ double s_xy[2 * SWZ_REGION_MAX_VERTICES];
+    for (uint32_t i = threadIdx.x; i < 2u * region.vertices; i += SEL_TILE) s_xy[i] = region.xy[i];
+    __syncthreads();
+    if (in) in = polygon_inside(s_xy, region.vertices, x, y);
+  } else if constexpr (std::is_same_v<R, RegionPlanes>) {
+    if (in) in = planes_inside(region, x, y, z);
+  }
+  for (uint32_t k = 0; k < filter.count; ++k)
+    if (in) in = clause_passes(filter.clause[k], cols.col[k], r);
+  uint32_t total;
+  uint64_t bal;
+  (void)select_rank(in, s_wave, &total, &bal);
+  if (threadIdx.x % WAVE == 0) ballots[(uint64_t)blockIdx.x * SEL_WAVES + threadIdx.x / WAVE] = bal;
+  if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
+}
+
+const char* attribute_name(int attribute) {
+  static const char* const names[SWZ_ATTR_COUNT] = {"SWZ_ATTR_RGB", "SWZ_ATTR_NORMAL", "SWZ_ATTR_INTENSITY", "SWZ_ATTR_CLASSIFICATION",
+                                                    "SWZ_ATTR_EDGE_OF_FLIGHT_LINE", "SWZ_ATTR_GPS_TIME", "SWZ_ATTR_NUMBER_OF_RETURNS",
+                                                    "SWZ_ATTR_RETURN_NUMBER", "SWZ_ATTR_POINT_SOURCE_ID", "SWZ_ATTR_SCAN_DIRECTION_FLAG",
+                                                    "SWZ_ATTR_SCAN_ANGLE_RANK", "SWZ_ATTR_USER_DATA"};
+  return attribute >= 0 && attribute < SWZ_ATTR_COUNT ? names[attribute] : "an attribute outside the table";
+}
+
+// the rules of include/swz_gpu.h, the one place they live
+int filter_check(swz_ctx* c, const char* who, const swz_filter* f, uint32_t* attrs_out) {
+  auto refuse = [&](const std::string& what) { return fail(c, SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
+  if (attrs_out) *attrs_out = 0;
+  if (!f) return SWZ_OK;
+  if (f->count > SWZ_FILTER_MAX_CLAUSES) return refuse("a filter holds " + std::to_string(SWZ_FILTER_MAX_CLAUSES) + " clauses at the most");
+  if (f->reserved) return refuse("the filter's reserved must be 0");
+  uint32_t attrs = 0;
+  for (uint32_t k = 0; k < f->count; ++k) {
+    const swz_filter_clause& cl = f->clause[k];
+    auto no = [&](const std::string& what) { return refuse("clause " + std::to_string(k) + ": " + what); };
+    if (cl.attribute < 0 || cl.attribute >= SWZ_ATTR_COUNT) return no("an attribute outside the table");
+    if (cl.attribute == SWZ_ATTR_RGB || cl.attribute == SWZ_ATTR_NORMAL)
+      return no(std::string(attribute_name(cl.attribute)) + " is not a scalar column");
+    if (cl.kind & ~(0xFFu | SWZ_FILTER_NOT)) return no("an unknown flag bit in kind");
+    const uint32_t kind = cl.kind & 0xFFu;
+    if (kind != SWZ_FILTER_RANGE && kind != SWZ_FILTER_SET) return no("an unknown kind");
+    const bool any_set = (cl.set[0] | cl.set[1] | cl.set[2] | cl.set[3]) != 0;
+    if (kind == SWZ_FILTER_SET) {
+      if (ATTR_BYTES[cl.attribute] != 1) return no(std::string("a SET on ") + attribute_name(cl.attribute) + ", a column wider than a byte");
+      if (!(cl.lo == 0.0 && cl.hi == 0.0)) return no("a SET with a lo or hi that is not 0");
+    } else {
+      if (std::isnan(cl.lo) || std::isnan(cl.hi)) return no("a RANGE with a NaN bound");
+      if (cl.lo > cl.hi) return no("a RANGE with lo > hi");
+      if (any_set) return no("a RANGE with a set that is not 0");
+    }
+    attrs |= 1u << cl.attribute;
+  }
+  if (attrs_out) *attrs_out = attrs;
+  return SWZ_OK;
+}
+
 int region_check(swz_ctx* c, const char* who, const swz_region* region, RegionHost* out) {
   auto refuse = [&](const std::string& what) { return fail(c, SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
   *out = RegionHost{};
@@ -278,8 +387,11 @@ static bool overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_b
 
 int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t mask,
                   const double box_min[3], const double box_max[3], const RegionDev* region, const RegionHost* upload, uint64_t capacity,
-                  double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_row_out, uint64_t* count_out) {
+                  double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_row_out, uint64_t* count_out, const swz_filter* filter) {
   const int kind = upload ? upload->kind : region ? region->kind : SWZ_REGION_BOX;
+  if (filter && !filter->count) filter = nullptr;  // no clause: the region call
+  uint32_t fmask = 0;  // the columns the clauses read
+  for (uint32_t k = 0; filter && k < filter->count; ++k) fmask |= 1u << filter->clause[k].attribute;
   auto refuse = [&](const std::string& what) { return c->fail(SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
   static_assert(SEL_BYTES[SWZ_ATTR_RGB] == 3 && SEL_BYTES[SWZ_ATTR_NORMAL] == 12 && SEL_BYTES[SWZ_ATTR_INTENSITY] == 2 &&
                   SEL_BYTES[SWZ_ATTR_POINT_SOURCE_ID] == 2 && SEL_BYTES[SWZ_ATTR_GPS_TIME] == 8,
@@ -304,6 +416,11 @@ int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, 
     if ((uintptr_t)d_in->column[k] % align || (!count_only && (uintptr_t)d_out->column[k] % align))
       return refuse("a column that is not aligned to its element");
   }
+  for (int k = 0; k < SWZ_ATTR_COUNT; ++k) {
+    if (!((fmask >> k) & 1u)) continue;
+    if (!d_in || !d_in->column[k]) return refuse(std::string("the filter names ") + attribute_name(k) + ", which has no input column");
+    if ((uintptr_t)d_in->column[k] % ATTR_BYTES[k]) return refuse("a column that is not aligned to its element");  // (1, 2 or 8 bytes)
+  }
   if (n && !d_xyz) return refuse("NULL d_xyz");
   if (((uintptr_t)d_xyz | (uintptr_t)d_xyz_out) % 8u || (uintptr_t)d_row_out % 4u) return refuse("positions or rows that are not aligned to their element");
   if (!count_only) {
@@ -321,7 +438,7 @@ int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, 
     for (int o = 0; o < SWZ_ATTR_COUNT + 2; ++o) {
       bool alias = overlap(outs[o], out_bytes[o], d_xyz, 24 * n);
       for (int k = 0; k < SWZ_ATTR_COUNT; ++k)
-        alias = alias || (((mask >> k) & 1u) && overlap(outs[o], out_bytes[o], d_in->column[k], (uint64_t)ATTR_BYTES[k] * n));
+        alias = alias || ((((mask | fmask) >> k) & 1u) && overlap(outs[o], out_bytes[o], d_in->column[k], (uint64_t)ATTR_BYTES[k] * n));
       if (alias) return refuse("an output aliases an input");
     }
   }
@@ -345,7 +462,26 @@ int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, 
     a.box.hi[k] = box_max[k];
   }
   uint64_t* d_ballots = nullptr;
-  if (kind == SWZ_REGION_BOX) {
+  if (filter) {
+    SWZ_TRY(c->get("sel_ballots", (size_t)nb * SEL_WAVES, &d_ballots));
+    FilterCols fc{};
+    uint64_t col_bytes = 0;  // (at the most: a lane reads only while its row is in)
+    for (uint32_t k = 0; k < filter->count; ++k) {
+      fc.col[k] = static_cast<const uint8_t*>(d_in->column[filter->clause[k].attribute]);
+      col_bytes += ATTR_BYTES[filter->clause[k].attribute];
+    }
+    ProfScope ps(c, "filter_select_count", (24 + col_bytes) * n + 8ull * nb * SEL_WAVES, 1);
+    if (kind == SWZ_REGION_PLANES)
+      hipLaunchKernelGGL(filter_count_kernel<RegionPlanes>, dim3(nb), dim3(SEL_TILE), 0, c->stream, d_xyz, a.n, a.box, region->planes, *filter, fc,
+                         d_tiles, d_ballots);
+    else if (kind == SWZ_REGION_POLYGON)
+      hipLaunchKernelGGL(filter_count_kernel<RegionPolygon>, dim3(nb), dim3(SEL_TILE), 0, c->stream, d_xyz, a.n, a.box,
+                         RegionPolygon{region->d_xy, region->vertices}, *filter, fc, d_tiles, d_ballots);
+    else
+      hipLaunchKernelGGL(filter_count_kernel<RegionNone>, dim3(nb), dim3(SEL_TILE), 0, c->stream, d_xyz, a.n, a.box, RegionNone{}, *filter, fc,
+                         d_tiles, d_ballots);
+    SWZ_LAUNCH_CHECK(c);
+  } else if (kind == SWZ_REGION_BOX) {
     ProfScope ps(c, "box_select_count", 24 * n, 1);
     hipLaunchKernelGGL(select_count_kernel, dim3(nb), dim3(SEL_TILE), 0, c->stream, d_xyz, a.n, a.box, d_tiles);
     SWZ_LAUNCH_CHECK(c);
@@ -370,7 +506,7 @@ int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, 
   if (count_only || total == 0) return SWZ_OK;
   if (total > capacity)
     return refuse("capacity " + std::to_string(capacity) + " is less than the " + std::to_string(total) +
-                  (kind == SWZ_REGION_BOX ? " rows of the box" : " rows of the region"));
+                  (filter ? " rows that pass the filter" : kind == SWZ_REGION_BOX ? " rows of the box" : " rows of the region"));
   a.tile_first = d_tiles;
   a.xyz_out = d_xyz_out;
   a.row_out = d_row_out;
@@ -381,12 +517,12 @@ int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, 
     a.out[k] = static_cast<uint8_t*>(d_out->column[k]);
     row_bytes += 2 * ATTR_BYTES[k];
   }
-  if (kind == SWZ_REGION_BOX) {
+  if (kind == SWZ_REGION_BOX && !filter) {
     ProfScope ps(c, "box_select_scatter", 24 * n + row_bytes * total, 1);
     hipLaunchKernelGGL(select_scatter_kernel<false>, dim3(nb), dim3(SEL_TILE), 0, c->stream, a, (const uint64_t*)nullptr);
     SWZ_LAUNCH_CHECK(c);
   } else {
-    ProfScope ps(c, kind == SWZ_REGION_PLANES ? "planes_select_scatter" : "polygon_select_scatter",
+    ProfScope ps(c, filter ? "filter_select_scatter" : kind == SWZ_REGION_PLANES ? "planes_select_scatter" : "polygon_select_scatter",
                  24 * n + 8ull * nb * SEL_WAVES + row_bytes * total, 1);
     hipLaunchKernelGGL(select_scatter_kernel<true>, dim3(nb), dim3(SEL_TILE), 0, c->stream, a, (const uint64_t*)d_ballots);
     SWZ_LAUNCH_CHECK(c);
@@ -420,6 +556,30 @@ int swz_region_select_device(swz_ctx* c, const double* d_xyz, uint64_t n, const 
   SWZ_TRY(region_check(c, who, region, &host));
   return region_select(c, who, d_xyz, n, d_in, attribute_mask, box_min, box_max, nullptr, &host, capacity, d_xyz_out, d_out, d_row_out,
                        count_out);
+}
+
+int swz_filter_check(const swz_filter* filter, char* why_out, uint64_t why_bytes) {
+  swz_ctx text;  // (only its error text is used: no device is touched)
+  const int st = filter_check(&text, "swz_filter_check", filter, nullptr);
+  if (why_out && why_bytes) {
+    const size_t len = std::min<size_t>(st == SWZ_OK ? 0 : text.err.size(), (size_t)why_bytes - 1);
+    memcpy(why_out, text.err.data(), len);
+    why_out[len] = 0;
+  }
+  return st;
+}
+
+int swz_filter_select_device(swz_ctx* c, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t attribute_mask,
+                             const double box_min[3], const double box_max[3], const swz_region* region, const swz_filter* filter,
+                             uint64_t capacity, double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_row_out,
+                             uint64_t* count_out) {
+  if (!c) return SWZ_ERR_BAD_ARG;
+  const char* who = "swz_filter_select_device";
+  RegionHost host;
+  SWZ_TRY(region_check(c, who, region, &host));
+  SWZ_TRY(filter_check(c, who, filter, nullptr));
+  return region_select(c, who, d_xyz, n, d_in, attribute_mask, box_min, box_max, nullptr, &host, capacity, d_xyz_out, d_out, d_row_out,
+                       count_out, filter);
 }
 
 }  // extern "C"

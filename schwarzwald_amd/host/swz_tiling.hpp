@@ -27,6 +27,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -197,12 +198,52 @@ struct QueryResult {
   std::vector<uint32_t> nodes;
   swz_query_stats stats{};
 };
-// query_dataset for the box cut by a region (swz_dataset_query_region): planes (a frustum: frustum_planes) or a polygon in
-// x-y; region == nullptr is the box alone.  Everything else is query_dataset's; nodes index swz_dataset_query_region_nodes'
-// table.
-inline QueryResult query_dataset_region(Context& ctx, const std::string& dir, const swz_query_params& params, const swz_region* region,
-                                        bool lossy_source = false, bool want_nodes = false) {
+// A swz_filter put together clause by clause: Filter().range(SWZ_ATTR_GPS_TIME, lo, hi).any_of(SWZ_ATTR_CLASSIFICATION, {2, 9})
+// .none_of(SWZ_ATTR_CLASSIFICATION, {7, 18}).  range: lo <= value <= hi as doubles, closed (infinities open an end; a NaN value
+// fails); any_of / none_of: the value is (not) one of these, on the one-byte columns -- a value is stored as its byte, so scan
+// angle rank -1 is bit 255.  A row passes iff it passes every clause.  Only what cannot be stored throws here (a ninth clause, a
+// value outside a byte); the library refuses the rest (include/swz_gpu.h), through query_dataset_filtered.
+class Filter {
+public:
+  Filter& range(int attribute, double lo, double hi) {
+    swz_filter_clause& c = next(attribute, SWZ_FILTER_RANGE);
+    c.lo = lo;
+    c.hi = hi;
+    return *this;
+  }
+  Filter& any_of(int attribute, std::initializer_list<int> values) { return set(attribute, SWZ_FILTER_SET, values); }
+  Filter& none_of(int attribute, std::initializer_list<int> values) { return set(attribute, SWZ_FILTER_SET | SWZ_FILTER_NOT, values); }
+  const swz_filter* get() const { return &_f; }
+
+private:
+  swz_filter_clause& next(int attribute, uint32_t kind) {
+    if (_f.count >= SWZ_FILTER_MAX_CLAUSES) throw std::runtime_error{"Filter: a filter holds 8 clauses at the most"};
+    swz_filter_clause& c = _f.clause[_f.count++];
+    c.attribute = attribute;
+    c.kind = kind;
+    return c;
+  }
+  Filter& set(int attribute, uint32_t kind, std::initializer_list<int> values) {
+    for (int v : values)
+      if (v < -128 || v > 255) throw std::runtime_error{"Filter: a set holds the values of one byte"};
+    swz_filter_clause& c = next(attribute, kind);
+    for (int v : values) c.set[(v & 255) >> 6] |= 1ull << (v & 63);
+    return *this;
+  }
+  swz_filter _f{};
+};
+
+// query_dataset_region for the rows that also pass a filter over the attribute columns (swz_dataset_query_filtered); filter ==
+// nullptr is query_dataset_region.  The columns of params.attribute_mask come back; the columns the filter names are read for
+// it whether the mask holds them or not.  No node drops out for a filter: nodes index swz_dataset_query_region_nodes' table.
+// A filter the library refuses throws with swz_filter_check's text before a file is read.
+inline QueryResult query_dataset_filtered(Context& ctx, const std::string& dir, const swz_query_params& params, const swz_region* region,
+                                          const swz_filter* filter, bool lossy_source = false, bool want_nodes = false) {
   static const uint32_t widths[SWZ_ATTR_COUNT] = {3, 12, 2, 1, 1, 8, 1, 1, 2, 1, 1, 1};
+  if (filter) {
+    char why[512];
+    if (swz_filter_check(filter, why, sizeof why) != SWZ_OK) throw std::runtime_error{why};
+  }
   swz_query_params p = params;
   if (lossy_source) p.source_flags |= SWZ_CONVERT_LOSSY_SOURCE;
   uint64_t kept = 0, bound = 0;
@@ -232,7 +273,9 @@ inline QueryResult query_dataset_region(Context& ctx, const std::string& dir, co
   for (int a = 0; a < SWZ_ATTR_COUNT; ++a)
     if ((p.attribute_mask >> a) & 1u) d_cols.column[a] = alloc(widths[a] * bound);
   uint32_t* d_nodes = want_nodes ? static_cast<uint32_t*>(alloc(4 * bound)) : nullptr;
-  if (region) ctx.check(swz_dataset_query_region(ctx.get(), dir.c_str(), &p, region, bound, d_xyz, &d_cols, d_nodes, &out.count, &out.stats));
+  if (filter)
+    ctx.check(swz_dataset_query_filtered(ctx.get(), dir.c_str(), &p, region, filter, bound, d_xyz, &d_cols, d_nodes, &out.count, &out.stats));
+  else if (region) ctx.check(swz_dataset_query_region(ctx.get(), dir.c_str(), &p, region, bound, d_xyz, &d_cols, d_nodes, &out.count, &out.stats));
   else ctx.check(swz_dataset_query(ctx.get(), dir.c_str(), &p, bound, d_xyz, &d_cols, d_nodes, &out.count, &out.stats));
   out.positions.resize(3 * out.count);
   if (out.count) ctx.check(swz_copy_to_host(ctx.get(), out.positions.data(), d_xyz, 24 * out.count));
@@ -246,6 +289,13 @@ inline QueryResult query_dataset_region(Context& ctx, const std::string& dir, co
     if (out.count) ctx.check(swz_copy_to_host(ctx.get(), out.nodes.data(), d_nodes, 4 * out.count));
   }
   return out;
+}
+// query_dataset for the box cut by a region (swz_dataset_query_region): planes (a frustum: frustum_planes) or a polygon in
+// x-y; region == nullptr is the box alone.  Everything else is query_dataset's; nodes index swz_dataset_query_region_nodes'
+// table.
+inline QueryResult query_dataset_region(Context& ctx, const std::string& dir, const swz_query_params& params, const swz_region* region,
+                                        bool lossy_source = false, bool want_nodes = false) {
+  return query_dataset_filtered(ctx, dir, params, region, nullptr, lossy_source, want_nodes);
 }
 inline QueryResult query_dataset(Context& ctx, const std::string& dir, const swz_query_params& params, bool lossy_source = false,
                                  bool want_nodes = false) {

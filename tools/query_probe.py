@@ -13,7 +13,13 @@ directory).  The work runs in one child process under `timeout`.
 frustum of a fixed camera above the corner (-0.6, -0.4, 1.2) looking at (0.5, 0.5, 0.3).  Per box then: the stats of the region
 query, beside them those of the box query of the region's bounding box (`box_query`), and the host recipe with the region's
 formula in numpy.
-usage: query_probe.py [points] [--batches K] [--dir DIR] [--host-nodes N] [--json FILE] [--polygon M | --planes]"""
+--filter NAME=V[,V...] or NAME=LO..HI, any number of times (e.g. --filter classification=2 --filter return_number=1..1): the
+data set also carries classification (0..15) and return_number (1..4), and every box -- or region -- is queried with the
+filter (dataset_query_filtered; a list of values is a set on a one-byte column, LO..HI a closed range).  Per box then:
+`filtered`, the stats of that call; `query`, the same region without the filter; and `filter_recipe`, what a caller did
+before: the unfiltered query with the filtered columns added, copied to the host, and a numpy mask.  The counts of the first
+and the last must agree.
+usage: query_probe.py [points] [--batches K] [--dir DIR] [--host-nodes N] [--json FILE] [--polygon M | --planes] [--filter SPEC]..."""
 import json
 import os
 import shutil
@@ -89,7 +95,42 @@ def host_recipe(swz, np, src, nodes, box, limit, region_mask=None):
     return time.perf_counter() - t0, done, inside
 
 
-def step(n, batches, base, host_nodes, spec=""):
+FILTER_COLUMNS = ("classification", "return_number")
+
+
+def make_filter(swz, np, specs):
+    """["classification=2", "return_number=1..1"] -> (Filter, the names it reads, its mask over a dict of host columns)"""
+    f, tests = swz.Filter(), []
+    for spec in specs:
+        name, _, value = spec.partition("=")
+        if ".." in value:
+            lo, hi = (float(v) for v in value.split(".."))
+            f.range(name, lo, hi)
+            tests.append((name, lambda v, lo=lo, hi=hi: (v.astype(np.float64) >= lo) & (v.astype(np.float64) <= hi)))
+        else:
+            values = [int(v) for v in value.split(",")]
+            f.any_of(name, values)
+            tests.append((name, lambda v, values=values: np.isin(v, values)))
+
+    def mask(cols):
+        m = None
+        for name, test in tests:
+            m = test(cols[name]) if m is None else m & test(cols[name])
+        return m
+    return f.check(), tuple(dict.fromkeys(name for name, _ in tests)), mask
+
+
+def filter_recipe(swz, np, ctx, src, box, region, names, mask):
+    """the unfiltered query with the filter's columns, copied out, and a numpy mask: seconds, rows moved, rows kept"""
+    t0 = time.perf_counter()
+    got = swz.dataset_query_region(ctx, src, box[0], box[1], region, attrs=NAMES + tuple(k for k in names if k not in NAMES))
+    host = {k: got[k].cpu().numpy() for k in ("xyz",) + NAMES + names}
+    sel = mask(host)
+    kept = {k: host[k][sel] for k in ("xyz",) + NAMES}
+    return time.perf_counter() - t0, got["count"], len(kept["xyz"])
+
+
+def step(n, batches, base, host_nodes, spec="", filters=()):
     import numpy as np
     import schwarzwald_amd as swz
     ctx = swz.Context(0)
@@ -100,20 +141,38 @@ def step(n, batches, base, host_nodes, spec=""):
     per = n // batches
     for b in range(batches):
         m = per if b + 1 < batches else n - per * (batches - 1)
-        t.add_batch(rng.random((m, 3)), {"rgb": rng.integers(0, 256, (m, 3), dtype=np.uint8),
-                                         "intensity": rng.integers(0, 65536, m, dtype=np.uint16)})
+        cols = {"rgb": rng.integers(0, 256, (m, 3), dtype=np.uint8), "intensity": rng.integers(0, 65536, m, dtype=np.uint16)}
+        if filters:
+            cols.update(classification=rng.integers(0, 16, m, dtype=np.uint8), return_number=rng.integers(1, 5, m, dtype=np.uint8))
+        t.add_batch(rng.random((m, 3)), cols)
     t.finalize()
     info, nodes = t.info(), t.node_table()
     stored = int(info["num_stored"])
     work = tempfile.mkdtemp(prefix="swz_query_probe_", dir=base)
     src = os.path.join(work, "src_bin")
-    out = dict(points=n, batches=batches, stored=stored, nodes=int(info["num_nodes"]), write_bin=t.write_output(src, "BIN", attrs=NAMES))
+    out = dict(points=n, batches=batches, stored=stored, nodes=int(info["num_nodes"]), write_bin=t.write_output(src, "BIN", attrs=NAMES + (FILTER_COLUMNS if filters else ())))
     t.write_properties(src)
     t.close()
     print("QUERY_PROBE " + json.dumps(dict(source=out)), flush=True)
     for name, box in BOXES.items():
         row = dict(box=name, region=spec or "box")
         region, bound, mask = make_region(swz, np, spec, box)
+        if filters:
+            flt, names, fmask = make_filter(swz, np, filters)
+            row["filter"] = list(filters)
+            for rep in ("warm", "timed"):
+                got = swz.dataset_query_filtered(ctx, src, box[0], box[1], region, flt, attrs=NAMES)
+                row["filtered"] = dict(got["stats"], count=got["count"])
+                del got
+                got = swz.dataset_query_region(ctx, src, box[0], box[1], region, attrs=NAMES)
+                row["query"] = dict(got["stats"], count=got["count"])
+                del got
+                secs, moved, kept = filter_recipe(swz, np, ctx, src, box, region, names, fmask)
+            row["filter_recipe"] = dict(wall_ms=secs * 1e3, rows_moved=moved, count=kept)
+            row["recipe_over_filtered"] = secs * 1e3 / row["filtered"]["wall_ms"]
+            assert kept == row["filtered"]["count"], (kept, row["filtered"]["count"])
+            print("QUERY_PROBE " + json.dumps(row), flush=True)
+            continue
         for rep in ("warm", "timed"):   # the first run pays allocations and the page cache
             got = swz.dataset_query_region(ctx, src, box[0], box[1], region, attrs=NAMES) if region is not None else \
                 swz.dataset_query(ctx, src, box[0], box[1], attrs=NAMES)
@@ -136,7 +195,8 @@ def step(n, batches, base, host_nodes, spec=""):
 def main():
     args = sys.argv[1:]
     if args and args[0] == "--step":
-        return step(int(args[1]), int(args[2]), args[3] or None, int(args[4]), args[5] if len(args) > 5 else "")
+        return step(int(args[1]), int(args[2]), args[3] or None, int(args[4]), args[5] if len(args) > 5 else "",
+                    tuple(v for v in (args[6] if len(args) > 6 else "").split(";") if v))
 
     def option(name, default):
         return args[args.index(name) + 1] if name in args else default
@@ -145,7 +205,8 @@ def main():
     spec = "planes" if "--planes" in args else "polygon:" + option("--polygon", "0") if "--polygon" in args else ""
     # one child under its own time limit; check=True: a failure ends the script here
     r = subprocess.run(["timeout", "-k", "10", limit, sys.executable, os.path.abspath(__file__), "--step", str(n), option("--batches", "10"),
-                        option("--dir", ""), option("--host-nodes", "0"), spec], check=True, stdout=subprocess.PIPE, text=True)
+                        option("--dir", ""), option("--host-nodes", "0"), spec,
+                        ";".join(args[i + 1] for i, a in enumerate(args) if a == "--filter")], check=True, stdout=subprocess.PIPE, text=True)
     results = [json.loads(l[len("QUERY_PROBE "):]) for l in r.stdout.splitlines() if l.startswith("QUERY_PROBE ")]
     for row in results:
         print(json.dumps(row), flush=True)
