@@ -878,43 +878,50 @@ def _query_params(box_min, box_max, max_depth, attrs, lossy_source, chunk_points
                         int(reserved), int(chunk_points))
 
 
+def _ref(struct):
+    return None if struct is None else C.byref(struct)
+
+
+def _query_nodes(entry, directory, params, *region_ref):
+    """the node table of a query as a dict.  entry: swz_dataset_query_nodes_why, or swz_dataset_query_region_nodes_why with
+    its region argument in region_ref; once for the number of nodes, once for the table"""
+    head = (os.fsencode(directory), C.byref(params)) + region_ref
+    num, bound = C.c_uint64(), C.c_uint64()
+    why = C.create_string_buffer(4096)
+
+    def call(cap, *arrays):
+        st = entry(*head, cap, *arrays, C.byref(num), C.byref(bound), why, len(why))
+        if st != 0:
+            raise SwzError(st, why.value.decode(errors="replace"))
+
+    call(0, None, None, None)
+    cap = max(int(num.value), 1)
+    nl, nk, nc = np.empty(cap, dtype=np.int8), np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint64)
+    call(cap, nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p))
+    m = int(num.value)
+    return dict(level=nl[:m].copy(), key=nk[:m].copy(), count=nc[:m].copy(), points_bound=int(bound.value))
+
+
 def dataset_query_nodes(directory, box_min, box_max, max_depth=None, lossy_source=False, source_flags=None, reserved=0):
     """swz_dataset_query_nodes (host, no GPU): the nodes of the written data set in directory that a query of the closed box
     [box_min, box_max] reads, as dict(level, key, count -- in the order of dataset_scan --, points_bound: the sum of the
     counts, the capacity that always suffices).  A node drops out only if its widened box misses the query box.  max_depth:
     only the nodes of depth <= max_depth; lossy_source: admits a 3DTILES source (source_flags: the raw word instead;
     reserved is passed on).  A refusal raises SwzError with the library's text."""
-    L = load_library()
     p = _query_params(box_min, box_max, max_depth, None, lossy_source, 0, source_flags, reserved)
-    num, bound = C.c_uint64(), C.c_uint64()
-    why = C.create_string_buffer(4096)
-    st = L.swz_dataset_query_nodes_why(os.fsencode(directory), C.byref(p), 0, None, None, None, C.byref(num), C.byref(bound), why, len(why))
-    if st != 0:
-        raise SwzError(st, why.value.decode(errors="replace"))
-    cap = max(int(num.value), 1)
-    nl, nk, nc = np.empty(cap, dtype=np.int8), np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint64)
-    st = L.swz_dataset_query_nodes_why(os.fsencode(directory), C.byref(p), cap, nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p),
-                                       nc.ctypes.data_as(_u64p), C.byref(num), C.byref(bound), why, len(why))
-    if st != 0:
-        raise SwzError(st, why.value.decode(errors="replace"))
-    m = int(num.value)
-    return dict(level=nl[:m].copy(), key=nk[:m].copy(), count=nc[:m].copy(), points_bound=int(bound.value))
+    return _query_nodes(load_library().swz_dataset_query_nodes_why, directory, p)
 
 
-def dataset_query(ctx, directory, box_min, box_max, max_depth=None, attrs=None, lossy_source=False, chunk_points=0, return_nodes=False,
-                  capacity=None, _region=None, _filter=None):
-    """swz_dataset_query: the points of the written data set in directory inside the closed box [box_min, box_max], of the nodes
-    of depth <= max_depth (None: all), streamed from the node files and selected on the device.  attrs: the columns wanted, a
-    subset of the source's (None: all it has); lossy_source: admits a 3DTILES source; chunk_points: as in Tiler.write_output.
-    The outputs are torch tensors on the context's device with points_bound rows (dataset_query_nodes; capacity: another row
-    count -- one that is too small is refused), trimmed to the count: dict(xyz, <column names>, node (with return_nodes: per
-    point the index into dataset_query_nodes' table, else None), count, stats (the fields of swz_query_stats))."""
+def _dataset_query(ctx, directory, box_min, box_max, max_depth, attrs, lossy_source, chunk_points, return_nodes, capacity, region, filter,
+                   entry):
+    """dataset_query, dataset_query_region and dataset_query_filtered.  entry names the C function: swz_dataset_query (region
+    and filter are not passed), swz_dataset_query_region (filter is not) or swz_dataset_query_filtered."""
     import torch
 
-    if _region is not None:   # dataset_query_region: (region,)
-        table = dataset_query_region_nodes(directory, box_min, box_max, _region[0], max_depth, lossy_source)
-    else:
+    if entry == "swz_dataset_query":
         table = dataset_query_nodes(directory, box_min, box_max, max_depth, lossy_source)
+    else:
+        table = dataset_query_region_nodes(directory, box_min, box_max, region, max_depth, lossy_source)
     names = attribute_names(dataset_scan(directory, max_depth)["attribute_mask"]) if attrs is None else list(attrs)
     rows = int(table["points_bound"]) if capacity is None else int(capacity)
     dev = torch.device("cuda", ctx.device)
@@ -928,24 +935,28 @@ def dataset_query(ctx, directory, box_min, box_max, max_depth=None, attrs=None, 
     d_cols = device_columns({k: v.data_ptr() for k, v in cols.items()})
     count, stats = C.c_uint64(), _QueryStats()
     d_node = C.c_void_p(node.data_ptr()) if return_nodes else None
-    if _filter is not None:   # dataset_query_filtered: (filter,), beside _region
-        rg = None if _region[0] is None else _region[0]._struct()
-        fl = None if _filter[0] is None else _filter[0]._struct()
-        ctx._check(ctx._lib.swz_dataset_query_filtered(ctx._ctx, os.fsencode(directory), C.byref(p), None if rg is None else C.byref(rg),
-                                                       None if fl is None else C.byref(fl), rows, C.c_void_p(xyz.data_ptr()), C.byref(d_cols),
-                                                       d_node, C.byref(count), C.byref(stats)))
-    elif _region is not None:
-        rg = None if _region[0] is None else _region[0]._struct()
-        ctx._check(ctx._lib.swz_dataset_query_region(ctx._ctx, os.fsencode(directory), C.byref(p), None if rg is None else C.byref(rg), rows,
-                                                     C.c_void_p(xyz.data_ptr()), C.byref(d_cols), d_node, C.byref(count), C.byref(stats)))
-    else:
-        ctx._check(ctx._lib.swz_dataset_query(ctx._ctx, os.fsencode(directory), C.byref(p), rows, C.c_void_p(xyz.data_ptr()), C.byref(d_cols),
-                                              d_node, C.byref(count), C.byref(stats)))
+    rg = None if region is None else region._struct()
+    fl = None if filter is None else filter._struct()
+    selection = {"swz_dataset_query": (), "swz_dataset_query_region": (_ref(rg),), "swz_dataset_query_filtered": (_ref(rg), _ref(fl))}[entry]
+    ctx._check(getattr(ctx._lib, entry)(ctx._ctx, os.fsencode(directory), C.byref(p), *selection, rows, C.c_void_p(xyz.data_ptr()),
+                                        C.byref(d_cols), d_node, C.byref(count), C.byref(stats)))
     m = int(count.value)
     out = dict(xyz=xyz[:m], node=node[:m] if return_nodes else None, count=m,
                stats={k: getattr(stats, k) for k, _ in _QueryStats._fields_})
     out.update({k: v[:m] for k, v in cols.items()})
     return out
+
+
+def dataset_query(ctx, directory, box_min, box_max, max_depth=None, attrs=None, lossy_source=False, chunk_points=0, return_nodes=False,
+                  capacity=None):
+    """swz_dataset_query: the points of the written data set in directory inside the closed box [box_min, box_max], of the nodes
+    of depth <= max_depth (None: all), streamed from the node files and selected on the device.  attrs: the columns wanted, a
+    subset of the source's (None: all it has); lossy_source: admits a 3DTILES source; chunk_points: as in Tiler.write_output.
+    The outputs are torch tensors on the context's device with points_bound rows (dataset_query_nodes; capacity: another row
+    count -- one that is too small is refused), trimmed to the count: dict(xyz, <column names>, node (with return_nodes: per
+    point the index into dataset_query_nodes' table, else None), count, stats (the fields of swz_query_stats))."""
+    return _dataset_query(ctx, directory, box_min, box_max, max_depth, attrs, lossy_source, chunk_points, return_nodes, capacity, None, None,
+                          "swz_dataset_query")
 
 
 # ---- the same by region: the box cut by planes or by a polygon in x-y (swz_region_select_device, swz_dataset_query_region*)
@@ -1014,25 +1025,10 @@ def dataset_query_region_nodes(directory, box_min, box_max, region, max_depth=No
     """swz_dataset_query_region_nodes (host, no GPU): dataset_query_nodes for the box cut by region (a Region; None: the box
     alone).  A node drops out only if its widened box misses the query box or cannot hold a row the region accepts.  box_min
     and box_max may both be None for a polygon: its x-y bounds and the root box's z.  The dict is dataset_query_nodes'."""
-    L = load_library()
     box_min, box_max = _region_box(directory, box_min, box_max, region, max_depth)
     p = _query_params(box_min, box_max, max_depth, None, lossy_source, 0, source_flags, reserved)
     rg = None if region is None else region._struct()
-    ref = None if rg is None else C.byref(rg)
-    num, bound = C.c_uint64(), C.c_uint64()
-    why = C.create_string_buffer(4096)
-    st = L.swz_dataset_query_region_nodes_why(os.fsencode(directory), C.byref(p), ref, 0, None, None, None, C.byref(num), C.byref(bound), why,
-                                              len(why))
-    if st != 0:
-        raise SwzError(st, why.value.decode(errors="replace"))
-    cap = max(int(num.value), 1)
-    nl, nk, nc = np.empty(cap, dtype=np.int8), np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint64)
-    st = L.swz_dataset_query_region_nodes_why(os.fsencode(directory), C.byref(p), ref, cap, nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p),
-                                              nc.ctypes.data_as(_u64p), C.byref(num), C.byref(bound), why, len(why))
-    if st != 0:
-        raise SwzError(st, why.value.decode(errors="replace"))
-    m = int(num.value)
-    return dict(level=nl[:m].copy(), key=nk[:m].copy(), count=nc[:m].copy(), points_bound=int(bound.value))
+    return _query_nodes(load_library().swz_dataset_query_region_nodes_why, directory, p, _ref(rg))
 
 
 def dataset_query_region(ctx, directory, box_min, box_max, region, max_depth=None, attrs=None, lossy_source=False, chunk_points=0,
@@ -1041,8 +1037,8 @@ def dataset_query_region(ctx, directory, box_min, box_max, region, max_depth=Non
     the same result dict; node indexes dataset_query_region_nodes' table.  box_min and box_max may both be None for a polygon:
     its x-y bounds and the root box's z; planes need the box."""
     box_min, box_max = _region_box(directory, box_min, box_max, region, max_depth)
-    return dataset_query(ctx, directory, box_min, box_max, max_depth, attrs, lossy_source, chunk_points, return_nodes, capacity,
-                         _region=(region,))
+    return _dataset_query(ctx, directory, box_min, box_max, max_depth, attrs, lossy_source, chunk_points, return_nodes, capacity, region, None,
+                          "swz_dataset_query_region")
 
 
 # ---- the same with a filter: clauses over the attribute columns, evaluated on the device behind the region
@@ -1128,9 +1124,9 @@ def dataset_query_filtered(ctx, directory, box_min, box_max, region=None, filter
     stats["points_read"] - stats["points_out"] is what region and filter refused."""
     box_min, box_max = _region_box(directory, box_min, box_max, region, max_depth)
     if filter is not None:
-        filter.check()   # (before dataset_query scans the directory for its table)
-    return dataset_query(ctx, directory, box_min, box_max, max_depth, attrs, lossy_source, chunk_points, return_nodes, capacity,
-                         _region=(region,), _filter=(filter,))
+        filter.check()   # (before the query scans the directory for its table)
+    return _dataset_query(ctx, directory, box_min, box_max, max_depth, attrs, lossy_source, chunk_points, return_nodes, capacity, region, filter,
+                          "swz_dataset_query_filtered")
 
 
 LAS_SCAN_SKIP_UNREADABLE = 1
@@ -1894,6 +1890,19 @@ class Context:
         self._check(self._lib.swz_pnts_unpack_segments_device(self._ctx, C.c_void_p(d_raw), int(raw_bytes), segs, len(segments),
                                                               C.c_void_p(d_xyz), C.byref(cols)))
 
+    def _select_device(self, call, selection, attrs, d_xyz, n, box_min, box_max, capacity, d_xyz_out, d_attrs, d_attrs_out, d_row_out):
+        """box_select_device, region_select_device and filter_select_device.  call: the C function; selection: the structs (or
+        None) it takes behind the box -- none, the region, or region and filter; attrs: names or a mask."""
+        cin, cout = device_columns(d_attrs), device_columns(d_attrs_out)
+        count = C.c_uint64()
+        st = call(self._ctx, C.c_void_p(d_xyz), int(n), C.byref(cin), _las_mask(attrs), _vec3(box_min), _vec3(box_max),
+                  *[_ref(x) for x in selection], int(capacity), C.c_void_p(d_xyz_out), C.byref(cout), C.c_void_p(d_row_out), C.byref(count))
+        if st != 0:
+            err = SwzError(st, self._lib.swz_last_error(self._ctx).decode())
+            err.needed = int(count.value)
+            raise err
+        return int(count.value)
+
     def box_select_device(self, d_xyz, n, box_min, box_max, capacity, d_xyz_out, d_attrs=None, d_attrs_out=None, attrs=None,
                           d_row_out=None):
         """swz_box_select_device: the rows of d_xyz (n rows on the device) inside the closed box [box_min, box_max], compacted
@@ -1901,53 +1910,27 @@ class Context:
         d_attrs_out (dicts name -> device pointer) and, where d_row_out is given, every output row's input row (u32).
         d_xyz_out None with capacity 0 counts only.  Returns the count; a count above capacity raises SwzError ("capacity")
         whose `needed` attribute is the count, and touches no output."""
-        mask = _las_mask(d_attrs.keys() if d_attrs else ()) if attrs is None else (int(attrs) if isinstance(attrs, (int, np.integer)) else _las_mask(attrs))
-        cin, cout = device_columns(d_attrs), device_columns(d_attrs_out)
-        count = C.c_uint64()
-        st = self._lib.swz_box_select_device(self._ctx, C.c_void_p(d_xyz), int(n), C.byref(cin), mask, _vec3(box_min), _vec3(box_max),
-                                             int(capacity), C.c_void_p(d_xyz_out), C.byref(cout), C.c_void_p(d_row_out), C.byref(count))
-        if st != 0:
-            err = SwzError(st, self._lib.swz_last_error(self._ctx).decode())
-            err.needed = int(count.value)
-            raise err
-        return int(count.value)
+        return self._select_device(self._lib.swz_box_select_device, (), list(d_attrs or ()) if attrs is None else attrs, d_xyz, n, box_min,
+                                   box_max, capacity, d_xyz_out, d_attrs, d_attrs_out, d_row_out)
 
     def region_select_device(self, d_xyz, n, box_min, box_max, region, capacity, d_xyz_out, d_attrs=None, d_attrs_out=None, attrs=None,
                              d_row_out=None):
         """swz_region_select_device: box_select_device for the box cut by region (a Region; None: the box alone, the bytes of
         box_select_device).  Everything else -- order, count-only mode, the capacity refusal and its `needed` -- is
         box_select_device's."""
-        mask = _las_mask(d_attrs.keys() if d_attrs else ()) if attrs is None else (int(attrs) if isinstance(attrs, (int, np.integer)) else _las_mask(attrs))
-        cin, cout = device_columns(d_attrs), device_columns(d_attrs_out)
-        count = C.c_uint64()
         rg = None if region is None else region._struct()
-        st = self._lib.swz_region_select_device(self._ctx, C.c_void_p(d_xyz), int(n), C.byref(cin), mask, _vec3(box_min), _vec3(box_max),
-                                                None if rg is None else C.byref(rg), int(capacity), C.c_void_p(d_xyz_out), C.byref(cout),
-                                                C.c_void_p(d_row_out), C.byref(count))
-        if st != 0:
-            err = SwzError(st, self._lib.swz_last_error(self._ctx).decode())
-            err.needed = int(count.value)
-            raise err
-        return int(count.value)
+        return self._select_device(self._lib.swz_region_select_device, (rg,), list(d_attrs or ()) if attrs is None else attrs, d_xyz, n,
+                                   box_min, box_max, capacity, d_xyz_out, d_attrs, d_attrs_out, d_row_out)
 
     def filter_select_device(self, d_xyz, n, box_min, box_max, region, filter, capacity, d_xyz_out, d_attrs=None, d_attrs_out=None,
                              attrs=None, d_row_out=None):
         """swz_filter_select_device: region_select_device for the rows that also pass filter (a Filter; None: the bytes of
         region_select_device).  d_attrs holds the columns of attrs (default: those of d_attrs_out) and the filter's; only the
         columns of attrs are written."""
-        mask = _las_mask(d_attrs_out.keys() if d_attrs_out else ()) if attrs is None else _las_mask(attrs)
-        cin, cout = device_columns(d_attrs), device_columns(d_attrs_out)
-        count = C.c_uint64()
         rg = None if region is None else region._struct()
         fl = None if filter is None else filter._struct()
-        st = self._lib.swz_filter_select_device(self._ctx, C.c_void_p(d_xyz), int(n), C.byref(cin), mask, _vec3(box_min), _vec3(box_max),
-                                                None if rg is None else C.byref(rg), None if fl is None else C.byref(fl), int(capacity),
-                                                C.c_void_p(d_xyz_out), C.byref(cout), C.c_void_p(d_row_out), C.byref(count))
-        if st != 0:
-            err = SwzError(st, self._lib.swz_last_error(self._ctx).decode())
-            err.needed = int(count.value)
-            raise err
-        return int(count.value)
+        return self._select_device(self._lib.swz_filter_select_device, (rg, fl), list(d_attrs_out or ()) if attrs is None else attrs, d_xyz, n,
+                                   box_min, box_max, capacity, d_xyz_out, d_attrs, d_attrs_out, d_row_out)
 
     def dataset_query_filtered(self, directory, box_min, box_max, region=None, filter=None, **kwargs):
         """dataset_query_filtered(self, directory, box_min, box_max, region, filter, ...)"""

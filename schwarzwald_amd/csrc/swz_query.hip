@@ -108,9 +108,10 @@ static bool polygon_misses(const RegionHost& r, const double lo[3], const double
 }
 
 // The table a query reads: `kept` holds the nodes of the (depth-limited) scan whose widened boxes meet the query box and can
-// hold a row of the region, in the scan's order; *scanned: the nodes of the scan; *region_out: the region, checked.
-static int query_plan(swz_ctx* c, const char* who, const char* dir, const swz_query_params* q, const swz_region* region, DatasetScan* kept,
-                      uint64_t* scanned, RegionHost* region_out, const swz_filter* filter = nullptr, uint32_t* filter_attrs = nullptr) {
+// hold a row of the region, in the scan's order; *scanned: the nodes of the scan; *region_out: the region, checked;
+// *filter_attrs: the mask of the columns the filter (NULL: none) reads.  No node drops out for a filter.
+static int query_plan(swz_ctx* c, const char* who, const char* dir, const swz_query_params* q, const swz_region* region, const swz_filter* filter,
+                      DatasetScan* kept, uint64_t* scanned, RegionHost* region_out, uint32_t* filter_attrs) {
   auto refuse = [&](const std::string& what) { return fail(c, SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
   if (!dir || !q) return refuse("NULL argument");
   if (!finite3(q->box_min) || !finite3(q->box_max)) return refuse("a bound of the box is not finite");
@@ -119,9 +120,8 @@ static int query_plan(swz_ctx* c, const char* who, const char* dir, const swz_qu
   if (q->source_flags & ~(uint32_t)SWZ_CONVERT_LOSSY_SOURCE) return refuse("an unknown bit in source_flags");
   if (q->reserved) return refuse("reserved must be 0");
   SWZ_TRY(region_check(c, who, region, region_out));  // (before any file is read)
-  uint32_t fattrs = 0;
-  SWZ_TRY(filter_check(c, who, filter, &fattrs));
-  if (filter_attrs) *filter_attrs = fattrs;
+  SWZ_TRY(filter_check(c, who, filter, filter_attrs));
+  const uint32_t fattrs = *filter_attrs;
   const RegionHost& rh = *region_out;
   DatasetScan scan;
   double rtc[3];
@@ -193,9 +193,9 @@ struct CopyStream {
   }
 };
 
-static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_params* q, const swz_region* region, uint64_t capacity,
-                 double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_node_out, uint64_t* count_out, swz_query_stats* stats,
-                 const swz_filter* filter = nullptr) {
+static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_params* q, const swz_region* region, const swz_filter* filter,
+                 uint64_t capacity, double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_node_out, uint64_t* count_out,
+                 swz_query_stats* stats) {
   auto refuse = [&](const std::string& what) { return c->fail(SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
   const auto t_wall = std::chrono::steady_clock::now();
   if (stats) *stats = swz_query_stats{};
@@ -205,7 +205,7 @@ static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_p
   uint64_t scanned = 0;
   RegionHost region_host;
   uint32_t fattrs = 0;  // the columns the filter reads: unpacked for it, handed to the caller only if the mask names them too
-  SWZ_TRY(query_plan(c, who, dir, q, region, &kept, &scanned, &region_host, filter, &fattrs));
+  SWZ_TRY(query_plan(c, who, dir, q, region, filter, &kept, &scanned, &region_host, &fattrs));
   const bool count_only = !d_xyz_out && capacity == 0;
   if (!d_xyz_out && !count_only) return refuse("NULL d_xyz_out with a capacity (count only: NULL and capacity 0)");
   uint32_t mask = q->attribute_mask == ~0u ? kept.info.attribute_mask : q->attribute_mask;
@@ -243,6 +243,7 @@ static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_p
     std::vector<uint32_t> node_first;
     RegionDev region_dev;  // a polygon's vertices go up once, not per chunk
     SWZ_TRY(region_upload(c, region_host, &region_dev));
+    const Selection sel{q->box_min, q->box_max, nullptr, &region_dev, filter};
     SWZ_HIP(c, hipStreamCreateWithFlags(&copy.s, hipStreamNonBlocking));
     SWZ_TRY(source.start(copy.s));
     for (uint64_t j = 0; j < source.num_chunks; ++j) {
@@ -256,8 +257,8 @@ static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_p
       const uint64_t room = count_only ? 0 : capacity - total;
       uint64_t cnt = 0;
       // (a chunk selects its rows at the most: the capacity the kernel's checks see ends with the chunk-local row array)
-      status = region_select(c, who, source.xyz, rows, &source.cols, mask, q->box_min, q->box_max, &region_dev, nullptr, std::min(room, rows),
-                             count_only ? nullptr : d_xyz_out + 3 * total, &at, d_rows, &cnt, filter);
+      status = region_select(c, who, source.xyz, rows, &source.cols, mask, sel, std::min(room, rows),
+                             count_only ? nullptr : d_xyz_out + 3 * total, &at, d_rows, &cnt);
       if (status != SWZ_OK) {
         if (!count_only && cnt > room) {  // the stream stops after this chunk's count
           *count_out = total + cnt;
@@ -303,7 +304,7 @@ using namespace swz;
 
 extern "C" {
 
-// swz_dataset_query_nodes and swz_dataset_query_region_nodes
+// swz_dataset_query_nodes and swz_dataset_query_region_nodes, and their _why forms on a context that only holds the text
 static int query_nodes(swz_ctx* c, const std::string& who, const char* dir, const swz_query_params* params, const swz_region* region,
                        uint64_t max_nodes, int8_t* level_out, uint64_t* key_out, uint64_t* count_out, uint64_t* num_out,
                        uint64_t* points_bound_out) {
@@ -313,7 +314,8 @@ static int query_nodes(swz_ctx* c, const std::string& who, const char* dir, cons
   DatasetScan kept;
   uint64_t scanned = 0;
   RegionHost region_host;
-  SWZ_TRY(query_plan(c, who.c_str(), dir, params, region, &kept, &scanned, &region_host));
+  uint32_t fattrs = 0;
+  SWZ_TRY(query_plan(c, who.c_str(), dir, params, region, nullptr, &kept, &scanned, &region_host, &fattrs));
   const uint64_t nn = kept.count.size();
   *num_out = nn;
   if (points_bound_out) *points_bound_out = kept.info.points;
@@ -338,19 +340,11 @@ int swz_dataset_query_region_nodes(swz_ctx* c, const char* dir, const swz_query_
                      points_bound_out);
 }
 
-static int why_text(int st, const swz_ctx& text, char* why_out, uint64_t why_bytes) {
-  if (why_out && why_bytes) {
-    const size_t len = std::min<size_t>(st == SWZ_OK ? 0 : text.err.size(), (size_t)why_bytes - 1);
-    memcpy(why_out, text.err.data(), len);
-    why_out[len] = 0;
-  }
-  return st;
-}
-
 int swz_dataset_query_nodes_why(const char* dir, const swz_query_params* params, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out,
                                 uint64_t* count_out, uint64_t* num_out, uint64_t* points_bound_out, char* why_out, uint64_t why_bytes) {
-  swz_ctx text;  // (only its error text is used: no device is touched)
-  const int st = swz_dataset_query_nodes(&text, dir, params, max_nodes, level_out, key_out, count_out, num_out, points_bound_out);
+  swz_ctx text;
+  const int st = query_nodes(&text, "swz_dataset_query_nodes", dir, params, nullptr, max_nodes, level_out, key_out, count_out, num_out,
+                             points_bound_out);
   return why_text(st, text, why_out, why_bytes);
 }
 
@@ -358,28 +352,29 @@ int swz_dataset_query_region_nodes_why(const char* dir, const swz_query_params* 
                                        int8_t* level_out, uint64_t* key_out, uint64_t* count_out, uint64_t* num_out,
                                        uint64_t* points_bound_out, char* why_out, uint64_t why_bytes) {
   swz_ctx text;
-  const int st = swz_dataset_query_region_nodes(&text, dir, params, region, max_nodes, level_out, key_out, count_out, num_out, points_bound_out);
+  const int st = query_nodes(&text, "swz_dataset_query_region_nodes", dir, params, region, max_nodes, level_out, key_out, count_out, num_out,
+                             points_bound_out);
   return why_text(st, text, why_out, why_bytes);
 }
 
 int swz_dataset_query(swz_ctx* c, const char* dir, const swz_query_params* params, uint64_t capacity, double* d_xyz_out,
                       const swz_attribute_columns* d_out, uint32_t* d_node_out, uint64_t* count_out, swz_query_stats* stats) {
   if (!c) return SWZ_ERR_BAD_ARG;
-  return query(c, "swz_dataset_query", dir, params, nullptr, capacity, d_xyz_out, d_out, d_node_out, count_out, stats);
+  return query(c, "swz_dataset_query", dir, params, nullptr, nullptr, capacity, d_xyz_out, d_out, d_node_out, count_out, stats);
 }
 
 int swz_dataset_query_region(swz_ctx* c, const char* dir, const swz_query_params* params, const swz_region* region, uint64_t capacity,
                              double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_node_out, uint64_t* count_out,
                              swz_query_stats* stats) {
   if (!c) return SWZ_ERR_BAD_ARG;
-  return query(c, "swz_dataset_query_region", dir, params, region, capacity, d_xyz_out, d_out, d_node_out, count_out, stats);
+  return query(c, "swz_dataset_query_region", dir, params, region, nullptr, capacity, d_xyz_out, d_out, d_node_out, count_out, stats);
 }
 
 int swz_dataset_query_filtered(swz_ctx* c, const char* dir, const swz_query_params* params, const swz_region* region,
                                const swz_filter* filter, uint64_t capacity, double* d_xyz_out, const swz_attribute_columns* d_out,
                                uint32_t* d_node_out, uint64_t* count_out, swz_query_stats* stats) {
   if (!c) return SWZ_ERR_BAD_ARG;
-  return query(c, "swz_dataset_query_filtered", dir, params, region, capacity, d_xyz_out, d_out, d_node_out, count_out, stats, filter);
+  return query(c, "swz_dataset_query_filtered", dir, params, region, filter, capacity, d_xyz_out, d_out, d_node_out, count_out, stats);
 }
 
 }  // extern "C"

@@ -1,6 +1,9 @@
-// swz_select.h -- the selection (swz_select.hip) for the callers inside the library: swz_box_select_device,
-// swz_region_select_device and swz_filter_select_device themselves and the data-set query (swz_query.hip), which runs it chunk by chunk.
+// swz_select.h -- the selection (swz_select.hip) for the callers inside the library: the three entries
+// swz_box_select_device, swz_region_select_device and swz_filter_select_device, and the data-set query (swz_query.hip),
+// which runs it chunk by chunk.  All of them describe what they select in one Selection and call region_select.
 #pragma once
+#include <algorithm>
+#include <cstring>
 #include <vector>
 
 #include "swz_internal.h"
@@ -38,13 +41,31 @@ int filter_check(swz_ctx* c, const char* who, const swz_filter* filter, uint32_t
 // "SWZ_ATTR_CLASSIFICATION", for the refusals
 const char* attribute_name(int attribute);
 
-// swz_region_select_device as include/swz_gpu.h describes it; `who` starts the messages.  The region: `region`, already on
-// the device (the query: once for all chunks), or `upload`, a checked one still on the host, which goes up once every other
-// check has passed; neither: the box alone, swz_box_select_device.  `filter`: one that filter_check has passed, or NULL; with
-// clauses the count pass is filter_count_kernel for every kind (swz_filter_select_device).  Synchronises c's stream.
+// What a call selects: the rows of the closed box that the region keeps and that pass the filter.  The region is one that
+// region_check has passed: `region`, still on the host -- region_select uploads it once every other check has passed -- or
+// `uploaded`, already on the device (the query: once for all chunks); neither is the box alone.  `filter`: one that
+// filter_check has passed, or NULL; one without a clause selects what NULL selects.
+struct Selection {
+  const double *box_min, *box_max;  // [3] each; a NULL is refused
+  const RegionHost* region;
+  const RegionDev* uploaded;
+  const swz_filter* filter;
+};
+
+// The three select entries as include/swz_gpu.h describes them; `who` starts the messages.  Synchronises c's stream.
 int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t mask,
-                  const double box_min[3], const double box_max[3], const RegionDev* region, const RegionHost* upload, uint64_t capacity,
-                  double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_row_out, uint64_t* count_out,
-                  const swz_filter* filter = nullptr);
+                  const Selection& sel, uint64_t capacity, double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_row_out,
+                  uint64_t* count_out);
+
+// the end of a host-only entry that reports through a text buffer: the refusal that `text` holds (nothing on SWZ_OK) goes
+// into why_out, cut to why_bytes with its terminator; returns st
+inline int why_text(int st, const swz_ctx& text, char* why_out, uint64_t why_bytes) {
+  if (why_out && why_bytes) {
+    const size_t len = std::min<size_t>(st == SWZ_OK ? 0 : text.err.size(), (size_t)why_bytes - 1);
+    memcpy(why_out, text.err.data(), len);
+    why_out[len] = 0;
+  }
+  return st;
+}
 
 }  // namespace swz

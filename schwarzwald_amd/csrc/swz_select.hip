@@ -1,26 +1,27 @@
-// swz_select.hip -- the rows of a closed box, compacted in their order (swz_box_select_device): what swz_dataset_query
-// (swz_query.hip) runs on every chunk.  Two launches around the library's scan: select_count_kernel leaves the number of
-// selected rows of every tile of SEL_TILE rows (wave ballot, popcount, the wave totals summed in LDS), scan_exclusive_u32
-// turns the tile counts into the tiles' first output rows and the total, which the host reads before anything is written
-// (the capacity refusal touches no output), and select_scatter_kernel evaluates the predicate again, ranks the selected rows
-// inside the tile the same way and moves them.  No atomic decides a place: the output is the same bytes on every run.
+// swz_select.hip -- the selection: the rows of a closed box, cut by a region (planes, or a polygon in x-y) and filtered by
+// up to eight clauses over the attribute columns (the formulas: include/swz_gpu.h), compacted in their order.  It is what
+// swz_box_select_device, swz_region_select_device and swz_filter_select_device run, and what swz_dataset_query* (swz_query.hip)
+// runs on every chunk: one host path, region_select, for all of them.
+//
+// Two launches around the library's scan.  select_count_kernel<R, FILTER> leaves the number of selected rows of every tile of
+// SEL_TILE rows (wave ballot, popcount, the wave totals summed in LDS); scan_exclusive_u32 turns the tile counts into the
+// tiles' first output rows and the total, which the host reads before anything is written (the capacity refusal touches no
+// output); select_scatter_kernel<BALLOTS> ranks the selected rows inside the tile the same way and moves them.  No atomic
+// decides a place: the output is the same bytes on every run.
+//
+// The count pass, per row: the box, then the region's test (R: RegionNone, RegionPlanes in the kernel arguments,
+// RegionPolygon staged in LDS), then with FILTER the clauses in order, a column element loaded only for a row that is still
+// in; the filter travels in the kernel arguments, and without one the instantiation has no such parameters.  Who decides a
+// row in the scatter follows from it.  The box alone, <RegionNone, false>: the scatter tests the box again
+// (select_scatter_kernel<false>).  Every other instantiation also stores each wave's ballot, and select_scatter_kernel<true>
+// reads it back in place of a predicate, so the edge loop of a polygon (up to 1024 iterations of FP64 per row) and the
+// clauses run once per row, in a kernel that holds no other LDS to speak of.
 //
 // The scatter, per workgroup: the tile's positions come into LDS as consecutive doubles; every lane takes its row's three
 // out of it, the selected ones go back into the SAME array at 3 x rank (rank <= lane, behind a barrier), and the compacted
 // run leaves as consecutive doubles.  The source row of every output row stays in LDS: lane t then moves output row t of the
 // tile column by column -- 8- and 12-byte rows as whole words, consecutive lanes consecutive addresses; the 1-, 2- and
 // 3-byte rows as plain per-row stores (putting them together into dwords has not been measured).
-//
-// A region (swz_region_select_device) is the box cut by planes or by a polygon in x-y (the formulas: include/swz_gpu.h).  Its
-// count pass, region_count_kernel<planes | polygon>, ranks like the box's and also stores every wave's ballot; its scatter,
-// select_scatter_kernel<true>, is the box's scatter with the ballot read back in place of the predicate, so the edge loop of
-// a polygon (up to 1024 iterations of FP64 per row) runs once per row, in a kernel that holds no other LDS to speak of.  The
-// box kernels are what they were: select_count_kernel untouched, select_scatter_kernel<false> the same instructions.
-//
-// A filter (swz_filter_select_device) is up to eight clauses over the attribute columns behind the region.  Its count pass,
-// filter_count_kernel<none | planes | polygon>, is one more kernel for all three kinds: box, the kind's test, then the clauses in
-// order, a column element loaded only for a row that is still in; the filter travels in the kernel arguments.  It leaves the
-// ballots for select_scatter_kernel<true>, which is unchanged -- so are the count kernels of the calls without a filter.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -76,17 +77,128 @@ __device__ __forceinline__ uint32_t select_rank(bool in, uint32_t* s_wave, uint3
   return before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
 }
 
+// ---- regions: the box cut by planes or by a polygon in x-y
+struct RegionNone {};  // the box alone
+
+struct RegionPolygon {
+  const double* xy;  // vertices x (x, y)
+  uint32_t vertices;
+};
+
+// every plane: ((a*x + b*y) + c*z) + d >= 0, four separately rounded operations (the library is built without contraction)
+__device__ __forceinline__ bool planes_inside(const RegionPlanes& P, double x, double y, double z) {
+  bool in = true;
+  for (uint32_t k = 0; k < P.count; ++k) in = in && ((P.p[k][0] * x + P.p[k][1] * y) + P.p[k][2] * z) + P.p[k][3] >= 0.0;
+  return in;
+}
+
+// even-odd over the edges (v[i], v[(i+1) mod m]); the parity does not care that the closing edge comes first.  Every lane
+// reads the same LDS address: a broadcast.
+__device__ __forceinline__ bool polygon_inside(const double* s_xy, uint32_t m, double px, double py) {
+  bool odd = false;
+  double x0 = s_xy[2 * (m - 1)], y0 = s_xy[2 * (m - 1) + 1];
+  for (uint32_t i = 0; i < m; ++i) {
+    const double x1 = s_xy[2 * i], y1 = s_xy[2 * i + 1];
+    if ((y0 > py) != (y1 > py)) {
+      const double t = (x1 - x0) * (py - y0) - (px - x0) * (y1 - y0);
+      odd ^= (t > 0.0) == (y1 > y0);
+    }
+    x0 = x1;
+    y0 = y1;
+  }
+  return odd;
+}
+
+// ---- filters: clauses over the attribute columns, behind the region
+struct FilterCols {
+  const uint8_t* col[SWZ_FILTER_MAX_CLAUSES];  // clause k's column
+};
+
+// one clause on row r.  Every field of cl and col are the same for all lanes (kernel arguments: scalar registers); only the
+// element is per lane.  The four words of a set are chosen by compares, not by an index a lane computes.
+__device__ __forceinline__ bool clause_passes(const swz_filter_clause& cl, const uint8_t* __restrict__ col, uint64_t r) {
+  bool pass;
+  if ((cl.kind & 0xFFu) == SWZ_FILTER_SET) {
+    const uint32_t b = col[r];  // the stored byte, unsigned
+    const uint64_t w01 = (b & 64u) ? cl.set[1] : cl.set[0], w23 = (b & 64u) ? cl.set[3] : cl.set[2];
+    pass = ((((b & 128u) ? w23 : w01) >> (b & 63u)) & 1ull) != 0;
+  } else {
+    double v;  // exact for every type
+    switch (cl.attribute) {
+      case SWZ_ATTR_GPS_TIME: v = reinterpret_cast<const double*>(col)[r]; break;
+      case SWZ_ATTR_INTENSITY:
+      case SWZ_ATTR_POINT_SOURCE_ID: v = (double)reinterpret_cast<const uint16_t*>(col)[r]; break;
+      case SWZ_ATTR_SCAN_ANGLE_RANK: v = (double)reinterpret_cast<const int8_t*>(col)[r]; break;
+      default: v = (double)col[r]; break;
+    }
+    pass = cl.lo <= v && v <= cl.hi;  // (a NaN fails both)
+  }
+  return pass != ((cl.kind & SWZ_FILTER_NOT) != 0u);
+}
+
+// ---- the count pass
+struct Absent {};  // in place of a kernel parameter that an instantiation does not have: one byte of the argument block
+template <bool HAS, class T>
+using ArgIf = std::conditional_t<HAS, T, Absent>;
+template <bool HAS, class T>
+static ArgIf<HAS, T> arg_if(const T* v) {
+  if constexpr (HAS) return *v;
+  else return {};
+}
+
+// does select_count_kernel<R, FILTER> leave ballots for select_scatter_kernel<true>?  All but the box alone.
+template <class R, bool FILTER>
+constexpr bool COUNT_BALLOTS = FILTER || !std::is_same_v<R, RegionNone>;
+
+// R is RegionNone, RegionPlanes (in the kernel arguments) or RegionPolygon (staged in LDS: 16 KiB at the most, which with the
+// 16 bytes of the ranking leaves the 32 waves of a CU their room in its 160 KiB).  Box, then the region's test -- only the
+// rows of the box walk a polygon's edges, and the box keeps NaN out of both tests --, then with FILTER the clauses in order:
+// a lane loads a clause's element only while its row is still in (r < n then), and the loop over the clauses is the same
+// for the whole wave.  ballots: one word per wave of every tile.  The parameters stay kernel parameters that the body reads
+// directly: behind an argument struct the compiler loads the whole block up front (EXPERIMENTS.md).
+template <class R, bool FILTER>
 __global__ __launch_bounds__(SEL_TILE) void select_count_kernel(const double* __restrict__ xyz, uint32_t n, SelectBox box,
-                                                                uint32_t* __restrict__ tile_count) {
+                                                                R region, ArgIf<FILTER, swz_filter> filter,
+                                                                ArgIf<FILTER, FilterCols> cols, uint32_t* __restrict__ tile_count,
+                                                                ArgIf<COUNT_BALLOTS<R, FILTER>, uint64_t* __restrict__> ballots) {
   __shared__ uint32_t s_wave[SEL_WAVES];
   const uint64_t r = (uint64_t)blockIdx.x * SEL_TILE + threadIdx.x;
+  double x = 0, y = 0, z = 0;
   bool in = false;
-  if (r < n) in = select_inside(box, xyz[3 * r], xyz[3 * r + 1], xyz[3 * r + 2]);
+  if (r < n) {
+    x = xyz[3 * r];
+    y = xyz[3 * r + 1];
+    z = xyz[3 * r + 2];
+    in = select_inside(box, x, y, z);
+  }
+  if constexpr (std::is_same_v<R, RegionPolygon>) {
+    __shared__ double s_xy[2 * SWZ_REGION_MAX_VERTICES];
+    for (uint32_t i = threadIdx.x; i < 2u * region.vertices; i += SEL_TILE) s_xy[i] = region.xy[i];
+    __syncthreads();
+    if (in) in = polygon_inside(s_xy, region.vertices, x, y);
+  } else if constexpr (std::is_same_v<R, RegionPlanes>) {
+    if (in) in = planes_inside(region, x, y, z);
+  }
+  if constexpr (FILTER)
+    for (uint32_t k = 0; k < filter.count; ++k)
+      if (in) in = clause_passes(filter.clause[k], cols.col[k], r);
   uint32_t total;
-  (void)select_rank(in, s_wave, &total);
+  uint64_t bal;
+  (void)select_rank(in, s_wave, &total, &bal);
+  if constexpr (COUNT_BALLOTS<R, FILTER>)
+    if (threadIdx.x % WAVE == 0) ballots[(uint64_t)blockIdx.x * SEL_WAVES + threadIdx.x / WAVE] = bal;
   if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
 }
 
+// the launch of one instantiation; `a` holds the rows and the box, filter and cols are read only with FILTER
+template <class R, bool FILTER>
+static void select_count_launch(hipStream_t stream, uint32_t nb, const SelectArgs& a, const R& region, const swz_filter* filter,
+                                const FilterCols* cols, uint32_t* d_tiles, uint64_t* d_ballots) {
+  hipLaunchKernelGGL((select_count_kernel<R, FILTER>), dim3(nb), dim3(SEL_TILE), 0, stream, a.xyz, a.n, a.box, region, arg_if<FILTER>(filter),
+                     arg_if<FILTER>(cols), d_tiles, arg_if<COUNT_BALLOTS<R, FILTER>>(&d_ballots));
+}
+
+// ---- the scatter
 template <uint32_t W>
 __device__ __forceinline__ void select_move(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint64_t src, uint64_t dst) {
   if constexpr (W == 8) {
@@ -106,8 +218,8 @@ __device__ __forceinline__ void select_move(const uint8_t* __restrict__ in, uint
   }
 }
 
-// The scatter, instantiated over who decides a row.  BALLOTS false: the box test, here (swz_box_select_device; `ballots` is
-// not read).  BALLOTS true: the count pass of a region has decided every row and left its waves' ballots.
+// The scatter, instantiated over who decides a row.  BALLOTS false: the box test, here (the box alone; `ballots` is not
+// read).  BALLOTS true: the count pass has decided every row and left its waves' ballots.
 template <bool BALLOTS>
 __global__ __launch_bounds__(SEL_TILE) void select_scatter_kernel(SelectArgs a, const uint64_t* __restrict__ ballots) {
   __shared__ double s_xyz[3 * SEL_TILE];
@@ -154,130 +266,6 @@ __global__ __launch_bounds__(SEL_TILE) void select_scatter_kernel(SelectArgs a, 
       default: select_move<1>(a.in[k], a.out[k], src, dst); break;
     }
   }
-}
-
-// ---- regions: the box cut by planes or by a polygon in x-y
-struct RegionPolygon {
-  const double* xy;  // vertices x (x, y)
-  uint32_t vertices;
-};
-
-// every plane: ((a*x + b*y) + c*z) + d >= 0, four separately rounded operations (the library is built without contraction)
-__device__ __forceinline__ bool planes_inside(const RegionPlanes& P, double x, double y, double z) {
-  bool in = true;
-  for (uint32_t k = 0; k < P.count; ++k) in = in && ((P.p[k][0] * x + P.p[k][1] * y) + P.p[k][2] * z) + P.p[k][3] >= 0.0;
-  return in;
-}
-
-// even-odd over the edges (v[i], v[(i+1) mod m]); the parity does not care that the closing edge comes first.  Every lane
-// reads the same LDS address: a broadcast.
-__device__ __forceinline__ bool polygon_inside(const double* s_xy, uint32_t m, double px, double py) {
-  bool odd = false;
-  double x0 = s_xy[2 * (m - 1)], y0 = s_xy[2 * (m - 1) + 1];
-  for (uint32_t i = 0; i < m; ++i) {
-    const double x1 = s_xy[2 * i], y1 = s_xy[2 * i + 1];
-    if ((y0 > py) != (y1 > py)) {
-      const double t = (x1 - x0) * (py - y0) - (px - x0) * (y1 - y0);
-      odd ^= (t > 0.0) == (y1 > y0);
-    }
-    x0 = x1;
-    y0 = y1;
-  }
-  return odd;
-}
-
-// the count pass of a region: R is RegionPlanes (in the kernel arguments) or RegionPolygon (staged in LDS: 16 KiB at the
-// most, which with the 16 bytes of the ranking leaves the 32 waves of a CU their room in its 160 KiB).  ballots: one word per
-// wave of every tile, what select_scatter_kernel<true> reads back.
-template <class R>
-__global__ __launch_bounds__(SEL_TILE) void region_count_kernel(const double* __restrict__ xyz, uint32_t n, SelectBox box, R region,
-                                                                uint32_t* __restrict__ tile_count, uint64_t* __restrict__ ballots) {
-  __shared__ uint32_t s_wave[SEL_WAVES];
-  const uint64_t r = (uint64_t)blockIdx.x * SEL_TILE + threadIdx.x;
-  double x = 0, y = 0, z = 0;
-  bool in = false;
-  if (r < n) {
-    x = xyz[3 * r];
-    y = xyz[3 * r + 1];
-    z = xyz[3 * r + 2];
-    in = select_inside(box, x, y, z);  // (keeps NaN out of the tests below)
-  }
-  if constexpr (std::is_same_v<R, RegionPolygon>) {
-    __shared__ double s_xy[2 * SWZ_REGION_MAX_VERTICES];
-    for (uint32_t i = threadIdx.x; i < 2u * region.vertices; i += SEL_TILE) s_xy[i] = region.xy[i];
-    __syncthreads();
-    if (in) in = polygon_inside(s_xy, region.vertices, x, y);  // only the rows of the box walk the edges
-  } else {
-    if (in) in = planes_inside(region, x, y, z);
-  }
-  uint32_t total;
-  uint64_t bal;
-  (void)select_rank(in, s_wave, &total, &bal);
-  if (threadIdx.x % WAVE == 0) ballots[(uint64_t)blockIdx.x * SEL_WAVES + threadIdx.x / WAVE] = bal;
-  if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
-}
-
-// ---- filters: clauses over the attribute columns, behind the region (swz_filter_select_device)
-struct RegionNone {};  // the box alone
-
-struct FilterCols {
-  const uint8_t* col[SWZ_FILTER_MAX_CLAUSES];  // clause k's column
-};
-
-// one clause on row r.  Every field of cl and col are the same for all lanes (kernel arguments: scalar registers); only the
-// element is per lane.  The four words of a set are chosen by compares, not by an index a lane computes.
-__device__ __forceinline__ bool clause_passes(const swz_filter_clause& cl, const uint8_t* __restrict__ col, uint64_t r) {
-  bool pass;
-  if ((cl.kind & 0xFFu) == SWZ_FILTER_SET) {
-    const uint32_t b = col[r];  // the stored byte, unsigned
-    const uint64_t w01 = (b & 64u) ? cl.set[1] : cl.set[0], w23 = (b & 64u) ? cl.set[3] : cl.set[2];
-    pass = ((((b & 128u) ? w23 : w01) >> (b & 63u)) & 1ull) != 0;
-  } else {
-    double v;  // exact for every type
-    switch (cl.attribute) {
-      case SWZ_ATTR_GPS_TIME: v = reinterpret_cast<const double*>(col)[r]; break;
-      case SWZ_ATTR_INTENSITY:
-      case SWZ_ATTR_POINT_SOURCE_ID: v = (double)reinterpret_cast<const uint16_t*>(col)[r]; break;
-      case SWZ_ATTR_SCAN_ANGLE_RANK: v = (double)reinterpret_cast<const int8_t*>(col)[r]; break;
-      default: v = (double)col[r]; break;
-    }
-    pass = cl.lo <= v && v <= cl.hi;  // (a NaN fails both)
-  }
-  return pass != ((cl.kind & SWZ_FILTER_NOT) != 0u);
-}
-
-// the count pass with a filter, for all three kinds: R is RegionNone, RegionPlanes or RegionPolygon.  Box, then the kind's
-// test, then the clauses in order -- a lane loads a clause's element only while its row is still in (r < n then).  The loop
-// over the clauses is the same for the whole wave.  Ballots and tile counts as region_count_kernel leaves them.
-template <class R>
-__global__ __launch_bounds__(SEL_TILE) void filter_count_kernel(const double* __restrict__ xyz, uint32_t n, SelectBox box, R region,
-                                                                swz_filter filter, FilterCols cols, uint32_t* __restrict__ tile_count,
-                                                                uint64_t* __restrict__ ballots) {
-  __shared__ uint32_t s_wave[SEL_WAVES];
-  const uint64_t r = (uint64_t)blockIdx.x * SEL_TILE + threadIdx.x;
-  double x = 0, y = 0, z = 0;
-  bool in = false;
-  if (r < n) {
-    x = xyz[3 * r];
-    y = xyz[3 * r + 1];
-    z = xyz[3 * r + 2];
-    in = select_inside(box, x, y, z);
-  }
-  if constexpr (std::is_same_v<R, RegionPolygon>) {
-    __shared__ double s_xy[2 * SWZ_REGION_MAX_VERTICES];
-    for (uint32_t i = threadIdx.x; i < 2u * region.vertices; i += SEL_TILE) s_xy[i] = region.xy[i];
-    __syncthreads();
-    if (in) in = polygon_inside(s_xy, region.vertices, x, y);
-  } else if constexpr (std::is_same_v<R, RegionPlanes>) {
-    if (in) in = planes_inside(region, x, y, z);
-  }
-  for (uint32_t k = 0; k < filter.count; ++k)
-    if (in) in = clause_passes(filter.clause[k], cols.col[k], r);
-  uint32_t total;
-  uint64_t bal;
-  (void)select_rank(in, s_wave, &total, &bal);
-  if (threadIdx.x % WAVE == 0) ballots[(uint64_t)blockIdx.x * SEL_WAVES + threadIdx.x / WAVE] = bal;
-  if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
 }
 
 const char* attribute_name(int attribute) {
@@ -386,10 +374,11 @@ static bool overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_b
 }
 
 int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t mask,
-                  const double box_min[3], const double box_max[3], const RegionDev* region, const RegionHost* upload, uint64_t capacity,
-                  double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_row_out, uint64_t* count_out, const swz_filter* filter) {
-  const int kind = upload ? upload->kind : region ? region->kind : SWZ_REGION_BOX;
-  if (filter && !filter->count) filter = nullptr;  // no clause: the region call
+                  const Selection& sel, uint64_t capacity, double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_row_out,
+                  uint64_t* count_out) {
+  const double *box_min = sel.box_min, *box_max = sel.box_max;
+  const int kind = sel.region ? sel.region->kind : sel.uploaded ? sel.uploaded->kind : SWZ_REGION_BOX;
+  const swz_filter* filter = sel.filter && sel.filter->count ? sel.filter : nullptr;  // no clause: no filter
   uint32_t fmask = 0;  // the columns the clauses read
   for (uint32_t k = 0; filter && k < filter->count; ++k) fmask |= 1u << filter->clause[k].attribute;
   auto refuse = [&](const std::string& what) { return c->fail(SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
@@ -445,9 +434,10 @@ int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, 
   if (n == 0) return SWZ_OK;
 
   SWZ_HIP(c, hipSetDevice(c->device));
+  const RegionDev* region = sel.uploaded;
   RegionDev uploaded;
-  if (upload) {
-    SWZ_TRY(region_upload(c, *upload, &uploaded));
+  if (sel.region) {
+    SWZ_TRY(region_upload(c, *sel.region, &uploaded));
     region = &uploaded;
   }
   const uint32_t nb = div_up(n, SEL_TILE);
@@ -461,43 +451,33 @@ int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, 
     a.box.lo[k] = box_min[k];
     a.box.hi[k] = box_max[k];
   }
+  // all but the box alone: the count pass decides every row and hands its ballots to the scatter
+  const bool ballots = filter || kind != SWZ_REGION_BOX;
+  const uint64_t ballot_bytes = ballots ? 8ull * nb * SEL_WAVES : 0;
   uint64_t* d_ballots = nullptr;
-  if (filter) {
-    SWZ_TRY(c->get("sel_ballots", (size_t)nb * SEL_WAVES, &d_ballots));
-    FilterCols fc{};
-    uint64_t col_bytes = 0;  // (at the most: a lane reads only while its row is in)
-    for (uint32_t k = 0; k < filter->count; ++k) {
-      fc.col[k] = static_cast<const uint8_t*>(d_in->column[filter->clause[k].attribute]);
-      col_bytes += ATTR_BYTES[filter->clause[k].attribute];
-    }
-    ProfScope ps(c, "filter_select_count", (24 + col_bytes) * n + 8ull * nb * SEL_WAVES, 1);
-    if (kind == SWZ_REGION_PLANES)
-      hipLaunchKernelGGL(filter_count_kernel<RegionPlanes>, dim3(nb), dim3(SEL_TILE), 0, c->stream, d_xyz, a.n, a.box, region->planes, *filter, fc,
-                         d_tiles, d_ballots);
-    else if (kind == SWZ_REGION_POLYGON)
-      hipLaunchKernelGGL(filter_count_kernel<RegionPolygon>, dim3(nb), dim3(SEL_TILE), 0, c->stream, d_xyz, a.n, a.box,
-                         RegionPolygon{region->d_xy, region->vertices}, *filter, fc, d_tiles, d_ballots);
-    else
-      hipLaunchKernelGGL(filter_count_kernel<RegionNone>, dim3(nb), dim3(SEL_TILE), 0, c->stream, d_xyz, a.n, a.box, RegionNone{}, *filter, fc,
-                         d_tiles, d_ballots);
+  if (ballots) SWZ_TRY(c->get("sel_ballots", (size_t)nb * SEL_WAVES, &d_ballots));
+  FilterCols fc{};
+  uint64_t col_bytes = 0;  // (at the most: a lane reads only while its row is in)
+  for (uint32_t k = 0; filter && k < filter->count; ++k) {
+    fc.col[k] = static_cast<const uint8_t*>(d_in->column[filter->clause[k].attribute]);
+    col_bytes += ATTR_BYTES[filter->clause[k].attribute];
+  }
+  static const char* const scopes[4][2] = {{"box_select_count", "box_select_scatter"},
+                                           {"planes_select_count", "planes_select_scatter"},
+                                           {"polygon_select_count", "polygon_select_scatter"},
+                                           {"filter_select_count", "filter_select_scatter"}};
+  static_assert(SWZ_REGION_BOX == 0 && SWZ_REGION_PLANES == 1 && SWZ_REGION_POLYGON == 2, "the rows of scopes");
+  const char* const* scope = scopes[filter ? 3 : kind];
+  {
+    ProfScope ps(c, scope[0], (24 + col_bytes) * n + ballot_bytes, 1);
+    auto count = [&](const auto& r) {
+      using R = std::decay_t<decltype(r)>;
+      (filter ? select_count_launch<R, true> : select_count_launch<R, false>)(c->stream, nb, a, r, filter, &fc, d_tiles, d_ballots);
+    };
+    if (kind == SWZ_REGION_PLANES) count(region->planes);
+    else if (kind == SWZ_REGION_POLYGON) count(RegionPolygon{region->d_xy, region->vertices});
+    else count(RegionNone{});
     SWZ_LAUNCH_CHECK(c);
-  } else if (kind == SWZ_REGION_BOX) {
-    ProfScope ps(c, "box_select_count", 24 * n, 1);
-    hipLaunchKernelGGL(select_count_kernel, dim3(nb), dim3(SEL_TILE), 0, c->stream, d_xyz, a.n, a.box, d_tiles);
-    SWZ_LAUNCH_CHECK(c);
-  } else {
-    SWZ_TRY(c->get("sel_ballots", (size_t)nb * SEL_WAVES, &d_ballots));
-    if (kind == SWZ_REGION_PLANES) {
-      ProfScope ps(c, "planes_select_count", 24 * n + 8ull * nb * SEL_WAVES, 1);
-      hipLaunchKernelGGL(region_count_kernel<RegionPlanes>, dim3(nb), dim3(SEL_TILE), 0, c->stream, d_xyz, a.n, a.box, region->planes, d_tiles,
-                         d_ballots);
-      SWZ_LAUNCH_CHECK(c);
-    } else {
-      ProfScope ps(c, "polygon_select_count", 24 * n + 8ull * nb * SEL_WAVES, 1);
-      hipLaunchKernelGGL(region_count_kernel<RegionPolygon>, dim3(nb), dim3(SEL_TILE), 0, c->stream, d_xyz, a.n, a.box,
-                         RegionPolygon{region->d_xy, region->vertices}, d_tiles, d_ballots);
-      SWZ_LAUNCH_CHECK(c);
-    }
   }
   SWZ_TRY(scan_exclusive_u32(c, d_tiles, d_tiles, nb, d_total, "sel"));
   uint32_t total = 0;
@@ -517,14 +497,10 @@ int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, 
     a.out[k] = static_cast<uint8_t*>(d_out->column[k]);
     row_bytes += 2 * ATTR_BYTES[k];
   }
-  if (kind == SWZ_REGION_BOX && !filter) {
-    ProfScope ps(c, "box_select_scatter", 24 * n + row_bytes * total, 1);
-    hipLaunchKernelGGL(select_scatter_kernel<false>, dim3(nb), dim3(SEL_TILE), 0, c->stream, a, (const uint64_t*)nullptr);
-    SWZ_LAUNCH_CHECK(c);
-  } else {
-    ProfScope ps(c, filter ? "filter_select_scatter" : kind == SWZ_REGION_PLANES ? "planes_select_scatter" : "polygon_select_scatter",
-                 24 * n + 8ull * nb * SEL_WAVES + row_bytes * total, 1);
-    hipLaunchKernelGGL(select_scatter_kernel<true>, dim3(nb), dim3(SEL_TILE), 0, c->stream, a, (const uint64_t*)d_ballots);
+  {
+    ProfScope ps(c, scope[1], 24 * n + ballot_bytes + row_bytes * total, 1);
+    if (ballots) hipLaunchKernelGGL(select_scatter_kernel<true>, dim3(nb), dim3(SEL_TILE), 0, c->stream, a, (const uint64_t*)d_ballots);
+    else hipLaunchKernelGGL(select_scatter_kernel<false>, dim3(nb), dim3(SEL_TILE), 0, c->stream, a, (const uint64_t*)nullptr);
     SWZ_LAUNCH_CHECK(c);
   }
   SWZ_HIP(c, hipStreamSynchronize(c->stream));
@@ -543,8 +519,8 @@ int swz_box_select_device(swz_ctx* c, const double* d_xyz, uint64_t n, const swz
                           const double box_min[3], const double box_max[3], uint64_t capacity, double* d_xyz_out,
                           const swz_attribute_columns* d_out, uint32_t* d_row_out, uint64_t* count_out) {
   if (!c) return SWZ_ERR_BAD_ARG;
-  return region_select(c, "swz_box_select_device", d_xyz, n, d_in, attribute_mask, box_min, box_max, nullptr, nullptr, capacity, d_xyz_out,
-                       d_out, d_row_out, count_out);
+  const Selection sel{box_min, box_max, nullptr, nullptr, nullptr};
+  return region_select(c, "swz_box_select_device", d_xyz, n, d_in, attribute_mask, sel, capacity, d_xyz_out, d_out, d_row_out, count_out);
 }
 
 int swz_region_select_device(swz_ctx* c, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t attribute_mask,
@@ -554,19 +530,13 @@ int swz_region_select_device(swz_ctx* c, const double* d_xyz, uint64_t n, const 
   const char* who = "swz_region_select_device";
   RegionHost host;
   SWZ_TRY(region_check(c, who, region, &host));
-  return region_select(c, who, d_xyz, n, d_in, attribute_mask, box_min, box_max, nullptr, &host, capacity, d_xyz_out, d_out, d_row_out,
-                       count_out);
+  const Selection sel{box_min, box_max, &host, nullptr, nullptr};
+  return region_select(c, who, d_xyz, n, d_in, attribute_mask, sel, capacity, d_xyz_out, d_out, d_row_out, count_out);
 }
 
 int swz_filter_check(const swz_filter* filter, char* why_out, uint64_t why_bytes) {
   swz_ctx text;  // (only its error text is used: no device is touched)
-  const int st = filter_check(&text, "swz_filter_check", filter, nullptr);
-  if (why_out && why_bytes) {
-    const size_t len = std::min<size_t>(st == SWZ_OK ? 0 : text.err.size(), (size_t)why_bytes - 1);
-    memcpy(why_out, text.err.data(), len);
-    why_out[len] = 0;
-  }
-  return st;
+  return why_text(filter_check(&text, "swz_filter_check", filter, nullptr), text, why_out, why_bytes);
 }
 
 int swz_filter_select_device(swz_ctx* c, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t attribute_mask,
@@ -578,8 +548,8 @@ int swz_filter_select_device(swz_ctx* c, const double* d_xyz, uint64_t n, const 
   RegionHost host;
   SWZ_TRY(region_check(c, who, region, &host));
   SWZ_TRY(filter_check(c, who, filter, nullptr));
-  return region_select(c, who, d_xyz, n, d_in, attribute_mask, box_min, box_max, nullptr, &host, capacity, d_xyz_out, d_out, d_row_out,
-                       count_out, filter);
+  const Selection sel{box_min, box_max, &host, nullptr, filter};
+  return region_select(c, who, d_xyz, n, d_in, attribute_mask, sel, capacity, d_xyz_out, d_out, d_row_out, count_out);
 }
 
 }  // extern "C"
