@@ -126,7 +126,11 @@ uint64_t swz_workspace_bytes(const swz_ctx* ctx);
 /* ---- index_points<21>(..., ClampToBounds): core/tiling/OctreeAlgorithms.h:145-197 with
  * calculate_morton_index<21> :64-87.  xyz is N x 3 doubles (AoS).  Outliers are clamped to the
  * bounds IN PLACE (index_point mutates the PointBuffer, :167-169), so xyz is read-write.
- * keys_out[i] is the 63-bit MortonIndex64 of point i. */
+ * keys_out[i] is the 63-bit MortonIndex64 of point i.
+ * Bounds (here and in every call that takes a root box): finite, max > min on every axis, and 2^21 / (max - min)
+ * finite and positive -- else SWZ_ERR_BAD_ARG before anything is launched.  (An extent below about 1.2e-302, one
+ * that overflows, or an infinite face makes the scale inf or 0 and the products NaN or inf, whose conversion to a
+ * cell index differs between x86-64 and the GPU.) */
 int swz_morton_encode(swz_ctx* ctx, double* xyz, uint64_t n, const double bounds_min[3],
                       const double bounds_max[3], uint64_t* keys_out);
 int swz_morton_encode_device(swz_ctx* ctx, double* d_xyz, uint64_t n, const double bounds_min[3],

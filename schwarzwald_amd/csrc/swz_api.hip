@@ -1,6 +1,7 @@
 // swz_api.hip -- the C-ABI entry points of include/swz_gpu.h: context, workspace, profiling,
 // host-buffer wrappers around the device-resident stages.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "swz_device.h"
@@ -220,6 +221,14 @@ int check_bounds(swz_ctx* c, const double mn[3], const double mx[3]) {
   if (!mn || !mx) return c->fail(SWZ_ERR_BAD_ARG, "bounds must not be NULL");
   for (int a = 0; a < 3; ++a)
     if (!(mx[a] > mn[a])) return c->fail(SWZ_ERR_BAD_ARG, "bounds must have positive extent on every axis");
+  // The encode multiplies by 2^21 / extent.  With a scale of inf (a subnormal extent) or 0 (an extent that overflows, or
+  // an infinite face) its products are NaN or inf, and what the truncating cast makes of those differs between the
+  // reference's x86-64 build and the GPU: there is no answer to match, so such bounds are not taken.
+  for (int a = 0; a < 3; ++a) {
+    const double scale = 2097152.0 / (mx[a] - mn[a]);
+    if (!std::isfinite(mn[a]) || !std::isfinite(mx[a]) || !std::isfinite(scale) || !(scale > 0.0))
+      return c->fail(SWZ_ERR_BAD_ARG, "bounds must be finite, with an extent whose 2^21 / extent is finite and positive, on every axis");
+  }
   return SWZ_OK;
 }
 
