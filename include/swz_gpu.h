@@ -1205,12 +1205,57 @@ int swz_convert_dataset(swz_ctx* ctx, const char* src_dir, const char* dst_dir, 
  *     attributes into its chunk-local arrays and hands the caller attribute_mask (~0u: all the source holds).  The filter sees
  *     exactly the values an unfiltered query of that source returns (a LAS source: what its decode yields).  Refused before any
  *     file of points is read: a filtered attribute the source does not hold (named, with the source's mask) and, for a
- *     3DTILES source, any filtered attribute .pnts files do not carry.  The data set holds no per-node summary of its
- *     attributes, so no node is dropped for a filter: the node table is swz_dataset_query_region_nodes', d_node_out indexes it,
- *     points_bound stays the safe capacity, and points_read less points_out shows what region and filter refused.
+ *     3DTILES source, any filtered attribute .pnts files do not carry.  The node table is swz_dataset_query_region_nodes',
+ *     d_node_out indexes it, points_bound stays the safe capacity, and points_read less points_out shows what region and filter
+ *     refused.  Without node-summaries.swz in dir (below) no node is dropped for a filter.
+ *   Per-node attribute summaries let a filtered query skip the node files that cannot contribute a row.
+ *     swz_node_summaries_device: n rows in STORED order (chunk-local columns as the unpack kernels leave them, no perm or order),
+ *       a host node table checked as swz_node_boxes_device checks its own, and per node and summarised column one
+ *       swz_attr_summary in summaries_out (HOST, num_nodes x popcount(attribute_mask) entries; entry (k, j) is node k and the
+ *       j-th set bit of the mask in ascending SWZ_ATTR_* order).  Summarised are the scalar columns a filter knows
+ *       (SWZ_SUMMARY_SCALARS).  One-byte columns: set holds bit (uint8_t)v of every value of the node, lo / hi are derived from
+ *       it on the host (SCAN_ANGLE_RANK as signed: bit 255 is -1, bit 128 is -128).  uint16 columns and GPS_TIME: lo / hi are
+ *       the exact min and max as doubles, set is 0; a NaN GPS time is left out of lo / hi and sets SWZ_SUMMARY_HAS_NAN; of
+ *       +0.0 and -0.0 either may come back.  A node of count 0, or one whose GPS times are all NaN, has lo = +inf, hi = -inf.
+ *       One workgroup takes swz_node_summaries_tile() consecutive rows and handles the columns one after the other: an
+ *       element per lane, runs of lanes of one node combined with shuffles, the runs of a node combined in LDS, then per
+ *       (tile, node, column) one round of relaxed agent-scope atomics on a table a small kernel preset (64-bit OR, words that
+ *       are 0 skipped; 32-bit min / max; 64-bit min / max on order-preserving codes).  OR, min and max are idempotent and
+ *       commute: the result is exact and depends neither on what the workspace held nor on any order.  SWZ_ERR_BAD_ARG with
+ *       a message before anything is launched: what swz_node_boxes_device refuses of the table, n above 2^32 - 65536, a mask
+ *       bit without its column, SWZ_ATTR_RGB, SWZ_ATTR_NORMAL or an unknown bit, a column not aligned to its element.
+ *       n == 0, no nodes, only empty nodes or an empty mask launch nothing; the output is preset on the host.
+ *     The sidecar is dir/node-summaries.swz (swz_dataset_scan skips extensions it does not know, so readers that ignore it are
+ *       not disturbed).  Little-endian: 8 bytes magic "SWZNSUM\0", u32 version 1, u32 format (SWZ_OUT_*), u32 mask, u32 entry
+ *       bytes (56), u64 nodes, u64 points, u64 0; then per node in (level, Morton index) order u64 key, u64 count, i8 level and
+ *       7 zero bytes; then the entries.  swz_dataset_summaries_write writes it under a temporary name in dir and renames it.
+ *       swz_dataset_summaries_read (all arrays NULL: the sizes only; else max_nodes must hold the nodes) checks the exact size
+ *       and refuses by name a wrong magic, version, entry size or file size, nodes out of order or twice, a nonzero reserved
+ *       field.  A directory without the file is no error: *present_out = 0.  Both are host only and take no context.
+ *     swz_dataset_summarize opens dir as the query does (every depth), streams all nodes through the query's stream with the
+ *       source's scalar columns unpacked (a 3DTILES source with SWZ_CONVERT_LOSSY_SOURCE: intensity, if the files carry it),
+ *       runs swz_node_summaries_device's kernel on every chunk and writes the sidecar at the end: it describes exactly the
+ *       values a query of that source sees.  A source without a scalar column gets a sidecar with mask 0.  Refused: what the
+ *       query refuses of a source.  Memory as the query.  The writers (swz_tiler_write_output, swz_convert_dataset) do not
+ *       write the sidecar: what a LAS target stores is not what the pools hold.
+ *     swz_dataset_query_filtered_nodes[_why] (host): swz_dataset_query_region_nodes' table, unchanged and in the same order,
+ *       and read_out[k] = 0 for every node the filter cannot reach; points_bound_out: the sum of the counts of the nodes that
+ *       are read.  Without a sidecar, with filter == NULL or count == 0, every node is read.  A node is dropped iff SOME
+ *       clause has no row of the node that could pass it, judged from that attribute's entry alone.  One-byte column: with P
+ *       the 256-bit set of byte values the clause's test accepts (SET: the clause's set; RANGE: the two double compares on
+ *       each of the 256 values, signed for the scan-angle rank; with SWZ_FILTER_NOT the complement), drop iff entry.set & P
+ *       == 0 -- exact: a single such clause drops a node iff no row passes.  uint16 column or GPS time, RANGE: drop iff
+ *       entry.hi < lo || entry.lo > hi (which covers a node without non-NaN values); NOT RANGE: drop iff the node has no NaN
+ *       and lo <= entry.lo && entry.hi <= hi.  A clause whose attribute the sidecar's mask lacks drops nothing.  The rule
+ *       errs towards reading a file.  Every node of the region table must be found in the sidecar by (level, key) with the
+ *       scan's count, and the sidecar must name the scan's format; else the call is refused ("node-summaries.swz is stale:
+ *       node r04 holds 120 points, the summary 118 -- run swz_dataset_summarize again"), as is a sidecar that fails its read
+ *       checks.  A data set rewritten with equal counts per node cannot be told from the one that was summarised.
+ *     swz_dataset_query_filtered applies the rule when the sidecar is there: the dropped nodes are neither read nor chunked.
+ *       d_node_out keeps indexing the region table; positions, columns, d_node_out and *count_out are byte for byte what they
+ *       are without the sidecar, only nodes_read, points_read, bytes_read, chunks and the times change.
  *   Not offered: a multi-GPU driver, polygons with holes or several rings, a shortcut that copies nodes wholly inside a
- *     region without testing their rows, depth chosen by screen-space error, per-node attribute summaries that would let a
- *     filter drop whole nodes. */
+ *     region without testing their rows, depth chosen by screen-space error. */
 typedef struct {
   double box_min[3], box_max[3]; /* closed */
   int32_t max_depth;             /* < 0: every node; else nodes of depth <= max_depth, as swz_dataset_scan counts depth */
@@ -1281,6 +1326,36 @@ int swz_filter_select_device(swz_ctx* ctx, const double* d_xyz, uint64_t n, cons
 int swz_dataset_query_filtered(swz_ctx* ctx, const char* dir, const swz_query_params* params, const swz_region* region,
                                const swz_filter* filter, uint64_t capacity, double* d_xyz_out, const swz_attribute_columns* d_out,
                                uint32_t* d_node_out /* may be NULL */, uint64_t* count_out, swz_query_stats* stats);
+enum { SWZ_SUMMARY_HAS_NAN = 1u };
+/* the columns that are summarised: every scalar column, bits SWZ_ATTR_INTENSITY .. SWZ_ATTR_USER_DATA */
+#define SWZ_SUMMARY_SCALARS 0xFFCu
+typedef struct {
+  double lo, hi;     /* min and max of the node's values as doubles (exact for every scalar type); NaN rows excluded */
+  uint64_t set[4];   /* one-byte columns: bit (uint8_t)v for every value the node holds; wider columns: 0 */
+  uint32_t flags;    /* SWZ_SUMMARY_HAS_NAN: a GPS time of the node is NaN */
+  uint32_t reserved; /* 0 */
+} swz_attr_summary;  /* 56 bytes */
+typedef struct {
+  uint64_t nodes, points, bytes_read, chunks;
+  double read_ms, unpack_ms, summary_ms, copy_ms, wall_ms;
+} swz_summarize_stats;
+uint32_t swz_node_summaries_tile(void); /* rows one workgroup takes; tests place their edges by it */
+int swz_node_summaries_device(swz_ctx* ctx, uint64_t n, const swz_attribute_columns* d_in, uint32_t attribute_mask, uint64_t num_nodes,
+                              const uint64_t* node_offset, const uint64_t* node_count, swz_attr_summary* summaries_out);
+int swz_dataset_summaries_write(const char* dir, int32_t format, uint32_t mask, uint64_t num_nodes, const int8_t* level,
+                                const uint64_t* key, const uint64_t* count, const swz_attr_summary* entries, char* why_out,
+                                uint64_t why_bytes);
+int swz_dataset_summaries_read(const char* dir, int32_t* present_out, int32_t* format_out, uint32_t* mask_out, uint64_t* num_nodes_out,
+                               uint64_t* points_out, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out, uint64_t* count_out,
+                               swz_attr_summary* entries_out, char* why_out, uint64_t why_bytes);
+int swz_dataset_summarize(swz_ctx* ctx, const char* dir, uint32_t source_flags, uint64_t chunk_points, swz_summarize_stats* stats);
+int swz_dataset_query_filtered_nodes(swz_ctx* ctx, const char* dir, const swz_query_params* params, const swz_region* region,
+                                     const swz_filter* filter, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out,
+                                     uint64_t* count_out, uint8_t* read_out, uint64_t* num_out, uint64_t* points_bound_out);
+int swz_dataset_query_filtered_nodes_why(const char* dir, const swz_query_params* params, const swz_region* region,
+                                         const swz_filter* filter, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out,
+                                         uint64_t* count_out, uint8_t* read_out, uint64_t* num_out, uint64_t* points_bound_out,
+                                         char* why_out, uint64_t why_bytes);
 /* ---- a source projection (the reference's --source-projection: Proj4Transform, core/util/Transformation.cpp:74-211, source
  * -> "+proj=geocent +datum=WGS84").  PROJ is not linked: the library maps the projection families LAS data comes in itself,
  * in double, and refuses every other definition by name.

@@ -1120,13 +1120,125 @@ def dataset_query_filtered(ctx, directory, box_min, box_max, region=None, filter
                            chunk_points=0, return_nodes=False, capacity=None):
     """swz_dataset_query_filtered: dataset_query_region for the rows that also pass filter (a Filter; None: no filter) -- the same
     keywords, the same result dict.  attrs are the columns returned; the columns the filter names are read for it whether
-    attrs holds them or not.  No node drops out for a filter: node indexes dataset_query_region_nodes' table, and
-    stats["points_read"] - stats["points_out"] is what region and filter refused."""
+    attrs holds them or not.  node indexes dataset_query_region_nodes' table, and stats["points_read"] - stats["points_out"] is
+    what region and filter refused.  Where dataset_summarize has left node-summaries.swz in directory, the nodes the filter cannot
+    reach (dataset_query_filtered_nodes) are not read: the outputs are the same bytes, stats["nodes_read"], ["points_read"],
+    ["bytes_read"] and ["chunks"] shrink."""
     box_min, box_max = _region_box(directory, box_min, box_max, region, max_depth)
     if filter is not None:
         filter.check()   # (before the query scans the directory for its table)
     return _dataset_query(ctx, directory, box_min, box_max, max_depth, attrs, lossy_source, chunk_points, return_nodes, capacity, region, filter,
                           "swz_dataset_query_filtered")
+
+
+# ---- per-node attribute summaries: node-summaries.swz beside a written data set lets a filtered query skip node files
+SUMMARY_HAS_NAN = 1
+SUMMARY_SCALARS = 0xFFC
+# an entry (swz_attr_summary) as numpy sees it: 56 bytes
+SUMMARY_DTYPE = np.dtype([("lo", "<f8"), ("hi", "<f8"), ("set", "<u8", (4,)), ("flags", "<u4"), ("reserved", "<u4")])
+
+
+class _SummarizeStats(C.Structure):
+    _fields_ = [("nodes", C.c_uint64), ("points", C.c_uint64), ("bytes_read", C.c_uint64), ("chunks", C.c_uint64), ("read_ms", C.c_double),
+                ("unpack_ms", C.c_double), ("summary_ms", C.c_double), ("copy_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+def _summary_mask(attrs):
+    """names or a mask => the mask; nothing is checked (the library refuses what it does not take)"""
+    if isinstance(attrs, (int, np.integer)):
+        return int(attrs)
+    mask = 0
+    for name in attrs:
+        mask |= 1 << ATTRIBUTES[name][0]
+    return mask
+
+
+def node_summaries_tile():
+    """Rows one workgroup of node_summaries_device takes (tests place their edges by it)."""
+    return int(load_library().swz_node_summaries_tile())
+
+
+def dataset_summaries_write(directory, format, attrs, nodes, entries):
+    """swz_dataset_summaries_write (host, no GPU): directory/node-summaries.swz out of a node table (dict of level / key / count in
+    (level, Morton index) order) and entries, an array of SUMMARY_DTYPE of shape (nodes, columns): entry (k, j) is node k and
+    the j-th of attrs (names or a mask) in ascending attribute index.  format: a key of OUTPUT_FORMATS or its value."""
+    fmt = OUTPUT_FORMATS[format] if isinstance(format, str) else int(format)
+    nl, nk, nc = _node_columns(nodes, "level", "key", "count")
+    mask = _summary_mask(attrs)
+    ent = np.ascontiguousarray(entries, dtype=SUMMARY_DTYPE).reshape(-1)
+    if ent.shape[0] != nl.shape[0] * bin(mask & 0xFFFFFFFF).count("1"):
+        raise ValueError("entries must hold one entry per node and column of the mask")
+    why = C.create_string_buffer(1024)
+    st = load_library().swz_dataset_summaries_write(os.fsencode(directory), fmt, mask, nl.shape[0], nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p),
+                                                    nc.ctypes.data_as(_u64p), ent.ctypes.data, why, len(why))
+    if st != 0:
+        raise SwzError(st, why.value.decode(errors="replace"))
+
+
+def dataset_summaries_read(directory):
+    """swz_dataset_summaries_read (host, no GPU): None when directory holds no node-summaries.swz, else dict(format (a key of
+    OUTPUT_FORMATS), attribute_mask, attrs, points, nodes (level, key, count), entries (SUMMARY_DTYPE, nodes x columns)).  A
+    file that fails its checks raises SwzError with the library's text."""
+    L = load_library()
+    present, fmt, mask, num, points = C.c_int32(), C.c_int32(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+    why = C.create_string_buffer(1024)
+
+    def call(cap, *arrays):
+        st = L.swz_dataset_summaries_read(os.fsencode(directory), C.byref(present), C.byref(fmt), C.byref(mask), C.byref(num), C.byref(points),
+                                          cap, *arrays, why, len(why))
+        if st != 0:
+            raise SwzError(st, why.value.decode(errors="replace"))
+
+    call(0, None, None, None, None)
+    if not present.value:
+        return None
+    m, cols = int(num.value), bin(mask.value).count("1")
+    nl, nk, nc = np.empty(max(m, 1), dtype=np.int8), np.empty(max(m, 1), dtype=np.uint64), np.empty(max(m, 1), dtype=np.uint64)
+    ent = np.zeros(max(m * cols, 1), dtype=SUMMARY_DTYPE)
+    call(m, nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p), ent.ctypes.data)
+    names = {v: k for k, v in OUTPUT_FORMATS.items()}
+    return dict(format=names[int(fmt.value)], attribute_mask=int(mask.value), attrs=attribute_names(mask.value), points=int(points.value),
+                nodes=dict(level=nl[:m].copy(), key=nk[:m].copy(), count=nc[:m].copy()), entries=ent[:m * cols].reshape(m, cols).copy())
+
+
+def dataset_summarize(ctx, directory, lossy_source=False, chunk_points=0, source_flags=None):
+    """swz_dataset_summarize: every node file of the written data set in directory streamed as a query streams it, the scalar
+    columns summarised per node on the device, and directory/node-summaries.swz written.  lossy_source admits a 3DTILES source
+    (intensity is summarised, if the files carry it); chunk_points as in Tiler.write_output.  Returns the stats as a dict (nodes,
+    points, bytes_read, chunks, read_ms, unpack_ms, summary_ms, copy_ms, wall_ms)."""
+    flags = int(source_flags) if source_flags is not None else (CONVERT_LOSSY_SOURCE if lossy_source else 0)
+    stats = _SummarizeStats()
+    ctx._check(ctx._lib.swz_dataset_summarize(ctx._ctx, os.fsencode(directory), flags, int(chunk_points), C.byref(stats)))
+    return {k: getattr(stats, k) for k, _ in _SummarizeStats._fields_}
+
+
+def dataset_query_filtered_nodes(directory, box_min, box_max, region=None, filter=None, max_depth=None, lossy_source=False, source_flags=None,
+                                 reserved=0):
+    """swz_dataset_query_filtered_nodes (host, no GPU): dataset_query_region_nodes' table, unchanged, with read -- a bool per
+    node: False for the nodes that directory's node-summaries.swz shows the filter (a Filter; None: no filter) cannot reach --
+    and points_bound, the sum of the counts of the nodes that are read.  Without the file or without a filter every node is
+    read.  A file that does not describe the data set (another count, a missing node, another format) is refused as stale."""
+    box_min, box_max = _region_box(directory, box_min, box_max, region, max_depth)
+    p = _query_params(box_min, box_max, max_depth, None, lossy_source, 0, source_flags, reserved)
+    rg = None if region is None else region._struct()
+    fl = None if filter is None else filter._struct()
+    head = (os.fsencode(directory), C.byref(p), _ref(rg), _ref(fl))
+    num, bound = C.c_uint64(), C.c_uint64()
+    why = C.create_string_buffer(4096)
+    entry = load_library().swz_dataset_query_filtered_nodes_why
+
+    def call(cap, *arrays):
+        st = entry(*head, cap, *arrays, C.byref(num), C.byref(bound), why, len(why))
+        if st != 0:
+            raise SwzError(st, why.value.decode(errors="replace"))
+
+    call(0, None, None, None, None)
+    cap = max(int(num.value), 1)
+    nl, nk, nc = np.empty(cap, dtype=np.int8), np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint64)
+    rd = np.empty(cap, dtype=np.uint8)
+    call(cap, nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p), rd.ctypes.data)
+    m = int(num.value)
+    return dict(level=nl[:m].copy(), key=nk[:m].copy(), count=nc[:m].copy(), read=rd[:m].astype(bool), points_bound=int(bound.value))
 
 
 LAS_SCAN_SKIP_UNREADABLE = 1
@@ -1432,6 +1544,20 @@ def load_library():
     L.swz_dataset_query_filtered.argtypes = [vp, C.c_char_p, C.POINTER(_QueryParams), rgp, flp, C.c_uint64, vp, cols, vp, _u64p,
                                              C.POINTER(_QueryStats)]
     for name in ("swz_filter_check", "swz_filter_select_device", "swz_dataset_query_filtered"):
+        getattr(L, name).restype = C.c_int
+    L.swz_node_summaries_tile.argtypes = []
+    L.swz_node_summaries_tile.restype = C.c_uint32
+    L.swz_node_summaries_device.argtypes = [vp, C.c_uint64, cols, C.c_uint32, C.c_uint64, _u64p, _u64p, vp]
+    L.swz_dataset_summaries_write.argtypes = [C.c_char_p, C.c_int32, C.c_uint32, C.c_uint64, _i8p, _u64p, _u64p, vp, C.c_char_p, C.c_uint64]
+    L.swz_dataset_summaries_read.argtypes = [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32p, _u64p, _u64p, C.c_uint64, _i8p, _u64p,
+                                             _u64p, vp, C.c_char_p, C.c_uint64]
+    L.swz_dataset_summarize.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint64, C.POINTER(_SummarizeStats)]
+    L.swz_dataset_query_filtered_nodes.argtypes = [vp, C.c_char_p, C.POINTER(_QueryParams), rgp, flp, C.c_uint64, _i8p, _u64p, _u64p, vp, _u64p,
+                                                   _u64p]
+    L.swz_dataset_query_filtered_nodes_why.argtypes = [C.c_char_p, C.POINTER(_QueryParams), rgp, flp, C.c_uint64, _i8p, _u64p, _u64p, vp, _u64p,
+                                                       _u64p, C.c_char_p, C.c_uint64]
+    for name in ("swz_node_summaries_device", "swz_dataset_summaries_write", "swz_dataset_summaries_read", "swz_dataset_summarize",
+                 "swz_dataset_query_filtered_nodes", "swz_dataset_query_filtered_nodes_why"):
         getattr(L, name).restype = C.c_int
     for name in ("swz_region_select_device", "swz_dataset_query_region_nodes", "swz_dataset_query_region_nodes_why", "swz_dataset_query_region"):
         getattr(L, name).restype = C.c_int
@@ -1935,6 +2061,24 @@ class Context:
     def dataset_query_filtered(self, directory, box_min, box_max, region=None, filter=None, **kwargs):
         """dataset_query_filtered(self, directory, box_min, box_max, region, filter, ...)"""
         return dataset_query_filtered(self, directory, box_min, box_max, region, filter, **kwargs)
+
+    def node_summaries_device(self, n, d_attrs, nodes, attrs=None):
+        """swz_node_summaries_device: per node of the table (dict of offset / count over n rows in stored order) and per column
+        of attrs (names or a mask; default: those of d_attrs, a dict name -> device pointer) one entry of SUMMARY_DTYPE, shape
+        (nodes, columns), columns in ascending attribute index: the set of values of a one-byte column with lo / hi derived
+        from it, the exact min and max of a uint16 column or of the GPS times (NaN left out and flagged)."""
+        cin = device_columns(d_attrs)
+        mask = _summary_mask(list(d_attrs or ()) if attrs is None else attrs)
+        no, nc = _node_columns(nodes, "offset", "count")
+        cols = bin(mask & 0xFFFFFFFF).count("1")
+        out = np.zeros((nc.shape[0], cols), dtype=SUMMARY_DTYPE)
+        self._check(self._lib.swz_node_summaries_device(self._ctx, int(n), C.byref(cin), mask, nc.shape[0], no.ctypes.data_as(_u64p),
+                                                        nc.ctypes.data_as(_u64p), out.ctypes.data if out.size else None))
+        return out
+
+    def dataset_summarize(self, directory, **kwargs):
+        """dataset_summarize(self, directory, ...)"""
+        return dataset_summarize(self, directory, **kwargs)
 
     def dataset_query_region(self, directory, box_min, box_max, region, **kwargs):
         """dataset_query_region(self, directory, box_min, box_max, region, ...)"""

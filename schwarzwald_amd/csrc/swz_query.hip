@@ -4,7 +4,9 @@
 // hold a row of the region drop out of the table (host only), and the rest is streamed chunk by chunk with the converter's SourceStream: every chunk's
 // chunk-local positions and columns go through the selection kernel (swz_select.hip) into the caller's arrays at the running
 // offset.  The readers of chunk j + 1 run while chunk j is selected.  With a filter (swz_dataset_query_filtered) the stream
-// unpacks the caller's columns and the filter's, the selection reads the latter, and no node drops out for it.
+// unpacks the caller's columns and the filter's, and the selection reads the latter.  Where the directory holds
+// node-summaries.swz (swz_dataset_summarize, below, writes it with the kernel of swz_summary.hip) the nodes that no row of
+// which can pass a clause are neither read nor chunked (filter_reads: the node rule of a filter).
 #include <chrono>
 #include <cmath>
 #include <cstddef>
@@ -16,6 +18,7 @@
 #include "swz_convert.h"
 #include "swz_hostio.h"
 #include "swz_select.h"
+#include "swz_summary.h"
 #include "swz_toutput.h"
 
 static_assert(sizeof(swz_query_params) == 72 && offsetof(swz_query_params, max_depth) == 48 && offsetof(swz_query_params, chunk_points) == 64 &&
@@ -29,9 +32,10 @@ static double ms_since(std::chrono::steady_clock::time_point t0) {
 }
 
 // per selected row of a chunk its node: the last node of the chunk whose first row is not behind the row (nodes without
-// points share their first row with the node behind them)
+// points share their first row with the node behind them); node_index: the chunk's nodes as indices of the query's table
 __global__ __launch_bounds__(256) void query_row_nodes_kernel(const uint32_t* __restrict__ rows, uint32_t cnt, const uint32_t* __restrict__ node_first,
-                                                              uint32_t nodes, uint32_t node0, uint32_t* __restrict__ node_out) {
+                                                              uint32_t nodes, const uint32_t* __restrict__ node_index,
+                                                              uint32_t* __restrict__ node_out) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= cnt) return;
   const uint32_t r = rows[i];
@@ -41,7 +45,7 @@ __global__ __launch_bounds__(256) void query_row_nodes_kernel(const uint32_t* __
     if (node_first[mid] <= r) lo = mid;
     else hi = mid;
   }
-  node_out[i] = node0 + lo;
+  node_out[i] = node_index[lo];
 }
 
 // ---- the node rule of a region, on the node's widened box [lo, hi] (every room term of the box rule already in it)
@@ -109,7 +113,7 @@ static bool polygon_misses(const RegionHost& r, const double lo[3], const double
 
 // The table a query reads: `kept` holds the nodes of the (depth-limited) scan whose widened boxes meet the query box and can
 // hold a row of the region, in the scan's order; *scanned: the nodes of the scan; *region_out: the region, checked;
-// *filter_attrs: the mask of the columns the filter (NULL: none) reads.  No node drops out for a filter.
+// *filter_attrs: the mask of the columns the filter (NULL: none) reads.  No node drops out for a filter here: filter_reads.
 static int query_plan(swz_ctx* c, const char* who, const char* dir, const swz_query_params* q, const swz_region* region, const swz_filter* filter,
                       DatasetScan* kept, uint64_t* scanned, RegionHost* region_out, uint32_t* filter_attrs) {
   auto refuse = [&](const std::string& what) { return fail(c, SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
@@ -186,6 +190,63 @@ static int query_plan(swz_ctx* c, const char* who, const char* dir, const swz_qu
   return SWZ_OK;
 }
 
+// ---- the node rule of a filter, on the summaries of node-summaries.swz
+
+// has the node no row that could pass the clause?  Judged from the entry of the clause's attribute alone.
+static bool clause_unreachable(const swz_filter_clause& cl, const swz_attr_summary& e) {
+  const bool negate = (cl.kind & SWZ_FILTER_NOT) != 0u;
+  if (ATTR_BYTES[cl.attribute] == 1) {  // exact: P is the set of byte values the clause's test accepts
+    const bool set = (cl.kind & 0xFFu) == SWZ_FILTER_SET, is_signed = cl.attribute == SWZ_ATTR_SCAN_ANGLE_RANK;
+    for (int b = 0; b < 256; ++b) {
+      if (!((e.set[b >> 6] >> (b & 63)) & 1ull)) continue;
+      const double v = is_signed ? (double)(int8_t)(uint8_t)b : (double)b;
+      const bool pass = set ? ((cl.set[b >> 6] >> (b & 63)) & 1ull) != 0 : (cl.lo <= v && v <= cl.hi);
+      if (pass != negate) return false;
+    }
+    return true;
+  }
+  if (!negate) return e.hi < cl.lo || e.lo > cl.hi;  // (a node without non-NaN values: hi = -inf)
+  return !(e.flags & SWZ_SUMMARY_HAS_NAN) && cl.lo <= e.lo && e.hi <= cl.hi;  // every value inside the range, and no NaN passes
+}
+
+// read->at(k) = 0 for the nodes of `kept` the filter cannot reach; all 1 without a filter or without a sidecar in dir.  A
+// sidecar that does not describe the scan is refused.
+static int filter_reads(swz_ctx* c, const char* who, const char* dir, const DatasetScan& kept, const swz_filter* filter,
+                        std::vector<uint8_t>* read) {
+  const uint64_t nn = kept.count.size();
+  read->assign(nn, 1);
+  if (!filter || !filter->count) return SWZ_OK;
+  Sidecar side;
+  std::string why;
+  if (sidecar_read(dir, &side, &why) != SWZ_OK)
+    return fail(c, SWZ_ERR_BAD_ARG, std::string(who) + ": " + why + " -- run swz_dataset_summarize again");
+  if (!side.present) return SWZ_OK;
+  auto stale = [&](const std::string& what) {
+    return fail(c, SWZ_ERR_BAD_ARG, std::string(who) + ": node-summaries.swz is stale: " + what + " -- run swz_dataset_summarize again");
+  };
+  if (side.format != kept.info.format)
+    return stale("the data set's format is " + std::to_string(kept.info.format) + ", the summary's " + std::to_string(side.format));
+  uint64_t at = 0;  // both tables ascend by (level, Morton index)
+  const uint64_t sn = side.key.size();
+  for (uint64_t k = 0; k < nn; ++k) {
+    const int8_t level = kept.level[k];
+    const uint64_t key = kept.key[k];
+    while (at < sn && (side.level[at] != level ? side.level[at] < level : side.key[at] < key)) ++at;
+    char name[24] = "?";
+    (void)swz_node_name(level, key, name);
+    if (at == sn || side.level[at] != level || side.key[at] != key) return stale(std::string("node ") + name + " is not in the summary");
+    if (side.count[at] != kept.count[k])
+      return stale(std::string("node ") + name + " holds " + std::to_string(kept.count[k]) + " points, the summary " + std::to_string(side.count[at]));
+    for (uint32_t q = 0; q < filter->count && (*read)[k]; ++q) {
+      const swz_filter_clause& cl = filter->clause[q];
+      if (!((side.mask >> cl.attribute) & 1u)) continue;  // not summarised: the clause drops nothing
+      const uint32_t j = (uint32_t)__builtin_popcount(side.mask & ((1u << cl.attribute) - 1u));
+      if (clause_unreachable(cl, side.entries[at * side.cols + j])) (*read)[k] = 0;
+    }
+  }
+  return SWZ_OK;
+}
+
 struct CopyStream {
   hipStream_t s = nullptr;
   ~CopyStream() {
@@ -215,7 +276,35 @@ static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_p
     if (((mask >> a) & 1u) && (!d_out || !d_out->column[a])) return refuse("a bit of the mask without an output column");
   SWZ_HIP(c, hipSetDevice(c->device));
 
-  // ---- the chunks: whole nodes of the kept table, as the converter cuts its source
+  // ---- the nodes that are read: all of the kept table, or those the filter can reach by the directory's summaries; `index`
+  // holds their places in the kept table, which d_node_out keeps indexing
+  std::vector<uint32_t> index;
+  {
+    std::vector<uint8_t> read;
+    SWZ_TRY(filter_reads(c, who, dir, kept, filter, &read));
+    const uint64_t all = kept.count.size();
+    for (uint64_t k = 0; k < all; ++k)
+      if (read[k]) index.push_back((uint32_t)k);
+    if (index.size() < all) {
+      DatasetScan reads;
+      reads.info = kept.info;
+      reads.info.points = 0;
+      const bool pnts = kept.info.format == SWZ_OUT_3DTILES;
+      for (uint32_t k : index) {
+        reads.level.push_back(kept.level[k]);
+        reads.key.push_back(kept.key[k]);
+        reads.count.push_back(kept.count[k]);
+        reads.path.push_back(kept.path[k]);
+        reads.layout.push_back(kept.layout[k]);
+        reads.data_at.push_back(kept.data_at[k]);
+        if (pnts) reads.file_bytes.push_back(kept.file_bytes[k]);
+        reads.info.points += kept.count[k];
+      }
+      reads.info.num_nodes = reads.count.size();
+      kept = std::move(reads);
+    }
+  }
+  // ---- the chunks: whole nodes of that table, as the converter cuts its source
   const uint64_t nn = kept.count.size();
   std::vector<uint64_t> first;
   {
@@ -238,7 +327,7 @@ static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_p
     uint32_t *d_rows = nullptr, *d_first = nullptr;
     if (d_node_out && !count_only) {
       SWZ_TRY(c->get("out_q_rows", (size_t)source.rows_max, &d_rows));
-      SWZ_TRY(c->get("out_q_first", (size_t)nodes_max + 1, &d_first));
+      SWZ_TRY(c->get("out_q_first", 2 * (size_t)nodes_max + 1, &d_first));  // the first rows, then the nodes' indices
     }
     std::vector<uint32_t> node_first;
     RegionDev region_dev;  // a polygon's vertices go up once, not per chunk
@@ -269,11 +358,15 @@ static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_p
       }
       if (d_rows && cnt) {
         const uint64_t k0 = first[j], k1 = first[j + 1];
-        node_first.assign(k1 - k0 + 1, 0);
-        for (uint64_t k = k0; k < k1; ++k) node_first[k - k0 + 1] = node_first[k - k0] + (uint32_t)kept.count[k];
+        const uint64_t nk = k1 - k0;
+        node_first.assign(2 * nk + 1, 0);
+        for (uint64_t k = k0; k < k1; ++k) {
+          node_first[k - k0 + 1] = node_first[k - k0] + (uint32_t)kept.count[k];
+          node_first[nk + 1 + (k - k0)] = index[k];
+        }
         SWZ_HIP(c, hipMemcpyAsync(d_first, node_first.data(), node_first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(query_row_nodes_kernel, dim3(div_up(cnt, 256)), dim3(256), 0, c->stream, d_rows, (uint32_t)cnt, d_first,
-                           (uint32_t)(k1 - k0), (uint32_t)k0, d_node_out + total);
+                           (uint32_t)nk, d_first + nk + 1, d_node_out + total);
         SWZ_LAUNCH_CHECK(c);
         SWZ_HIP(c, hipStreamSynchronize(c->stream));  // (node_first is the next chunk's)
       }
@@ -298,6 +391,68 @@ static int query(swz_ctx* c, const char* who, const char* dir, const swz_query_p
   return SWZ_OK;
 }
 
+// swz_dataset_summarize: every node of the source through the query's stream, the summaries kernel on every chunk, the sidecar
+static int summarize(swz_ctx* c, const char* who, const char* dir, uint32_t source_flags, uint64_t chunk_points_in, swz_summarize_stats* stats) {
+  auto refuse = [&](const std::string& what) { return c->fail(SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
+  const auto t_wall = std::chrono::steady_clock::now();
+  if (stats) *stats = swz_summarize_stats{};
+  if (!dir) return refuse("NULL argument");
+  if (source_flags & ~(uint32_t)SWZ_CONVERT_LOSSY_SOURCE) return refuse("an unknown bit in source_flags");
+  DatasetScan scan;
+  SWZ_TRY(source_open(c, who, dir, -1, source_flags, &scan, nullptr));
+  uint32_t mask = scan.info.attribute_mask & (uint32_t)SWZ_SUMMARY_SCALARS;
+  if (scan.info.format == SWZ_OUT_3DTILES) mask &= 1u << SWZ_ATTR_INTENSITY;  // all a .pnts file carries beside RGB
+  const uint32_t cols = (uint32_t)__builtin_popcount(mask);
+  const uint64_t nn = scan.count.size();
+  std::vector<swz_attr_summary> entries((size_t)(nn * cols), summary_empty());
+  uint64_t chunks = 0;
+  double summary_ms = 0;
+  OutputWorkspace ow{c};
+  CopyStream copy;
+  SourceStream source;
+  std::vector<uint64_t> first;
+  if (cols) {
+    const uint64_t chunk_points = output_chunk_points(c, chunk_points_in);
+    uint64_t num_chunks = 0;
+    (void)swz_output_chunks(nn, scan.count.data(), chunk_points, 0, nullptr, &num_chunks);
+    first.assign(num_chunks + 1, 0);
+    (void)swz_output_chunks(nn, scan.count.data(), chunk_points, num_chunks, first.data(), &num_chunks);
+    SWZ_HIP(c, hipSetDevice(c->device));
+    source.plan(c, who, &scan, &first, mask);
+    if (source.rows_max) {
+      SWZ_HIP(c, hipStreamCreateWithFlags(&copy.s, hipStreamNonBlocking));
+      SWZ_TRY(source.start(copy.s));
+      std::vector<uint64_t> offset;
+      for (uint64_t j = 0; j < source.num_chunks; ++j) {
+        SWZ_TRY(source.next(j));
+        ++chunks;
+        const auto t_summary = std::chrono::steady_clock::now();
+        const uint64_t k0 = first[j], k1 = first[j + 1];
+        offset.assign(k1 - k0, 0);
+        for (uint64_t k = k0 + 1; k < k1; ++k) offset[k - k0] = offset[k - k0 - 1] + scan.count[k - 1];
+        SWZ_TRY(node_summaries(c, who, source.rows(j), &source.cols, mask, k1 - k0, offset.data(), scan.count.data() + k0,
+                               entries.data() + k0 * cols));
+        summary_ms += ms_since(t_summary);
+      }
+    }
+  }
+  std::string why;
+  const int st = sidecar_write(dir, scan.info.format, mask, nn, scan.level.data(), scan.key.data(), scan.count.data(), entries.data(), &why);
+  if (st != SWZ_OK) return c->fail(st, std::string(who) + ": " + why);
+  if (stats) {
+    stats->nodes = nn;
+    stats->points = scan.info.points;
+    stats->bytes_read = source.bytes_read;
+    stats->chunks = chunks;
+    stats->read_ms = source.read_ms;
+    stats->unpack_ms = source.unpack_ms;
+    stats->summary_ms = summary_ms;
+    stats->copy_ms = source.copy_ms;
+    stats->wall_ms = ms_since(t_wall);
+  }
+  return SWZ_OK;
+}
+
 }  // namespace swz
 
 using namespace swz;
@@ -305,9 +460,10 @@ using namespace swz;
 extern "C" {
 
 // swz_dataset_query_nodes and swz_dataset_query_region_nodes, and their _why forms on a context that only holds the text
+// ... and swz_dataset_query_filtered_nodes, which also says which nodes of the table the filter lets the query read
 static int query_nodes(swz_ctx* c, const std::string& who, const char* dir, const swz_query_params* params, const swz_region* region,
                        uint64_t max_nodes, int8_t* level_out, uint64_t* key_out, uint64_t* count_out, uint64_t* num_out,
-                       uint64_t* points_bound_out) {
+                       uint64_t* points_bound_out, const swz_filter* filter = nullptr, uint8_t* read_out = nullptr) {
   swz_ctx text;  // (a NULL context: only the status comes back; no device is touched either way)
   if (!c) c = &text;
   if (!num_out) return c->fail(SWZ_ERR_BAD_ARG, who + ": NULL argument");
@@ -315,16 +471,22 @@ static int query_nodes(swz_ctx* c, const std::string& who, const char* dir, cons
   uint64_t scanned = 0;
   RegionHost region_host;
   uint32_t fattrs = 0;
-  SWZ_TRY(query_plan(c, who.c_str(), dir, params, region, nullptr, &kept, &scanned, &region_host, &fattrs));
+  SWZ_TRY(query_plan(c, who.c_str(), dir, params, region, filter, &kept, &scanned, &region_host, &fattrs));
   const uint64_t nn = kept.count.size();
+  std::vector<uint8_t> read;
+  SWZ_TRY(filter_reads(c, who.c_str(), dir, kept, filter, &read));
+  uint64_t bound = 0;
+  for (uint64_t k = 0; k < nn; ++k)
+    if (read[k]) bound += kept.count[k];
   *num_out = nn;
-  if (points_bound_out) *points_bound_out = kept.info.points;
-  if (!level_out && !key_out && !count_out) return SWZ_OK;
+  if (points_bound_out) *points_bound_out = bound;
+  if (!level_out && !key_out && !count_out && !read_out) return SWZ_OK;
   if (nn > max_nodes) return c->fail(SWZ_ERR_BAD_ARG, who + ": max_nodes too small");
   for (uint64_t k = 0; k < nn; ++k) {
     if (level_out) level_out[k] = kept.level[k];
     if (key_out) key_out[k] = kept.key[k];
     if (count_out) count_out[k] = kept.count[k];
+    if (read_out) read_out[k] = read[k];
   }
   return SWZ_OK;
 }
@@ -355,6 +517,28 @@ int swz_dataset_query_region_nodes_why(const char* dir, const swz_query_params* 
   const int st = query_nodes(&text, "swz_dataset_query_region_nodes", dir, params, region, max_nodes, level_out, key_out, count_out, num_out,
                              points_bound_out);
   return why_text(st, text, why_out, why_bytes);
+}
+
+int swz_dataset_query_filtered_nodes(swz_ctx* c, const char* dir, const swz_query_params* params, const swz_region* region,
+                                     const swz_filter* filter, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out,
+                                     uint64_t* count_out, uint8_t* read_out, uint64_t* num_out, uint64_t* points_bound_out) {
+  return query_nodes(c, "swz_dataset_query_filtered_nodes", dir, params, region, max_nodes, level_out, key_out, count_out, num_out,
+                     points_bound_out, filter, read_out);
+}
+
+int swz_dataset_query_filtered_nodes_why(const char* dir, const swz_query_params* params, const swz_region* region,
+                                         const swz_filter* filter, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out,
+                                         uint64_t* count_out, uint8_t* read_out, uint64_t* num_out, uint64_t* points_bound_out,
+                                         char* why_out, uint64_t why_bytes) {
+  swz_ctx text;
+  const int st = query_nodes(&text, "swz_dataset_query_filtered_nodes", dir, params, region, max_nodes, level_out, key_out, count_out,
+                             num_out, points_bound_out, filter, read_out);
+  return why_text(st, text, why_out, why_bytes);
+}
+
+int swz_dataset_summarize(swz_ctx* c, const char* dir, uint32_t source_flags, uint64_t chunk_points, swz_summarize_stats* stats) {
+  if (!c) return SWZ_ERR_BAD_ARG;
+  return summarize(c, "swz_dataset_summarize", dir, source_flags, chunk_points, stats);
 }
 
 int swz_dataset_query(swz_ctx* c, const char* dir, const swz_query_params* params, uint64_t capacity, double* d_xyz_out,

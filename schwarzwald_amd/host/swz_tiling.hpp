@@ -235,7 +235,8 @@ private:
 
 // query_dataset_region for the rows that also pass a filter over the attribute columns (swz_dataset_query_filtered); filter ==
 // nullptr is query_dataset_region.  The columns of params.attribute_mask come back; the columns the filter names are read for
-// it whether the mask holds them or not.  No node drops out for a filter: nodes index swz_dataset_query_region_nodes' table.
+// it whether the mask holds them or not.  nodes index swz_dataset_query_region_nodes' table; after summarize_dataset (below) the
+// node files the filter cannot reach are not read, which changes the stats and nothing else.
 // A filter the library refuses throws with swz_filter_check's text before a file is read.
 inline QueryResult query_dataset_filtered(Context& ctx, const std::string& dir, const swz_query_params& params, const swz_region* region,
                                           const swz_filter* filter, bool lossy_source = false, bool want_nodes = false) {
@@ -288,6 +289,39 @@ inline QueryResult query_dataset_filtered(Context& ctx, const std::string& dir, 
     out.nodes.resize(out.count);
     if (out.count) ctx.check(swz_copy_to_host(ctx.get(), out.nodes.data(), d_nodes, 4 * out.count));
   }
+  return out;
+}
+// Per-node attribute summaries (swz_dataset_summarize): every node file of dir is streamed once, the scalar columns are
+// summarised per node on the device and dir/node-summaries.swz is written.  Afterwards query_dataset_filtered skips the node
+// files the filter cannot reach -- the same rows, fewer nodes read.  Run it again after the data set changed: a summary that
+// does not describe the files is refused as stale.  lossy_source as in convert_dataset.
+inline swz_summarize_stats summarize_dataset(Context& ctx, const std::string& dir, bool lossy_source = false, uint64_t chunk_points = 0) {
+  swz_summarize_stats stats{};
+  ctx.check(swz_dataset_summarize(ctx.get(), dir.c_str(), lossy_source ? SWZ_CONVERT_LOSSY_SOURCE : 0u, chunk_points, &stats));
+  return stats;
+}
+// The nodes a filtered query reads (swz_dataset_query_filtered_nodes): the table of the region query, unchanged, and per node
+// whether the summaries of dir let the filter reach it (all of them without node-summaries.swz or without a filter).
+struct FilteredNodes {
+  std::vector<int8_t> level;
+  std::vector<uint64_t> key, count;
+  std::vector<uint8_t> read;
+  uint64_t points_bound = 0;  // the sum of the counts of the nodes that are read
+};
+inline FilteredNodes query_dataset_filtered_nodes(Context& ctx, const std::string& dir, const swz_query_params& params, const swz_region* region,
+                                                  const swz_filter* filter, bool lossy_source = false) {
+  swz_query_params p = params;
+  if (lossy_source) p.source_flags |= SWZ_CONVERT_LOSSY_SOURCE;
+  FilteredNodes out;
+  uint64_t num = 0;
+  ctx.check(swz_dataset_query_filtered_nodes(ctx.get(), dir.c_str(), &p, region, filter, 0, nullptr, nullptr, nullptr, nullptr, &num, &out.points_bound));
+  out.level.resize(num);
+  out.key.resize(num);
+  out.count.resize(num);
+  out.read.resize(num);
+  if (num)
+    ctx.check(swz_dataset_query_filtered_nodes(ctx.get(), dir.c_str(), &p, region, filter, num, out.level.data(), out.key.data(), out.count.data(),
+                                               out.read.data(), &num, &out.points_bound));
   return out;
 }
 // query_dataset for the box cut by a region (swz_dataset_query_region): planes (a frustum: frustum_planes) or a polygon in

@@ -19,7 +19,13 @@ filter (dataset_query_filtered; a list of values is a set on a one-byte column, 
 `filtered`, the stats of that call; `query`, the same region without the filter; and `filter_recipe`, what a caller did
 before: the unfiltered query with the filtered columns added, copied to the host, and a numpy mask.  The counts of the first
 and the last must agree.
-usage: query_probe.py [points] [--batches K] [--dir DIR] [--host-nodes N] [--json FILE] [--polygon M | --planes] [--filter SPEC]..."""
+--summaries (with one or more --filter): the data set also carries point_source_id, 16 flight strips along x
+(point_source_id=3..3 is a filter few nodes can pass, intensity=0..65535 one that every node passes).  Every --filter is taken
+as a filter of its own over the whole box: the filtered query (`without`), then dataset_summarize (`summarize`: its stats),
+then the same query again (`with`: fewer nodes_read and bytes_read where the summaries let nodes drop), and `count_only`, the
+unfiltered count-only query, which streams what dataset_summarize streams.  The counts of the two filtered runs must agree.
+usage: query_probe.py [points] [--batches K] [--dir DIR] [--host-nodes N] [--json FILE] [--polygon M | --planes] [--filter SPEC]...
+       [--summaries]"""
 import json
 import os
 import shutil
@@ -130,7 +136,7 @@ def filter_recipe(swz, np, ctx, src, box, region, names, mask):
     return time.perf_counter() - t0, got["count"], len(kept["xyz"])
 
 
-def step(n, batches, base, host_nodes, spec="", filters=()):
+def step(n, batches, base, host_nodes, spec="", filters=(), summaries=False):
     import numpy as np
     import schwarzwald_amd as swz
     ctx = swz.Context(0)
@@ -144,16 +150,46 @@ def step(n, batches, base, host_nodes, spec="", filters=()):
         cols = {"rgb": rng.integers(0, 256, (m, 3), dtype=np.uint8), "intensity": rng.integers(0, 65536, m, dtype=np.uint16)}
         if filters:
             cols.update(classification=rng.integers(0, 16, m, dtype=np.uint8), return_number=rng.integers(1, 5, m, dtype=np.uint8))
-        t.add_batch(rng.random((m, 3)), cols)
+        xyz = rng.random((m, 3))
+        if summaries:
+            cols.update(point_source_id=(1 + np.floor(xyz[:, 0] * 16)).astype(np.uint16))
+        t.add_batch(xyz, cols)
     t.finalize()
     info, nodes = t.info(), t.node_table()
     stored = int(info["num_stored"])
     work = tempfile.mkdtemp(prefix="swz_query_probe_", dir=base)
     src = os.path.join(work, "src_bin")
-    out = dict(points=n, batches=batches, stored=stored, nodes=int(info["num_nodes"]), write_bin=t.write_output(src, "BIN", attrs=NAMES + (FILTER_COLUMNS if filters else ())))
+    out = dict(points=n, batches=batches, stored=stored, nodes=int(info["num_nodes"]), write_bin=t.write_output(src, "BIN", attrs=NAMES + (FILTER_COLUMNS if filters else ()) + (("point_source_id",) if summaries else ())))
     t.write_properties(src)
     t.close()
     print("QUERY_PROBE " + json.dumps(dict(source=out)), flush=True)
+    if summaries:
+        import ctypes
+        from schwarzwald_amd import api
+        box = BOXES["whole"]
+        region, _, _ = make_region(swz, np, spec, box)
+        rows = [dict(filter=f, region=spec or "box") for f in filters]
+        for when in ("without", "with"):
+            for row in rows:
+                flt, _, _ = make_filter(swz, np, [row["filter"]])
+                for rep in ("warm", "timed"):
+                    got = swz.dataset_query_filtered(ctx, src, box[0], box[1], region, flt, attrs=NAMES)
+                    row[when] = dict(got["stats"], count=got["count"])
+                    del got
+            if when == "without":
+                for rep in ("warm", "timed"):   # (the unfiltered query never looks at the sidecar the first round leaves)
+                    p = api._query_params(box[0], box[1], None, (), False, 0)
+                    count, stats = ctypes.c_uint64(), api._QueryStats()
+                    ctx._check(ctx._lib.swz_dataset_query(ctx._ctx, os.fsencode(src), ctypes.byref(p), 0, None, None, None, ctypes.byref(count),
+                                                          ctypes.byref(stats)))
+                    count_only = dict({k: getattr(stats, k) for k, _ in api._QueryStats._fields_}, count=int(count.value))
+                    summarize = swz.dataset_summarize(ctx, src)
+        for row in rows:
+            assert row["with"]["count"] == row["without"]["count"], row
+            print("QUERY_PROBE " + json.dumps(dict(row, summarize=summarize, count_only=count_only)), flush=True)
+        shutil.rmtree(work, ignore_errors=True)
+        ctx.close()
+        return
     for name, box in BOXES.items():
         row = dict(box=name, region=spec or "box")
         region, bound, mask = make_region(swz, np, spec, box)
@@ -196,7 +232,7 @@ def main():
     args = sys.argv[1:]
     if args and args[0] == "--step":
         return step(int(args[1]), int(args[2]), args[3] or None, int(args[4]), args[5] if len(args) > 5 else "",
-                    tuple(v for v in (args[6] if len(args) > 6 else "").split(";") if v))
+                    tuple(v for v in (args[6] if len(args) > 6 else "").split(";") if v), len(args) > 7 and args[7] == "summaries")
 
     def option(name, default):
         return args[args.index(name) + 1] if name in args else default
@@ -206,7 +242,8 @@ def main():
     # one child under its own time limit; check=True: a failure ends the script here
     r = subprocess.run(["timeout", "-k", "10", limit, sys.executable, os.path.abspath(__file__), "--step", str(n), option("--batches", "10"),
                         option("--dir", ""), option("--host-nodes", "0"), spec,
-                        ";".join(args[i + 1] for i, a in enumerate(args) if a == "--filter")], check=True, stdout=subprocess.PIPE, text=True)
+                        ";".join(args[i + 1] for i, a in enumerate(args) if a == "--filter"), "summaries" if "--summaries" in args else ""],
+                       check=True, stdout=subprocess.PIPE, text=True)
     results = [json.loads(l[len("QUERY_PROBE "):]) for l in r.stdout.splitlines() if l.startswith("QUERY_PROBE ")]
     for row in results:
         print(json.dumps(row), flush=True)
