@@ -882,9 +882,10 @@ def _ref(struct):
     return None if struct is None else C.byref(struct)
 
 
-def _query_nodes(entry, directory, params, *region_ref):
+def _query_nodes(entry, directory, params, *region_ref, with_read=False):
     """the node table of a query as a dict.  entry: swz_dataset_query_nodes_why, or swz_dataset_query_region_nodes_why with
-    its region argument in region_ref; once for the number of nodes, once for the table"""
+    its region argument in region_ref, or (with_read) swz_dataset_query_filtered_nodes_why with its region and filter, whose
+    table has one more array: read, a bool per node; once for the number of nodes, once for the table"""
     head = (os.fsencode(directory), C.byref(params)) + region_ref
     num, bound = C.c_uint64(), C.c_uint64()
     why = C.create_string_buffer(4096)
@@ -894,12 +895,17 @@ def _query_nodes(entry, directory, params, *region_ref):
         if st != 0:
             raise SwzError(st, why.value.decode(errors="replace"))
 
-    call(0, None, None, None)
+    call(0, *[None] * (4 if with_read else 3))
     cap = max(int(num.value), 1)
     nl, nk, nc = np.empty(cap, dtype=np.int8), np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint64)
-    call(cap, nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p))
+    rd = np.empty(cap, dtype=np.uint8)
+    call(cap, nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p), *([rd.ctypes.data] if with_read else []))
     m = int(num.value)
-    return dict(level=nl[:m].copy(), key=nk[:m].copy(), count=nc[:m].copy(), points_bound=int(bound.value))
+    out = dict(level=nl[:m].copy(), key=nk[:m].copy(), count=nc[:m].copy())
+    if with_read:
+        out["read"] = rd[:m].astype(bool)
+    out["points_bound"] = int(bound.value)
+    return out
 
 
 def dataset_query_nodes(directory, box_min, box_max, max_depth=None, lossy_source=False, source_flags=None, reserved=0):
@@ -1222,23 +1228,7 @@ def dataset_query_filtered_nodes(directory, box_min, box_max, region=None, filte
     p = _query_params(box_min, box_max, max_depth, None, lossy_source, 0, source_flags, reserved)
     rg = None if region is None else region._struct()
     fl = None if filter is None else filter._struct()
-    head = (os.fsencode(directory), C.byref(p), _ref(rg), _ref(fl))
-    num, bound = C.c_uint64(), C.c_uint64()
-    why = C.create_string_buffer(4096)
-    entry = load_library().swz_dataset_query_filtered_nodes_why
-
-    def call(cap, *arrays):
-        st = entry(*head, cap, *arrays, C.byref(num), C.byref(bound), why, len(why))
-        if st != 0:
-            raise SwzError(st, why.value.decode(errors="replace"))
-
-    call(0, None, None, None, None)
-    cap = max(int(num.value), 1)
-    nl, nk, nc = np.empty(cap, dtype=np.int8), np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint64)
-    rd = np.empty(cap, dtype=np.uint8)
-    call(cap, nl.ctypes.data_as(_i8p), nk.ctypes.data_as(_u64p), nc.ctypes.data_as(_u64p), rd.ctypes.data)
-    m = int(num.value)
-    return dict(level=nl[:m].copy(), key=nk[:m].copy(), count=nc[:m].copy(), read=rd[:m].astype(bool), points_bound=int(bound.value))
+    return _query_nodes(load_library().swz_dataset_query_filtered_nodes_why, directory, p, _ref(rg), _ref(fl), with_read=True)
 
 
 LAS_SCAN_SKIP_UNREADABLE = 1

@@ -1,12 +1,16 @@
-// swz_convert.h -- what the parts of swz_convert_dataset share: the scanned source (swz_dataset.hip), the launch of the BIN
-// unpack kernel on a stream (swz_binunpack.hip), the stream of a source's chunks onto the device (swz_source.hip), which
-// swz_dataset_query (swz_query.hip) runs as well, and the call itself (swz_convert.hip).
+// swz_convert.h -- what the readers of a written data set share: the scanned source (swz_dataset.hip), the launch of the BIN
+// unpack kernel on a stream (swz_binunpack.hip) and the stream of a source's chunks onto the device (swz_source.hip).
+// swz_dataset_query* (swz_query.hip) and swz_dataset_summarize (swz_summary.hip) are chunk bodies of SourceLoop::each_chunk, which
+// owns the loop; swz_convert_dataset (swz_convert.hip) drives SourceStream's plan / start / next itself, from the feed of
+// output_stream, because there the output side owns the loop.
 #pragma once
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "swz_internal.h"
 #include "swz_tinput.h"
+#include "swz_toutput.h"
 
 namespace swz {
 
@@ -19,7 +23,10 @@ struct DatasetScan {
   std::vector<std::string> path;
   std::vector<swz_las_layout> layout;  // LAS sources
   std::vector<uint64_t> data_at;       // LAS sources: the offset to the point data
-  std::vector<uint64_t> file_bytes;    // 3DTILES sources, filled by swz_convert_dataset: the size of the file
+  std::vector<uint64_t> file_bytes;    // 3DTILES sources, filled by source_open: the size of the file
+  // the scan of the nodes index[0], index[1], ... alone: every per-node array that is filled, info.points and
+  // info.num_nodes counted anew, the rest of info as it is.  A new per-node array belongs in here, and nowhere else.
+  DatasetScan subset(const std::vector<uint32_t>& index) const;
 };
 // `who` starts the messages; ctx may be NULL
 int dataset_scan(swz_ctx* c, const char* who, const char* dir, int32_t max_depth, DatasetScan* out);
@@ -55,7 +62,7 @@ int pnts_read_head(const char* path, PntsImage* out, std::string* why);
 int pnts_unpack_launch(swz_ctx* c, hipStream_t stream, const uint8_t* d_raw, uint64_t raw_bytes, const swz_pnts_segment* d_table,
                        uint32_t num_segs, uint32_t rows, double* d_xyz_out, const swz_attribute_columns* d_out);
 
-// ---- the source half of swz_convert_dataset (swz_source.hip), shared with swz_dataset_query
+// ---- the source half of swz_convert_dataset (swz_source.hip), shared with swz_dataset_query* and swz_dataset_summarize
 // dataset_scan, then what is refused of a 3DTILES source: one without SWZ_CONVERT_LOSSY_SOURCE in source_flags, files whose
 // RTC_CENTER differ.  Fills scan->file_bytes of such a source; rtc_out (may be NULL): the files' common RTC_CENTER, else 0.
 int source_open(swz_ctx* c, const char* who, const char* dir, int32_t max_depth, uint32_t source_flags, DatasetScan* scan,
@@ -104,6 +111,54 @@ private:
   SourceChunk ch_[2];
   std::vector<const char*> paths_;
   long threads_ = 1;
+};
+
+// the chunks of a node table, whole nodes of chunk_points points at the most (0: the library's default, output_chunk_points;
+// a node larger than that is a chunk of its own): first->at(j) .. first->at(j + 1) are chunk j's nodes, counted from 0
+void source_cuts(swz_ctx* c, const uint64_t* counts, uint64_t n, uint64_t chunk_points, std::vector<uint64_t>* first);
+
+// chunk j of SourceLoop::each_chunk as its body sees it: the nodes [k0, k1) of the scan, their rows back to back in the
+// chunk-local arrays
+struct SourceChunkView {
+  uint64_t j, k0, k1, rows;
+  const double* xyz;
+  const swz_attribute_columns* cols;
+};
+using SourceChunkBody = std::function<int(const SourceChunkView&)>;
+struct SourceLoopStats {
+  uint64_t chunks = 0, bytes_read = 0;  // chunks: those next() delivered
+  double read_ms = 0, unpack_ms = 0, copy_ms = 0;
+  double body_ms = 0;  // host wall time of the bodies that returned SWZ_OK
+};
+// The chunk loop of a reader.  The constructor cuts the scan's nodes into chunks and sizes the stream for the columns of
+// `mask` (host only, nothing is allocated); rows_max / nodes_max are the largest chunk's, for what a caller sets up once
+// before the loop (rows_max 0: no points, no chunk comes).  each_chunk streams them: body(chunk) runs while the readers work
+// on the next chunk.  A next() or a body that fails ends the loop with its status (c's error; *stats is then not written).
+// The copy stream and the arrays exist only for a scan with points.  An object in the caller's frame and not a function:
+// what it holds is given up when the CALL ends, however it ends, behind the caller's wall_ms -- freeing the page-locked
+// images and the device arrays was never part of that figure, and a caller needs the sizes before the first chunk.
+// The members' order is the order they end in, backwards: the stream's readers are joined first (they write into its
+// page-locked images, and its unpack kernels run on the copy stream), then the copy stream is destroyed, and only then does
+// the call's part of the workspace ("out_*": the chunk-local arrays those kernels write, and a caller's own) go back.
+class SourceLoop {
+public:
+  SourceLoop(swz_ctx* c, const char* who, const DatasetScan& scan, uint32_t mask, uint64_t chunk_points);
+  uint64_t rows_max() const { return source_.rows_max; }
+  uint64_t nodes_max() const { return nodes_max_; }
+  int each_chunk(const SourceChunkBody& body, SourceLoopStats* stats);
+
+private:
+  struct CopyStream {
+    hipStream_t s = nullptr;
+    ~CopyStream() {
+      if (s) (void)hipStreamDestroy(s);
+    }
+  };
+  OutputWorkspace ow_;
+  CopyStream copy_;
+  std::vector<uint64_t> first_;
+  uint64_t nodes_max_ = 0;
+  SourceStream source_;
 };
 
 }  // namespace swz

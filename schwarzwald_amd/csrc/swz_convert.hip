@@ -1,7 +1,7 @@
 // swz_convert.hip -- a written data set converted to another format in one call (swz_convert_dataset): the reference's
 // --converter mode (ConverterProcess::run, core/process/ConverterProcess.cpp).  The source is scanned (swz_dataset.hip), the
 // target is planned with the parts of swz_tiler_write_output (swz_toutput.h), and the node table is streamed chunk by chunk:
-// SourceStream (swz_source.hip, shared with swz_dataset_query) reads, copies and unpacks a chunk into chunk-local positions and
+// SourceStream (swz_source.hip, which the query shares) reads, copies and unpacks a chunk into chunk-local positions and
 // columns (a .pnts source only with SWZ_CONVERT_LOSSY_SOURCE), and output_stream packs, copies back and writes them in the
 // target format.  The readers of chunk k + 1 run while chunk k is packed and written.
 //
@@ -30,10 +30,6 @@ static_assert(sizeof(swz_convert_params) == 128 && offsetof(swz_convert_params, 
               "the structs of the converter as include/swz_gpu.h and the bindings lay them out");
 
 namespace swz {
-
-static double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 
 __global__ __launch_bounds__(256) void iota_kernel(uint32_t* out, uint32_t n) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;

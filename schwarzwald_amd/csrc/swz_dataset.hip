@@ -334,6 +334,27 @@ int dataset_scan(swz_ctx* c, const char* who_c, const char* dir_c, int32_t max_d
   return SWZ_OK;
 }
 
+DatasetScan DatasetScan::subset(const std::vector<uint32_t>& index) const {
+  DatasetScan out;
+  out.info = info;
+  out.info.points = 0;
+  auto take = [&index](const auto& from, auto* to) {
+    if (from.empty()) return;
+    to->reserve(index.size());
+    for (uint32_t k : index) to->push_back(from[k]);
+  };
+  take(level, &out.level);
+  take(key, &out.key);
+  take(count, &out.count);
+  take(path, &out.path);
+  take(layout, &out.layout);
+  take(data_at, &out.data_at);
+  take(file_bytes, &out.file_bytes);
+  for (uint64_t n : out.count) out.info.points += n;
+  out.info.num_nodes = out.count.size();
+  return out;
+}
+
 }  // namespace swz
 
 using namespace swz;
@@ -409,12 +430,7 @@ int swz_dataset_scan_why(const char* dir, int32_t max_depth, swz_dataset_info* i
                          uint64_t* node_key_out, uint64_t* node_count_out, uint64_t* num_nodes_out, char* why_out, uint64_t why_bytes) {
   swz_ctx text;  // (only its error text is used: no device is touched)
   const int st = swz_dataset_scan(&text, dir, max_depth, info_out, max_nodes, node_level_out, node_key_out, node_count_out, num_nodes_out);
-  if (why_out && why_bytes) {
-    const size_t len = std::min<size_t>(st == SWZ_OK ? 0 : text.err.size(), (size_t)why_bytes - 1);
-    memcpy(why_out, text.err.data(), len);
-    why_out[len] = 0;
-  }
-  return st;
+  return why_text(st, text, why_out, why_bytes);
 }
 
 }  // extern "C"

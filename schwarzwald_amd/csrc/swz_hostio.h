@@ -1,6 +1,7 @@
 // swz_hostio.h -- what the host side of the node-file writers shares (swz_payload.hip, swz_binpack.hip, swz_pnts.hip,
-// swz_las.hip, swz_toutput.hip): errors with or without a context, whole files in and out, numbers in JSON text, the pool
-// of writer threads and the attribute arrays of a BIN node file.
+// swz_las.hip, swz_toutput.hip) and the readers of a written data set: errors with or without a context (why_text: into a
+// caller's text buffer), host wall time (ms_since), whole files in and out, numbers in JSON text, the pool of writer threads
+// and the attribute arrays of a BIN node file.
 #pragma once
 
 #include <fcntl.h>
@@ -13,6 +14,7 @@
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <algorithm>
 #include <mutex>
 #include <string>
@@ -37,6 +39,22 @@ static const int FILE_ORDER[SWZ_ATTR_COUNT] = {SWZ_ATTR_RGB, SWZ_ATTR_NORMAL, SW
                                                SWZ_ATTR_SCAN_DIRECTION_FLAG, SWZ_ATTR_USER_DATA};
 
 inline bool finite3(const double v[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+
+// host wall time since t0, for the *_ms fields of the calls' stats
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// the end of a host-only entry that reports through a text buffer: the refusal that `text` holds (nothing on SWZ_OK) goes
+// into why_out, cut to why_bytes with its terminator; returns st
+inline int why_text(int st, const swz_ctx& text, char* why_out, uint64_t why_bytes) {
+  if (why_out && why_bytes) {
+    const size_t len = std::min<size_t>(st == SWZ_OK ? 0 : text.err.size(), (size_t)why_bytes - 1);
+    memcpy(why_out, text.err.data(), len);
+    why_out[len] = 0;
+  }
+  return st;
+}
 
 inline int read_whole_file(swz_ctx* c, const char* path, std::vector<unsigned char>* out) {
   FILE* f = fopen(path, "rb");

@@ -10,7 +10,7 @@
 
 namespace swz {
 
-// a swz_region checked and copied (host only): what the node rule of swz_query.hip reads
+// a swz_region checked and copied (host only): what the node rule of swz_qplan.hip reads
 struct RegionHost {
   int kind = SWZ_REGION_BOX;
   uint32_t count = 0;
@@ -56,16 +56,5 @@ struct Selection {
 int region_select(swz_ctx* c, const char* who, const double* d_xyz, uint64_t n, const swz_attribute_columns* d_in, uint32_t mask,
                   const Selection& sel, uint64_t capacity, double* d_xyz_out, const swz_attribute_columns* d_out, uint32_t* d_row_out,
                   uint64_t* count_out);
-
-// the end of a host-only entry that reports through a text buffer: the refusal that `text` holds (nothing on SWZ_OK) goes
-// into why_out, cut to why_bytes with its terminator; returns st
-inline int why_text(int st, const swz_ctx& text, char* why_out, uint64_t why_bytes) {
-  if (why_out && why_bytes) {
-    const size_t len = std::min<size_t>(st == SWZ_OK ? 0 : text.err.size(), (size_t)why_bytes - 1);
-    memcpy(why_out, text.err.data(), len);
-    why_out[len] = 0;
-  }
-  return st;
-}
 
 }  // namespace swz

@@ -1,9 +1,11 @@
-// swz_source.hip -- the source half of swz_convert_dataset, which swz_dataset_query shares (swz_convert.h): a scanned data
-// set opened with the refusals of a 3DTILES source (source_open) and streamed chunk by chunk onto the device (SourceStream).
-// Reader threads fill one of two page-locked images with the chunk's files (BINZ inflated, LAS as record ranges, .pnts
-// whole), the copy stream moves it to the device, and the unpack kernel (swz_binunpack.hip; LAS sources: the segment kernel
-// of swz_tinput.hip; .pnts sources: swz_pntsunpack.hip) makes chunk-local positions and columns of it.  The readers of chunk
-// k + 1 run while the caller works on chunk k.
+// swz_source.hip -- the source half of every reader of a written data set (swz_convert.h): a scanned data set opened with
+// the refusals of a 3DTILES source (source_open) and streamed chunk by chunk onto the device (SourceStream).  Reader threads
+// fill one of two page-locked images with the chunk's files (BINZ inflated, LAS as record ranges, .pnts whole), the copy
+// stream moves it to the device, and the unpack kernel (swz_binunpack.hip; LAS sources: the segment kernel of
+// swz_tinput.hip; .pnts sources: swz_pntsunpack.hip) makes chunk-local positions and columns of it.  The readers of chunk
+// k + 1 run while the caller works on chunk k.  SourceLoop::each_chunk is the loop around it -- cuts, workspace, copy
+// stream, plan, start, next, stats -- for the callers that only have something to do per chunk: swz_dataset_query* and
+// swz_dataset_summarize.  swz_convert_dataset calls next() from output_stream's feed instead.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -14,6 +16,7 @@
 #include "swz_convert.h"
 #include "swz_hostio.h"
 #include "swz_tinput.h"
+#include "swz_toutput.h"
 
 namespace swz {
 
@@ -276,6 +279,43 @@ int SourceStream::next(uint64_t j) {
   if (hipEventElapsedTime(&t, ib_.begin[b], ib_.copied[b]) == hipSuccess) copy_ms += t;
   if (hipEventElapsedTime(&t, ib_.copied[b], ib_.decoded[b]) == hipSuccess) unpack_ms += t;
   if (j + 1 < num_chunks) read_chunk(j + 1);  // (its host image: chunk j - 1's, whose copy has ended)
+  return SWZ_OK;
+}
+
+void source_cuts(swz_ctx* c, const uint64_t* counts, uint64_t n, uint64_t chunk_points, std::vector<uint64_t>* first) {
+  chunk_points = output_chunk_points(c, chunk_points);
+  uint64_t num_chunks = 0;
+  (void)swz_output_chunks(n, counts, chunk_points, 0, nullptr, &num_chunks);
+  first->assign(num_chunks + 1, 0);
+  (void)swz_output_chunks(n, counts, chunk_points, num_chunks, first->data(), &num_chunks);
+}
+
+SourceLoop::SourceLoop(swz_ctx* c, const char* who, const DatasetScan& scan, uint32_t mask, uint64_t chunk_points) : ow_{c} {
+  source_cuts(c, scan.count.data(), scan.count.size(), chunk_points, &first_);
+  source_.plan(c, who, &scan, &first_, mask);
+  for (uint64_t j = 0; j < source_.num_chunks; ++j) nodes_max_ = std::max(nodes_max_, first_[j + 1] - first_[j]);
+}
+
+int SourceLoop::each_chunk(const SourceChunkBody& body, SourceLoopStats* stats) {
+  swz_ctx* c = ow_.c;
+  SourceLoopStats st;
+  if (source_.rows_max) {
+    SWZ_HIP(c, hipStreamCreateWithFlags(&copy_.s, hipStreamNonBlocking));
+    SWZ_TRY(source_.start(copy_.s));
+    for (uint64_t j = 0; j < source_.num_chunks; ++j) {
+      SWZ_TRY(source_.next(j));  // (a read error: the stream stops here, the file is named)
+      ++st.chunks;
+      const SourceChunkView v{j, first_[j], first_[j + 1], source_.rows(j), source_.xyz, &source_.cols};
+      const auto t_body = std::chrono::steady_clock::now();
+      SWZ_TRY(body(v));
+      st.body_ms += ms_since(t_body);
+    }
+  }
+  st.bytes_read = source_.bytes_read;
+  st.read_ms = source_.read_ms;
+  st.unpack_ms = source_.unpack_ms;
+  st.copy_ms = source_.copy_ms;
+  *stats = st;
   return SWZ_OK;
 }
 

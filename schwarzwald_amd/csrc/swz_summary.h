@@ -1,6 +1,6 @@
 // swz_summary.h -- per-node attribute summaries (swz_summary.hip) for the callers inside the library: the reduction of a
 // chunk's columns, which swz_dataset_summarize runs chunk by chunk, and the sidecar file node-summaries.swz, which the node
-// rule of the filtered query reads (swz_query.hip).
+// rule of the filtered query reads (swz_qplan.hip).
 #pragma once
 #include <limits>
 #include <string>

@@ -1,6 +1,8 @@
 // swz_summary.hip -- per-node attribute summaries: what every scalar column of a node holds, reduced on the device
-// (swz_node_summaries_device), and the sidecar file node-summaries.swz that keeps the result beside a written data set
-// (swz_dataset_summaries_write / _read), so that a filtered query can skip the node files no row of which can pass.
+// (swz_node_summaries_device), the sidecar file node-summaries.swz that keeps the result beside a written data set
+// (swz_dataset_summaries_write / _read), so that a filtered query can skip the node files no row of which can pass, and
+// swz_dataset_summarize, which streams a data set chunk by chunk (SourceLoop::each_chunk, swz_source.hip), reduces every chunk
+// and writes that file.
 //
 // The rows are in stored order (a chunk's columns as the unpack kernels leave them), so the rows of a node are neighbours.  One
 // block takes SUM_TILE consecutive rows, one per thread, and finds their nodes with the window helpers of swz_nodepack.h.  The
@@ -18,6 +20,7 @@
 #include <vector>
 
 #include "swz_internal.h"
+#include "swz_convert.h"
 #include "swz_device.h"
 #include "swz_hostio.h"
 #include "swz_nodebox.h"
@@ -420,6 +423,52 @@ int sidecar_read(const std::string& dir, Sidecar* out, std::string* why) {
   return SWZ_OK;
 }
 
+// ---------------------------------------------------------------------------------- a data set's summaries
+// swz_dataset_summarize: every node of the source through the query's stream (SourceLoop::each_chunk, swz_source.hip), the
+// summaries kernel on every chunk, the sidecar.  A source without scalar columns gets its empty sidecar without a stream.
+static int summarize(swz_ctx* c, const char* who, const char* dir, uint32_t source_flags, uint64_t chunk_points, swz_summarize_stats* stats) {
+  auto refuse = [&](const std::string& what) { return c->fail(SWZ_ERR_BAD_ARG, std::string(who) + ": " + what); };
+  const auto t_wall = std::chrono::steady_clock::now();
+  if (stats) *stats = swz_summarize_stats{};
+  if (!dir) return refuse("NULL argument");
+  if (source_flags & ~(uint32_t)SWZ_CONVERT_LOSSY_SOURCE) return refuse("an unknown bit in source_flags");
+  DatasetScan scan;
+  SWZ_TRY(source_open(c, who, dir, -1, source_flags, &scan, nullptr));
+  uint32_t mask = scan.info.attribute_mask & (uint32_t)SWZ_SUMMARY_SCALARS;
+  if (scan.info.format == SWZ_OUT_3DTILES) mask &= 1u << SWZ_ATTR_INTENSITY;  // all a .pnts file carries beside RGB
+  const uint32_t cols = (uint32_t)__builtin_popcount(mask);
+  const uint64_t nn = scan.count.size();
+  std::vector<swz_attr_summary> entries((size_t)(nn * cols), summary_empty());
+  SourceLoopStats ls;
+  SourceLoop loop{c, who, scan, mask, chunk_points};
+  if (cols) {
+    SWZ_HIP(c, hipSetDevice(c->device));
+    std::vector<uint64_t> offset;
+    const SourceChunkBody body = [&](const SourceChunkView& ch) -> int {
+      offset.assign(ch.k1 - ch.k0, 0);
+      for (uint64_t k = ch.k0 + 1; k < ch.k1; ++k) offset[k - ch.k0] = offset[k - ch.k0 - 1] + scan.count[k - 1];
+      return node_summaries(c, who, ch.rows, ch.cols, mask, ch.k1 - ch.k0, offset.data(), scan.count.data() + ch.k0,
+                            entries.data() + ch.k0 * cols);
+    };
+    SWZ_TRY(loop.each_chunk(body, &ls));
+  }
+  std::string why;
+  const int st = sidecar_write(dir, scan.info.format, mask, nn, scan.level.data(), scan.key.data(), scan.count.data(), entries.data(), &why);
+  if (st != SWZ_OK) return c->fail(st, std::string(who) + ": " + why);
+  if (stats) {
+    stats->nodes = nn;
+    stats->points = scan.info.points;
+    stats->bytes_read = ls.bytes_read;
+    stats->chunks = ls.chunks;
+    stats->read_ms = ls.read_ms;
+    stats->unpack_ms = ls.unpack_ms;
+    stats->summary_ms = ls.body_ms;
+    stats->copy_ms = ls.copy_ms;
+    stats->wall_ms = ms_since(t_wall);
+  }
+  return SWZ_OK;
+}
+
 }  // namespace swz
 
 using namespace swz;
@@ -427,6 +476,11 @@ using namespace swz;
 extern "C" {
 
 uint32_t swz_node_summaries_tile(void) { return (uint32_t)SUM_TILE; }
+
+int swz_dataset_summarize(swz_ctx* c, const char* dir, uint32_t source_flags, uint64_t chunk_points, swz_summarize_stats* stats) {
+  if (!c) return SWZ_ERR_BAD_ARG;
+  return summarize(c, "swz_dataset_summarize", dir, source_flags, chunk_points, stats);
+}
 
 int swz_node_summaries_device(swz_ctx* c, uint64_t n, const swz_attribute_columns* d_in, uint32_t attribute_mask, uint64_t num_nodes,
                               const uint64_t* node_offset, const uint64_t* node_count, swz_attr_summary* summaries_out) {

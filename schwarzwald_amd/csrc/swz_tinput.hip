@@ -45,10 +45,6 @@ constexpr uint32_t LAS_MASK_ALWAYS =
   (1u << SWZ_ATTR_NUMBER_OF_RETURNS) | (1u << SWZ_ATTR_RETURN_NUMBER) | (1u << SWZ_ATTR_POINT_SOURCE_ID) |
   (1u << SWZ_ATTR_SCAN_DIRECTION_FLAG) | (1u << SWZ_ATTR_SCAN_ANGLE_RANK) | (1u << SWZ_ATTR_USER_DATA);
 
-static double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // ---------------------------------------------------------------------------------- the segment kernel
 struct LasSegArgs {
   const uint8_t* raw;

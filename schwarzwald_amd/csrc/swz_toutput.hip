@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "swz_convert.h"
 #include "swz_toutput.h"
 #include "swz_hostio.h"
 
@@ -29,10 +30,6 @@ static_assert(sizeof(swz_output_params) == 56 && offsetof(swz_output_params, for
 namespace swz {
 
 constexpr uint64_t OUTPUT_CHUNK_POINTS = 16ull << 20;  // TilingAlgorithmGPU's export chunk
-
-static double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 
 static int plan_layout(swz_ctx* c, const char* who, OutputPlan& p) {
   const uint64_t nn = p.count.size();
@@ -214,15 +211,10 @@ uint64_t output_chunk_points(swz_ctx* c, uint64_t chunk_points) {
 
 void output_cuts(swz_ctx* c, const OutputPlan& p, uint64_t k0, uint64_t k1, uint64_t chunk_points, std::vector<uint64_t>* first,
                  uint64_t* image_max) {
-  chunk_points = output_chunk_points(c, chunk_points);
-  uint64_t num_chunks = 0;
-  const uint64_t* counts = p.count.data() + k0;
-  (void)swz_output_chunks(k1 - k0, counts, chunk_points, 0, nullptr, &num_chunks);
-  first->assign(num_chunks + 1, 0);
-  (void)swz_output_chunks(k1 - k0, counts, chunk_points, num_chunks, first->data(), &num_chunks);
+  source_cuts(c, p.count.data() + k0, k1 - k0, chunk_points, first);
   for (uint64_t& f : *first) f += k0;
   *image_max = 0;
-  for (uint64_t j = 0; j < num_chunks; ++j) *image_max = std::max(*image_max, image_at(p, (*first)[j + 1]) - image_at(p, (*first)[j]));
+  for (size_t j = 0; j + 1 < first->size(); ++j) *image_max = std::max(*image_max, image_at(p, (*first)[j + 1]) - image_at(p, (*first)[j]));
 }
 
 int output_stream(swz_ctx* c, OutputPlan& p, const std::vector<uint64_t>& first, const OutputSource& source, OutputImages& ob,
