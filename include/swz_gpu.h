@@ -1356,6 +1356,97 @@ int swz_dataset_query_filtered_nodes_why(const char* dir, const swz_query_params
                                          const swz_filter* filter, uint64_t max_nodes, int8_t* level_out, uint64_t* key_out,
                                          uint64_t* count_out, uint8_t* read_out, uint64_t* num_out, uint64_t* points_bound_out,
                                          char* why_out, uint64_t why_bytes);
+/* ---- a written data set rasterized: per cell of a grid in x-y the count, min, max and mean of a value of the selected rows,
+ * accumulated on the device in integers.  The result is a few MB whatever the number of rows, and bit-exact: it depends on
+ * no order, on no chunking and -- where the formats store the same values -- on no format.
+ *   The grid (swz_raster_grid) has nx x ny cells over the x-y rectangle of the query's closed box [box_min, box_max].  All six
+ *     bounds must be finite with box_min[i] <= box_max[i].  cw = (box_max[0] - box_min[0]) / nx and ch = (box_max[1] -
+ *     box_min[1]) / ny are computed once, on the host.  A row (x, y, z) that the selection keeps falls into
+ *       ix = min((uint32)floor((x - box_min[0]) / cw), nx - 1),  iy = min((uint32)floor((y - box_min[1]) / ch), ny - 1),
+ *     cell iy * nx + ix: iy ascends with y.  The subtraction, the division and the floor are three separately rounded double
+ *     operations (the library is built without contraction; numpy reproduces them bit for bit).  A row on box_max lands in the
+ *     last cell, because the box is closed.  An axis with box_max == box_min has a cell size of 0: that is taken only with ONE
+ *     cell along that axis, whose index is then 0 without a division; with more cells it is refused.
+ *   The value v (swz_raster_grid::value): SWZ_RASTER_VALUE_Z (-1), the row's z, or a scalar attribute of one or two bytes --
+ *     SWZ_ATTR_INTENSITY, SWZ_ATTR_POINT_SOURCE_ID or a one-byte column; SWZ_ATTR_SCAN_ANGLE_RANK is read as signed -- whose
+ *     element becomes a double as a filter's RANGE clause makes it one (exact).  SWZ_ATTR_GPS_TIME, SWZ_ATTR_RGB and
+ *     SWZ_ATTR_NORMAL are refused by name.
+ *   Per cell one swz_raster_cell (32 bytes):
+ *       count     the rows of the cell.
+ *       sum       the sum of q = llrint((v - v0) * scale) over them (round to nearest, ties to even).  z: v0 = box_min[2] and
+ *                 scale = 2^k, k = 0 for range = box_max[2] - box_min[2] == 0, else k = 30 - ilogb(range) clamped to
+ *                 [-900, 900], so that 2^30 <= range * scale < 2^31 without the clamp.  An attribute: v0 = 0, scale = 1, q is the
+ *                 element.  |q| < 2^31 and a call holds at most 2^32 - 1 rows, hence |sum| < 2^63: a data set whose read nodes
+ *                 hold more rows is refused before a node file is read.
+ *       min_code, max_code   the smallest and the largest v as ORDER-PRESERVING codes: of the double's 64 bits b, ~b for a
+ *                 negative and b | 2^63 otherwise, so the codes ascend with the values and -0.0 lies just below +0.0.  They are
+ *                 preset to the codes of +inf (0xFFF0000000000000) and -inf (0x000FFFFFFFFFFFFF).
+ *     swz_raster_frame holds what a kernel and a reader of the table need: x0, y0, cw, ch, v0, scale, nx, ny, value.
+ *   swz_raster_frame_of (host only, no context: it runs on a machine without a GPU) checks the inputs and derives the frame.
+ *     SWZ_ERR_BAD_ARG with the text in why_out (why_bytes bytes, may be NULL), by name: nx or ny equal to 0, nx * ny above
+ *     SWZ_RASTER_MAX_CELLS, a bound that is not finite, box_min > box_max, a flat axis with more than one cell, a value the
+ *     raster does not take, reserved != 0.
+ *   swz_raster_finish (host only) decodes a table of frame->nx * frame->ny cells into arrays of as many elements (each may be
+ *     NULL): count; min and max, exact -- of +0.0 and -0.0 either may come back --; and
+ *       mean = v0 + ((double)sum / (double)count) / scale,  three separately rounded operations.
+ *     An empty cell has count 0, min +inf, max -inf and mean NaN.  q is off (v - v0) * scale by half a unit at the most, so
+ *     mean is off the exact mean of the doubles by at most half a step, 1 / (2 scale) <= range * 2^-31 (z; an attribute's sum
+ *     is exact), and by the rounding of its own three operations.
+ *   swz_raster_clear_device presets the nx * ny cells of d_cells (a small kernel on the context's stream).
+ *   swz_raster_accumulate_device ADDS n rows to d_cells and does not clear it: that is how chunks accumulate.  d_value is the
+ *     value's column (NULL for z).  One workgroup takes swz_raster_tile() consecutive rows, one per lane, and applies the closed
+ *     box test of swz_box_select_device to x, y and z itself: a NaN is outside, rows outside the box are skipped, and the clamp
+ *     keeps every index inside the table whatever the input holds.  Stored rows are close to Morton order, so neighbouring
+ *     lanes often share a cell: a lane whose cell differs from the lane below it (a shuffle) heads a run, an outside lane
+ *     breaks one; the runs of a wave are reduced with segmented shuffles over count, sum, min code and max code, and the head
+ *     of a run issues four relaxed agent-scope 64-bit atomics: add, add, min, max.  Integer add, min and max commute: the table
+ *     depends on no order.  SWZ_ERR_BAD_ARG with a message before anything is launched: n above 2^32 - 65536, a NULL d_xyz
+ *     with n > 0, an attribute value without its column or with a misaligned one, misaligned positions or cells, a frame that
+ *     swz_raster_frame_of does not produce from box_min, box_max and the frame's nx, ny and value.  n == 0 launches nothing.
+ *     Both synchronise the context's stream.
+ *   swz_dataset_rasterize: the rows swz_dataset_query_filtered selects for params, region and filter (each of the two may be
+ *     NULL), rastered into cells_out (HOST, nx * ny cells); frame_out receives the frame.  Planning is the query's: the same
+ *     refusals, the same node rule, the same use of node-summaries.swz when it is there.  The stream unpacks only what is
+ *     needed -- the filter's columns and the value's -- never the caller's columns: params->attribute_mask must be 0 or ~0u
+ *     and is ignored.  Refused before a file of points is read: a value attribute the source does not hold (named, with the
+ *     source's mask) and, for a 3DTILES source, any value .pnts files do not carry.  Per chunk: the box alone (no region, no
+ *     filter) runs the accumulate kernel straight on the chunk-local arrays, one pass and nothing compacted; otherwise
+ *     swz_filter_select_device's selection compacts positions and the value column into the workspace and the kernel runs on
+ *     the compacted rows.  The table lives in the workspace, is cleared once before the first chunk and copied out after the
+ *     last.  stats: points_out is the sum of the counts, select_ms the time of the chunks' bodies.  A file that cannot be read
+ *     stops the stream and is named, as for the query; cells_out is then unspecified.
+ *   Not offered: GPS time or colours as values, percentiles, a multi-GPU driver, grid files (GeoTIFF, ASCII). */
+#define SWZ_RASTER_VALUE_Z (-1)
+#define SWZ_RASTER_MAX_CELLS (1u << 26)
+typedef struct {
+  uint32_t nx, ny;   /* cells along x and y */
+  int32_t value;     /* SWZ_RASTER_VALUE_Z or SWZ_ATTR_* */
+  uint32_t reserved; /* 0 */
+} swz_raster_grid;   /* 16 bytes */
+typedef struct {
+  double x0, y0;     /* box_min[0], box_min[1] */
+  double cw, ch;     /* the cell's sides; 0 along a flat axis */
+  double v0, scale;  /* q = llrint((v - v0) * scale) */
+  uint32_t nx, ny;
+  int32_t value;
+  uint32_t reserved; /* 0 */
+} swz_raster_frame;  /* 64 bytes */
+typedef struct {
+  uint64_t count;
+  int64_t sum;
+  uint64_t min_code, max_code;
+} swz_raster_cell; /* 32 bytes */
+uint32_t swz_raster_tile(void); /* rows one workgroup takes; tests place their edges by it */
+int swz_raster_frame_of(const double box_min[3], const double box_max[3], const swz_raster_grid* grid, swz_raster_frame* frame_out,
+                        char* why_out, uint64_t why_bytes);
+int swz_raster_finish(const swz_raster_frame* frame, const swz_raster_cell* cells, uint64_t* count_out, double* min_out, double* max_out,
+                      double* mean_out);
+int swz_raster_clear_device(swz_ctx* ctx, const swz_raster_frame* frame, swz_raster_cell* d_cells);
+int swz_raster_accumulate_device(swz_ctx* ctx, const double* d_xyz, uint64_t n, const void* d_value /* NULL for z */, const double box_min[3],
+                                 const double box_max[3], const swz_raster_frame* frame, swz_raster_cell* d_cells);
+int swz_dataset_rasterize(swz_ctx* ctx, const char* dir, const swz_query_params* params, const swz_region* region /* may be NULL */,
+                          const swz_filter* filter /* may be NULL */, const swz_raster_grid* grid, swz_raster_cell* cells_out /* HOST */,
+                          swz_raster_frame* frame_out, swz_query_stats* stats);
 /* ---- a source projection (the reference's --source-projection: Proj4Transform, core/util/Transformation.cpp:74-211, source
  * -> "+proj=geocent +datum=WGS84").  PROJ is not linked: the library maps the projection families LAS data comes in itself,
  * in double, and refuses every other definition by name.

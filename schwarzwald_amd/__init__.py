@@ -15,13 +15,13 @@ from .api import (ACCURATE, FLAG_MIN_DISTANCE_PROPERTY, ALWAYS_ADHERE_TO_MIN_SPA
                   las_record_layout, las_pack_tile, las_image_layout, las_write_node, las_write_node_rows, las_persist_nodes,
                   las_read_header, las_read_node, ept_create_dirs, ept_hierarchy_write, ept_json_write, bin_layout, bin_pack_tile,
                   node_boxes_tile, las_stored_box, OUT_TIGHT_BOUNDS, properties_json_write, properties_json_read, dataset_scan,
-                  bin_unpack_tile, pnts_unpack_tile, pnts_parse_image, CONVERT_LOSSY_SOURCE, convert_dataset, convert_dataset_world, box_select_tile, dataset_query_nodes, dataset_query, Region, REGION_BOX, REGION_PLANES, REGION_POLYGON, frustum_planes, dataset_query_region_nodes, dataset_query_region, Filter, FILTER_RANGE, FILTER_SET, FILTER_NOT, dataset_query_filtered, dataset_query_filtered_nodes, dataset_summarize, dataset_summaries_read, dataset_summaries_write, node_summaries_tile, SUMMARY_HAS_NAN, SUMMARY_SCALARS, SUMMARY_DTYPE, tileset_oriented_boxes, tileset_write_oriented,
+                  bin_unpack_tile, pnts_unpack_tile, pnts_parse_image, CONVERT_LOSSY_SOURCE, convert_dataset, convert_dataset_world, box_select_tile, dataset_query_nodes, dataset_query, Region, REGION_BOX, REGION_PLANES, REGION_POLYGON, frustum_planes, dataset_query_region_nodes, dataset_query_region, Filter, FILTER_RANGE, FILTER_SET, FILTER_NOT, dataset_query_filtered, dataset_query_filtered_nodes, dataset_summarize, dataset_summaries_read, dataset_summaries_write, node_summaries_tile, SUMMARY_HAS_NAN, SUMMARY_SCALARS, SUMMARY_DTYPE, raster_tile, raster_frame_of, raster_finish, dataset_rasterize, RASTER_VALUE_Z, RASTER_MAX_CELLS, RASTER_CELL_DTYPE, tileset_oriented_boxes, tileset_write_oriented,
                   DATASET_ROOT_ABSENT, DATASET_ROOT_PROPERTIES, DATASET_ROOT_EPT,
                   bin_persist_nodes_image, output_chunks, merge_shard_node_tables, OUTPUT_FORMATS, las_scan_files, input_batches, las_input_tile,
                   attribute_names, Srs, srs_transform, srs_transform_box, srs_tile, SRS_ECEF, SRS_WGS84, SRS_LONGLAT, SRS_TMERC,
                   LAS_SCAN_SKIP_UNREADABLE, LAS_FILE_OK, LAS_FILE_UNREADABLE, LAS_FILE_BAD_HEADER, LAS_FILE_COMPRESSED)
 
-__all__ = ["properties_json_write", "properties_json_read", "dataset_scan", "bin_unpack_tile", "pnts_unpack_tile", "pnts_parse_image", "CONVERT_LOSSY_SOURCE", "convert_dataset", "convert_dataset_world", "box_select_tile", "dataset_query_nodes", "dataset_query", "Region", "REGION_BOX", "REGION_PLANES", "REGION_POLYGON", "frustum_planes", "dataset_query_region_nodes", "dataset_query_region", "Filter", "FILTER_RANGE", "FILTER_SET", "FILTER_NOT", "dataset_query_filtered", "dataset_query_filtered_nodes", "dataset_summarize", "dataset_summaries_read", "dataset_summaries_write", "node_summaries_tile", "SUMMARY_HAS_NAN", "SUMMARY_SCALARS", "SUMMARY_DTYPE",
+__all__ = ["properties_json_write", "properties_json_read", "dataset_scan", "bin_unpack_tile", "pnts_unpack_tile", "pnts_parse_image", "CONVERT_LOSSY_SOURCE", "convert_dataset", "convert_dataset_world", "box_select_tile", "dataset_query_nodes", "dataset_query", "Region", "REGION_BOX", "REGION_PLANES", "REGION_POLYGON", "frustum_planes", "dataset_query_region_nodes", "dataset_query_region", "Filter", "FILTER_RANGE", "FILTER_SET", "FILTER_NOT", "dataset_query_filtered", "dataset_query_filtered_nodes", "dataset_summarize", "dataset_summaries_read", "dataset_summaries_write", "node_summaries_tile", "SUMMARY_HAS_NAN", "SUMMARY_SCALARS", "SUMMARY_DTYPE", "raster_tile", "raster_frame_of", "raster_finish", "dataset_rasterize", "RASTER_VALUE_Z", "RASTER_MAX_CELLS", "RASTER_CELL_DTYPE",
            "tileset_oriented_boxes", "tileset_write_oriented", "DATASET_ROOT_ABSENT",
            "DATASET_ROOT_PROPERTIES", "DATASET_ROOT_EPT", "node_boxes_tile", "las_stored_box", "OUT_TIGHT_BOUNDS", "Srs", "srs_transform", "srs_transform_box", "srs_tile", "SRS_ECEF", "SRS_WGS84", "SRS_LONGLAT", "SRS_TMERC", "merge_shard_node_tables", "las_scan_files", "input_batches", "las_input_tile", "attribute_names", "LAS_SCAN_SKIP_UNREADABLE", "LAS_FILE_OK",
            "LAS_FILE_UNREADABLE", "LAS_FILE_BAD_HEADER", "LAS_FILE_COMPRESSED", "bin_layout", "bin_pack_tile", "bin_persist_nodes_image", "output_chunks", "OUTPUT_FORMATS", "LAS_NAMING_POTREE", "LAS_NAMING_ENTWINE", "las_scale_from_bounds", "las_record_layout", "las_pack_tile", "las_image_layout",

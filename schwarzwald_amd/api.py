@@ -1231,6 +1231,116 @@ def dataset_query_filtered_nodes(directory, box_min, box_max, region=None, filte
     return _query_nodes(load_library().swz_dataset_query_filtered_nodes_why, directory, p, _ref(rg), _ref(fl), with_read=True)
 
 
+# ---- a written data set rasterized: count, min, max and mean of a value per cell of a grid in x-y (swz_raster_*, swz_dataset_rasterize)
+RASTER_VALUE_Z = -1
+RASTER_MAX_CELLS = 1 << 26
+# a cell (swz_raster_cell) as numpy sees it: 32 bytes
+RASTER_CELL_DTYPE = np.dtype([("count", "<u8"), ("sum", "<i8"), ("min_code", "<u8"), ("max_code", "<u8")])
+
+
+class _RasterGrid(C.Structure):
+    _fields_ = [("nx", C.c_uint32), ("ny", C.c_uint32), ("value", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class _RasterFrame(C.Structure):
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("cw", C.c_double), ("ch", C.c_double), ("v0", C.c_double), ("scale", C.c_double),
+                ("nx", C.c_uint32), ("ny", C.c_uint32), ("value", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class _RasterCell(C.Structure):
+    _fields_ = [("count", C.c_uint64), ("sum", C.c_int64), ("min_code", C.c_uint64), ("max_code", C.c_uint64)]
+
+
+def raster_tile():
+    """Rows one workgroup of raster_accumulate_device takes (tests place their edges by it)."""
+    return int(load_library().swz_raster_tile())
+
+
+def _raster_value(value):
+    """"z", an attribute's name, or the raw number => swz_raster_grid::value; nothing is checked"""
+    if isinstance(value, (int, np.integer)):
+        return int(value)
+    return RASTER_VALUE_Z if value == "z" else ATTRIBUTES[value][0]
+
+
+def _raster_frame_struct(frame):
+    return _RasterFrame(*[frame[k] for k, _ in _RasterFrame._fields_])
+
+
+def raster_frame_of(box_min, box_max, nx, ny, value="z", reserved=0):
+    """swz_raster_frame_of (host, no GPU): the frame of an nx x ny grid over the x-y rectangle of the closed box, for the value
+    "z" or a scalar attribute of one or two bytes (a name of ATTRIBUTES or its index): dict(x0, y0, cw, ch, v0, scale, nx, ny,
+    value, reserved).  What the library refuses -- no cell, more than RASTER_MAX_CELLS, a box that is not finite or inverted, a
+    flat axis with several cells, gps_time / rgb / normal -- raises SwzError with its text."""
+    grid = _RasterGrid(int(nx), int(ny), _raster_value(value), int(reserved))
+    frame = _RasterFrame()
+    why = C.create_string_buffer(1024)
+    st = load_library().swz_raster_frame_of(_vec3(box_min), _vec3(box_max), C.byref(grid), C.byref(frame), why, len(why))
+    if st != 0:
+        raise SwzError(st, why.value.decode(errors="replace"))
+    return {k: getattr(frame, k) for k, _ in _RasterFrame._fields_}
+
+
+def raster_finish(frame, cells):
+    """swz_raster_finish (host, no GPU): a table of frame["nx"] * frame["ny"] cells (RASTER_CELL_DTYPE) decoded into
+    dict(count, min, max, mean), arrays of shape (ny, nx), row iy ascending with y.  An empty cell: 0, +inf, -inf, NaN."""
+    f = _raster_frame_struct(frame)
+    n = int(frame["nx"]) * int(frame["ny"])
+    table = np.ascontiguousarray(cells, dtype=RASTER_CELL_DTYPE).reshape(-1)
+    if table.shape[0] != n:
+        raise ValueError("cells must hold nx * ny cells")
+    count = np.empty(n, dtype=np.uint64)
+    lo, hi, mean = (np.empty(n, dtype=np.float64) for _ in range(3))
+    st = load_library().swz_raster_finish(C.byref(f), table.ctypes.data, count.ctypes.data_as(_u64p), lo.ctypes.data_as(_dp),
+                                          hi.ctypes.data_as(_dp), mean.ctypes.data_as(_dp))
+    if st != 0:
+        raise SwzError(st, "swz_raster_finish: a frame of no cell or of more than RASTER_MAX_CELLS")
+    shape = (int(frame["ny"]), int(frame["nx"]))
+    return dict(count=count.reshape(shape), min=lo.reshape(shape), max=hi.reshape(shape), mean=mean.reshape(shape))
+
+
+def _raster_box(directory, box_min, box_max, region, max_depth):
+    """the box of a raster: given; or, with both left out, a polygon's x-y bounds and the root box's z, else the root box"""
+    if box_min is not None and box_max is not None:
+        return box_min, box_max
+    if (box_min is None) != (box_max is None):
+        raise ValueError("box_min and box_max are given together or left out together")
+    if region is not None and region.kind == REGION_POLYGON and region.values is not None:
+        return _region_box(directory, None, None, region, max_depth)
+    scan = dataset_scan(directory, max_depth)
+    if scan["root_source"] == DATASET_ROOT_ABSENT or scan["format"] == "3DTILES":
+        raise ValueError("no box to derive: the source has no root box, or stores positions relative to an RTC_CENTER")
+    return list(scan["root_min"]), list(scan["root_max"])
+
+
+def dataset_rasterize(ctx, directory, box_min, box_max, nx, ny, value="z", region=None, filter=None, max_depth=None, lossy_source=False,
+                      chunk_points=0):
+    """swz_dataset_rasterize: the rows dataset_query_filtered selects -- the closed box, cut by region (a Region) and filter (a
+    Filter), of the nodes of depth <= max_depth -- rastered on the device into an nx x ny grid over the box's x-y rectangle:
+    per cell the count and the min, max and mean of value ("z", or a scalar attribute of one or two bytes).  No point leaves
+    the device; the result is the grid.  box_min and box_max may both be None: the root box of the data set, or for a polygon
+    its x-y bounds and the root box's z.  Returns dict(count, min, max, mean, sum -- numpy arrays of shape (ny, nx), row iy
+    ascending with y; sum is the integer sum of llrint((v - v0) * scale) --, cells (the raw table, RASTER_CELL_DTYPE), frame
+    (raster_frame_of's dict) and stats (the fields of swz_query_stats; points_out is the sum of the counts)).  The table is
+    bit-exact: it depends on no order and no chunking.  An empty cell has count 0, min +inf, max -inf, mean NaN."""
+    box_min, box_max = _raster_box(directory, box_min, box_max, region, max_depth)
+    if filter is not None:
+        filter.check()   # (before the directory is scanned)
+    grid = _RasterGrid(int(nx), int(ny), _raster_value(value), 0)
+    cells = np.zeros(max(int(nx) * int(ny), 1) if int(nx) * int(ny) <= RASTER_MAX_CELLS else 1, dtype=RASTER_CELL_DTYPE)
+    p = _query_params(box_min, box_max, max_depth, None, lossy_source, chunk_points)
+    rg = None if region is None else region._struct()
+    fl = None if filter is None else filter._struct()
+    frame, stats = _RasterFrame(), _QueryStats()
+    ctx._check(ctx._lib.swz_dataset_rasterize(ctx._ctx, os.fsencode(directory), C.byref(p), _ref(rg), _ref(fl), C.byref(grid), cells.ctypes.data,
+                                              C.byref(frame), C.byref(stats)))
+    fr = {k: getattr(frame, k) for k, _ in _RasterFrame._fields_}
+    out = raster_finish(fr, cells)
+    out.update(sum=cells["sum"].reshape(out["count"].shape).copy(), cells=cells, frame=fr,
+               stats={k: getattr(stats, k) for k, _ in _QueryStats._fields_})
+    return out
+
+
 LAS_SCAN_SKIP_UNREADABLE = 1
 
 
@@ -1548,6 +1658,16 @@ def load_library():
                                                        _u64p, C.c_char_p, C.c_uint64]
     for name in ("swz_node_summaries_device", "swz_dataset_summaries_write", "swz_dataset_summaries_read", "swz_dataset_summarize",
                  "swz_dataset_query_filtered_nodes", "swz_dataset_query_filtered_nodes_why"):
+        getattr(L, name).restype = C.c_int
+    rfp = C.POINTER(_RasterFrame)
+    L.swz_raster_tile.argtypes = []
+    L.swz_raster_tile.restype = C.c_uint32
+    L.swz_raster_frame_of.argtypes = [_dp, _dp, C.POINTER(_RasterGrid), rfp, C.c_char_p, C.c_uint64]
+    L.swz_raster_finish.argtypes = [rfp, vp, _u64p, _dp, _dp, _dp]
+    L.swz_raster_clear_device.argtypes = [vp, rfp, vp]
+    L.swz_raster_accumulate_device.argtypes = [vp, vp, C.c_uint64, vp, _dp, _dp, rfp, vp]
+    L.swz_dataset_rasterize.argtypes = [vp, C.c_char_p, C.POINTER(_QueryParams), rgp, flp, C.POINTER(_RasterGrid), vp, rfp, C.POINTER(_QueryStats)]
+    for name in ("swz_raster_frame_of", "swz_raster_finish", "swz_raster_clear_device", "swz_raster_accumulate_device", "swz_dataset_rasterize"):
         getattr(L, name).restype = C.c_int
     for name in ("swz_region_select_device", "swz_dataset_query_region_nodes", "swz_dataset_query_region_nodes_why", "swz_dataset_query_region"):
         getattr(L, name).restype = C.c_int
@@ -2051,6 +2171,23 @@ class Context:
     def dataset_query_filtered(self, directory, box_min, box_max, region=None, filter=None, **kwargs):
         """dataset_query_filtered(self, directory, box_min, box_max, region, filter, ...)"""
         return dataset_query_filtered(self, directory, box_min, box_max, region, filter, **kwargs)
+
+    def raster_clear_device(self, frame, d_cells):
+        """swz_raster_clear_device: presets the frame's nx * ny cells at d_cells (a device pointer; 32 bytes per cell)."""
+        f = _raster_frame_struct(frame)
+        self._check(self._lib.swz_raster_clear_device(self._ctx, C.byref(f), C.c_void_p(d_cells)))
+
+    def raster_accumulate_device(self, d_xyz, n, box_min, box_max, frame, d_cells, d_value=None):
+        """swz_raster_accumulate_device: adds the rows of d_xyz (n rows on the device) inside the closed box to the table at
+        d_cells, which it does not clear; frame is raster_frame_of's for this box; d_value is the device pointer of the value's
+        column (None for z)."""
+        f = _raster_frame_struct(frame)
+        self._check(self._lib.swz_raster_accumulate_device(self._ctx, C.c_void_p(d_xyz), int(n), C.c_void_p(d_value), _vec3(box_min),
+                                                           _vec3(box_max), C.byref(f), C.c_void_p(d_cells)))
+
+    def dataset_rasterize(self, directory, box_min, box_max, nx, ny, **kwargs):
+        """dataset_rasterize(self, directory, box_min, box_max, nx, ny, ...)"""
+        return dataset_rasterize(self, directory, box_min, box_max, nx, ny, **kwargs)
 
     def node_summaries_device(self, n, d_attrs, nodes, attrs=None):
         """swz_node_summaries_device: per node of the table (dict of offset / count over n rows in stored order) and per column

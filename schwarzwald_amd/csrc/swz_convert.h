@@ -1,7 +1,7 @@
 // swz_convert.h -- what the readers of a written data set share: the scanned source (swz_dataset.hip), the launch of the BIN
 // unpack kernel on a stream (swz_binunpack.hip) and the stream of a source's chunks onto the device (swz_source.hip).
-// swz_dataset_query* (swz_query.hip) and swz_dataset_summarize (swz_summary.hip) are chunk bodies of SourceLoop::each_chunk, which
-// owns the loop; swz_convert_dataset (swz_convert.hip) drives SourceStream's plan / start / next itself, from the feed of
+// swz_dataset_query* (swz_query.hip), swz_dataset_summarize (swz_summary.hip) and swz_dataset_rasterize (swz_qraster.hip) are
+// chunk bodies of SourceLoop::each_chunk, which owns the loop; swz_convert_dataset (swz_convert.hip) drives SourceStream's plan / start / next itself, from the feed of
 // output_stream, because there the output side owns the loop.
 #pragma once
 #include <functional>

@@ -4,8 +4,8 @@
 // stream moves it to the device, and the unpack kernel (swz_binunpack.hip; LAS sources: the segment kernel of
 // swz_tinput.hip; .pnts sources: swz_pntsunpack.hip) makes chunk-local positions and columns of it.  The readers of chunk
 // k + 1 run while the caller works on chunk k.  SourceLoop::each_chunk is the loop around it -- cuts, workspace, copy
-// stream, plan, start, next, stats -- for the callers that only have something to do per chunk: swz_dataset_query* and
-// swz_dataset_summarize.  swz_convert_dataset calls next() from output_stream's feed instead.
+// stream, plan, start, next, stats -- for the callers that only have something to do per chunk: swz_dataset_query*,
+// swz_dataset_summarize and swz_dataset_rasterize.  swz_convert_dataset calls next() from output_stream's feed instead.
 #include <sys/stat.h>
 
 #include <algorithm>

@@ -291,6 +291,38 @@ inline QueryResult query_dataset_filtered(Context& ctx, const std::string& dir, 
   }
   return out;
 }
+// The rows query_dataset_filtered selects, rastered on the device instead of returned (swz_dataset_rasterize): per cell of
+// grid.nx x grid.ny cells over the x-y rectangle of params' box the count and the min, max and mean of grid.value -- the row's
+// z (SWZ_RASTER_VALUE_Z) or a scalar attribute of one or two bytes.  Only the table comes back: cells as the device left them
+// (integer sums and order-preserving codes, bit-exact whatever the chunking), decoded by swz_raster_finish into count, min, max
+// and mean; element iy * nx + ix, iy ascending with y; an empty cell has count 0, min +inf, max -inf, mean NaN.
+// params.attribute_mask is ignored (0 or ~0u).  region and filter may be nullptr.  A grid or a filter the library refuses
+// throws with its text before a file is read.
+struct RasterResult {
+  swz_raster_frame frame{};
+  std::vector<swz_raster_cell> cells;
+  std::vector<uint64_t> count;
+  std::vector<double> min, max, mean;
+  swz_query_stats stats{};
+};
+inline RasterResult rasterize_dataset(Context& ctx, const std::string& dir, const swz_query_params& params, const swz_region* region,
+                                      const swz_filter* filter, const swz_raster_grid& grid, bool lossy_source = false) {
+  char why[512];
+  if (filter && swz_filter_check(filter, why, sizeof why) != SWZ_OK) throw std::runtime_error{why};
+  RasterResult out;
+  if (swz_raster_frame_of(params.box_min, params.box_max, &grid, &out.frame, why, sizeof why) != SWZ_OK) throw std::runtime_error{why};
+  swz_query_params p = params;
+  if (lossy_source) p.source_flags |= SWZ_CONVERT_LOSSY_SOURCE;
+  const size_t n = (size_t)grid.nx * grid.ny;
+  out.cells.resize(n);
+  ctx.check(swz_dataset_rasterize(ctx.get(), dir.c_str(), &p, region, filter, &grid, out.cells.data(), &out.frame, &out.stats));
+  out.count.resize(n);
+  out.min.resize(n);
+  out.max.resize(n);
+  out.mean.resize(n);
+  ctx.check(swz_raster_finish(&out.frame, out.cells.data(), out.count.data(), out.min.data(), out.max.data(), out.mean.data()));
+  return out;
+}
 // Per-node attribute summaries (swz_dataset_summarize): every node file of dir is streamed once, the scalar columns are
 // summarised per node on the device and dir/node-summaries.swz is written.  Afterwards query_dataset_filtered skips the node
 // files the filter cannot reach -- the same rows, fewer nodes read.  Run it again after the data set changed: a summary that
